@@ -10,7 +10,9 @@ over one batch of 1024 synthetic frames per GPU, inputs and outputs resident in 
 The contract's region (W warm-up steps, then exactly K timed ones between barrier + synchronize) is timed behind the IK legs,
 on a chip that has been busy; `cold_start` is the same region timed first, right behind model creation (clocks still ramping).
 Frames are independent, so N GPUs run N independent shards (weak scaling) with no data-path collective; timing is
-barrier + synchronize on both sides, max over ranks.  Rank 0 prints ONE JSON line.
+barrier + synchronize on both sides, max over ranks.  Rank 0 prints ONE JSON line.  `ms_per_step` is the headline region's time per
+timed step.  With --dump-outputs DIR, rank 0 also writes the verts its last timed step returned (a fixed seeded sample of frames) to
+DIR/verts.npy; the inputs depend on the arguments only, so two builds can be compared output for output.
 
 Also reported in the same line:
   roofline      dominant kernel (skin_kernel): algorithmic FLOPs / bytes per launch divided by
@@ -56,6 +58,9 @@ PEAK_HBM_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 PEAK_MFMA_F32_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 MFMA (v_mfma_f32_32x32x2_f32)
 PEAK_MFMA_16BIT_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 / f16 MFMA (no sparsity)
 MFMA_32X32X16_FLOPS = 2 * 32 * 32 * 16
+# --dump-outputs: at most this many frames of verts (512 x 6890 x 3 fp32 = 42 MB, under the 64 MB cap), chosen by DUMP_SEED
+DUMP_MAX_FRAMES = 512
+DUMP_SEED = 0
 
 
 def issued_mfma_flops(form, n):
@@ -237,7 +242,13 @@ def main():
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--all-ranks-on-device0", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses GPU 0 (use with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline FK step returned in its last timed launch (rank 0) as DIR/verts.npy, float32 "
+                         "[frames, V, 3]: a fixed seeded sample of at most %d frames (sorted frame order), for output-for-output "
+                         "comparison of two builds on the same arguments" % DUMP_MAX_FRAMES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from smplpp_amd import dist as D
 
@@ -493,6 +504,12 @@ def main():
         smpl.launch(beta, theta, want=("verts",), out=out)
     elapsed_sp = timed(smpl, args.steps)
     elapsed = elapsed_sp["max"]
+    # --dump-outputs: the last timed launch's verts, copied to the host now (the legs below launch into the same `out`), written at the end
+    dump = None
+    if args.dump_outputs and rank == 0:
+        k = min(n, DUMP_MAX_FRAMES)
+        frames = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+        dump = {"verts": out["verts"].index_select(0, torch.from_numpy(frames).cuda()).cpu().numpy().astype(np.float32)}
     launches, skin_ms = kernel_ms(smpl, args.profile_steps)
     # the steady clock: after idle the chip ramps its clocks UP over the first ~400 launches (57 -> 49 us per step over 25 ms,
     # tools/fk_ramp.py), so a short --steps region right behind model creation is timed on a chip that has not settled; the
@@ -656,6 +673,12 @@ def main():
                 ikb = None
             if ikb is not None:
                 ik["cpu_baseline"] = ikb
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        line["dump_outputs"] = {"dir": args.dump_outputs, "files": sorted(name + ".npy" for name in dump),
+                                "frames": int(dump["verts"].shape[0]), "frames_per_step": n, "sample_seed": DUMP_SEED}
     print(json.dumps(line))
 
 

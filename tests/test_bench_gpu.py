@@ -69,3 +69,32 @@ def test_bench_gpus_2_starts_its_own_ranks():
     assert "frames_below_1e-3" in d["vposer_ik"] and d["vposer_ik"]["final_median_e_sqnorm"] <= d["vposer_ik"]["final_max_e_sqnorm"]
     assert d["mocap"]["restarts_this_rank"] == 32 and d["vposer_ik"]["frames_this_rank"] == 256
     assert d["value"] > 1e4
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_steps_verts(tmp_path):
+    """--dump-outputs DIR: the last timed step's verts (a seeded frame sample, float32, under 64 MB) equal the oracle's FK of the
+    same frames of the bench's own inputs (synthetic model, seed 1 for rank 0)."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import cpu
+    from smplpp_amd import model_io
+
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-ik", "--no-extra",
+                        "--no-cpu-baseline", "--sustained-steps", "0", "--no-exact-form", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert line["steps"] == 5 and line["ms_per_step"] > 0 and line["dump_outputs"]["files"] == ["verts.npy"]
+    assert sorted(os.listdir(d)) == ["verts.npy"] and os.path.getsize(d / "verts.npy") <= 64 * 2**20
+    verts = np.load(d / "verts.npy")
+    n = line["config"]["frames_per_gpu"]
+    assert verts.dtype == np.float32 and verts.shape == (bench.DUMP_MAX_FRAMES, 6890, 3) and np.isfinite(verts).all()
+    frames = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, bench.DUMP_MAX_FRAMES, replace=False))
+    beta, theta = model_io.synthetic_inputs(n, seed=1)
+    pick = np.arange(0, len(frames), 64)
+    ref = cpu.OracleModel(model_io.synthetic_model()).fk(beta[frames[pick]], theta[frames[pick]])["verts"]
+    assert np.abs(verts[pick] - ref).max() < 1e-5

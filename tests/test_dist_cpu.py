@@ -182,12 +182,15 @@ d.destroy_process_group()
 """
 
 
-def test_timed_region_keeps_collectives_out_of_the_clock_and_counts_ranks_by_allreduce(tmp_path):
+def test_timed_region_keeps_collectives_out_of_the_clock_and_counts_ranks_by_allreduce(tmp_path, monkeypatch):
     """the closing barrier is outside every rank's clock (the fast rank's own time stays its own), the
     spread over ranks names the slow rank, and the rank count in the line comes from a collective, labelled with the backend that ran
     it ("gloo" here — never "rccl")."""
     import io
 
+    # the ranks must see launch_ranks' own defaults, whatever the environment this test runs in already sets
+    monkeypatch.delenv("NCCL_DEBUG", raising=False)
+    monkeypatch.delenv("HSA_ENABLE_IPC_MODE_LEGACY", raising=False)
     script = tmp_path / "measured.py"
     script.write_text(MEASURED.format(root=ROOT))
     out, err = io.StringIO(), io.StringIO()
