@@ -21,6 +21,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <unordered_map>
 #include <vector>
 
@@ -222,6 +223,26 @@ public:
     xforms_ = Tensor({n, JOINT_NUM, 4, 4});
     check(smplpp_fk(m_.get(), n, beta.ptr(), theta.ptr(), verts_.ptr(), joints_.ptr(), xforms_.ptr(), rest_.ptr(), SMPLPP_HOST, nullptr),
           "SMPL");
+    beta_ = beta;
+    theta_ = theta;
+  }
+
+  // What backward() through the last launch's graph gave the reference (e.g. node/node.cpp:823-869): for the beta / theta of the
+  // last launch, dL/dbeta [N,10] and dL/dtheta [N,25,3] of a loss with dL/dverts = gradVert [N,V,3] and dL/djoints = gradJoint
+  // [N,24,3] (an empty Tensor = zero).  smplpp_fk_vjp, reusing the launch's rest shape.
+  std::pair<Tensor, Tensor> launchBackward(const Tensor & gradVert, const Tensor & gradJoint) const
+  {
+    const Tensor & rest = need(rest_);
+    const int64_t n = beta_.size(0);
+    const bool hv = !gradVert.data.empty(), hj = !gradJoint.data.empty();
+    if((hv && (gradVert.numel() != n * V_ * 3 || gradVert.dtype != kFloat32)) ||
+       (hj && (gradJoint.numel() != n * JOINT_NUM * 3 || gradJoint.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot back-propagate through a SMPL model!");
+    Tensor gb({n, SHAPE_BASIS_DIM}), gt({n, JOINT_NUM + 1, 3});
+    check(smplpp_fk_vjp(m_.get(), n, beta_.ptr(), theta_.ptr(), rest.ptr(), hv ? gradVert.ptr() : nullptr, hj ? gradJoint.ptr() : nullptr,
+                        gb.ptr(), gt.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return {gb, gt};
   }
 
   Tensor getVertex() const { return need(verts_); }       // [N,6890,3] copy (src/SMPL.cpp:492-506)
@@ -334,6 +355,7 @@ private:
   int64_t V_ = 0, F_ = 0;
   Tensor faces1_;
   Tensor verts_, rest_, joints_, xforms_;
+  Tensor beta_, theta_; // inputs of the last launch (launchBackward)
 };
 } // namespace smplpp
 #endif

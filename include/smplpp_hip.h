@@ -86,6 +86,14 @@ int smplpp_model_info(const smplpp_model * m, int64_t * vertex_num, int64_t * fa
  * the IK loops' internal forward passes use by default), b (round 1's bf16x3 kernel), p / v (fp32 MFMA). */
 int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * verts, float * joints,
               float * xforms, float * rest, int space, void * stream);
+/* Vector-Jacobian product of smplpp_fk (the backward pass the reference gets from libtorch autograd through SMPL::launch, e.g.
+ * node/node.cpp:823-869): given dL/dverts [n,V,3] and/or dL/djoints [n,24,3] (either may be NULL = zero), writes dL/dbeta [n,10]
+ * and dL/dtheta [n,25,3] (row 0 = root translation; either output may be NULL).  rest [n,V,3]: the rest shape smplpp_fk returned for
+ * these inputs; NULL = recomputed inside the call with the model's form, in the backward's own workspace (smplpp_fk's workspace,
+ * status words and profiling record are left as they were).  Overwrites its outputs; deterministic (same inputs -> same bits).
+ * The first call on a model builds the basis operand image of the backward (~19 MB for SMPL; freed by smplpp_model_destroy). */
+int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * grad_verts,
+                  const float * grad_joints, float * grad_beta, float * grad_theta, int space, void * stream);
 /* Input range of the fp16x2 form (SMPLPP_SKIN=h): |beta| < 1023 and relative transforms whose
  * translations stay within 16 x the template's extent (65504 / sG).  Outside it the operand pieces overflow fp16 and the
  * vertices of the frame are not finite, where the reference and the default form (and SMPLPP_SKIN=b|p|v) stay finite.  A launch that

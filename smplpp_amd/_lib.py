@@ -60,6 +60,7 @@ def load():
         "smplpp_profile_read": [vp, i64p, f64p],
         "smplpp_fk": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_fk_status": [vp, C.POINTER(C.c_int), vp],
+        "smplpp_fk_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_blend_shape": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_joint_regression": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_world_transformation": [C.c_int, C.c_int64, vp, vp, vp, vp, C.c_int, vp],

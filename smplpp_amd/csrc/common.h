@@ -206,6 +206,8 @@ struct Workspace
   int64_t ldA = 0;
   DevBuf dummy;   // write-only sink for masked-off lanes of branch-free epilogues (skin_p.hip)
 };
+struct VjpState;                   // smplpp_fk_vjp's operand image and workspace (fk_vjp.hip), created by its first call
+void vjp_release(VjpState * s);
 } // namespace smplpp_hip
 
 struct smplpp_model
@@ -252,4 +254,5 @@ struct smplpp_model
   bool profiling = false;
   std::vector<hipEvent_t> prof_events; // begin/end pairs around the fused kernel
   smplpp_hip::Workspace ws;
+  smplpp_hip::VjpState * vjp = nullptr; // backward pass (smplpp_fk_vjp): null until its first call on the model
 };

@@ -164,6 +164,52 @@ class SMPL:
         self._out, self._n, self._theta = out, n, theta
         return out
 
+    def launchBackward(self, beta, theta, grad_verts=None, grad_joints=None, rest=None):
+        """Vector-Jacobian product of `launch` (smplpp_fk_vjp): dL/dbeta [N,10] and dL/dtheta [N,25,3] for dL/dverts = grad_verts
+        [N,V,3] and dL/djoints = grad_joints [N,24,3] (None = zero).  `rest` [N,V,3] is the rest shape `launch` returned for these
+        inputs; None recomputes it inside the call.  numpy in, numpy out (the call synchronises), or torch tensors on the device
+        (enqueued on torch's current stream).  Returns {"beta": ..., "theta": ...}."""
+        V = self.vertex_num
+        L = _lib.load()
+        dev = _is_torch(beta)
+        args = (theta, grad_verts, grad_joints, rest)
+        if any(a is not None and _is_torch(a) != dev for a in args):
+            raise SmplppError(1, "launchBackward: mix of torch tensors and numpy arrays")
+        if dev:
+            def prep(a, shape):
+                if a is None:
+                    return None
+                if not (a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == shape):
+                    raise SmplppError(1, "launchBackward: expected a float32 device tensor of shape %s" % (shape,))
+                return a.contiguous()
+            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=beta.device)
+            space = DEVICE
+        else:
+            def prep(a, shape):
+                if a is None:
+                    return None
+                a = _np32(a)
+                if a.shape != shape:
+                    raise SmplppError(1, "launchBackward: expected shape %s, got %s" % (shape, a.shape))
+                return a
+            mk = lambda *s: np.empty(s, np.float32)
+            space = HOST
+        n = beta.shape[0]
+        beta, theta = prep(beta, (n, 10)), prep(theta, (n, 25, 3))
+        gv, gj, rest = prep(grad_verts, (n, V, 3)), prep(grad_joints, (n, 24, 3)), prep(rest, (n, V, 3))
+        out = {"beta": mk(n, 10), "theta": mk(n, 25, 3)}
+        check(L.smplpp_fk_vjp(self.handle, n, _ptr(beta), _ptr(theta), _ptr(rest), _ptr(gv), _ptr(gj), _ptr(out["beta"]),
+                              _ptr(out["theta"]), space, _stream() if space == DEVICE else None))
+        return out
+
+    def forward_differentiable(self, beta, theta):
+        """(verts [N,V,3], joints [N,24,3]) for device tensors beta [N,10], theta [N,25,3], differentiable with torch.autograd:
+        the forward is one smplpp_fk (rest shape kept for the backward), the backward one smplpp_fk_vjp, both on torch's current
+        stream.  First derivatives with respect to beta and theta only."""
+        if torch is None:
+            raise SmplppError(1, "forward_differentiable needs torch")
+        return _FKFunction.apply(beta, theta, self)
+
     def launchStatus(self):
         """Status word of the launches since the last read (synchronises the current stream): bit 0 = an operand left the
         input range of the default fused kernel (include/smplpp_hip.h, smplpp_fk_status).  Host-space launches raise instead."""
@@ -320,6 +366,36 @@ class SMPL:
                 f.write("v %f %f %f\n" % (p[0], p[1], p[2]))
             for t in self._model["face_indices"]:
                 f.write("f %d %d %d\n" % (t[0], t[1], t[2]))
+
+
+if torch is not None:
+    class _FKFunction(torch.autograd.Function):
+        """smplpp_fk forward / smplpp_fk_vjp backward (SMPL.forward_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, beta, theta, smpl):
+            beta, theta = beta.detach().contiguous(), theta.detach().contiguous()
+            n, V = beta.shape[0], smpl.vertex_num
+            if not (beta.is_cuda and theta.is_cuda and beta.dtype == torch.float32 and theta.dtype == torch.float32
+                    and tuple(beta.shape) == (n, 10) and tuple(theta.shape) == (n, 25, 3)):
+                raise SmplppError(1, "Cannot launch a SMPL model!")
+            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=beta.device)
+            verts, joints, rest = mk(n, V, 3), mk(n, 24, 3), mk(n, V, 3)
+            check(_lib.load().smplpp_fk(smpl.handle, n, _ptr(beta), _ptr(theta), _ptr(verts), _ptr(joints), None, _ptr(rest), DEVICE,
+                                        _stream()))
+            ctx.smpl = smpl
+            ctx.save_for_backward(beta, theta, rest)
+            return verts, joints
+
+        @staticmethod
+        def backward(ctx, grad_verts, grad_joints):
+            beta, theta, rest = ctx.saved_tensors
+            if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+                return None, None, None
+            gv = grad_verts.contiguous() if grad_verts is not None else None
+            gj = grad_joints.contiguous() if grad_joints is not None else None
+            g = ctx.smpl.launchBackward(beta, theta, grad_verts=gv, grad_joints=gj, rest=rest)
+            return (g["beta"] if ctx.needs_input_grad[0] else None, g["theta"] if ctx.needs_input_grad[1] else None, None)
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
