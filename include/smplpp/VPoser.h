@@ -77,6 +77,19 @@ public:
     check(smplpp_vposer_forward(v_, n, latent.ptr(), out.ptr(), jac ? jac->ptr() : nullptr, SMPLPP_HOST, nullptr), "VPoser");
     return out;
   }
+  // What backward() through vposer->forward(latent) gives the reference (node/node.cpp:761-772): dL/dlatent [B,32] for
+  // dL/dangles = gradOut [B,21,3], taken at the decode forward(latent) (no jac) returns.  smplpp_vposer_vjp.
+  Tensor launchBackward(const Tensor & latent, const Tensor & gradOut) const
+  {
+    if(!v_) throw Exception("VPoser", "VPoserDecoder: parameters not loaded");
+    if(latent.numel() % LATENT_DIM != 0 || latent.dtype != kFloat32) throw Exception("VPoser", "launchBackward: latent must be [B,32]");
+    const int64_t n = latent.numel() / LATENT_DIM;
+    if(gradOut.numel() != n * jointNum_ * 3 || gradOut.dtype != kFloat32)
+      throw Exception("VPoser", "launchBackward: gradOut must be [B,21,3]");
+    Tensor gz({n, LATENT_DIM});
+    check(smplpp_vposer_vjp(v_, n, 0, latent.ptr(), gradOut.ptr(), gz.ptr(), nullptr, SMPLPP_HOST, nullptr), "VPoser");
+    return gz;
+  }
   smplpp_vposer * handle() const { return v_; }
 
 private:

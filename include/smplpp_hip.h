@@ -261,6 +261,15 @@ int smplpp_vposer_forward(smplpp_vposer * v, int64_t n, const float * z, float *
  * (node/node.cpp:372); SURVEY 8(e). */
 int smplpp_vposer_forward_at(smplpp_vposer * v, int64_t n, int64_t frame_base, const float * z, float * out, float * jac, int space,
                              void * stream);
+/* Vector-Jacobian product of smplpp_vposer_forward_at (the backward pass the reference gets from libtorch autograd through
+ * vposer->forward(latent), node/node.cpp:761-772): given dL/dout [n,21,3], writes dL/dz [n,32] (overwritten).
+ * out (nullable) [n,21,3]: the decoded angles the product was taken at, bit-identical to smplpp_vposer_forward with jac NULL (the
+ * product differentiates that exact-fp32 decode, so the LeakyReLU masks and the axis-angle branches are the ones the caller's loss
+ * saw).  Deterministic; a frame's bits do not depend on n or frame_base.  The first call on a decoder builds copies of its
+ * weights in [out][in] layout (1.3 MB, freed by smplpp_vposer_destroy).  One workspace per decoder: concurrent calls on one
+ * handle from different streams need the caller's own ordering. */
+int smplpp_vposer_vjp(smplpp_vposer * v, int64_t n, int64_t frame_base, const float * z, const float * grad_out,
+                      float * grad_z, float * out, int space, void * stream);
 /* convertRotMatToAxisAngle (src/VPoser.cpp:25-120): rot [n,3,3] -> aa [n,3]. */
 int smplpp_rotmat_to_axis_angle(int device, int64_t n, const float * rot, float * aa, int space, void * stream);
 

@@ -92,6 +92,7 @@ def load():
         "smplpp_vposer_destroy": [vp],
         "smplpp_vposer_forward": [vp, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_vposer_forward_at": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, vp],
+        "smplpp_vposer_vjp": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_rotmat_to_axis_angle": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
     }
     for name, argtypes in sig.items():

@@ -20,239 +20,23 @@
 // differently: a frame's bits must not depend on the batch it travels in.)
 #pragma clang fp contract(on)
 
-struct smplpp_vposer
-{
-  int device = 0;
-  float *w0t = nullptr, *b0 = nullptr, *w1t = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr;
-  // layers 1 and 2 once more as fp16x2 pieces in MFMA fragment order (the A operand of the tangent GEMMs, layout below)
-  uint8_t *w1h = nullptr, *w2h = nullptr;
-  float sW1 = 1.f, sW2 = 1.f, sD1 = 1.f, sD2 = 1.f; // power-of-two scales: weights of layers 1 / 2, tangent blocks of layers 0 / 1
-  // vposer_jac2_kernel (several frames per workgroup): W0 once more as the B operand of layer 1's tangent GEMM (fragment order,
-  // scale sD1, no slopes) and the constant product C10 = W1 . W0 [512][32] (fp32, from an fp64 sum on the host)
-  uint8_t * w0h = nullptr;
-  float * c10 = nullptr;
-};
+#include "vposer_state.h"
+#include "vposer_tail.h"
 
 namespace smplpp_hip
 {
-constexpr int LAT = SMPLPP_LATENT_DIM; // 32
-constexpr int HID = 512;               // VPoser.h hiddenDim_
-constexpr int OUT6 = 126;              // 6 * 21
-
-// dual number: a value and ND directional derivatives (ND = 6: all six inputs of a joint at once; ND = 1: one direction per
-// thread — the components never mix, so both give the same bits)
-template<int ND>
-struct DN
-{
-  float v;
-  float d[ND];
-};
-typedef DN<6> D6;
-template<int ND>
-__device__ inline DN<ND> mk(float v)
-{
-  DN<ND> r;
-  r.v = v;
-  for(int i = 0; i < ND; i++) r.d[i] = 0.f;
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> operator+(const DN<ND> & a, const DN<ND> & b)
-{
-  DN<ND> r;
-  r.v = a.v + b.v;
-  for(int i = 0; i < ND; i++) r.d[i] = a.d[i] + b.d[i];
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> operator-(const DN<ND> & a, const DN<ND> & b)
-{
-  DN<ND> r;
-  r.v = a.v - b.v;
-  for(int i = 0; i < ND; i++) r.d[i] = a.d[i] - b.d[i];
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> operator*(const DN<ND> & a, const DN<ND> & b)
-{
-  DN<ND> r;
-  r.v = a.v * b.v;
-  for(int i = 0; i < ND; i++) r.d[i] = a.d[i] * b.v + a.v * b.d[i];
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> operator/(const DN<ND> & a, const DN<ND> & b)
-{
-  DN<ND> r;
-  r.v = a.v / b.v;
-  for(int i = 0; i < ND; i++) r.d[i] = (a.d[i] - r.v * b.d[i]) / b.v;
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> operator*(float s, const DN<ND> & a)
-{
-  DN<ND> r;
-  r.v = s * a.v;
-  for(int i = 0; i < ND; i++) r.d[i] = s * a.d[i];
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> operator+(const DN<ND> & a, float s)
-{
-  DN<ND> r = a;
-  r.v += s;
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> neg(const DN<ND> & a)
-{
-  return -1.0f * a;
-}
-template<int ND>
-__device__ inline DN<ND> dsqrt(const DN<ND> & a)
-{
-  DN<ND> r;
-  r.v = sqrtf(a.v);
-  for(int i = 0; i < ND; i++) r.d[i] = a.d[i] / (2.0f * r.v);
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> dacos(const DN<ND> & a)
-{
-  DN<ND> r;
-  r.v = acosf(a.v);
-  const float g = -1.0f / sqrtf(1.0f - a.v * a.v);
-  for(int i = 0; i < ND; i++) r.d[i] = g * a.d[i];
-  return r;
-}
-template<int ND>
-__device__ inline DN<ND> dsin(const DN<ND> & a)
-{
-  DN<ND> r;
-  r.v = sinf(a.v);
-  const float c = cosf(a.v);
-  for(int i = 0; i < ND; i++) r.d[i] = c * a.d[i];
-  return r;
-}
-// torch::nn::functional::normalize of a 3-vector: x / max(||x||, 1e-12) (clamp_min passes no gradient when active)
-template<int ND>
-__device__ inline void dnormalize3(const DN<ND> * x, DN<ND> * o)
-{
-  DN<ND> n2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-  DN<ND> n = dsqrt(n2);
-  if(n.v < 1e-12f) n = mk<ND>(1e-12f);
-  for(int i = 0; i < 3; i++) o[i] = x[i] / n;
-}
-
-// convertRotMatToAxisAngle (src/VPoser.cpp:25-120) on one matrix, value + derivative
-template<int ND>
-__device__ inline void rotmat_to_aa(const DN<ND> R[3][3], DN<ND> aa[3])
-{
-  const float eps = FLT_EPSILON;
-  const float epsSqrt = sqrtf(eps);
-  const float epsSqrt2 = sqrtf(epsSqrt);
-  const float kPi = 3.14159265358979323846f;
-  DN<ND> trace = R[0][0] + R[1][1] + R[2][2];
-  DN<ND> theta = dacos((float)((1.0 - (double)eps) * 0.5) * (trace + (-1.0f))); // :41
-  DN<ND> w[3] = {R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1]};      // :43-49
-  if(1.0f + trace.v < epsSqrt2) // near pi (:53-103)
-  {
-    DN<ND> tn2[3];
-    DN<ND> one_m_tr = neg(trace) + 1.0f, three_m_tr = neg(trace) + 3.0f;
-    for(int i = 0; i < 3; i++)
-    {
-      DN<ND> s = (2.0f * R[i][i] + one_m_tr) / three_m_tr; // :54-56
-      tn2[i] = dsqrt(s + eps) * theta;                   // :60
-    }
-    if(theta.v > kPi - 1e-4f) // :62-94
-    {
-      if(tn2[0].v > 0.0f)
-      {
-        if(R[0][1].v + R[1][0].v < 0.0f) tn2[1] = neg(tn2[1]);
-        if(R[0][2].v + R[2][0].v < 0.0f) tn2[2] = neg(tn2[2]);
-      }
-      else if(tn2[1].v > 0.0f)
-      {
-        if(R[1][2].v + R[2][1].v < 0.0f) tn2[2] = neg(tn2[2]);
-      }
-    }
-    else // :96-99
-    {
-      for(int i = 0; i < 3; i++)
-        if(!(w[i].v >= 0.0f)) tn2[i] = neg(tn2[i]);
-    }
-    for(int i = 0; i < 3; i++) aa[i] = tn2[i];
-  }
-  else if(fabsf(3.0f - trace.v) < epsSqrt) // near zero: Taylor (:105-111)
-  {
-    DN<ND> t2 = theta * theta;
-    DN<ND> f = (1.0f / 6.0f) * t2 + (7.0f / 360.0f) * (t2 * t2) + 1.0f;
-    for(int i = 0; i < 3; i++) aa[i] = 0.5f * (w[i] * f);
-  }
-  else // :112-116
-  {
-    DN<ND> f = theta / (2.0f * dsin(theta));
-    for(int i = 0; i < 3; i++) aa[i] = w[i] * f;
-  }
-}
-
-// ContinousRotReprDecoderImpl::forward (:129-141) on one joint's 6 numbers (view [3,2]) then -> axis-angle.  ND = 6: all six
-// derivative directions (jac36 [3][6]); ND = 1: direction `dir` only (jac36 [3]: d aa / d o6[dir])
-template<int ND>
-__device__ inline void sixd_to_aa_dir(const float * o6, int dir, float * aa_out, float * jac)
-{
-  DN<ND> c1[3], c2[3];
-  for(int r = 0; r < 3; r++)
-  {
-    c1[r] = mk<ND>(o6[2 * r]);
-    c2[r] = mk<ND>(o6[2 * r + 1]);
-    if(ND == 6)
-    {
-      c1[r].d[(2 * r) % ND] = 1.0f;
-      c2[r].d[(2 * r + 1) % ND] = 1.0f;
-    }
-    else
-    {
-      c1[r].d[0] = (2 * r == dir) ? 1.0f : 0.0f;
-      c2[r].d[0] = (2 * r + 1 == dir) ? 1.0f : 0.0f;
-    }
-  }
-  DN<ND> a1[3], a2[3], t[3];
-  dnormalize3(c1, a1);
-  DN<ND> dot = a1[0] * c2[0] + a1[1] * c2[1] + a1[2] * c2[2];
-  for(int r = 0; r < 3; r++) t[r] = c2[r] - dot * a1[r];
-  dnormalize3(t, a2);
-  DN<ND> a3[3] = {a1[1] * a2[2] - a1[2] * a2[1], a1[2] * a2[0] - a1[0] * a2[2], a1[0] * a2[1] - a1[1] * a2[0]};
-  DN<ND> R[3][3];
-  for(int r = 0; r < 3; r++)
-  {
-    R[r][0] = a1[r];
-    R[r][1] = a2[r];
-    R[r][2] = a3[r];
-  }
-  DN<ND> aa[3];
-  rotmat_to_aa(R, aa);
-  for(int i = 0; i < 3; i++)
-  {
-    aa_out[i] = aa[i].v;
-    if(jac)
-      for(int q = 0; q < ND; q++) jac[i * ND + q] = aa[i].d[q];
-  }
-}
-__device__ inline void sixd_to_aa(const float * o6, float * aa_out, float * jac36 /*[3][6]*/)
-{
-  sixd_to_aa_dir<6>(o6, 0, aa_out, jac36);
-}
 
 // Value-only forward (no Jacobian: decoding a stored latent, node/node.cpp:1376-1391): grid = n frames, block = 256, exact
 // fp32 on the VALU.  LDS: activations of layers 0 / 1 in column 32 of [512][VS] rows (the layout the first Jacobian form
-// shared), the layer-2 output [126][33] reuses the first region.
+// shared), the layer-2 output [126][33] reuses the first region.  STORE (the backward's recompute, vposer_vjp.hip): the same
+// arithmetic, and what the backward needs is also written to ws [n][VW_FRAME] (vposer_state.h); `out` may then be null.
 constexpr int VS = 36;
+template<bool STORE>
 __global__ __launch_bounds__(256) void vposer_kernel(const float * __restrict__ z, int64_t z_stride, const float * __restrict__ w0t,
                                                      const float * __restrict__ b0, const float * __restrict__ w1t,
                                                      const float * __restrict__ b1, const float * __restrict__ w2t,
                                                      const float * __restrict__ b2, float * __restrict__ out, int64_t out_stride,
-                                                     float * __restrict__ /*unused*/, int /*unused*/)
+                                                     float * __restrict__ ws)
 {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float * L1 = lds;                  // [512][VS]
@@ -271,6 +55,7 @@ __global__ __launch_bounds__(256) void vposer_kernel(const float * __restrict__ 
     for(int c = 0; c < LAT; c++) h += w0t[c * HID + row] * sz[c];
     const float slope = (h > 0.0f) ? 1.0f : 0.01f;
     L1[row * VS + 32] = h * slope;
+    if constexpr(STORE) ws[f * VW_FRAME + VW_S0 + row] = slope;
   }
   __syncthreads();
   // layer 1 (+ LeakyReLU): a matrix-vector product on the VALU, two rows per thread, even and odd k summed separately
@@ -317,6 +102,11 @@ __global__ __launch_bounds__(256) void vposer_kernel(const float * __restrict__ 
     L2[r1 * VS + 32] = h1 * s1;
     sSlope[r0] = s0;
     sSlope[r1] = s1;
+    if constexpr(STORE)
+    {
+      ws[f * VW_FRAME + VW_S1 + r0] = s0;
+      ws[f * VW_FRAME + VW_S1 + r1] = s1;
+    }
   }
   __syncthreads();
   // layer 2: 126 rows
@@ -342,11 +132,12 @@ __global__ __launch_bounds__(256) void vposer_kernel(const float * __restrict__ 
       for(int u = 0; u < KU; u++) wv[u] = wvn[u];
     }
     so[tid * 33 + 32] = (h + ho) + b2[tid];
+    if constexpr(STORE) ws[f * VW_FRAME + VW_O6 + tid] = so[tid * 33 + 32];
   }
   __syncthreads();
   // rotation tail: 6D -> axis-angle and its 3 x 6 Jacobian, one thread per joint; the chain rule into the 32 latent columns
   // (63 x 32 entries, six terms each) by all threads, coalesced over the columns
-  if(tid < 21)
+  if(tid < 21 && (!STORE || out))
   {
     float o6[6], aa[3];
     for(int q = 0; q < 6; q++) o6[q] = so[(tid * 6 + q) * 33 + 32];
@@ -954,9 +745,21 @@ int vposer_forward_device(smplpp_vposer * v, int64_t n, const float * z, int64_t
   if(jac) return fail(SMPLPP_ERR_INVALID, "smplpp_vposer_forward: this decoder has no Jacobian operands");
   const size_t shmem = sizeof(float) * (size_t)(2 * HID * VS + LAT + HID);
   static PerDeviceOnce once;
-  HIP_TRY(lds_opt_in(once, v->device, reinterpret_cast<const void *>(&vposer_kernel), (int)shmem));
-  vposer_kernel<<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out, out_stride,
-                                                            nullptr, 0);
+  HIP_TRY(lds_opt_in(once, v->device, reinterpret_cast<const void *>(&vposer_kernel<false>), (int)shmem));
+  vposer_kernel<false><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out,
+                                                                   out_stride, nullptr);
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+
+// the value path above once more (vposer_kernel<true>: the same arithmetic, so `out` has the bits smplpp_vposer_forward gives when
+// jac is NULL), also storing the slopes and the layer-2 output of every frame into ws [n][VW_FRAME] for the backward
+int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * out, float * ws, hipStream_t st)
+{
+  const size_t shmem = sizeof(float) * (size_t)(2 * HID * VS + LAT + HID);
+  static PerDeviceOnce once;
+  HIP_TRY(lds_opt_in(once, v->device, reinterpret_cast<const void *>(&vposer_kernel<true>), (int)shmem));
+  vposer_kernel<true><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, LAT, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out, 63, ws);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -974,6 +777,7 @@ extern "C" int smplpp_vposer_destroy(smplpp_vposer * v)
   if(v->w2h) (void)hipFree(v->w2h);
   if(v->w0h) (void)hipFree(v->w0h);
   if(v->c10) (void)hipFree(v->c10);
+  vposer_vjp_release(v->vjp);
   delete v;
   return SMPLPP_OK;
 }

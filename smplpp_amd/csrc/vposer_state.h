@@ -1,0 +1,35 @@
+// The VPoser decoder handle (vposer.hip) and its shapes, shared by the forward (vposer.hip) and its backward (vposer_vjp.hip).
+#pragma once
+#include "common.h"
+
+namespace smplpp_hip
+{
+struct VPoserVjp; // smplpp_vposer_vjp's weight copies and workspace (vposer_vjp.hip), created by its first call
+void vposer_vjp_release(VPoserVjp * s);
+} // namespace smplpp_hip
+
+struct smplpp_vposer
+{
+  int device = 0;
+  float *w0t = nullptr, *b0 = nullptr, *w1t = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr;
+  // layers 1 and 2 once more as fp16x2 pieces in MFMA fragment order (the A operand of the tangent GEMMs, layout below)
+  uint8_t *w1h = nullptr, *w2h = nullptr;
+  float sW1 = 1.f, sW2 = 1.f, sD1 = 1.f, sD2 = 1.f; // power-of-two scales: weights of layers 1 / 2, tangent blocks of layers 0 / 1
+  // vposer_jac2_kernel (several frames per workgroup): W0 once more as the B operand of layer 1's tangent GEMM (fragment order,
+  // scale sD1, no slopes) and the constant product C10 = W1 . W0 [512][32] (fp32, from an fp64 sum on the host)
+  uint8_t * w0h = nullptr;
+  float * c10 = nullptr;
+  smplpp_hip::VPoserVjp * vjp = nullptr; // backward pass (smplpp_vposer_vjp): null until its first call on the decoder
+};
+
+namespace smplpp_hip
+{
+constexpr int LAT = SMPLPP_LATENT_DIM; // 32
+constexpr int HID = 512;               // VPoser.h hiddenDim_
+constexpr int OUT6 = 126;              // 6 * 21
+
+// Value-only decoder (vposer_kernel, exact fp32): what smplpp_vposer_forward runs when jac is NULL.  ws (nullable) [n][VW_FRAME]:
+// per frame the LeakyReLU slopes of layers 0 and 1 and the layer-2 output, as the backward reads them (vposer_vjp.hip).
+constexpr int VW_S0 = 0, VW_S1 = HID, VW_O6 = 2 * HID, VW_FRAME = 2 * HID + 128;
+int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * out, float * ws, hipStream_t st);
+} // namespace smplpp_hip

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DEVICE, HOST, SmplppError, check
-from .smpl import SMPL, _np32, _ptr
+from .smpl import SMPL, _is_torch, _np32, _ptr, _stream, torch
 
 LATENT_DIM = 32
 LATENT_POSE_DIM = LATENT_DIM + 12  # node/node.cpp:42
@@ -130,6 +130,43 @@ class VPoserDecoder:
         check(_lib.load().smplpp_vposer_forward_at(self._h, n, int(frame_base), _ptr(z), _ptr(out), _ptr(jac), HOST, None))
         return (out, jac) if want_jac else out
 
+    def launchBackward(self, latent, grad_out, frame_base=0, want_out=False):
+        """Vector-Jacobian product of the decode (smplpp_vposer_vjp): dL/dz [N,32] for dL/dout = grad_out [N,21,3] at latent
+        [N,32].  The product is taken at the exact-fp32 decode `forward(latent)` returns; want_out=True also returns those angles
+        ((grad_z, out)).  numpy in, numpy out (the call synchronises), or float32 device tensors (enqueued on torch's current
+        stream).  `frame_base`: as in `forward` (the result does not depend on it)."""
+        dev = _is_torch(latent)
+        if _is_torch(grad_out) != dev:
+            raise SmplppError(1, "launchBackward: mix of torch tensors and numpy arrays")
+        if dev:
+            n = latent.shape[0]
+            for a, shape in ((latent, (n, 32)), (grad_out, (n, 21, 3))):
+                if not (a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == shape):
+                    raise SmplppError(1, "launchBackward: expected a float32 device tensor of shape %s" % (shape,))
+            z, g = latent.contiguous(), grad_out.contiguous()
+            gz = torch.empty((n, 32), dtype=torch.float32, device=z.device)
+            out = torch.empty((n, 21, 3), dtype=torch.float32, device=z.device) if want_out else None
+            space, stream = DEVICE, _stream()
+        else:
+            z = _np32(latent).reshape(-1, 32)
+            n = z.shape[0]
+            g = _np32(grad_out)
+            if g.shape != (n, 21, 3):
+                raise SmplppError(1, "launchBackward: expected grad_out of shape %s, got %s" % ((n, 21, 3), g.shape))
+            gz = np.empty((n, 32), np.float32)
+            out = np.empty((n, 21, 3), np.float32) if want_out else None
+            space, stream = HOST, None
+        check(_lib.load().smplpp_vposer_vjp(self._h, n, int(frame_base), _ptr(z), _ptr(g), _ptr(gz), _ptr(out), space, stream))
+        return (gz, out) if want_out else gz
+
+    def forward_differentiable(self, latent):
+        """Joint angles [N,21,3] for a float32 device tensor latent [N,32], differentiable with torch.autograd: the forward is
+        smplpp_vposer_forward without a Jacobian (the exact-fp32 decode), the backward one smplpp_vposer_vjp, both on torch's
+        current stream.  First derivatives with respect to the latent only."""
+        if torch is None:
+            raise SmplppError(1, "forward_differentiable needs torch")
+        return _VPoserFunction.apply(latent, self)
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -137,6 +174,43 @@ class VPoserDecoder:
                 self._h = None
         except Exception:
             pass
+
+
+if torch is not None:
+    class _VPoserFunction(torch.autograd.Function):
+        """smplpp_vposer_forward (jac NULL) forward / smplpp_vposer_vjp backward (VPoserDecoder.forward_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, latent, vposer):
+            z = latent.detach().contiguous()
+            n = z.shape[0]
+            if not (z.is_cuda and z.dtype == torch.float32 and tuple(z.shape) == (n, 32)):
+                raise SmplppError(1, "VPoserDecoder.forward_differentiable: expected a float32 device tensor [N,32]")
+            out = torch.empty((n, 21, 3), dtype=torch.float32, device=z.device)
+            check(_lib.load().smplpp_vposer_forward_at(vposer._h, n, 0, _ptr(z), _ptr(out), None, DEVICE, _stream()))
+            ctx.vposer = vposer
+            ctx.save_for_backward(z)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            z, = ctx.saved_tensors
+            if not ctx.needs_input_grad[0]:
+                return None, None
+            return ctx.vposer.launchBackward(z, grad_out.contiguous()), None
+
+
+def theta_from_latent_layout(vposer: VPoserDecoder, q):
+    """theta [N,25,3] from the reference's 44-d configuration q [N,44] = [root pos 3 | root rot 3 | z 32 | joint 22 aa 3 |
+    joint 23 aa 3] (node/node.cpp:761-772, mocap.py's decode_theta): rows 0-1 and 23-24 are copied, rows 2-22 are the decode of z.
+    Differentiable with torch.autograd (VPoserDecoder.forward_differentiable) for a float32 device tensor q."""
+    if torch is None:
+        raise SmplppError(1, "theta_from_latent_layout needs torch")
+    if q.dim() != 2 or q.shape[1] != LATENT_POSE_DIM:
+        raise SmplppError(1, "theta_from_latent_layout: expected q [N,%d], got %s" % (LATENT_POSE_DIM, tuple(q.shape)))
+    n = q.shape[0]
+    body = vposer.forward_differentiable(q[:, 6:38])
+    return torch.cat([q[:, :6].reshape(n, 2, 3), body, q[:, 38:44].reshape(n, 2, 3)], dim=1)
 
 
 def convertRotMatToAxisAngle(rotMat, device=0):
