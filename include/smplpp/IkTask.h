@@ -152,6 +152,12 @@ public:
     check(smplpp_ik_create(smpl->handle(), n, K, vposer ? vposer->handle() : nullptr, &s_), "node");
   }
   int64_t thetaDim() const { return vposer_ ? (int64_t)(LATENT_DIM + 12) : (int64_t)SMPLPP_THETA_DIM; }
+  // true: the reference's arithmetic inside the loops (smplpp_ik_set_arithmetic EXACT: the model's forward form and the exact-fp32
+  // decoder Jacobian); false: the default.  From the next call on.
+  void setExactArithmetic(bool exact)
+  {
+    check(smplpp_ik_set_arithmetic(s_, exact ? SMPLPP_IK_ARITH_EXACT : SMPLPP_IK_ARITH_DEFAULT), "node");
+  }
   ~IkSolver() { smplpp_ik_destroy(s_); }
   IkSolver(const IkSolver &) = delete;
   IkSolver & operator=(const IkSolver &) = delete;

@@ -90,6 +90,20 @@ public:
     check(smplpp_vposer_vjp(v_, n, 0, latent.ptr(), gradOut.ptr(), gz.ptr(), nullptr, SMPLPP_HOST, nullptr), "VPoser");
     return gz;
   }
+  // d(out)/dz [B,63,32] in exact fp32 (smplpp_vposer_jacobian), what autograd gives node/node.cpp:761-772; `out` (optional)
+  // receives the decoded angles [B,21,3] it was taken at, the bits forward(latent) returns
+  Tensor jacobian(const Tensor & latent, Tensor * out = nullptr) const
+  {
+    if(!v_) throw Exception("VPoser", "VPoserDecoder: parameters not loaded");
+    if(latent.numel() % LATENT_DIM != 0 || latent.dtype != kFloat32) throw Exception("VPoser", "jacobian: latent must be [B,32]");
+    const int64_t n = latent.numel() / LATENT_DIM;
+    Tensor jac({n, jointNum_ * 3, LATENT_DIM});
+    Tensor o;
+    if(out) o = Tensor({n, jointNum_, 3});
+    check(smplpp_vposer_jacobian(v_, n, 0, latent.ptr(), out ? o.ptr() : nullptr, jac.ptr(), SMPLPP_HOST, nullptr), "VPoser");
+    if(out) *out = o;
+    return jac;
+  }
   smplpp_vposer * handle() const { return v_; }
 
 private:

@@ -161,6 +161,15 @@ int smplpp_ik_destroy(smplpp_ik * s);
  * decoder's Jacobian) takes the position from the GLOBAL index, so a frame's trajectory has the same bits on 1, 2, 4 or 8 GPUs.
  * Default 0.  No reference counterpart (single device, node/node.cpp:372). */
 int smplpp_ik_set_frame_base(smplpp_ik * s, int64_t frame_base);
+/* Arithmetic of the solver's loops (smplpp_ik_eval, _iterate, _solve_sequence, _solve_sequence_shared, the body stage included).
+ * EXACT is the reference's (node/node.cpp:761-777 in fp32 libtorch): the internal forward passes run the model's smplpp_fk form
+ * instead of the loops' fp16x2 one, and a latent solver decodes with the exact-fp32 value kernel and pulls its rows back through
+ * smplpp_vposer_jacobian's exact-fp32 Jacobian (its own workspace, the caller's stream; no side-stream schedule).  Status bit 3
+ * is never raised in this mode.  Per solver; takes effect from the next call; EXACT is refused on a model created with
+ * SMPLPP_SKIN=h; an unknown mode is SMPLPP_ERR_INVALID. */
+#define SMPLPP_IK_ARITH_DEFAULT 0 /* today's loops: the model's IK form (h) and the fp16x2 decoder Jacobian */
+#define SMPLPP_IK_ARITH_EXACT 1   /* the reference's arithmetic inside the loops */
+int smplpp_ik_set_arithmetic(smplpp_ik * s, int mode);
 /* IkTask public fields (IkTask.h:54-84), struct-of-arrays over [n,K]; any pointer may be NULL = keep current.
  * Defaults match the header: weights 1, phiLimit 0.04, normalOffset 0, vertexWeights 1/3, targetNormal +Z. */
 int smplpp_ik_set_tasks(smplpp_ik * s, const int64_t * face_idx /*[n,K]*/, const float * vertex_weights /*[n,K,3]*/,
@@ -270,6 +279,12 @@ int smplpp_vposer_forward_at(smplpp_vposer * v, int64_t n, int64_t frame_base, c
  * handle from different streams need the caller's own ordering. */
 int smplpp_vposer_vjp(smplpp_vposer * v, int64_t n, int64_t frame_base, const float * z, const float * grad_out,
                       float * grad_z, float * out, int space, void * stream);
+/* d(out)/dz [n,63,32] in exact fp32 (fp32 products and sums, as libtorch autograd runs the reference's node/node.cpp:761-772),
+ * at the decode smplpp_vposer_forward returns with jac NULL.  out (nullable) [n,21,3]: those angles, bit-identical to that call.
+ * Deterministic; a frame's bits do not depend on n or frame_base.  The decoder owns the workspace (64 KB per frame, grown to n,
+ * freed by smplpp_vposer_destroy): concurrent calls on one handle from different streams need the caller's own ordering. */
+int smplpp_vposer_jacobian(smplpp_vposer * v, int64_t n, int64_t frame_base, const float * z, float * out, float * jac, int space,
+                           void * stream);
 /* convertRotMatToAxisAngle (src/VPoser.cpp:25-120): rot [n,3,3] -> aa [n,3]. */
 int smplpp_rotmat_to_axis_angle(int device, int64_t n, const float * rot, float * aa, int space, void * stream);
 

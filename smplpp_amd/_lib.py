@@ -74,6 +74,7 @@ def load():
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],
         "smplpp_ik_destroy": [vp],
         "smplpp_ik_set_frame_base": [vp, C.c_int64],
+        "smplpp_ik_set_arithmetic": [vp, C.c_int],
         "smplpp_ik_set_tasks": [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int],
         "smplpp_ik_set_config": [vp, vp, vp, C.c_int],
         "smplpp_ik_get_config": [vp, vp, vp, C.c_int],
@@ -93,6 +94,7 @@ def load():
         "smplpp_vposer_forward": [vp, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_vposer_forward_at": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_vposer_vjp": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_vposer_jacobian": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_rotmat_to_axis_angle": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
     }
     for name, argtypes in sig.items():

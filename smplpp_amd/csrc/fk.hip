@@ -286,9 +286,10 @@ PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const flo
 // first form.  The IK / VPoser loops' internal launches (range_slot RANGE_INTERNAL: intermediate iterates whose mesh feeds the
 // residual's few vertices and the re-projection's face scan) run m->form_ik: h unless SMPLPP_SKIN chose a form for everything.
 // p (32-bit output offsets) falls back to v for outputs of 2 GiB and more.
-static char launch_form(const smplpp_model * m, int64_t n, int range_slot)
+// form_override (0: none): the form the caller chose for this launch (an IK solver in exact-arithmetic mode runs m->form).
+static char launch_form(const smplpp_model * m, int64_t n, int range_slot, char form_override)
 {
-  char form = range_slot == RANGE_INTERNAL ? m->form_ik : m->form;
+  char form = form_override ? form_override : range_slot == RANGE_INTERNAL ? m->form_ik : m->form;
   if(form == 'p' && n * m->V * 12 >= 0x7fffff00LL) form = 'v';
   return form;
 }
@@ -385,9 +386,9 @@ static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * 
 // range_word: where a launch of the fp16x2 form reports an operand outside its range — the model's word of `range_slot`, or the word
 // of the IK solver whose loop the launch belongs to (each solver has its own: one solver's overflow is not another's status bit)
 int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * verts, float * joints,
-              float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word)
+              float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word, char form_override = 0)
 {
-  const char form = launch_form(m, n, range_slot);
+  const char form = launch_form(m, n, range_slot, form_override);
   int rc = fk_pose_device(m, form, n, beta, theta, joints, xforms44, poserot, st, range_word ? range_word : m->range_flag + range_slot, verts || rest);
   if(rc) return rc;
   return fk_skin_device(m, form, n, theta, verts, rest, st);

@@ -36,7 +36,7 @@
 namespace smplpp_hip
 {
 int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * verts, float * joints, float * xforms44,
-              float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word);
+              float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word, char form_override = 0);
 PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * joints, float * poserot, float * xforms44,
                       bool with_ops);
 

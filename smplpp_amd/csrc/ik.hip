@@ -18,6 +18,7 @@
 #include "ik_eval.h"
 #include "ik_solve.h"
 #include "ik_proj.h"
+#include "vposer_state.h"
 
 #include <algorithm>
 #include <chrono>
@@ -69,6 +70,12 @@ struct smplpp_ik
   // (tests/test_mocap_gpu.py).  SMPLPP_IK_LATENT_SPLIT=0/1 (read at creation) overrides the n <= 128 rule.
   double last_enqueue_us = 0.0; // host time of the last smplpp_ik_solve_sequence's / smplpp_ik_iterate's enqueue loop
   bool latent_split = false;
+  bool latent_split_default = false; // (what creation chose: the default arithmetic mode's schedule)
+  // smplpp_ik_set_arithmetic(SMPLPP_IK_ARITH_EXACT): the loops' forward passes run the model's smplpp_fk form (m->form), and the
+  // decoder decodes with the exact-fp32 value kernel and makes vjac with the exact-fp32 Jacobian kernels (vposer_jac_exact.hip), on
+  // the main stream, in this solver's own workspace jxw; latent_split is off
+  bool exact = false;
+  VPoserJxWork * jxw = nullptr;
   bool jac_ahead = false; // the decoder Jacobian of the CURRENT configuration is (being) made on the side stream; the join flag follows it
   // development switches, read ONCE at creation (never in the per-call path): SMPLPP_DEBUG_SYNC, SMPLPP_IK_DBG_STOP,
   // SMPLPP_IK_OVERLAP=0 (re-projection behind the solve on one stream), SMPLPP_SCAN_BLOCKS
@@ -119,6 +126,7 @@ extern "C" int smplpp_ik_destroy(smplpp_ik * s)
   if(s->ev_join) (void)hipEventDestroy(s->ev_join);
   if(s->side) (void)hipStreamDestroy(s->side);
   for(void * p : s->owned) (void)hipFree(p);
+  vposer_jx_release(s->jxw);
   delete s;
   return SMPLPP_OK;
 }
@@ -127,6 +135,22 @@ extern "C" int smplpp_ik_set_frame_base(smplpp_ik * s, int64_t frame_base)
 {
   if(!s || frame_base < 0) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_frame_base: bad argument");
   s->frame_base = frame_base;
+  s->jac_ahead = false;
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_ik_set_arithmetic(smplpp_ik * s, int mode)
+{
+  if(!s) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_arithmetic: null solver");
+  if(mode != SMPLPP_IK_ARITH_DEFAULT && mode != SMPLPP_IK_ARITH_EXACT) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_arithmetic: unknown mode");
+  if(mode == SMPLPP_IK_ARITH_EXACT && s->m->form == 'h')
+    return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_arithmetic: the model's forward form is the fp16x2 one (SMPLPP_SKIN=h)");
+  HIP_TRY(hipSetDevice(s->m->device));
+  // whatever the side stream still has in flight for the old mode (a Jacobian made ahead writes vjac) ends first
+  if(s->side) HIP_TRY(hipStreamSynchronize(s->side));
+  HIP_TRY(hipDeviceSynchronize());
+  s->exact = mode == SMPLPP_IK_ARITH_EXACT;
+  s->latent_split = s->exact ? false : s->latent_split_default;
   s->jac_ahead = false;
   return SMPLPP_OK;
 }
@@ -302,6 +326,7 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
       (void)hipGetLastError();
     }
     if(!s->use_flags) s->latent_split = false; // (the hand-overs of that schedule are flags)
+    s->latent_split_default = s->latent_split;
   }
   S_TRY(hipDeviceSynchronize());
 #undef S_TRY
@@ -444,7 +469,13 @@ static int ik_forward_eval(smplpp_ik * s, int optimize_beta, int phi_live, int64
   const bool jac_elsewhere = s->vp && s->jac_ahead;
   {
     TraceRange tr_fwd("forward SMPL"); // node.cpp:752-781 (the VPoser splice is inside that span there too)
-    if(s->vp) // node.cpp:761-772
+    if(s->vp && s->exact) // node.cpp:761-772 in the reference's arithmetic: exact-fp32 value and Jacobian
+    {
+      int rc = vposer_jacobian_device(s->vp, &s->jxw, n, s->theta + 6, TD44, s->theta25 + 6, 75, s->vjac, st);
+      if(rc) return rc;
+      th25 = s->theta25;
+    }
+    else if(s->vp) // node.cpp:761-772
     {
       // the decoder writes its 63 angles straight into theta25[:, 6:69]; the pass-through entries (root translation / rotation,
       // joints 22-23) are kept current by whoever changes the configuration: smplpp_ik_set_config and the solve kernel's update
@@ -455,7 +486,8 @@ static int ik_forward_eval(smplpp_ik * s, int optimize_beta, int phi_live, int64
     }
     s->vcur ^= 1;
     s->verts = s->vbuf[s->vcur];
-    int rc = fk_device(m, n, s->beta, th25, s->verts, s->joints, nullptr, s->rest, s->poserot, st, RANGE_INTERNAL, s->range_word); // node.cpp:777
+    int rc = fk_device(m, n, s->beta, th25, s->verts, s->joints, nullptr, s->rest, s->poserot, st, RANGE_INTERNAL, s->range_word,
+                       s->exact ? m->form : 0); // node.cpp:777
     if(rc) return rc;
   }
   TraceRange tr_eval("calculate IK matrices"); // node.cpp:796-881

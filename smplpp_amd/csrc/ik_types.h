@@ -13,7 +13,8 @@ struct smplpp_vposer;
 namespace smplpp_hip
 {
 int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * verts, float * joints,
-              float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word = nullptr);
+              float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word = nullptr,
+              char form_override = 0);
 int vposer_forward_device(smplpp_vposer * v, int64_t n, const float * z, int64_t z_stride, float * out, int64_t out_stride,
                           float * jac, hipStream_t st, int64_t frame_base, bool value_like_jac = false, unsigned * sig_flag = nullptr,
                           unsigned * sig_counter = nullptr, unsigned sig_tick = 0u);

@@ -754,12 +754,14 @@ int vposer_forward_device(smplpp_vposer * v, int64_t n, const float * z, int64_t
 
 // the value path above once more (vposer_kernel<true>: the same arithmetic, so `out` has the bits smplpp_vposer_forward gives when
 // jac is NULL), also storing the slopes and the layer-2 output of every frame into ws [n][VW_FRAME] for the backward
-int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * out, float * ws, hipStream_t st)
+int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * out, float * ws, hipStream_t st, int64_t z_stride,
+                        int64_t out_stride)
 {
   const size_t shmem = sizeof(float) * (size_t)(2 * HID * VS + LAT + HID);
   static PerDeviceOnce once;
   HIP_TRY(lds_opt_in(once, v->device, reinterpret_cast<const void *>(&vposer_kernel<true>), (int)shmem));
-  vposer_kernel<true><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, LAT, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out, 63, ws);
+  vposer_kernel<true><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out,
+                                                                  out_stride, ws);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -778,6 +780,8 @@ extern "C" int smplpp_vposer_destroy(smplpp_vposer * v)
   if(v->w0h) (void)hipFree(v->w0h);
   if(v->c10) (void)hipFree(v->c10);
   vposer_vjp_release(v->vjp);
+  if(v->w0r) (void)hipFree(v->w0r);
+  vposer_jx_release(v->jx);
   delete v;
   return SMPLPP_OK;
 }

@@ -6,6 +6,8 @@ namespace smplpp_hip
 {
 struct VPoserVjp; // smplpp_vposer_vjp's weight copies and workspace (vposer_vjp.hip), created by its first call
 void vposer_vjp_release(VPoserVjp * s);
+struct VPoserJxWork; // a workspace of the exact-fp32 Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
+void vposer_jx_release(VPoserJxWork * w);
 } // namespace smplpp_hip
 
 struct smplpp_vposer
@@ -20,6 +22,10 @@ struct smplpp_vposer
   uint8_t * w0h = nullptr;
   float * c10 = nullptr;
   smplpp_hip::VPoserVjp * vjp = nullptr; // backward pass (smplpp_vposer_vjp): null until its first call on the decoder
+  // exact-fp32 Jacobian (smplpp_vposer_jacobian): W0 [512][32] in torch's [out][in] layout and the decoder's own workspace, null
+  // until its first call on the decoder
+  float * w0r = nullptr;
+  smplpp_hip::VPoserJxWork * jx = nullptr;
 };
 
 namespace smplpp_hip
@@ -31,5 +37,12 @@ constexpr int OUT6 = 126;              // 6 * 21
 // Value-only decoder (vposer_kernel, exact fp32): what smplpp_vposer_forward runs when jac is NULL.  ws (nullable) [n][VW_FRAME]:
 // per frame the LeakyReLU slopes of layers 0 and 1 and the layer-2 output, as the backward reads them (vposer_vjp.hip).
 constexpr int VW_S0 = 0, VW_S1 = HID, VW_O6 = 2 * HID, VW_FRAME = 2 * HID + 128;
-int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * out, float * ws, hipStream_t st);
+// z_stride / out_stride: floats between frames of z and out (a splice into a wider layout, e.g. the IK solver's theta25)
+int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * out, float * ws, hipStream_t st, int64_t z_stride = LAT,
+                        int64_t out_stride = 63);
+
+// Exact-fp32 d(out)/dz [n][63][32] (vposer_jac_exact.hip) at the decode vposer_value_device gives, which it also writes to out
+// (nullable).  work: the caller's workspace, created on first use (*work null) and grown to n.
+int vposer_jacobian_device(smplpp_vposer * v, VPoserJxWork ** work, int64_t n, const float * z, int64_t z_stride, float * out,
+                           int64_t out_stride, float * jac, hipStream_t st);
 } // namespace smplpp_hip

@@ -159,6 +159,27 @@ class VPoserDecoder:
         check(_lib.load().smplpp_vposer_vjp(self._h, n, int(frame_base), _ptr(z), _ptr(g), _ptr(gz), _ptr(out), space, stream))
         return (gz, out) if want_out else gz
 
+    def jacobian(self, latent, frame_base=0, want_out=False):
+        """d(out)/dz [N,63,32] in exact fp32 (smplpp_vposer_jacobian) at latent [N,32], taken at the exact-fp32 decode `forward(latent)`
+        returns; want_out=True also returns those angles ((jac, out)).  numpy in, numpy out (the call synchronises), or a float32
+        device tensor (enqueued on torch's current stream).  `frame_base`: as in `forward` (the result does not depend on it)."""
+        if _is_torch(latent):
+            n = latent.shape[0]
+            if not (latent.is_cuda and latent.dtype == torch.float32 and tuple(latent.shape) == (n, 32)):
+                raise SmplppError(1, "jacobian: expected a float32 device tensor of shape %s" % ((n, 32),))
+            z = latent.contiguous()
+            jac = torch.empty((n, 63, 32), dtype=torch.float32, device=z.device)
+            out = torch.empty((n, 21, 3), dtype=torch.float32, device=z.device) if want_out else None
+            space, stream = DEVICE, _stream()
+        else:
+            z = _np32(latent).reshape(-1, 32)
+            n = z.shape[0]
+            jac = np.empty((n, 63, 32), np.float32)
+            out = np.empty((n, 21, 3), np.float32) if want_out else None
+            space, stream = HOST, None
+        check(_lib.load().smplpp_vposer_jacobian(self._h, n, int(frame_base), _ptr(z), _ptr(out), _ptr(jac), space, stream))
+        return (jac, out) if want_out else jac
+
     def forward_differentiable(self, latent):
         """Joint angles [N,21,3] for a float32 device tensor latent [N,32], differentiable with torch.autograd: the forward is
         smplpp_vposer_forward without a Jacobian (the exact-fp32 decode), the backward one smplpp_vposer_vjp, both on torch's
@@ -224,8 +245,10 @@ def convertRotMatToAxisAngle(rotMat, device=0):
 class IkSolver:
     """The loop body of node/node.cpp:645-1002 for `n` independent frames with `K` tasks each."""
 
-    def __init__(self, smpl: SMPL, n: int, K: int, vposer: Optional[VPoserDecoder] = None, frame_base: int = 0):
-        """`frame_base`: global index of this solver's frame 0 when it holds one shard of a larger job (dist.shard_range)."""
+    def __init__(self, smpl: SMPL, n: int, K: int, vposer: Optional[VPoserDecoder] = None, frame_base: int = 0, exact: bool = False):
+        """`frame_base`: global index of this solver's frame 0 when it holds one shard of a larger job (dist.shard_range).
+        `exact`: the loops run the reference's arithmetic (smplpp_ik_set_arithmetic EXACT): the model's smplpp_fk form and the
+        exact-fp32 decoder Jacobian; see setExactArithmetic."""
         self.smpl, self.n, self.K, self.vposer = smpl, int(n), int(K), vposer
         self.theta_dim = LATENT_POSE_DIM if vposer is not None else 75
         h = C.c_void_p()
@@ -233,7 +256,14 @@ class IkSolver:
         self._h = h
         if frame_base:
             check(_lib.load().smplpp_ik_set_frame_base(self._h, int(frame_base)))
+        if exact:
+            self.setExactArithmetic(True)
         self.task_names: Optional[List[str]] = None
+
+    def setExactArithmetic(self, exact: bool = True):
+        """smplpp_ik_set_arithmetic: True, the reference's arithmetic inside the loops (refused on a model created with
+        SMPLPP_SKIN=h); False, the default (fp16x2 forward form and decoder Jacobian).  Takes effect from the next call."""
+        check(_lib.load().smplpp_ik_set_arithmetic(self._h, 1 if exact else 0))
 
     def __del__(self):
         try:
