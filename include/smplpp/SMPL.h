@@ -306,6 +306,23 @@ public:
     check(smplpp_mesh_vertex_normals(m_.get(), verts_.size(0), verts_.ptr(), t.ptr(), SMPLPP_HOST, nullptr), "SMPL");
     return t;
   }
+  // What backward() through calcNormal / calcVertexNormal / calcMeshVertexNormals on the last launch's vertices gave the reference
+  // (the normal terms of node/node.cpp:803-869): dL/dverts [N,V,3] for dL/dnormals = gradNormal ([N,count,3] for the id lists,
+  // [N,V,3] for the whole mesh).  `accumulate` non-null: the product is added into it (and it is returned), so normal and position
+  // terms share one buffer that goes straight to launchBackward.  smplpp_face_normals_vjp / smplpp_vertex_normals_vjp /
+  // smplpp_mesh_vertex_normals_vjp.
+  Tensor calcNormalBackward(const std::vector<int64_t> & faceIds, const Tensor & gradNormal, Tensor * accumulate = nullptr) const
+  {
+    return normalsBackward(0, faceIds, gradNormal, accumulate);
+  }
+  Tensor calcVertexNormalBackward(const std::vector<int64_t> & vertexIds, const Tensor & gradNormal, Tensor * accumulate = nullptr) const
+  {
+    return normalsBackward(1, vertexIds, gradNormal, accumulate);
+  }
+  Tensor calcMeshVertexNormalsBackward(const Tensor & gradNormal, Tensor * accumulate = nullptr) const
+  {
+    return normalsBackward(2, {}, gradNormal, accumulate);
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const
@@ -347,6 +364,25 @@ private:
   {
     if(t.data.empty()) throw Exception("LinearBlendSknning", "Failed to get vertices of new pose!"); // LinearBlendSkinning.cpp:413
     return t;
+  }
+  Tensor normalsBackward(int kind, const std::vector<int64_t> & ids, const Tensor & gradNormal, Tensor * accumulate) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0), rows = kind == 2 ? V_ : (int64_t)ids.size();
+    if(gradNormal.dtype != kFloat32 || gradNormal.numel() != n * rows * 3 || (kind != 2 && ids.empty()) ||
+       (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3)))
+      throw Exception("SMPL", "Cannot back-propagate through the normals!");
+    Tensor fresh;
+    if(!accumulate) fresh = Tensor(verts_.shape);
+    Tensor & g = accumulate ? *accumulate : fresh;
+    const int acc = accumulate ? 1 : 0;
+    if(kind == 2)
+      check(smplpp_mesh_vertex_normals_vjp(m_.get(), n, verts_.ptr(), gradNormal.ptr(), g.ptr(), acc, SMPLPP_HOST, nullptr), "SMPL");
+    else
+      check((kind == 1 ? smplpp_vertex_normals_vjp : smplpp_face_normals_vjp)(m_.get(), n, verts_.ptr(), rows, ids.data(), gradNormal.ptr(),
+                                                                             g.ptr(), acc, SMPLPP_HOST, nullptr),
+            "SMPL");
+    return g;
   }
   std::shared_ptr<smplpp_model> m_;
   std::shared_ptr<const std::vector<std::unordered_map<int64_t, float>>> adjacent_;

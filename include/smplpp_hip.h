@@ -136,6 +136,30 @@ int smplpp_closest_points(smplpp_model * m, int64_t n, const float * verts, int6
                           int64_t * face, float * closest, float * sqdist, int space, void * stream);
 /* SMPL::calcVertexNormal (src/SMPL.cpp:527-535) for EVERY vertex of every frame: normals [n,V,3]. */
 int smplpp_mesh_vertex_normals(smplpp_model * m, int64_t n, const float * verts, float * normals, int space, void * stream);
+/* Vector-Jacobian products of the three normal queries above (the backward pass libtorch autograd runs through
+ * SMPL::calcNormal / calcVertexNormal in the reference's IK residual, node/node.cpp:803-869): grad_verts [n,V,3] for
+ * dL/dnormals = grad_normals ([n,count,3] for the list forms, [n,V,3] for the whole mesh), at `verts`.
+ *  - what is differentiated: exactly the forward the matching call computes (cross3 / normalize3, weights 1/deg, adjacent
+ *    faces in ascending face id, torch's normalize x / max(|x|, 1e-12)).  A face enters a vertex's sum once, even when the
+ *    vertex is repeated in it.
+ *  - where a face's cross product or a vertex's weighted sum is shorter than 1e-12, the product is torch's gradient of that
+ *    branch, g / 1e-12 (finite, not NaN).  A vertex without faces gets zero.
+ *  - accumulate = 0: grad_verts is overwritten; vertices the query does not touch get 0.  accumulate = 1: the product is
+ *    added into grad_verts (so normal and position terms can share one buffer for smplpp_fk_vjp).
+ *  - an id list may repeat ids: their cotangents sum.
+ *  - deterministic: no floating-point atomics; each element is one fixed-order sum (a vertex's adjacent faces in ascending
+ *    face id for the whole mesh, list order for the list forms), so a frame's bits do not depend on n or on its position
+ *    in the batch.  No bound on a vertex's valence, and no status bit.
+ *  - the list forms touch only the vertices of the faces involved (with accumulate = 0 they also zero the rest).
+ *  - SMPLPP_ERR_INVALID: bad arguments, host-space ids out of range (device-space ids are not read on the host, like the
+ *    forward; an id out of range there contributes nothing), a model without faces.  SMPLPP_ERR_HIP without a GPU. */
+int smplpp_face_normals_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t count, const int64_t * face_ids,
+                            const float * grad_normals /*[n,count,3]*/, float * grad_verts /*[n,V,3]*/, int accumulate, int space,
+                            void * stream);
+int smplpp_vertex_normals_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t count, const int64_t * vertex_ids,
+                              const float * grad_normals /*[n,count,3]*/, float * grad_verts, int accumulate, int space, void * stream);
+int smplpp_mesh_vertex_normals_vjp(smplpp_model * m, int64_t n, const float * verts, const float * grad_normals /*[n,V,3]*/,
+                                   float * grad_verts, int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -208,6 +208,8 @@ struct Workspace
 };
 struct VjpState;                   // smplpp_fk_vjp's operand image and workspace (fk_vjp.hip), created by its first call
 void vjp_release(VjpState * s);
+struct NormalsVjpState;            // the normals' backward pass (mesh_vjp.hip), created by its first call
+void nvjp_release(NormalsVjpState * s);
 } // namespace smplpp_hip
 
 struct smplpp_model
@@ -255,4 +257,5 @@ struct smplpp_model
   std::vector<hipEvent_t> prof_events; // begin/end pairs around the fused kernel
   smplpp_hip::Workspace ws;
   smplpp_hip::VjpState * vjp = nullptr; // backward pass (smplpp_fk_vjp): null until its first call on the model
+  smplpp_hip::NormalsVjpState * nvjp = nullptr; // backward pass of the normal queries (mesh_vjp.hip): null until its first call
 };

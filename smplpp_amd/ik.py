@@ -372,6 +372,42 @@ class IkSolver:
         return v
 
 
+def task_surface_differentiable(smpl: SMPL, verts, face_idx, vertex_weights, normal_offset):
+    """IkTask::calcActualPos / calcActualNormal (src/IkTask.cpp:58-86) batched over frames and tasks, differentiable with
+    torch.autograd in `verts` [n,V,3] and in `vertex_weights` [n,K,3] (so a torch calcTriangleVertexWeights carries phi):
+    face_idx [n,K] (0-based), normal_offset [n,K].  Returns (actual_pos [n,K,3], actual_normal [n,K,3]):
+    actual_normal = normalize(sum_i w_i calcVertexNormal(face vertex i)), actual_pos = sum_i w_i v_i, plus
+    normal_offset * actual_normal where normal_offset > 0.  The vertex normals are the engine's (vertex_normals_differentiable over
+    the distinct vertices of the tasks' faces, backward through smplpp_vertex_normals_vjp); the rest is a few gathers."""
+    if torch is None:
+        raise SmplppError(1, "task_surface_differentiable needs torch")
+    dev = verts.device
+    n = verts.shape[0]
+    faces = getattr(smpl, "_faces0_dev", None)
+    if faces is None or faces.device != dev:
+        faces = torch.from_numpy(smpl.getFaceIndex().astype(np.int64) - 1).to(dev)
+        smpl._faces0_dev = faces
+    face_idx = torch.as_tensor(face_idx, dtype=torch.int64, device=dev).reshape(n, -1)
+    K = face_idx.shape[1]
+    fv = faces[face_idx]  # [n,K,3] vertex ids
+    ids, inv = torch.unique(fv.reshape(-1), sorted=True, return_inverse=True)
+    vn = smpl.vertex_normals_differentiable(verts, ids)  # [n,U,3]
+    fvn = vn.gather(1, inv.reshape(n, K * 3)[..., None].expand(n, K * 3, 3)).reshape(n, K, 3, 3)
+    pts = verts.gather(1, fv.reshape(n, K * 3)[..., None].expand(n, K * 3, 3)).reshape(n, K, 3, 3)
+    w = torch.as_tensor(vertex_weights, device=dev).to(verts.dtype).reshape(n, K, 3)
+    # the reference's order: zeros, then += w_i * n_i for i = 0, 1, 2
+    acc = w[..., 0:1] * fvn[:, :, 0]
+    acc = acc + w[..., 1:2] * fvn[:, :, 1]
+    acc = acc + w[..., 2:3] * fvn[:, :, 2]
+    normal = torch.nn.functional.normalize(acc, dim=-1, eps=1e-12)
+    # torch::matmul(faceVertices^T, vertexWeights)
+    pos = (pts * w[..., None]).sum(dim=2)
+    off = torch.as_tensor(normal_offset, device=dev).to(verts.dtype).reshape(n, K)
+    off = torch.where(off > 0, off, torch.zeros_like(off))
+    pos = pos + off[..., None] * normal
+    return pos, normal
+
+
 def reference_task_faces(K=6):
     """The reference's four end-effector tasks (node/node.cpp:538-550: LeftFoot f5925, LeftHand f2581, RightFoot f12812,
     RightHand f9469) plus HeadTop f7324 and Chest f6842 from its mocap table (:455,:459), in std::map order."""

@@ -302,6 +302,91 @@ class SMPL:
             check(L.smplpp_mesh_vertex_normals(self.handle, verts.shape[0], _ptr(verts), _ptr(out), HOST, None))
         return out
 
+    # ---- backward of the normal queries (smplpp_face_normals_vjp / smplpp_vertex_normals_vjp / smplpp_mesh_vertex_normals_vjp)
+    def _normals_vjp(self, kind, verts, ids, grad_normals, out):
+        """kind 0 = face list, 1 = vertex list, 2 = whole mesh.  Returns grad_verts [N,V,3]; `out` given = accumulate into it."""
+        V = self.vertex_num
+        L = _lib.load()
+        name = ("calcNormalBackward", "calcVertexNormalBackward", "calcMeshVertexNormalsBackward")[kind]
+        dev = _is_torch(verts)
+        if any(a is not None and _is_torch(a) != dev for a in (grad_normals, out)):
+            raise SmplppError(1, "%s: mix of torch tensors and numpy arrays" % name)
+        n = verts.shape[0]
+        ids_np = None
+        if kind == 2:
+            count = V
+        elif _is_torch(ids):
+            count = ids.numel()
+            if not (dev and ids.is_cuda):
+                ids_np = np.ascontiguousarray(ids.detach().cpu().numpy(), np.int64).reshape(-1)
+        else:
+            ids_np = np.ascontiguousarray(np.atleast_1d(ids), np.int64).reshape(-1)
+            count = len(ids_np)
+        if dev:
+            def prep(a, shape):
+                if not (a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == shape):
+                    raise SmplppError(1, "%s: expected a float32 device tensor of shape %s" % (name, shape))
+                return a.detach().contiguous()
+            verts, gn = prep(verts, (n, V, 3)), prep(grad_normals, (n, count, 3))
+            if out is not None and not out.is_contiguous():
+                raise SmplppError(1, "%s: out must be contiguous" % name)
+            acc = out is not None
+            out = prep(out, (n, V, 3)) if acc else torch.empty((n, V, 3), dtype=torch.float32, device=verts.device)
+            if kind != 2:
+                if ids_np is None:
+                    idt = ids.detach().to(dtype=torch.int64).contiguous().reshape(-1)
+                else:
+                    idt = torch.from_numpy(ids_np).to(verts.device)
+            space, st = DEVICE, _stream()
+        else:
+            def prep(a, shape):
+                a = np.asarray(a)
+                if a.shape != shape:
+                    raise SmplppError(1, "%s: expected shape %s, got %s" % (name, shape, a.shape))
+                return _np32(a)
+            verts, gn = prep(verts, (n, V, 3)), prep(grad_normals, (n, count, 3))
+            acc = out is not None
+            if acc and not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == (n, V, 3) and out.flags.c_contiguous):
+                raise SmplppError(1, "%s: out must be a C-contiguous float32 array of shape %s" % (name, (n, V, 3)))
+            if not acc:
+                out = np.empty((n, V, 3), np.float32)
+            idt = ids_np if kind != 2 else None
+            space, st = HOST, None
+        if kind == 2:
+            check(L.smplpp_mesh_vertex_normals_vjp(self.handle, n, _ptr(verts), _ptr(gn), _ptr(out), int(acc), space, st))
+        else:
+            fn = L.smplpp_vertex_normals_vjp if kind == 1 else L.smplpp_face_normals_vjp
+            check(fn(self.handle, n, _ptr(verts), count, _ptr(idt), _ptr(gn), _ptr(out), int(acc), space, st))
+        return out
+
+    def calcNormalBackward(self, verts, face_ids, grad_normals, out=None):
+        """Vector-Jacobian product of calcNormalBatch at `verts` [N,V,3]: dL/dverts for dL/dnormals = grad_normals [N,count,3]
+        (smplpp_face_normals_vjp).  numpy (the call synchronises) or float32 device tensors (torch's current stream).  `out`
+        [N,V,3] given: the product is added into it (and returned)."""
+        return self._normals_vjp(0, verts, face_ids, grad_normals, out)
+
+    def calcVertexNormalBackward(self, verts, vertex_ids, grad_normals, out=None):
+        """Vector-Jacobian product of calcVertexNormalBatch at `verts` (smplpp_vertex_normals_vjp); as calcNormalBackward."""
+        return self._normals_vjp(1, verts, vertex_ids, grad_normals, out)
+
+    def calcMeshVertexNormalsBackward(self, verts, grad_normals, out=None):
+        """Vector-Jacobian product of calcMeshVertexNormals at `verts` for grad_normals [N,V,3] (smplpp_mesh_vertex_normals_vjp)."""
+        return self._normals_vjp(2, verts, None, grad_normals, out)
+
+    def face_normals_differentiable(self, verts, face_ids):
+        """Unit face normals [N,count,3] of device vertices verts [N,V,3] (the bits of calcNormalBatch), differentiable in verts with
+        torch.autograd: smplpp_face_normals forward, smplpp_face_normals_vjp backward, on torch's current stream."""
+        if torch is None:
+            raise SmplppError(1, "face_normals_differentiable needs torch")
+        return _NormalsFunction.apply(verts, self, 0, face_ids)
+
+    def vertex_normals_differentiable(self, verts, vertex_ids=None):
+        """Vertex normals [N,count,3] (vertex_ids given; the bits of calcVertexNormalBatch) or [N,V,3] (None: the whole mesh, the
+        bits of calcMeshVertexNormals) of device vertices verts [N,V,3], differentiable in verts with torch.autograd."""
+        if torch is None:
+            raise SmplppError(1, "vertex_normals_differentiable needs torch")
+        return _NormalsFunction.apply(verts, self, 2 if vertex_ids is None else 1, vertex_ids)
+
     def calcSweepGrid(self, frame=0):
         """The sweep grid of node/node.cpp:1023-1073 for one frame of the last launch: dict(grid_min [3], grid_num [3],
         winding [cells], inside [cells] bool, grid_idx [cells,3] int32 in the reference's cell order, positions = 0.025 *
@@ -396,6 +481,41 @@ if torch is not None:
             gj = grad_joints.contiguous() if grad_joints is not None else None
             g = ctx.smpl.launchBackward(beta, theta, grad_verts=gv, grad_joints=gj, rest=rest)
             return (g["beta"] if ctx.needs_input_grad[0] else None, g["theta"] if ctx.needs_input_grad[1] else None, None)
+
+    class _NormalsFunction(torch.autograd.Function):
+        """The normal queries forward / their vector-Jacobian products backward (SMPL.face_normals_differentiable,
+        SMPL.vertex_normals_differentiable).  kind 0 = face list, 1 = vertex list, 2 = whole mesh."""
+
+        @staticmethod
+        def forward(ctx, verts, smpl, kind, ids):
+            verts = verts.detach().contiguous()
+            n, V = verts.shape[0], smpl.vertex_num
+            if not (verts.is_cuda and verts.dtype == torch.float32 and tuple(verts.shape) == (n, V, 3)):
+                raise SmplppError(1, "normals: expected float32 device vertices of shape %s" % ((n, V, 3),))
+            L = _lib.load()
+            if kind == 2:
+                out = torch.empty_like(verts)
+                check(L.smplpp_mesh_vertex_normals(smpl.handle, n, _ptr(verts), _ptr(out), DEVICE, _stream()))
+                idt = None
+            else:
+                if _is_torch(ids):
+                    idt = ids.detach().to(device=verts.device, dtype=torch.int64).contiguous().reshape(-1)
+                else:
+                    idt = torch.from_numpy(np.ascontiguousarray(np.atleast_1d(ids), np.int64).reshape(-1)).to(verts.device)
+                out = torch.empty((n, idt.numel(), 3), dtype=torch.float32, device=verts.device)
+                fn = L.smplpp_vertex_normals if kind == 1 else L.smplpp_face_normals
+                check(fn(smpl.handle, n, _ptr(verts), idt.numel(), _ptr(idt), _ptr(out), DEVICE, _stream()))
+            ctx.smpl, ctx.kind, ctx.idt = smpl, kind, idt
+            ctx.save_for_backward(verts)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad):
+            (verts,) = ctx.saved_tensors
+            if not ctx.needs_input_grad[0]:
+                return None, None, None, None
+            gv = ctx.smpl._normals_vjp(ctx.kind, verts, ctx.idt, grad.contiguous(), None)
+            return gv, None, None, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
