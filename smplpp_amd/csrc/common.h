@@ -201,7 +201,6 @@ struct Workspace
   DevBuf G2h;     // relative transforms as fp16x2 pieces, the A operand of the blend MFMAs (skin_h.hip)
   DevBuf Gp;      // [n][24][12] relative transforms, 3x4 row-major
   DevBuf joints;  // [n][24][3]
-  DevBuf poserot; // [n][24][9]
   DevBuf beta, theta, verts, rest, xf44; // staging for host-pointer calls
   int64_t ldA = 0;
   DevBuf dummy;   // write-only sink for masked-off lanes of branch-free epilogues (skin_p.hip)

@@ -31,6 +31,7 @@ extern "C" int smplpp_debug_pose_stamps(unsigned long long * out)
 }
 #endif
 #include "pose_body.h"
+#include "staging.h"
 #include "trace.h"
 
 namespace smplpp_hip
@@ -452,34 +453,31 @@ extern "C" int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const 
 {
   if(!m) return fail(SMPLPP_ERR_INVALID, "Cannot launch a SMPL model!"); // src/SMPL.cpp:676
   if(n <= 0 || !beta || !theta) return fail(SMPLPP_ERR_INVALID, "Cannot launch a SMPL model!");
-  if(space != SMPLPP_HOST && space != SMPLPP_DEVICE) return fail(SMPLPP_ERR_INVALID, "smplpp_fk: bad memory space");
+  if(int rc = check_space(space, "smplpp_fk")) return rc;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceRange tr_fwd("forward SMPL"); // the reference's span around SMPL::launch (node/node.cpp:752-781)
   if(space == SMPLPP_DEVICE) return fk_device(m, n, beta, theta, verts, joints, xforms, rest, nullptr, st, RANGE_DEVICE, nullptr);
 
   Workspace & ws = m->ws;
-  const size_t nb = sizeof(float) * (size_t)n * NB, nt = sizeof(float) * (size_t)n * (NJ + 1) * 3;
-  const size_t nv = sizeof(float) * (size_t)n * m->V * 3;
-  HIP_TRY(ws.beta.reserve(nb));
-  HIP_TRY(ws.theta.reserve(nt));
-  if(verts) HIP_TRY(ws.verts.reserve(nv));
-  if(rest) HIP_TRY(ws.rest.reserve(nv));
-  if(joints) HIP_TRY(ws.joints.reserve(sizeof(float) * (size_t)n * NJ * 3));
-  if(xforms) HIP_TRY(ws.xf44.reserve(sizeof(float) * (size_t)n * NJ * 16));
-  HIP_TRY(hipMemcpyAsync(ws.beta.p, beta, nb, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ws.theta.p, theta, nt, hipMemcpyHostToDevice, st));
+  const size_t nv = (size_t)n * m->V * 3;
+  In<float> b, t;
+  Out<float> v, j, x, r;
+  HIP_TRY(b.init(beta, (size_t)n * NB, space, st, &ws.beta));
+  HIP_TRY(t.init(theta, (size_t)n * (NJ + 1) * 3, space, st, &ws.theta));
+  HIP_TRY(v.init(verts, nv, space, &ws.verts));
+  HIP_TRY(r.init(rest, nv, space, &ws.rest));
+  HIP_TRY(j.init(joints, (size_t)n * NJ * 3, space, &ws.joints));
+  HIP_TRY(x.init(xforms, (size_t)n * NJ * 16, space, &ws.xf44));
   // this call's own range word: cleared in front of the launch, read back on the launch stream beside the results
   const bool ranged = m->range_flag && m->form == 'h';
   if(ranged) HIP_TRY(hipMemsetAsync(m->range_flag + RANGE_HOST, 0, sizeof(int), st));
-  int rc = fk_device(m, n, ws.beta.as<float>(), ws.theta.as<float>(), verts ? ws.verts.as<float>() : nullptr,
-                     joints ? ws.joints.as<float>() : nullptr, xforms ? ws.xf44.as<float>() : nullptr,
-                     rest ? ws.rest.as<float>() : nullptr, nullptr, st, RANGE_HOST, nullptr);
+  int rc = fk_device(m, n, b.d, t.d, v.d, j.d, x.d, r.d, nullptr, st, RANGE_HOST, nullptr);
   if(rc) return rc;
-  if(verts) HIP_TRY(hipMemcpyAsync(verts, ws.verts.p, nv, hipMemcpyDeviceToHost, st));
-  if(rest) HIP_TRY(hipMemcpyAsync(rest, ws.rest.p, nv, hipMemcpyDeviceToHost, st));
-  if(joints) HIP_TRY(hipMemcpyAsync(joints, ws.joints.p, sizeof(float) * (size_t)n * NJ * 3, hipMemcpyDeviceToHost, st));
-  if(xforms) HIP_TRY(hipMemcpyAsync(xforms, ws.xf44.p, sizeof(float) * (size_t)n * NJ * 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(v.finish(st));
+  HIP_TRY(r.finish(st));
+  HIP_TRY(j.finish(st));
+  HIP_TRY(x.finish(st));
   HIP_TRY(hipStreamSynchronize(st));
   // (read AFTER the synchronisation, synchronously: an asynchronous copy into this frame's stack could still be pending when one of
   // the copies above fails and the function returns)

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "pose_body.h"
 #include "rodrigues_grad.h"
+#include "staging.h"
 #include "trace.h"
 
 #include <algorithm>
@@ -63,7 +64,7 @@ void vjp_release(VjpState * s)
   if(s->BT) (void)hipFree(s->BT);
   if(s->range_word) (void)hipFree(s->range_word);
   Workspace & w = s->fws;
-  for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.poserot, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
+  for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
   for(DevBuf * b : {&s->Gp, &s->joints, &s->rot, &s->slab, &s->rest, &s->beta, &s->theta, &s->gv, &s->gj, &s->gbeta, &s->gtheta}) b->release();
   delete s;
 }
@@ -489,7 +490,7 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
 {
   if(!m) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: null model");
   if(n <= 0 || !beta || !theta) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: needs n > 0, beta and theta");
-  if(space != SMPLPP_HOST && space != SMPLPP_DEVICE) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: bad memory space");
+  if(int rc = check_space(space, "smplpp_fk_vjp")) return rc;
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: too many frames");
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -513,37 +514,20 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
   if(space == SMPLPP_DEVICE) return vjp_device(m, n, beta, theta, rest, grad_verts, grad_joints, grad_beta, grad_theta, st);
 
   VjpState * s = m->vjp;
-  const size_t nb = sizeof(float) * (size_t)n * NB, nt = sizeof(float) * (size_t)n * (NJ + 1) * 3;
-  const size_t nv = sizeof(float) * (size_t)n * m->V * 3, nj = sizeof(float) * (size_t)n * NJ * 3;
-  HIP_TRY(s->beta.reserve(nb));
-  HIP_TRY(s->theta.reserve(nt));
-  HIP_TRY(hipMemcpyAsync(s->beta.p, beta, nb, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->theta.p, theta, nt, hipMemcpyHostToDevice, st));
-  const float * d_rest = nullptr;
-  if(rest && grad_verts)
-  {
-    HIP_TRY(s->rest.reserve(nv));
-    HIP_TRY(hipMemcpyAsync(s->rest.p, rest, nv, hipMemcpyHostToDevice, st));
-    d_rest = s->rest.as<float>();
-  }
-  if(grad_verts)
-  {
-    HIP_TRY(s->gv.reserve(nv));
-    HIP_TRY(hipMemcpyAsync(s->gv.p, grad_verts, nv, hipMemcpyHostToDevice, st));
-  }
-  if(grad_joints)
-  {
-    HIP_TRY(s->gj.reserve(nj));
-    HIP_TRY(hipMemcpyAsync(s->gj.p, grad_joints, nj, hipMemcpyHostToDevice, st));
-  }
-  if(grad_beta) HIP_TRY(s->gbeta.reserve(nb));
-  if(grad_theta) HIP_TRY(s->gtheta.reserve(nt));
-  int rc = vjp_device(m, n, s->beta.as<float>(), s->theta.as<float>(), d_rest, grad_verts ? s->gv.as<float>() : nullptr,
-                      grad_joints ? s->gj.as<float>() : nullptr, grad_beta ? s->gbeta.as<float>() : nullptr,
-                      grad_theta ? s->gtheta.as<float>() : nullptr, st);
+  const size_t nb = (size_t)n * NB, nt = (size_t)n * (NJ + 1) * 3, nv = (size_t)n * m->V * 3;
+  In<float> b, t, r, gv, gj;
+  Out<float> gb, gt;
+  HIP_TRY(b.init(beta, nb, space, st, &s->beta));
+  HIP_TRY(t.init(theta, nt, space, st, &s->theta));
+  if(grad_verts) HIP_TRY(r.init(rest, nv, space, st, &s->rest));
+  HIP_TRY(gv.init(grad_verts, nv, space, st, &s->gv));
+  HIP_TRY(gj.init(grad_joints, (size_t)n * NJ * 3, space, st, &s->gj));
+  HIP_TRY(gb.init(grad_beta, nb, space, &s->gbeta));
+  HIP_TRY(gt.init(grad_theta, nt, space, &s->gtheta));
+  int rc = vjp_device(m, n, b.d, t.d, r.d, gv.d, gj.d, gb.d, gt.d, st);
   if(rc) return rc;
-  if(grad_beta) HIP_TRY(hipMemcpyAsync(grad_beta, s->gbeta.p, nb, hipMemcpyDeviceToHost, st));
-  if(grad_theta) HIP_TRY(hipMemcpyAsync(grad_theta, s->gtheta.p, nt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(gb.finish(st));
+  HIP_TRY(gt.finish(st));
   HIP_TRY(hipStreamSynchronize(st));
   return SMPLPP_OK;
 }

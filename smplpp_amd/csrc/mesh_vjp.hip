@@ -434,39 +434,22 @@ static int normals_vjp_common(const char * fn, smplpp_model * m, int64_t n, cons
   TraceRange tr("normals VJP");
   NormalsVjpState * s = nvjp_state(m);
   const int64_t V = m->V, rows = kind == 2 ? V : count;
-  const size_t nv = sizeof(float) * (size_t)n * V * 3, ng = sizeof(float) * (size_t)n * rows * 3;
-  const float * dv = verts;
-  const float * dg = grad_normals;
-  const int64_t * di = ids;
-  float * dout = grad_verts;
-  if(space == SMPLPP_HOST)
-  {
-    HIP_TRY(s->verts.reserve(nv));
-    HIP_TRY(s->gn.reserve(ng));
-    HIP_TRY(s->gv.reserve(nv));
-    HIP_TRY(hipMemcpyAsync(s->verts.p, verts, nv, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->gn.p, grad_normals, ng, hipMemcpyHostToDevice, st));
-    if(accumulate) HIP_TRY(hipMemcpyAsync(s->gv.p, grad_verts, nv, hipMemcpyHostToDevice, st));
-    if(kind != 2)
-    {
-      HIP_TRY(s->ids.reserve(sizeof(int64_t) * (size_t)count));
-      HIP_TRY(hipMemcpyAsync(s->ids.p, ids, sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, st));
-      di = s->ids.as<int64_t>();
-    }
-    dv = s->verts.as<float>();
-    dg = s->gn.as<float>();
-    dout = s->gv.as<float>();
-  }
+  const size_t nv = (size_t)n * V * 3;
+  In<float> v, g;
+  In<int64_t> id;
+  Out<float> gv;
+  HIP_TRY(v.init(verts, nv, space, st, &s->verts));
+  HIP_TRY(g.init(grad_normals, (size_t)n * rows * 3, space, st, &s->gn));
+  HIP_TRY(gv.init(grad_verts, nv, space, &s->gv));
+  if(accumulate) HIP_TRY(gv.load(st));
+  HIP_TRY(id.init(ids, (size_t)count, space, st, &s->ids));
   // a list form writes only the vertices it touches: without accumulate the rest is zeroed first
-  if(kind != 2 && !accumulate) HIP_TRY(hipMemsetAsync(dout, 0, nv, st));
-  rc = kind == 2 ? mesh_vjp_device(m, s, n, dv, dg, dout, accumulate, st)
-                 : list_vjp_device(m, s, n, dv, count, di, dg, dout, accumulate, kind == 1, st);
+  if(kind != 2 && !accumulate) HIP_TRY(hipMemsetAsync(gv.d, 0, sizeof(float) * nv, st));
+  rc = kind == 2 ? mesh_vjp_device(m, s, n, v.d, g.d, gv.d, accumulate, st)
+                 : list_vjp_device(m, s, n, v.d, count, id.d, g.d, gv.d, accumulate, kind == 1, st);
   if(rc) return rc;
-  if(space == SMPLPP_HOST)
-  {
-    HIP_TRY(hipMemcpyAsync(grad_verts, dout, nv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
+  HIP_TRY(gv.finish(st));
+  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
   return SMPLPP_OK;
 }
 

@@ -290,7 +290,7 @@ extern "C" int smplpp_model_destroy(smplpp_model * m)
   for(void * p : ptrs)
     if(p) (void)hipFree(p);
   Workspace & w = m->ws;
-  for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.poserot, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
+  for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
   vjp_release(m->vjp);
   nvjp_release(m->nvjp);
   delete m;

@@ -1,16 +1,18 @@
-// Host/device argument staging for the non-hot entry points (stage-level ops, mesh queries, setters/getters).
+// Host/device argument staging for the non-hot entry points (stage-level ops, mesh queries, setters/getters, the host form of
+// smplpp_fk and of the backward passes).  A host-space argument goes through `buf` when one is given (a persistent per-handle
+// buffer, grown as needed), else through a temporary freed with the In / Out.
 #pragma once
 #include "common.h"
 
 namespace smplpp_hip
 {
-// An input that must be readable on the device: either the caller's device pointer or a temporary upload.
+// An input that must be readable on the device: either the caller's device pointer or an upload.
 template<class T>
 struct In
 {
   const T * d = nullptr;
   T * tmp = nullptr;
-  hipError_t init(const T * p, size_t count, int space, hipStream_t st)
+  hipError_t init(const T * p, size_t count, int space, hipStream_t st, DevBuf * buf = nullptr)
   {
     if(!p || count == 0) return hipSuccess;
     if(space == SMPLPP_DEVICE)
@@ -18,10 +20,11 @@ struct In
       d = p;
       return hipSuccess;
     }
-    hipError_t e = hipMalloc((void **)&tmp, sizeof(T) * count);
+    hipError_t e = buf ? buf->reserve(sizeof(T) * count) : hipMalloc((void **)&tmp, sizeof(T) * count);
     if(e != hipSuccess) return e;
-    d = tmp;
-    return hipMemcpyAsync(tmp, p, sizeof(T) * count, hipMemcpyHostToDevice, st);
+    T * dst = buf ? buf->as<T>() : tmp;
+    d = dst;
+    return hipMemcpyAsync(dst, p, sizeof(T) * count, hipMemcpyHostToDevice, st);
   }
   ~In()
   {
@@ -29,7 +32,7 @@ struct In
   }
 };
 
-// An output: the caller's device pointer, or a temporary that is copied back by finish().
+// An output: the caller's device pointer, or a device copy that finish() copies back.
 template<class T>
 struct Out
 {
@@ -37,7 +40,7 @@ struct Out
   T * tmp = nullptr;
   T * host = nullptr;
   size_t count = 0;
-  hipError_t init(T * p, size_t cnt, int space)
+  hipError_t init(T * p, size_t cnt, int space, DevBuf * buf = nullptr)
   {
     if(!p || cnt == 0) return hipSuccess;
     count = cnt;
@@ -47,14 +50,20 @@ struct Out
       return hipSuccess;
     }
     host = p;
-    hipError_t e = hipMalloc((void **)&tmp, sizeof(T) * cnt);
-    if(e == hipSuccess) d = tmp;
+    hipError_t e = buf ? buf->reserve(sizeof(T) * cnt) : hipMalloc((void **)&tmp, sizeof(T) * cnt);
+    if(e == hipSuccess) d = buf ? buf->as<T>() : tmp;
     return e;
+  }
+  // the caller's host values into the device copy (an output the call adds into)
+  hipError_t load(hipStream_t st)
+  {
+    if(!host) return hipSuccess;
+    return hipMemcpyAsync(d, host, sizeof(T) * count, hipMemcpyHostToDevice, st);
   }
   hipError_t finish(hipStream_t st)
   {
-    if(!tmp) return hipSuccess;
-    return hipMemcpyAsync(host, tmp, sizeof(T) * count, hipMemcpyDeviceToHost, st);
+    if(!host) return hipSuccess;
+    return hipMemcpyAsync(host, d, sizeof(T) * count, hipMemcpyDeviceToHost, st);
   }
   ~Out()
   {

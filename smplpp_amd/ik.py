@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DEVICE, HOST, SmplppError, check
-from .smpl import SMPL, _is_torch, _np32, _ptr, _stream, torch
+from .smpl import SMPL, _Call, _np32, _ptr, torch
 
 LATENT_DIM = 32
 LATENT_POSE_DIM = LATENT_DIM + 12  # node/node.cpp:42
@@ -123,61 +123,42 @@ class VPoserDecoder:
 
     def forward(self, latent, want_jac=False, frame_base=0):
         """`frame_base`: global index of latent[0] when the call decodes a shard of a larger job (same bits as the unsharded call)."""
-        z = _np32(latent).reshape(-1, 32)
-        n = z.shape[0]
-        out = np.empty((n, 21, 3), np.float32)
-        jac = np.empty((n, 63, 32), np.float32) if want_jac else None
-        check(_lib.load().smplpp_vposer_forward_at(self._h, n, int(frame_base), _ptr(z), _ptr(out), _ptr(jac), HOST, None))
+        c, z = self._latent("forward", _np32(latent))
+        out, jac = self._decode(c, z, want_jac, frame_base)
         return (out, jac) if want_jac else out
+
+    def _latent(self, name, latent, *others, device_only=False):
+        """The call of `name` and its latent [N,32] (numpy input: any shape of N * 32 values)."""
+        c = _Call(name, latent, *others, device_only=device_only)
+        z = latent if c.dev else _np32(latent).reshape(-1, 32)
+        return c, c.input(z, (len(z), 32))
+
+    def _decode(self, c, z, want_jac, frame_base):
+        n = len(z)
+        out, jac = c.empty((n, 21, 3)), c.empty((n, 63, 32)) if want_jac else None
+        check(_lib.load().smplpp_vposer_forward_at(self._h, n, int(frame_base), _ptr(z), _ptr(out), _ptr(jac), c.space, c.stream))
+        return out, jac
 
     def launchBackward(self, latent, grad_out, frame_base=0, want_out=False):
         """Vector-Jacobian product of the decode (smplpp_vposer_vjp): dL/dz [N,32] for dL/dout = grad_out [N,21,3] at latent
         [N,32].  The product is taken at the exact-fp32 decode `forward(latent)` returns; want_out=True also returns those angles
         ((grad_z, out)).  numpy in, numpy out (the call synchronises), or float32 device tensors (enqueued on torch's current
         stream).  `frame_base`: as in `forward` (the result does not depend on it)."""
-        dev = _is_torch(latent)
-        if _is_torch(grad_out) != dev:
-            raise SmplppError(1, "launchBackward: mix of torch tensors and numpy arrays")
-        if dev:
-            n = latent.shape[0]
-            for a, shape in ((latent, (n, 32)), (grad_out, (n, 21, 3))):
-                if not (a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == shape):
-                    raise SmplppError(1, "launchBackward: expected a float32 device tensor of shape %s" % (shape,))
-            z, g = latent.contiguous(), grad_out.contiguous()
-            gz = torch.empty((n, 32), dtype=torch.float32, device=z.device)
-            out = torch.empty((n, 21, 3), dtype=torch.float32, device=z.device) if want_out else None
-            space, stream = DEVICE, _stream()
-        else:
-            z = _np32(latent).reshape(-1, 32)
-            n = z.shape[0]
-            g = _np32(grad_out)
-            if g.shape != (n, 21, 3):
-                raise SmplppError(1, "launchBackward: expected grad_out of shape %s, got %s" % ((n, 21, 3), g.shape))
-            gz = np.empty((n, 32), np.float32)
-            out = np.empty((n, 21, 3), np.float32) if want_out else None
-            space, stream = HOST, None
-        check(_lib.load().smplpp_vposer_vjp(self._h, n, int(frame_base), _ptr(z), _ptr(g), _ptr(gz), _ptr(out), space, stream))
+        c, z = self._latent("launchBackward", latent, grad_out)
+        n = len(z)
+        g = c.input(grad_out, (n, 21, 3))
+        gz, out = c.empty((n, 32)), c.empty((n, 21, 3)) if want_out else None
+        check(_lib.load().smplpp_vposer_vjp(self._h, n, int(frame_base), _ptr(z), _ptr(g), _ptr(gz), _ptr(out), c.space, c.stream))
         return (gz, out) if want_out else gz
 
     def jacobian(self, latent, frame_base=0, want_out=False):
         """d(out)/dz [N,63,32] in exact fp32 (smplpp_vposer_jacobian) at latent [N,32], taken at the exact-fp32 decode `forward(latent)`
         returns; want_out=True also returns those angles ((jac, out)).  numpy in, numpy out (the call synchronises), or a float32
         device tensor (enqueued on torch's current stream).  `frame_base`: as in `forward` (the result does not depend on it)."""
-        if _is_torch(latent):
-            n = latent.shape[0]
-            if not (latent.is_cuda and latent.dtype == torch.float32 and tuple(latent.shape) == (n, 32)):
-                raise SmplppError(1, "jacobian: expected a float32 device tensor of shape %s" % ((n, 32),))
-            z = latent.contiguous()
-            jac = torch.empty((n, 63, 32), dtype=torch.float32, device=z.device)
-            out = torch.empty((n, 21, 3), dtype=torch.float32, device=z.device) if want_out else None
-            space, stream = DEVICE, _stream()
-        else:
-            z = _np32(latent).reshape(-1, 32)
-            n = z.shape[0]
-            jac = np.empty((n, 63, 32), np.float32)
-            out = np.empty((n, 21, 3), np.float32) if want_out else None
-            space, stream = HOST, None
-        check(_lib.load().smplpp_vposer_jacobian(self._h, n, int(frame_base), _ptr(z), _ptr(out), _ptr(jac), space, stream))
+        c, z = self._latent("jacobian", latent)
+        n = len(z)
+        jac, out = c.empty((n, 63, 32)), c.empty((n, 21, 3)) if want_out else None
+        check(_lib.load().smplpp_vposer_jacobian(self._h, n, int(frame_base), _ptr(z), _ptr(out), _ptr(jac), c.space, c.stream))
         return (jac, out) if want_out else jac
 
     def forward_differentiable(self, latent):
@@ -203,12 +184,8 @@ if torch is not None:
 
         @staticmethod
         def forward(ctx, latent, vposer):
-            z = latent.detach().contiguous()
-            n = z.shape[0]
-            if not (z.is_cuda and z.dtype == torch.float32 and tuple(z.shape) == (n, 32)):
-                raise SmplppError(1, "VPoserDecoder.forward_differentiable: expected a float32 device tensor [N,32]")
-            out = torch.empty((n, 21, 3), dtype=torch.float32, device=z.device)
-            check(_lib.load().smplpp_vposer_forward_at(vposer._h, n, 0, _ptr(z), _ptr(out), None, DEVICE, _stream()))
+            c, z = vposer._latent("forward_differentiable", latent, device_only=True)
+            out, _ = vposer._decode(c, z, False, 0)
             ctx.vposer = vposer
             ctx.save_for_backward(z)
             return out
@@ -218,7 +195,7 @@ if torch is not None:
             z, = ctx.saved_tensors
             if not ctx.needs_input_grad[0]:
                 return None, None
-            return ctx.vposer.launchBackward(z, grad_out.contiguous()), None
+            return ctx.vposer.launchBackward(z, grad_out), None
 
 
 def theta_from_latent_layout(vposer: VPoserDecoder, q):

@@ -44,6 +44,62 @@ def _stream():
     return None
 
 
+class _Call:
+    """The memory space of one ABI call, decided by its first array argument: numpy arrays are host space (converted to float32; the
+    call stages and synchronises), torch tensors device space (CUDA float32 only; enqueued on torch's current stream).  `fail` is
+    the message of every refusal when the reference words it; `device_only` refuses host space."""
+
+    def __init__(self, name, *arrays, fail=None, device_only=False):
+        self.name, self.fail = name, fail
+        first = next(a for a in arrays if a is not None)
+        self.dev = _is_torch(first)
+        for a in arrays:
+            if a is not None and _is_torch(a) != self.dev:
+                self.refuse("mix of torch tensors and numpy arrays")
+        if device_only and not self.dev:
+            self.refuse("expected float32 device tensors")
+        self.space, self.stream = (DEVICE, _stream()) if self.dev else (HOST, None)
+        self.device = first.device if self.dev else None
+
+    def refuse(self, what):
+        raise SmplppError(1, self.fail or "%s: %s" % (self.name, what))
+
+    def input(self, a, shape):
+        """`a` checked against `shape` and ready to pass (None stays None)."""
+        if a is None:
+            return None
+        if self.dev:
+            if not (a.is_cuda and a.dtype == torch.float32 and a.shape == shape):
+                self.refuse("expected a float32 device tensor of shape %s" % (shape,))
+            return (a.detach() if a.requires_grad else a).contiguous()  # a detach() is a new tensor object per call
+        a = _np32(a)
+        if a.shape != shape:
+            self.refuse("expected shape %s, got %s" % (shape, a.shape))
+        return a
+
+    def inout(self, a, shape):
+        """An array the call adds into: checked, never converted."""
+        if self.dev:
+            ok = a.is_cuda and a.dtype == torch.float32 and a.shape == shape and a.is_contiguous()
+        else:
+            ok = isinstance(a, np.ndarray) and a.dtype == np.float32 and a.shape == shape and a.flags.c_contiguous
+        if not ok:
+            self.refuse("out must be a contiguous float32 array of shape %s" % (shape,))
+        return a.detach() if self.dev else a
+
+    def ids(self, ids):
+        """Flat int64 ids in this call's space."""
+        if self.dev and _is_torch(ids) and ids.is_cuda:
+            return ids.detach().to(dtype=torch.int64).contiguous().reshape(-1)
+        ids = np.ascontiguousarray(ids.detach().cpu().numpy() if _is_torch(ids) else np.atleast_1d(ids), np.int64).reshape(-1)
+        return torch.from_numpy(ids).to(self.device) if self.dev else ids
+
+    def empty(self, shape, dtype="float32"):
+        if self.dev:
+            return torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
+        return np.empty(shape, dtype)
+
+
 def parse_device(device) -> int:
     """Reference: `torch::Device` with an explicit index (src/SMPL.cpp:289-297); "CUDA" selects the GPU engine
     (node/node.cpp:360-371).  There is no CPU engine here."""
@@ -132,74 +188,34 @@ class SMPL:
     def launch(self, beta, theta, want=("verts", "joints", "xforms", "rest"), out=None):
         """beta [N,10], theta [N,25,3] (row 0 = root translation).  Outputs are kept for the getters.
         `out` (optional dict of preallocated arrays/tensors keyed like `want`) avoids per-call allocation."""
-        V = self.vertex_num
-        L = _lib.load()
-        if _is_torch(beta) != _is_torch(theta):
-            raise SmplppError(1, "Cannot launch a SMPL model!")
-        if _is_torch(beta):
-            if not (beta.is_cuda and theta.is_cuda and beta.dtype == torch.float32 and theta.dtype == torch.float32):
-                raise SmplppError(1, "Cannot launch a SMPL model!")
-            beta, theta = beta.contiguous(), theta.contiguous()
-            n = beta.shape[0]
-            if tuple(beta.shape) != (n, 10) or tuple(theta.shape) != (n, 25, 3):
-                raise SmplppError(1, "Cannot launch a SMPL model!")
-            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=beta.device)
-            space = DEVICE
-        else:
-            beta, theta = _np32(beta), _np32(theta)
-            n = beta.shape[0]
-            if beta.shape != (n, 10) or theta.shape != (n, 25, 3):
-                raise SmplppError(1, "Cannot launch a SMPL model!")
-            mk = lambda *s: np.empty(s, np.float32)
-            space = HOST
-        pre = out or {}
-        out = {
-            "verts": pre.get("verts", mk(n, V, 3) if "verts" in want else None),
-            "joints": pre.get("joints", mk(n, 24, 3) if "joints" in want else None),
-            "xforms": pre.get("xforms", mk(n, 24, 4, 4) if "xforms" in want else None),
-            "rest": pre.get("rest", mk(n, V, 3) if "rest" in want else None),
-        }
-        check(L.smplpp_fk(self.handle, n, _ptr(beta), _ptr(theta), _ptr(out["verts"]), _ptr(out["joints"]),
-                          _ptr(out["xforms"]), _ptr(out["rest"]), space, _stream() if space == DEVICE else None))
-        self._out, self._n, self._theta = out, n, theta
+        c = _Call("launch", beta, theta, fail="Cannot launch a SMPL model!")
+        _, theta, out = self._fk(c, beta, theta, want, out)
+        self._out, self._n, self._theta = out, theta.shape[0], theta
         return out
+
+    def _fk(self, c, beta, theta, want, out=None):
+        """smplpp_fk in the space of `c`: (beta, theta as passed to it, {"verts", "joints", "xforms", "rest"})."""
+        n, V = beta.shape[0] if c.dev else len(beta), self.vertex_num  # shape[0]: Tensor.__len__ is Python code
+        beta, theta = c.input(beta, (n, 10)), c.input(theta, (n, 25, 3))
+        pre = out or {}
+        out = {k: pre[k] if k in pre else (c.empty(s) if k in want else None)
+               for k, s in (("verts", (n, V, 3)), ("joints", (n, 24, 3)), ("xforms", (n, 24, 4, 4)), ("rest", (n, V, 3)))}
+        check(_lib.load().smplpp_fk(self.handle, n, _ptr(beta), _ptr(theta), _ptr(out["verts"]), _ptr(out["joints"]),
+                                    _ptr(out["xforms"]), _ptr(out["rest"]), c.space, c.stream))
+        return beta, theta, out
 
     def launchBackward(self, beta, theta, grad_verts=None, grad_joints=None, rest=None):
         """Vector-Jacobian product of `launch` (smplpp_fk_vjp): dL/dbeta [N,10] and dL/dtheta [N,25,3] for dL/dverts = grad_verts
         [N,V,3] and dL/djoints = grad_joints [N,24,3] (None = zero).  `rest` [N,V,3] is the rest shape `launch` returned for these
         inputs; None recomputes it inside the call.  numpy in, numpy out (the call synchronises), or torch tensors on the device
         (enqueued on torch's current stream).  Returns {"beta": ..., "theta": ...}."""
-        V = self.vertex_num
-        L = _lib.load()
-        dev = _is_torch(beta)
-        args = (theta, grad_verts, grad_joints, rest)
-        if any(a is not None and _is_torch(a) != dev for a in args):
-            raise SmplppError(1, "launchBackward: mix of torch tensors and numpy arrays")
-        if dev:
-            def prep(a, shape):
-                if a is None:
-                    return None
-                if not (a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == shape):
-                    raise SmplppError(1, "launchBackward: expected a float32 device tensor of shape %s" % (shape,))
-                return a.contiguous()
-            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=beta.device)
-            space = DEVICE
-        else:
-            def prep(a, shape):
-                if a is None:
-                    return None
-                a = _np32(a)
-                if a.shape != shape:
-                    raise SmplppError(1, "launchBackward: expected shape %s, got %s" % (shape, a.shape))
-                return a
-            mk = lambda *s: np.empty(s, np.float32)
-            space = HOST
-        n = beta.shape[0]
-        beta, theta = prep(beta, (n, 10)), prep(theta, (n, 25, 3))
-        gv, gj, rest = prep(grad_verts, (n, V, 3)), prep(grad_joints, (n, 24, 3)), prep(rest, (n, V, 3))
-        out = {"beta": mk(n, 10), "theta": mk(n, 25, 3)}
-        check(L.smplpp_fk_vjp(self.handle, n, _ptr(beta), _ptr(theta), _ptr(rest), _ptr(gv), _ptr(gj), _ptr(out["beta"]),
-                              _ptr(out["theta"]), space, _stream() if space == DEVICE else None))
+        c = _Call("launchBackward", beta, theta, grad_verts, grad_joints, rest)
+        n, V = len(beta), self.vertex_num
+        beta, theta = c.input(beta, (n, 10)), c.input(theta, (n, 25, 3))
+        gv, gj, rest = c.input(grad_verts, (n, V, 3)), c.input(grad_joints, (n, 24, 3)), c.input(rest, (n, V, 3))
+        out = {"beta": c.empty((n, 10)), "theta": c.empty((n, 25, 3))}
+        check(_lib.load().smplpp_fk_vjp(self.handle, n, _ptr(beta), _ptr(theta), _ptr(rest), _ptr(gv), _ptr(gj), _ptr(out["beta"]),
+                                        _ptr(out["theta"]), c.space, c.stream))
         return out
 
     def forward_differentiable(self, beta, theta):
@@ -258,23 +274,28 @@ class SMPL:
 
     def _normals(self, ids, vertex, frame=None):
         verts = self._need("verts")
-        single = np.isscalar(ids)
-        ids_np = np.ascontiguousarray(np.atleast_1d(ids), np.int64)
-        L = _lib.load()
-        fn = L.smplpp_vertex_normals if vertex else L.smplpp_face_normals
-        if _is_torch(verts):
-            v = verts if frame is None else verts[frame:frame + 1]
-            idt = torch.from_numpy(ids_np).to(verts.device)
-            out = torch.empty((v.shape[0], len(ids_np), 3), dtype=torch.float32, device=verts.device)
-            check(fn(self.handle, v.shape[0], _ptr(v), len(ids_np), _ptr(idt), _ptr(out), DEVICE, _stream()))
-        else:
-            v = verts if frame is None else verts[frame:frame + 1]
-            out = np.empty((v.shape[0], len(ids_np), 3), np.float32)
-            check(fn(self.handle, v.shape[0], _ptr(v), len(ids_np), _ptr(ids_np), _ptr(out), HOST, None))
+        v = verts if frame is None else verts[frame:frame + 1]
+        c = _Call("calcVertexNormal" if vertex else "calcNormal", v)
+        out, _ = self._normals_at(c, c.input(v, (len(v), self.vertex_num, 3)), 1 if vertex else 0, ids)
         if frame is not None:
             out = out[0]
-            return out[0] if single else out
+            return out[0] if np.isscalar(ids) else out
         return out
+
+    def _normals_at(self, c, verts, kind, ids):
+        """The normal queries at `verts` [N,V,3] in the space of `c`: kind 0 = face list, 1 = vertex list, 2 = whole mesh.
+        Returns (normals, ids as passed to the call)."""
+        L = _lib.load()
+        n = len(verts)
+        if kind == 2:
+            out = c.empty((n, self.vertex_num, 3))
+            check(L.smplpp_mesh_vertex_normals(self.handle, n, _ptr(verts), _ptr(out), c.space, c.stream))
+            return out, None
+        idt = c.ids(ids)
+        out = c.empty((n, len(idt), 3))
+        fn = L.smplpp_vertex_normals if kind == 1 else L.smplpp_face_normals
+        check(fn(self.handle, n, _ptr(verts), len(idt), _ptr(idt), _ptr(out), c.space, c.stream))
+        return out, idt
 
     def calcNormal(self, faceIdx):
         """SMPL::calcNormal (src/SMPL.cpp:518-525): batch 0, like the reference."""
@@ -293,70 +314,25 @@ class SMPL:
     def calcMeshVertexNormals(self):
         """SMPL::calcVertexNormal (src/SMPL.cpp:527-535) for every vertex of every frame of the last launch: [N,V,3]."""
         verts = self._need("verts")
-        L = _lib.load()
-        if _is_torch(verts):
-            out = torch.empty_like(verts)
-            check(L.smplpp_mesh_vertex_normals(self.handle, verts.shape[0], _ptr(verts), _ptr(out), DEVICE, _stream()))
-        else:
-            out = np.empty_like(verts)
-            check(L.smplpp_mesh_vertex_normals(self.handle, verts.shape[0], _ptr(verts), _ptr(out), HOST, None))
-        return out
+        c = _Call("calcMeshVertexNormals", verts)
+        return self._normals_at(c, c.input(verts, (len(verts), self.vertex_num, 3)), 2, None)[0]
 
     # ---- backward of the normal queries (smplpp_face_normals_vjp / smplpp_vertex_normals_vjp / smplpp_mesh_vertex_normals_vjp)
     def _normals_vjp(self, kind, verts, ids, grad_normals, out):
         """kind 0 = face list, 1 = vertex list, 2 = whole mesh.  Returns grad_verts [N,V,3]; `out` given = accumulate into it."""
-        V = self.vertex_num
+        c = _Call(("calcNormalBackward", "calcVertexNormalBackward", "calcMeshVertexNormalsBackward")[kind], verts, grad_normals, out)
+        n, V = len(verts), self.vertex_num
+        idt = None if kind == 2 else c.ids(ids)
+        count = V if kind == 2 else len(idt)
+        verts, gn = c.input(verts, (n, V, 3)), c.input(grad_normals, (n, count, 3))
+        acc = out is not None
+        out = c.inout(out, (n, V, 3)) if acc else c.empty((n, V, 3))
         L = _lib.load()
-        name = ("calcNormalBackward", "calcVertexNormalBackward", "calcMeshVertexNormalsBackward")[kind]
-        dev = _is_torch(verts)
-        if any(a is not None and _is_torch(a) != dev for a in (grad_normals, out)):
-            raise SmplppError(1, "%s: mix of torch tensors and numpy arrays" % name)
-        n = verts.shape[0]
-        ids_np = None
         if kind == 2:
-            count = V
-        elif _is_torch(ids):
-            count = ids.numel()
-            if not (dev and ids.is_cuda):
-                ids_np = np.ascontiguousarray(ids.detach().cpu().numpy(), np.int64).reshape(-1)
-        else:
-            ids_np = np.ascontiguousarray(np.atleast_1d(ids), np.int64).reshape(-1)
-            count = len(ids_np)
-        if dev:
-            def prep(a, shape):
-                if not (a.is_cuda and a.dtype == torch.float32 and tuple(a.shape) == shape):
-                    raise SmplppError(1, "%s: expected a float32 device tensor of shape %s" % (name, shape))
-                return a.detach().contiguous()
-            verts, gn = prep(verts, (n, V, 3)), prep(grad_normals, (n, count, 3))
-            if out is not None and not out.is_contiguous():
-                raise SmplppError(1, "%s: out must be contiguous" % name)
-            acc = out is not None
-            out = prep(out, (n, V, 3)) if acc else torch.empty((n, V, 3), dtype=torch.float32, device=verts.device)
-            if kind != 2:
-                if ids_np is None:
-                    idt = ids.detach().to(dtype=torch.int64).contiguous().reshape(-1)
-                else:
-                    idt = torch.from_numpy(ids_np).to(verts.device)
-            space, st = DEVICE, _stream()
-        else:
-            def prep(a, shape):
-                a = np.asarray(a)
-                if a.shape != shape:
-                    raise SmplppError(1, "%s: expected shape %s, got %s" % (name, shape, a.shape))
-                return _np32(a)
-            verts, gn = prep(verts, (n, V, 3)), prep(grad_normals, (n, count, 3))
-            acc = out is not None
-            if acc and not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == (n, V, 3) and out.flags.c_contiguous):
-                raise SmplppError(1, "%s: out must be a C-contiguous float32 array of shape %s" % (name, (n, V, 3)))
-            if not acc:
-                out = np.empty((n, V, 3), np.float32)
-            idt = ids_np if kind != 2 else None
-            space, st = HOST, None
-        if kind == 2:
-            check(L.smplpp_mesh_vertex_normals_vjp(self.handle, n, _ptr(verts), _ptr(gn), _ptr(out), int(acc), space, st))
+            check(L.smplpp_mesh_vertex_normals_vjp(self.handle, n, _ptr(verts), _ptr(gn), _ptr(out), int(acc), c.space, c.stream))
         else:
             fn = L.smplpp_vertex_normals_vjp if kind == 1 else L.smplpp_face_normals_vjp
-            check(fn(self.handle, n, _ptr(verts), count, _ptr(idt), _ptr(gn), _ptr(out), int(acc), space, st))
+            check(fn(self.handle, n, _ptr(verts), count, _ptr(idt), _ptr(gn), _ptr(out), int(acc), c.space, c.stream))
         return out
 
     def calcNormalBackward(self, verts, face_ids, grad_normals, out=None):
@@ -392,27 +368,17 @@ class SMPL:
         winding [cells], inside [cells] bool, grid_idx [cells,3] int32 in the reference's cell order, positions = 0.025 *
         grid_idx). `inside` marks the cells the reference enters into g_sweepGridList (winding number > 0.5)."""
         verts = self._need("verts")
-        v = verts[frame]
-        if _is_torch(v):
-            v = v.contiguous()
-            space, st = DEVICE, _stream()
-        else:
-            v = np.ascontiguousarray(v)
-            space, st = HOST, None
+        c = _Call("calcSweepGrid", verts)
+        v = c.input(verts[frame], (self.vertex_num, 3))
         L = _lib.load()
         gmin = np.zeros(3, np.int32)
         gnum = np.zeros(3, np.int32)
         cells = C.c_int64(0)
-        check(L.smplpp_sweep_grid(self.handle, _ptr(v), _ptr(gmin), _ptr(gnum), 0, None, None, C.byref(cells), space, st))
+        check(L.smplpp_sweep_grid(self.handle, _ptr(v), _ptr(gmin), _ptr(gnum), 0, None, None, C.byref(cells), c.space, c.stream))
         n = int(cells.value)
-        if space == DEVICE:
-            w = torch.empty(n, dtype=torch.float32, device=v.device)
-            ins = torch.empty(n, dtype=torch.uint8, device=v.device)
-        else:
-            w = np.empty(n, np.float32)
-            ins = np.empty(n, np.uint8)
-        check(L.smplpp_sweep_grid(self.handle, _ptr(v), _ptr(gmin), _ptr(gnum), n, _ptr(w), _ptr(ins), C.byref(cells), space, st))
-        if space == DEVICE:
+        w, ins = c.empty(n), c.empty(n, "uint8")
+        check(L.smplpp_sweep_grid(self.handle, _ptr(v), _ptr(gmin), _ptr(gnum), n, _ptr(w), _ptr(ins), C.byref(cells), c.space, c.stream))
+        if c.dev:
             torch.cuda.synchronize()
             w, ins = w.cpu().numpy(), ins.cpu().numpy()
         ix, iy, iz = np.meshgrid(*[np.arange(gmin[a], gmin[a] + gnum[a], dtype=np.int32) for a in range(3)], indexing="ij")
@@ -422,24 +388,14 @@ class SMPL:
     def closestPoints(self, points):
         """igl::point_mesh_squared_distance as used at node/node.cpp:982 — points [N,K,3] vs each frame's mesh."""
         verts = self._need("verts")
-        L = _lib.load()
-        n = verts.shape[0]
-        if _is_torch(verts):
-            points = points.contiguous()
-            K = points.shape[1]
-            face = torch.empty((n, K), dtype=torch.int64, device=verts.device)
-            closest = torch.empty((n, K, 3), dtype=torch.float32, device=verts.device)
-            sq = torch.empty((n, K), dtype=torch.float32, device=verts.device)
-            check(L.smplpp_closest_points(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(face), _ptr(closest), _ptr(sq),
-                                          DEVICE, _stream()))
-        else:
-            points = _np32(points).reshape(n, -1, 3)
-            K = points.shape[1]
-            face = np.empty((n, K), np.int64)
-            closest = np.empty((n, K, 3), np.float32)
-            sq = np.empty((n, K), np.float32)
-            check(L.smplpp_closest_points(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(face), _ptr(closest), _ptr(sq),
-                                          HOST, None))
+        c = _Call("closestPoints", verts, points)
+        n = len(verts)
+        points = points if c.dev else _np32(points).reshape(n, -1, 3)
+        K = points.shape[1]
+        verts, points = c.input(verts, (n, self.vertex_num, 3)), c.input(points, (n, K, 3))
+        face, closest, sq = c.empty((n, K), "int64"), c.empty((n, K, 3)), c.empty((n, K))
+        check(_lib.load().smplpp_closest_points(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(face), _ptr(closest), _ptr(sq),
+                                                c.space, c.stream))
         return face, closest, sq
 
     def out(self, index: int, path: str):
@@ -459,27 +415,18 @@ if torch is not None:
 
         @staticmethod
         def forward(ctx, beta, theta, smpl):
-            beta, theta = beta.detach().contiguous(), theta.detach().contiguous()
-            n, V = beta.shape[0], smpl.vertex_num
-            if not (beta.is_cuda and theta.is_cuda and beta.dtype == torch.float32 and theta.dtype == torch.float32
-                    and tuple(beta.shape) == (n, 10) and tuple(theta.shape) == (n, 25, 3)):
-                raise SmplppError(1, "Cannot launch a SMPL model!")
-            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=beta.device)
-            verts, joints, rest = mk(n, V, 3), mk(n, 24, 3), mk(n, V, 3)
-            check(_lib.load().smplpp_fk(smpl.handle, n, _ptr(beta), _ptr(theta), _ptr(verts), _ptr(joints), None, _ptr(rest), DEVICE,
-                                        _stream()))
+            c = _Call("forward_differentiable", beta, theta, fail="Cannot launch a SMPL model!", device_only=True)
+            beta, theta, out = smpl._fk(c, beta, theta, ("verts", "joints", "rest"))
             ctx.smpl = smpl
-            ctx.save_for_backward(beta, theta, rest)
-            return verts, joints
+            ctx.save_for_backward(beta, theta, out["rest"])
+            return out["verts"], out["joints"]
 
         @staticmethod
         def backward(ctx, grad_verts, grad_joints):
             beta, theta, rest = ctx.saved_tensors
             if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
                 return None, None, None
-            gv = grad_verts.contiguous() if grad_verts is not None else None
-            gj = grad_joints.contiguous() if grad_joints is not None else None
-            g = ctx.smpl.launchBackward(beta, theta, grad_verts=gv, grad_joints=gj, rest=rest)
+            g = ctx.smpl.launchBackward(beta, theta, grad_verts=grad_verts, grad_joints=grad_joints, rest=rest)
             return (g["beta"] if ctx.needs_input_grad[0] else None, g["theta"] if ctx.needs_input_grad[1] else None, None)
 
     class _NormalsFunction(torch.autograd.Function):
@@ -488,23 +435,9 @@ if torch is not None:
 
         @staticmethod
         def forward(ctx, verts, smpl, kind, ids):
-            verts = verts.detach().contiguous()
-            n, V = verts.shape[0], smpl.vertex_num
-            if not (verts.is_cuda and verts.dtype == torch.float32 and tuple(verts.shape) == (n, V, 3)):
-                raise SmplppError(1, "normals: expected float32 device vertices of shape %s" % ((n, V, 3),))
-            L = _lib.load()
-            if kind == 2:
-                out = torch.empty_like(verts)
-                check(L.smplpp_mesh_vertex_normals(smpl.handle, n, _ptr(verts), _ptr(out), DEVICE, _stream()))
-                idt = None
-            else:
-                if _is_torch(ids):
-                    idt = ids.detach().to(device=verts.device, dtype=torch.int64).contiguous().reshape(-1)
-                else:
-                    idt = torch.from_numpy(np.ascontiguousarray(np.atleast_1d(ids), np.int64).reshape(-1)).to(verts.device)
-                out = torch.empty((n, idt.numel(), 3), dtype=torch.float32, device=verts.device)
-                fn = L.smplpp_vertex_normals if kind == 1 else L.smplpp_face_normals
-                check(fn(smpl.handle, n, _ptr(verts), idt.numel(), _ptr(idt), _ptr(out), DEVICE, _stream()))
+            c = _Call("normals_differentiable", verts, device_only=True)
+            verts = c.input(verts, (len(verts), smpl.vertex_num, 3))
+            out, idt = smpl._normals_at(c, verts, kind, ids)
             ctx.smpl, ctx.kind, ctx.idt = smpl, kind, idt
             ctx.save_for_backward(verts)
             return out
@@ -514,7 +447,7 @@ if torch is not None:
             (verts,) = ctx.saved_tensors
             if not ctx.needs_input_grad[0]:
                 return None, None, None, None
-            gv = ctx.smpl._normals_vjp(ctx.kind, verts, ctx.idt, grad.contiguous(), None)
+            gv = ctx.smpl._normals_vjp(ctx.kind, verts, ctx.idt, grad, None)
             return gv, None, None, None
 
 
