@@ -11,10 +11,10 @@ namespace smplpp_hip
 // tested against all K queries: proj_scan_kernel (one workgroup per frame x face chunk) culls with the bounding-sphere
 // test against each query's hint distance (exact distance to the task's current face), evaluates the exact distance of
 // the few survivors and appends (distance, face) to a short per-(frame, task) list; proj_finish_kernel (one workgroup per
-// frame) takes the minimum of each list, applies the tie rule (lowest face id within 1e-6 relative of the minimum — every
-// face in that band passes the cull, whose slack is larger) and writes the new face id and area-ratio weights.  A list
+// frame) takes the minimum mn of each list, applies the tie rule (lowest face id with d <= mn * (1 + 1e-6) + 1e-12 — every face
+// in that band passes both the cull and the listing bound: see proj_scan_kernel) and writes the new face id and area-ratio weights.  A list
 // that overflows (a far-off hint, e.g. the very first iteration) falls back to the exhaustive block scan.
-constexpr int PROJ_LIST = 512; // (generous since the lists only take faces at least as close as the task's own: see proj_scan_kernel)
+constexpr int PROJ_LIST = 512; // (generous since the lists only take faces at least as close as the task's own, up to the tie band: see proj_scan_kernel)
 constexpr int PROJ_MAXK = IK_MAXK;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -55,12 +55,16 @@ __global__ __launch_bounds__(256) void proj_scan_kernel(ModelView mv, TaskArrays
       d = tri_sqdist_dev(verts, mv.faces, ta.face[tb + k], p, c);
     }
     sreach[k] = (d == d) ? sqrtf(d) : INFINITY;
-    // The task's own face is a candidate, at exactly this distance (same evaluation): the minimum is <= it, and every face the
-    // tie rule may prefer lies within 1e-6 relative of the minimum.  Survivors of the sphere cull beyond that bound are not
-    // listed at all — the lists shrink from hundreds of entries (every face inside the cull sphere of a marker 15 mm off a
-    // densely triangulated region: they overflowed in two of three frames of sample_walk.c3d and sent the finish kernel to
-    // its exhaustive fallback) to the handful of faces at least as close as the current one.
-    sbound[k] = (d == d) ? d * 1.00001f + 1e-30f : INFINITY;
+    // The task's own face is a candidate, at exactly this distance (same evaluation): the minimum mn is <= d, so every face
+    // the tie rule may prefer has a distance <= mn * (1 + 1e-6) + 1e-12 <= d * (1 + 1e-6) + 1e-12, which the bound below
+    // covers, its absolute term included: a query ON its face (d ~ 1e-15: every task without a normal offset, every converged
+    // one) is within 1e-12 of a lower-id neighbour up to 1 um from their shared edge.  Survivors of the sphere cull beyond
+    // the bound are not listed at all — the lists shrink from hundreds of entries (every face inside the cull sphere of a
+    // marker 15 mm off a densely triangulated region: they overflowed in two of three frames of sample_walk.c3d and sent the
+    // finish kernel to its exhaustive fallback) to the handful of faces at least as close as the current one (on the surface:
+    // plus those within ~1.4 um).  The cull itself lets every such face through: sqrt(d * (1 + 1e-6) + 1e-12) <=
+    // sqrt(d) * (1 + 5e-7) + 1e-6, inside its reach (sqrt(d) + r) * 1.00001 + 2e-6.
+    sbound[k] = (d == d) ? d * 1.00001f + 2e-12f : INFINITY;
   }
   else if((int)threadIdx.x == K) // the odd pair's second half: a query no face can reach
   {
