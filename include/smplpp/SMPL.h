@@ -323,6 +323,49 @@ public:
   {
     return normalsBackward(2, {}, gradNormal, accumulate);
   }
+  // Point-to-mesh distance on the last launch's vertices (fitting to a point cloud or scan): for points [N,K,3], the closest face of
+  // each frame's mesh (smplpp_point_mesh_distance).  face [N,K] kInt64, weights [N,K,3] (the closest point's vertex weights),
+  // closest [N,K,3] and sqdist [N,K]; face / closest / sqdist have the bits of smplpp_closest_points.
+  struct PointMeshDistance
+  {
+    Tensor face, weights, closest, sqdist;
+  };
+  PointMeshDistance pointMeshDistance(const Tensor & points) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || points.size(1) < 1 || points.size(2) != 3)
+      throw Exception("SMPL", "Cannot compute the point-to-mesh distance!");
+    const int64_t K = points.size(1);
+    PointMeshDistance r{Tensor({n, K}, kInt64), Tensor({n, K, 3}), Tensor({n, K, 3}), Tensor({n, K})};
+    check(smplpp_point_mesh_distance(m_.get(), n, verts_.ptr(), K, points.ptr(), r.face.idata.data(), r.weights.ptr(), r.closest.ptr(),
+                                     r.sqdist.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
+  // Its backward pass (smplpp_point_mesh_distance_vjp): dL/dverts [N,V,3] for dL/dsqdist = gradSqdist [N,K] at the faces `face` [N,K]
+  // pointMeshDistance chose.  `gradPoints` non-null receives dL/dpoints [N,K,3].  `accumulate` non-null: the vertex product is added
+  // into it (and it is returned), as calcNormalBackward does, and the point product into *gradPoints, which must then hold [N,K,3].
+  Tensor pointMeshDistanceBackward(const Tensor & points, const Tensor & face, const Tensor & gradSqdist, Tensor * gradPoints = nullptr,
+                                   Tensor * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const int64_t K = points.dim() == 3 ? points.size(1) : 0;
+    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || K < 1 || points.size(2) != 3 ||
+       (face.dtype != kInt64 && face.dtype != kInt32) || face.numel() != n * K || gradSqdist.dtype != kFloat32 || gradSqdist.numel() != n * K ||
+       (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3)) ||
+       (accumulate && gradPoints && (gradPoints->dtype != kFloat32 || gradPoints->numel() != n * K * 3)))
+      throw Exception("SMPL", "Cannot back-propagate through the point-to-mesh distance!");
+    Tensor fresh;
+    if(!accumulate) fresh = Tensor(verts_.shape);
+    Tensor & g = accumulate ? *accumulate : fresh;
+    if(gradPoints && !accumulate) *gradPoints = Tensor({n, K, 3});
+    check(smplpp_point_mesh_distance_vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), face.idata.data(), gradSqdist.ptr(), g.ptr(),
+                                         gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return g;
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const

@@ -160,6 +160,38 @@ int smplpp_vertex_normals_vjp(smplpp_model * m, int64_t n, const float * verts, 
                               const float * grad_normals /*[n,count,3]*/, float * grad_verts, int accumulate, int space, void * stream);
 int smplpp_mesh_vertex_normals_vjp(smplpp_model * m, int64_t n, const float * verts, const float * grad_normals /*[n,V,3]*/,
                                    float * grad_verts, int accumulate, int space, void * stream);
+/* Point-to-mesh distance for many query points per frame (fitting to a point cloud or scan): for each of n frames, the
+ * closest face of that frame's posed mesh verts [n,V,3] to each of K points [n,K,3].
+ *  - face [n,K], closest [n,K,3] and sqdist [n,K] have the bits smplpp_closest_points gives on the same inputs (the same
+ *    rule: the lowest face id with d <= mn (1 + 1e-6) + 1e-12, every distance from the same point-triangle evaluation).
+ *  - weights [n,K,3]: the vertex weights of the closest point, from the branch of the point-triangle evaluation that produced
+ *    it: one-hot at a vertex, (1-v, v, 0) / (1-w, 0, w) / (0, 1-w, w) on edge ab / ac / bc, (1-v-w, v, w) inside.  They sum
+ *    to 1 and sum_j w_j v_j is `closest` up to rounding (at a region boundary a weight may round to a few ulps below 0).  (Not the IK tasks' area-ratio weights of an arbitrary position.)
+ *  - form: a tiled scan (64 queries per workgroup, Morton-ordered within the frame, triangles through LDS) when the call has
+ *    n * K >= 8192 queries, one workgroup per query below; SMPLPP_POINT_DISTANCE_FORM = query | tiled, read at model creation,
+ *    forces one.  Every form returns the same bits.
+ *  - weights and closest are nullable; face and sqdist are not.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, n * K beyond int32 indexing. */
+int smplpp_point_mesh_distance(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t K, const float * points /*[n,K,3]*/,
+                               int64_t * face /*[n,K]*/, float * weights /*[n,K,3] nullable*/, float * closest /*[n,K,3] nullable*/,
+                               float * sqdist /*[n,K]*/, int space, void * stream);
+/* Vector-Jacobian product of sqdist above: grad_verts [n,V,3] and grad_points [n,K,3] for dL/dsqdist = grad_sqdist [n,K], at
+ * the faces `face` [n,K] the forward chose.  The point c and weights w are recomputed from (verts, points, face) with the
+ * forward's evaluation (no new search); with r = p - c and g = grad_sqdist:
+ *    grad_points[k] = 2 g_k r_k,    grad_verts[u] = sum over (k, corner j) with faces[face_k][j] == u of -2 g_k w_kj r_k.
+ *  - exact in every region (envelope theorem); where tied faces share the closest point, they give the same gradient.
+ *  - accumulate = 0: both outputs are overwritten (vertices no query touches get 0); accumulate = 1: the product is added
+ *    (so the distance term can share one buffer with normal and position terms on its way to smplpp_fk_vjp).  Either output
+ *    may be NULL, not both.
+ *  - a query whose cotangent is exactly 0 contributes nothing, even if its point is NaN (padded rows of ragged scans).
+ *  - deterministic: no floating-point atomics; each element of grad_verts is one fixed-order sum in ascending k, then corner
+ *    j, so a frame's bits do not depend on n or on its position in the batch.  No cap on the records one vertex receives.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, n * K beyond int32 indexing, host-space face ids out of
+ *    range (a device-space face id out of range contributes nothing). */
+int smplpp_point_mesh_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
+                                   const int64_t * face /*[n,K]*/, const float * grad_sqdist /*[n,K]*/,
+                                   float * grad_verts /*[n,V,3] nullable*/, float * grad_points /*[n,K,3] nullable*/,
+                                   int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

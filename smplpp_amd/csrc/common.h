@@ -209,6 +209,8 @@ struct VjpState;                   // smplpp_fk_vjp's operand image and workspac
 void vjp_release(VjpState * s);
 struct NormalsVjpState;            // the normals' backward pass (mesh_vjp.hip), created by its first call
 void nvjp_release(NormalsVjpState * s);
+struct PointDistState;             // point-to-mesh distance and its backward pass (point_distance.hip), created by the first call
+void pd_release(PointDistState * s);
 } // namespace smplpp_hip
 
 struct smplpp_model
@@ -257,4 +259,6 @@ struct smplpp_model
   smplpp_hip::Workspace ws;
   smplpp_hip::VjpState * vjp = nullptr; // backward pass (smplpp_fk_vjp): null until its first call on the model
   smplpp_hip::NormalsVjpState * nvjp = nullptr; // backward pass of the normal queries (mesh_vjp.hip): null until its first call
+  char pd_form = 0;             // point-to-mesh distance form (SMPLPP_POINT_DISTANCE_FORM, read at model creation): 0 = by K | q | t
+  smplpp_hip::PointDistState * pd = nullptr; // point-to-mesh distance workspace (point_distance.hip): null until its first call
 };

@@ -74,8 +74,13 @@ __device__ inline void triangle_weights_dev(const float * pos, const float * tri
   w[2] /= s;
 }
 
-// closest point on triangle abc to p (Ericson, Real-Time Collision Detection 5.1.5)
-__device__ inline void closest_on_triangle_dev(const float * p, const float * a, const float * b, const float * c, float * out)
+// closest point on triangle abc to p (Ericson, Real-Time Collision Detection 5.1.5).  WEIGHTS also writes wt[3], the vertex weights
+// of the branch that produced the point: vertex a / b / c one-hot, edge ab (1-v, v, 0), edge ac (1-w, 0, w), edge bc (0, 1-w, w),
+// interior (1-v-w, v, w).  These are barycentric weights of the closest point, not calcTriangleVertexWeights' area ratios of an
+// arbitrary position (triangle_weights_dev).  The two forms share every branch and every value the point is computed from; the
+// <false> form is closest_on_triangle_dev.
+template<bool WEIGHTS>
+__device__ inline void closest_on_triangle_t(const float * p, const float * a, const float * b, const float * c, float * out, float * wt)
 {
   float ab[3], ac[3], ap[3], bp[3], cp[3];
   for(int x = 0; x < 3; x++)
@@ -94,11 +99,13 @@ __device__ inline void closest_on_triangle_dev(const float * p, const float * a,
   if(d1 <= 0.0f && d2 <= 0.0f)
   {
     out[0] = a[0]; out[1] = a[1]; out[2] = a[2];
+    if constexpr(WEIGHTS) { wt[0] = 1.0f; wt[1] = 0.0f; wt[2] = 0.0f; }
     return;
   }
   if(d3 >= 0.0f && d4 <= d3)
   {
     out[0] = b[0]; out[1] = b[1]; out[2] = b[2];
+    if constexpr(WEIGHTS) { wt[0] = 0.0f; wt[1] = 1.0f; wt[2] = 0.0f; }
     return;
   }
   const float vc = d1 * d4 - d3 * d2;
@@ -106,11 +113,13 @@ __device__ inline void closest_on_triangle_dev(const float * p, const float * a,
   {
     const float v = d1 / (d1 - d3);
     for(int x = 0; x < 3; x++) out[x] = a[x] + v * ab[x];
+    if constexpr(WEIGHTS) { wt[0] = 1.0f - v; wt[1] = v; wt[2] = 0.0f; }
     return;
   }
   if(d6 >= 0.0f && d5 <= d6)
   {
     out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
+    if constexpr(WEIGHTS) { wt[0] = 0.0f; wt[1] = 0.0f; wt[2] = 1.0f; }
     return;
   }
   const float vb = d5 * d2 - d1 * d6;
@@ -118,6 +127,7 @@ __device__ inline void closest_on_triangle_dev(const float * p, const float * a,
   {
     const float w = d2 / (d2 - d6);
     for(int x = 0; x < 3; x++) out[x] = a[x] + w * ac[x];
+    if constexpr(WEIGHTS) { wt[0] = 1.0f - w; wt[1] = 0.0f; wt[2] = w; }
     return;
   }
   const float va = d3 * d6 - d5 * d4;
@@ -125,11 +135,17 @@ __device__ inline void closest_on_triangle_dev(const float * p, const float * a,
   {
     const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
     for(int x = 0; x < 3; x++) out[x] = b[x] + w * (c[x] - b[x]);
+    if constexpr(WEIGHTS) { wt[0] = 0.0f; wt[1] = 1.0f - w; wt[2] = w; }
     return;
   }
   const float denom = 1.0f / (va + vb + vc);
   const float v = vb * denom, w = vc * denom;
   for(int x = 0; x < 3; x++) out[x] = a[x] + ab[x] * v + ac[x] * w;
+  if constexpr(WEIGHTS) { wt[0] = 1.0f - v - w; wt[1] = v; wt[2] = w; }
+}
+__device__ inline void closest_on_triangle_dev(const float * p, const float * a, const float * b, const float * c, float * out)
+{
+  closest_on_triangle_t<false>(p, a, b, c, out, nullptr);
 }
 
 // Block-wide (256 threads) closest point of ONE query against all F faces of one frame's mesh.

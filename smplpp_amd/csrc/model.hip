@@ -293,6 +293,7 @@ extern "C" int smplpp_model_destroy(smplpp_model * m)
   for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
   vjp_release(m->vjp);
   nvjp_release(m->nvjp);
+  pd_release(m->pd);
   delete m;
   return SMPLPP_OK;
 }
@@ -355,6 +356,10 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
       m->form = 'e';
       m->form_ik = 'h';
     }
+  }
+  {
+    const char * pd_env = getenv("SMPLPP_POINT_DISTANCE_FORM"); // query | tiled: one form of smplpp_point_mesh_distance for every K
+    m->pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
   }
   auto uses = [&](char f) { return m->form == f || m->form_ik == f; };
   // (the vertex-major uploads are owned by the handle from the start, so a failure below frees them with it)

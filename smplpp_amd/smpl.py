@@ -398,6 +398,74 @@ class SMPL:
                                                 c.space, c.stream))
         return face, closest, sq
 
+    # ---- point-to-mesh distance (smplpp_point_mesh_distance / smplpp_point_mesh_distance_vjp)
+    def _pmd_inputs(self, c, verts, points):
+        """verts [N,V,3] and points [N,K,3] checked in the space of `c`; returns (verts, points, K)."""
+        n = len(verts)
+        shape = tuple(points.shape) if c.dev else np.shape(points)
+        if len(shape) != 3 or shape[0] != n or shape[1] < 1 or shape[2] != 3:
+            c.refuse("expected points of shape (%d, K, 3), got %s" % (n, shape))
+        K = int(shape[1])
+        return c.input(verts, (n, self.vertex_num, 3)), c.input(points, (n, K, 3)), K
+
+    def _pmd(self, c, verts, points, K, want_closest=True):
+        n = len(verts)
+        face, w, sq = c.empty((n, K), "int64"), c.empty((n, K, 3)), c.empty((n, K))
+        closest = c.empty((n, K, 3)) if want_closest else None
+        check(_lib.load().smplpp_point_mesh_distance(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(face), _ptr(w), _ptr(closest), _ptr(sq),
+                                                     c.space, c.stream))
+        return face, w, closest, sq
+
+    def _pmd_vjp(self, c, verts, points, K, face, grad_sqdist, out, grad_points, want_verts=True, want_points=True):
+        n, V = len(verts), self.vertex_num
+        fid = c.ids(face)
+        if fid.shape[0] != n * K:
+            c.refuse("expected face of shape (%d, %d)" % (n, K))
+        g = c.input(grad_sqdist, (n, K))
+        acc = out is not None or grad_points is not None
+
+        def buf(a, shape, want):
+            if a is not None:
+                return c.inout(a, shape)
+            if not want:
+                return None
+            if not acc:
+                return c.empty(shape)
+            return torch.zeros(shape, dtype=torch.float32, device=c.device) if c.dev else np.zeros(shape, np.float32)
+
+        gv, gp = buf(out, (n, V, 3), want_verts), buf(grad_points, (n, K, 3), want_points)
+        check(_lib.load().smplpp_point_mesh_distance_vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(fid), _ptr(g), _ptr(gv), _ptr(gp),
+                                                         int(acc), c.space, c.stream))
+        return gv, gp
+
+    def pointMeshDistance(self, verts, points):
+        """The closest face of each frame's mesh verts [N,V,3] to each of K points [N,K,3] (smplpp_point_mesh_distance): returns
+        (face [N,K] int64, weights [N,K,3], closest [N,K,3], sqdist [N,K]).  face / closest / sqdist have the bits of closestPoints;
+        weights are the closest point's vertex weights (sum_j weights[..., j] * verts[face[..., j]] = closest up to rounding).
+        numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("pointMeshDistance", verts, points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        return self._pmd(c, verts, points, K)
+
+    def pointMeshDistanceBackward(self, verts, points, face, grad_sqdist, out=None, grad_points=None):
+        """Vector-Jacobian product of pointMeshDistance's sqdist at the faces `face` [N,K] it chose: (grad_verts [N,V,3],
+        grad_points [N,K,3]) for dL/dsqdist = grad_sqdist [N,K] (smplpp_point_mesh_distance_vjp).  `out` [N,V,3] and / or
+        `grad_points` [N,K,3] given: the product is added into them (and they are returned); an array not given is then
+        returned holding the product alone."""
+        c = _Call("pointMeshDistanceBackward", verts, points, grad_sqdist, out, grad_points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        return self._pmd_vjp(c, verts, points, K, face, grad_sqdist, out, grad_points)
+
+    def point_mesh_distance_differentiable(self, verts, points):
+        """(face [N,K], weights [N,K,3], sqdist [N,K]) of device points [N,K,3] against device vertices verts [N,V,3] (the bits of
+        pointMeshDistance), with sqdist differentiable in both verts and points through torch.autograd: smplpp_point_mesh_distance
+        forward, smplpp_point_mesh_distance_vjp backward, on torch's current stream.  face and weights are not differentiable.
+        For a fixed-correspondence or point-to-plane (ICP-style) term, pass face and weights to ik.task_surface_differentiable,
+        which gives the position and normal of those surface points differentiably."""
+        if torch is None:
+            raise SmplppError(1, "point_mesh_distance_differentiable needs torch")
+        return _PointDistanceFunction.apply(verts, points, self)
+
     def out(self, index: int, path: str):
         """SMPL::out (src/SMPL.cpp:757-790): Wavefront OBJ of frame `index` (v lines, then 1-based f lines)."""
         verts = self._need("verts")
@@ -449,6 +517,29 @@ if torch is not None:
                 return None, None, None, None
             gv = ctx.smpl._normals_vjp(ctx.kind, verts, ctx.idt, grad, None)
             return gv, None, None, None
+
+    class _PointDistanceFunction(torch.autograd.Function):
+        """smplpp_point_mesh_distance forward / smplpp_point_mesh_distance_vjp backward (SMPL.point_mesh_distance_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, points, smpl):
+            c = _Call("point_mesh_distance_differentiable", verts, points, device_only=True)
+            verts, points, K = smpl._pmd_inputs(c, verts, points)
+            face, w, _, sq = smpl._pmd(c, verts, points, K, want_closest=False)
+            ctx.mark_non_differentiable(face, w)
+            ctx.smpl, ctx.K = smpl, K
+            ctx.save_for_backward(verts, points, face)
+            return face, w, sq
+
+        @staticmethod
+        def backward(ctx, grad_face, grad_weights, grad_sqdist):
+            verts, points, face = ctx.saved_tensors
+            want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if grad_sqdist is None or not (want_v or want_p):
+                return None, None, None
+            c = _Call("point_mesh_distance_differentiable", verts, device_only=True)
+            gv, gp = ctx.smpl._pmd_vjp(c, verts, points, ctx.K, face, grad_sqdist.contiguous(), None, None, want_v, want_p)
+            return gv, gp, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
