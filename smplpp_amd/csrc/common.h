@@ -6,7 +6,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/smplpp_hip.h"
@@ -164,32 +166,52 @@ inline int device_cus(int device) // compute units of a device (cached per devic
   return c;
 }
 
-// Growable device buffer
+// Owners of device memory: DevPtr for an exact-size array, DevBuf for a buffer grown on demand.
+struct HipFree
+{
+  void operator()(void * p) const { (void)hipFree(p); }
+};
+template<class T>
+using DevPtr = std::unique_ptr<T, HipFree>;
+// count elements of T (at least one: hipMalloc of 0 bytes gives no pointer)
+template<class T>
+hipError_t dev_alloc(DevPtr<T> & p, size_t count)
+{
+  T * raw = nullptr;
+  hipError_t e = hipMalloc((void **)&raw, sizeof(T) * (count ? count : 1));
+  p.reset(raw);
+  return e;
+}
+
+// Growable device buffer: a reserve that grows it frees the old allocation first and keeps 25 % slack
 struct DevBuf
 {
-  void * p = nullptr;
+  DevPtr<void> p;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf && o) noexcept : p(std::move(o.p)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf & operator=(DevBuf && o) noexcept
+  {
+    p = std::move(o.p);
+    cap = std::exchange(o.cap, 0);
+    return *this;
+  }
   hipError_t reserve(size_t bytes)
   {
     if(bytes <= cap) return hipSuccess;
-    if(p) (void)hipFree(p);
-    p = nullptr;
+    p.reset();
     cap = 0;
     size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc(&p, want);
+    void * raw = nullptr;
+    hipError_t e = hipMalloc(&raw, want);
+    p.reset(raw);
     if(e == hipSuccess) cap = want;
     return e;
-  }
-  void release()
-  {
-    if(p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
   }
   template<class T>
   T * as() const
   {
-    return static_cast<T *>(p);
+    return static_cast<T *>(p.get());
   }
 };
 
@@ -205,12 +227,21 @@ struct Workspace
   int64_t ldA = 0;
   DevBuf dummy;   // write-only sink for masked-off lanes of branch-free epilogues (skin_p.hip)
 };
-struct VjpState;                   // smplpp_fk_vjp's operand image and workspace (fk_vjp.hip), created by its first call
-void vjp_release(VjpState * s);
-struct NormalsVjpState;            // the normals' backward pass (mesh_vjp.hip), created by its first call
-void nvjp_release(NormalsVjpState * s);
-struct PointDistState;             // point-to-mesh distance and its backward pass (point_distance.hip), created by the first call
-void pd_release(PointDistState * s);
+// Per-feature state of a handle, created by the feature's first call on it and owned by the handle
+struct VjpState;        // smplpp_fk_vjp's operand image and workspace (fk_vjp.hip)
+struct NormalsVjpState; // the normals' backward pass (mesh_vjp.hip)
+struct PointDistState;  // point-to-mesh distance and its backward pass (point_distance.hip)
+struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
+// each overload is `delete s`, defined where its state is
+struct StateDelete
+{
+  void operator()(VjpState * s) const;
+  void operator()(NormalsVjpState * s) const;
+  void operator()(PointDistState * s) const;
+  void operator()(VPoserJxWork * s) const;
+};
+template<class T>
+using StatePtr = std::unique_ptr<T, StateDelete>;
 } // namespace smplpp_hip
 
 struct smplpp_model
@@ -221,44 +252,46 @@ struct smplpp_model
   int64_t ldB = 0;  // VGn * 96
   int maxw = 0;     // skinning weights kept per vertex: 4, 8 or 24
   // device arrays
-  float * Bm = nullptr;        // [KP][ldB]
-  uint8_t * B3 = nullptr;      // Bm as bf16x3 pieces in MFMA fragment order (layout above)
+  smplpp_hip::DevPtr<float> Bm; // [KP][ldB]
+  smplpp_hip::DevPtr<uint8_t> B3; // Bm as bf16x3 pieces in MFMA fragment order (layout above)
   int64_t VGPn = 0;            // vertex-group pairs: ceil(V / 64)
-  uint8_t * B2h = nullptr;     // bases + skinning weights as fp16x2 pieces in MFMA fragment order (layout above)
+  smplpp_hip::DevPtr<uint8_t> B2h; // bases + skinning weights as fp16x2 pieces in MFMA fragment order (layout above)
   float sB = 1.0f, sG = 1.0f;  // power-of-two scales of the basis operand and of the relative transforms (fp16 range)
-  int * range_flag = nullptr;  // device words [RANGE_SLOTS]: bit 0 = a launch of the fp16x2 form met an operand outside fp16's range
-  uint8_t * B3e = nullptr;     // bases + skinning tables of the exact form, one 20 KiB image per (vertex group, k-step) (layout above, EB_*)
+  smplpp_hip::DevPtr<int> range_flag; // device words [RANGE_SLOTS]: bit 0 = a launch of the fp16x2 form met an operand outside fp16's range
+  smplpp_hip::DevPtr<uint8_t> B3e; // bases + skinning tables of the exact form, one 20 KiB image per (vertex group, k-step) (layout above, EB_*)
   char form = 'e';             // fused-kernel form of smplpp_fk (SMPLPP_SKIN, read once at model creation): e | h | b | p | v
   char form_ik = 'h';          // ... of the IK / VPoser loops' internal launches (h unless SMPLPP_SKIN chose one form for everything)
-  uint8_t * wIdx = nullptr;    // [VGn*32][maxw]
-  float * wVal = nullptr;      // [VGn*32][maxw]
-  float * wSum = nullptr;      // [VGn*32]  sum_j W[v,j] in ascending j (the blended homogeneous w)
-  float * J0 = nullptr;        // [24][3]      Jreg . T
-  float * JS = nullptr;        // [24][3][10]  Jreg . S
-  float * JSp = nullptr;       // [72][12] the two once more, a 48-byte row per joint coordinate: [JS row (10) | J0 | 0] (pose_kernel: three 16-byte loads)
-  int32_t * parent = nullptr;  // [24]
-  int32_t * lvl = nullptr;     // [25 + 24] kinematic tree by depth: level offsets, then the joints sorted by level
+  smplpp_hip::DevPtr<uint8_t> wIdx; // [VGn*32][maxw]
+  smplpp_hip::DevPtr<float> wVal; // [VGn*32][maxw]
+  smplpp_hip::DevPtr<float> wSum; // [VGn*32]  sum_j W[v,j] in ascending j (the blended homogeneous w)
+  smplpp_hip::DevPtr<float> J0; // [24][3]      Jreg . T
+  smplpp_hip::DevPtr<float> JS; // [24][3][10]  Jreg . S
+  smplpp_hip::DevPtr<float> JSp; // [72][12] the two once more, a 48-byte row per joint coordinate: [JS row (10) | J0 | 0]
+                                 // (pose_kernel: three 16-byte loads)
+  smplpp_hip::DevPtr<int32_t> parent; // [24]
+  smplpp_hip::DevPtr<int32_t> lvl; // [25 + 24] kinematic tree by depth: level offsets, then the joints sorted by level
   int nlev = 0;
   bool chain_fast = false;     // lvl also holds the pose kernel's chain table: per chain lane (60) and level (CT_LEV) joint | parent << 8 | parent's slot << 16 (0xff = none)
-  int32_t * faces = nullptr;   // [F][3] 0-based
-  int32_t * adjOff = nullptr;  // [V+1]
-  int32_t * adjFace = nullptr; // [adjOff[V]] ascending face id per vertex
+  smplpp_hip::DevPtr<int32_t> faces; // [F][3] 0-based
+  smplpp_hip::DevPtr<int32_t> adjOff; // [V+1]
+  smplpp_hip::DevPtr<int32_t> adjFace; // [adjOff[V]] ascending face id per vertex
   int madj = smplpp_hip::MAXADJ;  // width of the IK ring tables below: MAXADJ, or MAXADJ_WIDE when some vertex has more than MAXADJ adjacent faces
-  uint16_t * faceRing = nullptr; // [F][3 (madj + 1) + 2] IK ring of a task on face f: count, the face's three vertices, then the distinct
-                                 // vertices of the faces adjacent to them in (vertex, adjacent face, corner) order (V <= 65535)
-  uint8_t * faceMap = nullptr;   // [F][3 madj 3] (vertex of the face, adjacent face, corner) -> slot in that ring
-  int32_t * anc = nullptr;       // [TREE_SIZE] tree tables of the IK evaluation (TREE_* above)
-  float * Wdense = nullptr;    // [V][24] original weights (stage entry points / IK)
-  float * Pvm = nullptr;       // [V][3][207] posedirs, vertex-major (IK Jacobian: pose-corrective term of a few vertices)
-  float * Svm = nullptr;       // [V][3][10]  shapedirs, vertex-major (IK Jacobian: beta columns)
+  smplpp_hip::DevPtr<uint16_t> faceRing; // [F][3 (madj + 1) + 2] IK ring of a task on face f: count, the face's three vertices, then the distinct
+                                         // vertices of the faces adjacent to them in (vertex, adjacent face, corner) order (V <= 65535)
+  smplpp_hip::DevPtr<uint8_t> faceMap; // [F][3 madj 3] (vertex of the face, adjacent face, corner) -> slot in that ring
+  smplpp_hip::DevPtr<int32_t> anc; // [TREE_SIZE] tree tables of the IK evaluation (TREE_* above)
+  smplpp_hip::DevPtr<float> Wdense; // [V][24] original weights (stage entry points / IK)
+  smplpp_hip::DevPtr<float> Pvm; // [V][3][207] posedirs, vertex-major (IK Jacobian: pose-corrective term of a few vertices)
+  smplpp_hip::DevPtr<float> Svm; // [V][3][10]  shapedirs, vertex-major (IK Jacobian: beta columns)
   // host mirrors
   std::vector<int32_t> h_parent, h_faces, h_adjOff, h_adjFace;
   // measurement hook (smplpp_profile_*)
   bool profiling = false;
   std::vector<hipEvent_t> prof_events; // begin/end pairs around the fused kernel
   smplpp_hip::Workspace ws;
-  smplpp_hip::VjpState * vjp = nullptr; // backward pass (smplpp_fk_vjp): null until its first call on the model
-  smplpp_hip::NormalsVjpState * nvjp = nullptr; // backward pass of the normal queries (mesh_vjp.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::VjpState> vjp; // backward pass (smplpp_fk_vjp): null until its first call on the model
+  smplpp_hip::StatePtr<smplpp_hip::NormalsVjpState> nvjp; // backward pass of the normal queries (mesh_vjp.hip): null until its first call
   char pd_form = 0;             // point-to-mesh distance form (SMPLPP_POINT_DISTANCE_FORM, read at model creation): 0 = by K | q | t
-  smplpp_hip::PointDistState * pd = nullptr; // point-to-mesh distance workspace (point_distance.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::PointDistState> pd; // point-to-mesh distance workspace (point_distance.hip): null until its first call
+  ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

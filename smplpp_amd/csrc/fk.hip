@@ -220,8 +220,8 @@ static hipError_t launch_skin(const smplpp_model * m, int64_t n, const float * t
     hipError_t e = lds_opt_in(once, m->device, reinterpret_cast<const void *>(&skin_kernel<FT, MAXW>), (int)shmem);
     if(e != hipSuccess) return e;
   }
-  skin_kernel<FT, MAXW><<<dim3(grid), dim3(256), shmem, st>>>(m->ws.AT.as<float>(), m->ws.ldA, m->Bm, m->ldB,
-                                                              m->ws.Gp.as<float>(), theta, m->wIdx, m->wVal, m->wSum, verts,
+  skin_kernel<FT, MAXW><<<dim3(grid), dim3(256), shmem, st>>>(m->ws.AT.as<float>(), m->ws.ldA, m->Bm.get(), m->ldB,
+                                                              m->ws.Gp.as<float>(), theta, m->wIdx.get(), m->wVal.get(), m->wSum.get(), verts,
                                                               rest, n, m->V, (int)m->VGn, nft);
   return hipGetLastError();
 }
@@ -257,12 +257,12 @@ PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const flo
   PoseArgs pa;
   pa.beta = beta;
   pa.theta = theta;
-  pa.J0 = m->J0;
-  pa.JS = m->JS;
-  pa.JSp = m->JSp;
-  pa.parent = m->parent;
-  pa.lvl_off = m->lvl;
-  pa.lvl_joint = m->lvl + NJ + 1;
+  pa.J0 = m->J0.get();
+  pa.JS = m->JS.get();
+  pa.JSp = m->JSp.get();
+  pa.parent = m->parent.get();
+  pa.lvl_off = m->lvl.get();
+  pa.lvl_joint = m->lvl.get() + NJ + 1;
   pa.nlev = m->nlev;
   pa.AT = nullptr;
   pa.ldA = 0;
@@ -275,8 +275,8 @@ PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const flo
   pa.A2h = with_ops ? ws.A2h.as<_Float16>() : nullptr;
   pa.G2h = with_ops ? ws.G2h.as<_Float16>() : nullptr;
   pa.gscale = m->sG;
-  pa.ctab = m->chain_fast ? m->lvl + CT_OFF : nullptr;
-  pa.range_flag = m->range_flag;
+  pa.ctab = m->chain_fast ? m->lvl.get() + CT_OFF : nullptr;
+  pa.range_flag = m->range_flag.get();
   return pa;
 }
 
@@ -355,7 +355,7 @@ static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * 
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if(m->profiling)
     {
-      // (owned by the handle from the moment they exist: smplpp_profile_read / smplpp_model_destroy release them)
+      // (owned by the handle from the moment they exist: smplpp_profile_read / the model's destructor release them)
       // (owned by the handle as a PAIR: a failed second creation must not leave the begin/end list misaligned)
       HIP_TRY(hipEventCreate(&e0));
       if(hipError_t ee = hipEventCreate(&e1); ee != hipSuccess)
@@ -390,7 +390,8 @@ int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * the
               float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word, char form_override = 0)
 {
   const char form = launch_form(m, n, range_slot, form_override);
-  int rc = fk_pose_device(m, form, n, beta, theta, joints, xforms44, poserot, st, range_word ? range_word : m->range_flag + range_slot, verts || rest);
+  int rc = fk_pose_device(m, form, n, beta, theta, joints, xforms44, poserot, st, range_word ? range_word : m->range_flag.get() + range_slot,
+                          verts || rest);
   if(rc) return rc;
   return fk_skin_device(m, form, n, theta, verts, rest, st);
 }
@@ -435,8 +436,8 @@ static int fk_range_status(smplpp_model * m, int * bits)
 {
   *bits = 0;
   if(!m->range_flag || m->form != 'h') return SMPLPP_OK;
-  HIP_TRY(hipMemcpy(bits, m->range_flag + RANGE_DEVICE, sizeof(int), hipMemcpyDeviceToHost));
-  if(*bits) HIP_TRY(hipMemset(m->range_flag + RANGE_DEVICE, 0, sizeof(int)));
+  HIP_TRY(hipMemcpy(bits, m->range_flag.get() + RANGE_DEVICE, sizeof(int), hipMemcpyDeviceToHost));
+  if(*bits) HIP_TRY(hipMemset(m->range_flag.get() + RANGE_DEVICE, 0, sizeof(int)));
   return SMPLPP_OK;
 }
 
@@ -471,7 +472,7 @@ extern "C" int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const 
   HIP_TRY(x.init(xforms, (size_t)n * NJ * 16, space, &ws.xf44));
   // this call's own range word: cleared in front of the launch, read back on the launch stream beside the results
   const bool ranged = m->range_flag && m->form == 'h';
-  if(ranged) HIP_TRY(hipMemsetAsync(m->range_flag + RANGE_HOST, 0, sizeof(int), st));
+  if(ranged) HIP_TRY(hipMemsetAsync(m->range_flag.get() + RANGE_HOST, 0, sizeof(int), st));
   int rc = fk_device(m, n, b.d, t.d, v.d, j.d, x.d, r.d, nullptr, st, RANGE_HOST, nullptr);
   if(rc) return rc;
   HIP_TRY(v.finish(st));
@@ -482,7 +483,7 @@ extern "C" int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const 
   // (read AFTER the synchronisation, synchronously: an asynchronous copy into this frame's stack could still be pending when one of
   // the copies above fails and the function returns)
   int bits = 0;
-  if(ranged) HIP_TRY(hipMemcpy(&bits, m->range_flag + RANGE_HOST, sizeof(int), hipMemcpyDeviceToHost));
+  if(ranged) HIP_TRY(hipMemcpy(&bits, m->range_flag.get() + RANGE_HOST, sizeof(int), hipMemcpyDeviceToHost));
   if(bits & 1)
     return fail(SMPLPP_ERR_NUMERIC, "smplpp_fk: an operand left the range of the fp16x2 form (|beta| < 1023, relative transforms within 16 x the "
                                     "template's extent): the vertices of such frames are not finite; create the model under SMPLPP_SKIN=b or p");

@@ -25,7 +25,7 @@
 //
 // Operand image BT [VGn*32*3][224] fp32, row (v, x) = [posedirs P[v][x][0..207) | shapedirs S[v][x][0..10) | 0 x 7]: the basis with
 // the vertex coordinates along K.  Built from the vertex-major bases the model keeps (Pvm / Svm; the K-major Bm is freed by the
-// default forms) on the first call on a model, freed by smplpp_model_destroy.
+// default forms) on the first call on a model, owned by the model's backward state.
 #include "common.h"
 #include "pose_body.h"
 #include "rodrigues_grad.h"
@@ -51,21 +51,15 @@ constexpr int VJ_DG = VJ_KN, VJ_ROOT = VJ_KN + NJ * 12, VJ_SLAB = VJ_ROOT + 8;
 
 struct VjpState
 {
-  float * BT = nullptr; // operand image (above)
+  DevPtr<float> BT;     // operand image (above)
   Workspace fws;        // the forward's workspace while smplpp_fk_vjp recomputes `rest` (smplpp_fk's own stays untouched)
-  int * range_word = nullptr; // where that recomputation reports an fp16x2 range miss (not smplpp_fk's words)
+  DevPtr<int> range_word; // where that recomputation reports an fp16x2 range miss (not smplpp_fk's words)
   DevBuf Gp, joints, rot, slab, rest;
   DevBuf beta, theta, gv, gj, gbeta, gtheta; // staging for host-space calls
 };
 
-void vjp_release(VjpState * s)
+void StateDelete::operator()(VjpState * s) const
 {
-  if(!s) return;
-  if(s->BT) (void)hipFree(s->BT);
-  if(s->range_word) (void)hipFree(s->range_word);
-  Workspace & w = s->fws;
-  for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
-  for(DevBuf * b : {&s->Gp, &s->joints, &s->rot, &s->slab, &s->rest, &s->beta, &s->theta, &s->gv, &s->gj, &s->gbeta, &s->gtheta}) b->release();
   delete s;
 }
 
@@ -412,8 +406,8 @@ template<int MAXW>
 static hipError_t launch_vjp_skin(const smplpp_model * m, const VjpState * s, int64_t n, const float * rest, const float * gv, float * slab,
                                   int nft, int nch, int gpc, hipStream_t st)
 {
-  vjp_skin_kernel<MAXW><<<dim3((unsigned)(nft * nch)), dim3(256), 0, st>>>(s->BT, s->Gp.as<float>(), rest, gv, m->wIdx, m->wVal, m->wSum,
-                                                                            m->Wdense, slab, n, m->V, (int)m->VGn, gpc, nft);
+  vjp_skin_kernel<MAXW><<<dim3((unsigned)(nft * nch)), dim3(256), 0, st>>>(s->BT.get(), s->Gp.as<float>(), rest, gv, m->wIdx.get(), m->wVal.get(),
+                                                                            m->wSum.get(), m->Wdense.get(), slab, n, m->V, (int)m->VGn, gpc, nft);
   return hipGetLastError();
 }
 
@@ -430,12 +424,12 @@ static void vjp_chunks(const smplpp_model * m, int64_t n, int & nft, int & nch, 
 static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * gv,
                       const float * gj, float * gbeta, float * gtheta, hipStream_t st)
 {
-  VjpState * s = m->vjp;
+  VjpState * s = m->vjp.get();
   if(!s->BT)
   {
     const int64_t rows = m->VGn * VG * 3;
-    HIP_TRY(hipMalloc((void **)&s->BT, sizeof(float) * (size_t)rows * VJ_KN));
-    vjp_image_kernel<<<dim3((unsigned)((rows * VJ_KN + 255) / 256)), dim3(256), 0, st>>>(m->Pvm, m->Svm, s->BT, m->V, rows);
+    HIP_TRY(dev_alloc(s->BT, (size_t)rows * VJ_KN));
+    vjp_image_kernel<<<dim3((unsigned)((rows * VJ_KN + 255) / 256)), dim3(256), 0, st>>>(m->Pvm.get(), m->Svm.get(), s->BT.get(), m->V, rows);
     HIP_TRY(hipGetLastError());
   }
   if(gv && !rest)
@@ -445,7 +439,7 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
     std::swap(m->ws, s->fws);
     const bool prof = m->profiling;
     m->profiling = false;
-    int rc = fk_device(m, n, beta, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), nullptr, st, RANGE_DEVICE, s->range_word);
+    int rc = fk_device(m, n, beta, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), nullptr, st, RANGE_DEVICE, s->range_word.get());
     m->profiling = prof;
     std::swap(m->ws, s->fws);
     if(rc) return rc;
@@ -476,7 +470,7 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
     }
   }
   vjp_chain_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(gv ? s->slab.as<float>() : nullptr, gv ? nch : 0, s->Gp.as<float>(),
-                                                           s->joints.as<float>(), s->rot.as<float>(), theta, gj, m->JS, m->parent,
+                                                           s->joints.as<float>(), s->rot.as<float>(), theta, gj, m->JS.get(), m->parent.get(),
                                                            gbeta, gtheta, n);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
@@ -497,23 +491,15 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
   TraceRange tr("backward SMPL");
   if(!m->vjp)
   {
-    VjpState * s = new VjpState();
-    if(hipError_t e = hipMalloc((void **)&s->range_word, sizeof(int)); e != hipSuccess)
-    {
-      vjp_release(s);
-      return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-    }
-    if(hipError_t e = hipMemset(s->range_word, 0, sizeof(int)); e != hipSuccess)
-    {
-      vjp_release(s);
-      return hip_fail(e, "hipMemset", __FILE__, __LINE__);
-    }
-    m->vjp = s;
+    StatePtr<VjpState> s(new VjpState());
+    HIP_TRY(dev_alloc(s->range_word, 1));
+    HIP_TRY(hipMemset(s->range_word.get(), 0, sizeof(int)));
+    m->vjp = std::move(s);
   }
   if(!grad_beta && !grad_theta) return SMPLPP_OK;
   if(space == SMPLPP_DEVICE) return vjp_device(m, n, beta, theta, rest, grad_verts, grad_joints, grad_beta, grad_theta, st);
 
-  VjpState * s = m->vjp;
+  VjpState * s = m->vjp.get();
   const size_t nb = (size_t)n * NB, nt = (size_t)n * (NJ + 1) * 3, nv = (size_t)n * m->V * 3;
   In<float> b, t, r, gv, gj;
   Out<float> gb, gt;

@@ -41,7 +41,7 @@ struct smplpp_ik
   int * range_word = nullptr; // this solver's own "an operand left the fp16x2 form's range" word (status bit 3): its loops' forward passes report here
   int32_t * roles = nullptr; // [DMAX][EVAL_NT] the chain-derivative entries of every thread of ik_eval_kernel (slot u: row u)
   float * list_d = nullptr;
-  std::vector<void *> owned;
+  std::vector<DevPtr<void>> owned; // what the raw pointers of this struct point to
   bool have_eval = false;
   // re-projection beside the solve: when no task's surface coordinates can move (phiLimit_ <= 0 everywhere, or the
   // motion stage's forced zero, node.cpp:699) the query points are the actual positions the evaluation already wrote,
@@ -75,7 +75,7 @@ struct smplpp_ik
   // decoder decodes with the exact-fp32 value kernel and makes vjac with the exact-fp32 Jacobian kernels (vposer_jac_exact.hip), on
   // the main stream, in this solver's own workspace jxw; latent_split is off
   bool exact = false;
-  VPoserJxWork * jxw = nullptr;
+  StatePtr<VPoserJxWork> jxw;
   bool jac_ahead = false; // the decoder Jacobian of the CURRENT configuration is (being) made on the side stream; the join flag follows it
   // development switches, read ONCE at creation (never in the per-call path): SMPLPP_DEBUG_SYNC, SMPLPP_IK_DBG_STOP,
   // SMPLPP_IK_OVERLAP=0 (re-projection behind the solve on one stream), SMPLPP_SCAN_BLOCKS
@@ -85,32 +85,42 @@ struct smplpp_ik
   int scan_form = -1; // development switch SMPLPP_SCAN_FORM (read at creation): 0 forces the K > 8 instantiations of the face scan
   float * vbuf[2] = {nullptr, nullptr};
   int vcur = 0;
+  ~smplpp_ik()
+  {
+    (void)hipSetDevice(m->device);
+    if(side) (void)hipStreamSynchronize(side);
+    if(ev_fork) (void)hipEventDestroy(ev_fork);
+    if(ev_join) (void)hipEventDestroy(ev_join);
+    if(side) (void)hipStreamDestroy(side);
+  }
 };
 
 template<class T>
 static hipError_t dalloc(smplpp_ik * s, T ** p, size_t count)
 {
-  hipError_t e = hipMalloc((void **)p, sizeof(T) * std::max<size_t>(count, 1));
-  if(e == hipSuccess) s->owned.push_back(*p);
+  DevPtr<T> d;
+  hipError_t e = dev_alloc(d, count);
+  *p = d.get();
+  if(e == hipSuccess) s->owned.emplace_back(std::move(d));
   return e;
 }
 
 static ModelView view_of(const smplpp_model * m)
 {
   ModelView mv;
-  mv.faces = m->faces;
-  mv.adjOff = m->adjOff;
-  mv.adjFace = m->adjFace;
-  mv.parent = m->parent;
-  mv.wIdx = m->wIdx;
-  mv.wVal = m->wVal;
-  mv.wSum = m->wSum;
-  mv.Pvm = m->Pvm;
-  mv.Svm = m->Svm;
-  mv.JS = m->JS;
-  mv.faceRing = m->faceRing;
-  mv.faceMap = m->faceMap;
-  mv.anc = m->anc;
+  mv.faces = m->faces.get();
+  mv.adjOff = m->adjOff.get();
+  mv.adjFace = m->adjFace.get();
+  mv.parent = m->parent.get();
+  mv.wIdx = m->wIdx.get();
+  mv.wVal = m->wVal.get();
+  mv.wSum = m->wSum.get();
+  mv.Pvm = m->Pvm.get();
+  mv.Svm = m->Svm.get();
+  mv.JS = m->JS.get();
+  mv.faceRing = m->faceRing.get();
+  mv.faceMap = m->faceMap.get();
+  mv.anc = m->anc.get();
   mv.nlev = m->nlev;
   mv.V = m->V;
   mv.maxw = m->maxw;
@@ -119,15 +129,7 @@ static ModelView view_of(const smplpp_model * m)
 
 extern "C" int smplpp_ik_destroy(smplpp_ik * s)
 {
-  if(!s) return SMPLPP_OK;
-  (void)hipSetDevice(s->m->device);
-  if(s->side) (void)hipStreamSynchronize(s->side);
-  if(s->ev_fork) (void)hipEventDestroy(s->ev_fork);
-  if(s->ev_join) (void)hipEventDestroy(s->ev_join);
-  if(s->side) (void)hipStreamDestroy(s->side);
-  for(void * p : s->owned) (void)hipFree(p);
-  vposer_jx_release(s->jxw);
-  delete s;
+  if(s) delete s;
   return SMPLPP_OK;
 }
 
@@ -197,7 +199,7 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
   // (a vertex with more than 16 adjacent faces — the widest table the evaluation is instantiated for — does not stop the solver from being created: position-only tasks anywhere and
   // normal-term tasks away from such a vertex are unaffected; a normal-term task that touches one is reported when it is evaluated)
   HIP_TRY(hipSetDevice(m->device));
-  smplpp_ik * s = new smplpp_ik();
+  std::unique_ptr<smplpp_ik> s(new smplpp_ik());
   s->m = m;
   s->vp = vposer;
   s->n = n;
@@ -224,73 +226,49 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
   }
   const size_t nk = (size_t)n * K;
   const size_t Dmax = TD75 + 2 * K + NB;
-#define A_(field, count)                                         \
-  do                                                             \
-  {                                                              \
-    hipError_t _e = dalloc(s, &s->field, (count));               \
-    if(_e != hipSuccess)                                         \
-    {                                                            \
-      int _rc = hip_fail(_e, #field, __FILE__, __LINE__);        \
-      smplpp_ik_destroy(s);                                      \
-      return _rc;                                                \
-    }                                                            \
-  } while(0)
-  A_(ta.face, nk);
-  A_(ta.vw, nk * 3);
-  A_(ta.tang, nk * 6);
-  A_(ta.tpos, nk * 3);
-  A_(ta.tnrm, nk * 3);
-  A_(ta.posw, nk);
-  A_(ta.nrmw, nk);
-  A_(ta.philim, nk);
-  A_(ta.noff, nk);
-  A_(ta.apos, nk * 3);
-  A_(ta.anrm, nk * 3);
-  A_(ta.hint, nk);
-  A_(ta.roww, nk * 2);
-  A_(theta, (size_t)n * s->theta_dim);
-  A_(beta, (size_t)n * NB);
-  A_(theta25, (size_t)n * 75);
-  A_(vbuf[0], (size_t)n * m->V * 3);
-  A_(vbuf[1], (size_t)n * m->V * 3);
-  A_(rest, (size_t)n * m->V * 3);
-  A_(joints, (size_t)n * NJ * 3);
-  A_(poserot, (size_t)n * NJ * 9);
-  A_(pts, nk * 3);
-  A_(e, nk * 4);
-  A_(J, nk * 4 * Dmax);
-  A_(e2, (size_t)n);
-  A_(xout, (size_t)n * Dmax);
-  A_(roles, roles.size());
-  A_(list_cnt, nk);
-  A_(list_d, nk * PROJ_LIST);
-  A_(list_f, nk * PROJ_LIST);
-  A_(skip, (size_t)n);
-  A_(status, (size_t)n);
-  A_(sticky, (size_t)n);
-  A_(range_word, 1);
+  HIP_TRY(dalloc(s.get(), &s->ta.face, nk));
+  HIP_TRY(dalloc(s.get(), &s->ta.vw, nk * 3));
+  HIP_TRY(dalloc(s.get(), &s->ta.tang, nk * 6));
+  HIP_TRY(dalloc(s.get(), &s->ta.tpos, nk * 3));
+  HIP_TRY(dalloc(s.get(), &s->ta.tnrm, nk * 3));
+  HIP_TRY(dalloc(s.get(), &s->ta.posw, nk));
+  HIP_TRY(dalloc(s.get(), &s->ta.nrmw, nk));
+  HIP_TRY(dalloc(s.get(), &s->ta.philim, nk));
+  HIP_TRY(dalloc(s.get(), &s->ta.noff, nk));
+  HIP_TRY(dalloc(s.get(), &s->ta.apos, nk * 3));
+  HIP_TRY(dalloc(s.get(), &s->ta.anrm, nk * 3));
+  HIP_TRY(dalloc(s.get(), &s->ta.hint, nk));
+  HIP_TRY(dalloc(s.get(), &s->ta.roww, nk * 2));
+  HIP_TRY(dalloc(s.get(), &s->theta, (size_t)n * s->theta_dim));
+  HIP_TRY(dalloc(s.get(), &s->beta, (size_t)n * NB));
+  HIP_TRY(dalloc(s.get(), &s->theta25, (size_t)n * 75));
+  HIP_TRY(dalloc(s.get(), &s->vbuf[0], (size_t)n * m->V * 3));
+  HIP_TRY(dalloc(s.get(), &s->vbuf[1], (size_t)n * m->V * 3));
+  HIP_TRY(dalloc(s.get(), &s->rest, (size_t)n * m->V * 3));
+  HIP_TRY(dalloc(s.get(), &s->joints, (size_t)n * NJ * 3));
+  HIP_TRY(dalloc(s.get(), &s->poserot, (size_t)n * NJ * 9));
+  HIP_TRY(dalloc(s.get(), &s->pts, nk * 3));
+  HIP_TRY(dalloc(s.get(), &s->e, nk * 4));
+  HIP_TRY(dalloc(s.get(), &s->J, nk * 4 * Dmax));
+  HIP_TRY(dalloc(s.get(), &s->e2, (size_t)n));
+  HIP_TRY(dalloc(s.get(), &s->xout, (size_t)n * Dmax));
+  HIP_TRY(dalloc(s.get(), &s->roles, roles.size()));
+  HIP_TRY(dalloc(s.get(), &s->list_cnt, nk));
+  HIP_TRY(dalloc(s.get(), &s->list_d, nk * PROJ_LIST));
+  HIP_TRY(dalloc(s.get(), &s->list_f, nk * PROJ_LIST));
+  HIP_TRY(dalloc(s.get(), &s->skip, (size_t)n));
+  HIP_TRY(dalloc(s.get(), &s->status, (size_t)n));
+  HIP_TRY(dalloc(s.get(), &s->sticky, (size_t)n));
+  HIP_TRY(dalloc(s.get(), &s->range_word, 1));
   s->ta.flags = s->sticky;
   if(vposer)
   {
-    A_(Jl, nk * 4 * Dmax);
-    A_(vjac, (size_t)n * 63 * 32);
+    HIP_TRY(dalloc(s.get(), &s->Jl, nk * 4 * Dmax));
+    HIP_TRY(dalloc(s.get(), &s->vjac, (size_t)n * 63 * 32));
   }
-#undef A_
-  // (from here on a failure releases the solver with everything it already owns: arrays, side stream, events)
-#define S_TRY(expr)                                            \
-  do                                                           \
-  {                                                            \
-    hipError_t _e = (expr);                                    \
-    if(_e != hipSuccess)                                       \
-    {                                                          \
-      int _rc = hip_fail(_e, #expr, __FILE__, __LINE__);       \
-      smplpp_ik_destroy(s);                                    \
-      return _rc;                                              \
-    }                                                          \
-  } while(0)
   // IkTask defaults (include/smplpp/IkTask.h:54-84)
   auto grid = [](size_t c) { return dim3((unsigned)((c + 255) / 256)); };
-  S_TRY(hipMemset(s->ta.face, 0, sizeof(int32_t) * nk));
+  HIP_TRY(hipMemset(s->ta.face, 0, sizeof(int32_t) * nk));
   fill_f32_kernel<<<grid(nk * 3), 256>>>(s->ta.vw, 1.0f / 3.0f, nk * 3);
   fill_f32_kernel<<<grid(nk * 6), 256>>>(s->ta.tang, 0.0f, nk * 6);
   fill_f32_kernel<<<grid(nk * 3), 256>>>(s->ta.tpos, 0.0f, nk * 3);
@@ -299,25 +277,25 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
   fill_f32_kernel<<<grid(nk), 256>>>(s->ta.nrmw, 1.0f, nk);
   fill_f32_kernel<<<grid(nk), 256>>>(s->ta.philim, 0.04f, nk);
   fill_f32_kernel<<<grid(nk), 256>>>(s->ta.noff, 0.0f, nk);
-  S_TRY(hipMemset(s->theta, 0, sizeof(float) * n * s->theta_dim));
-  S_TRY(hipMemset(s->theta25, 0, sizeof(float) * n * 75));
-  S_TRY(hipMemset(s->beta, 0, sizeof(float) * n * NB));
-  S_TRY(hipMemset(s->skip, 0, sizeof(int) * n));
-  S_TRY(hipMemcpy(s->roles, roles.data(), sizeof(int32_t) * roles.size(), hipMemcpyHostToDevice));
-  S_TRY(hipMemset(s->list_cnt, 0, sizeof(int) * nk));
-  S_TRY(hipMemset(s->status, 0, sizeof(int) * n));
-  S_TRY(hipMemset(s->sticky, 0, sizeof(int) * n));
-  S_TRY(hipMemset(s->range_word, 0, sizeof(int)));
+  HIP_TRY(hipMemset(s->theta, 0, sizeof(float) * n * s->theta_dim));
+  HIP_TRY(hipMemset(s->theta25, 0, sizeof(float) * n * 75));
+  HIP_TRY(hipMemset(s->beta, 0, sizeof(float) * n * NB));
+  HIP_TRY(hipMemset(s->skip, 0, sizeof(int) * n));
+  HIP_TRY(hipMemcpy(s->roles, roles.data(), sizeof(int32_t) * roles.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(s->list_cnt, 0, sizeof(int) * nk));
+  HIP_TRY(hipMemset(s->status, 0, sizeof(int) * n));
+  HIP_TRY(hipMemset(s->sticky, 0, sizeof(int) * n));
+  HIP_TRY(hipMemset(s->range_word, 0, sizeof(int)));
   s->verts = s->vbuf[0];
   // (default priority: a lowest-priority side stream — tried against the scan being dispatched ahead of the solve — halved the
   // latent-IK leg of bench.py, where several solvers' streams exist; what fixes that order is the solve kernel's own "all my
   // workgroups run" flag, see ik_solve_kernel)
-  S_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-  S_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-  S_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
+  HIP_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
   {
-    S_TRY(dalloc(s, &s->sig, 128));
-    S_TRY(hipMemset(s->sig, 0, sizeof(unsigned) * 128));
+    HIP_TRY(dalloc(s.get(), &s->sig, 128));
+    HIP_TRY(hipMemset(s->sig, 0, sizeof(unsigned) * 128));
     // stream memory operations are optional in HIP: probe once (flag 0 >= 0 is satisfied at once); SMPLPP_IK_EVENTS=1 keeps events
     const char * e = getenv("SMPLPP_IK_EVENTS");
     if(!(e && e[0] != '0'))
@@ -328,9 +306,8 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
     if(!s->use_flags) s->latent_split = false; // (the hand-overs of that schedule are flags)
     s->latent_split_default = s->latent_split;
   }
-  S_TRY(hipDeviceSynchronize());
-#undef S_TRY
-  *out = s;
+  HIP_TRY(hipDeviceSynchronize());
+  *out = s.release();
   return SMPLPP_OK;
 }
 
@@ -471,7 +448,7 @@ static int ik_forward_eval(smplpp_ik * s, int optimize_beta, int phi_live, int64
     TraceRange tr_fwd("forward SMPL"); // node.cpp:752-781 (the VPoser splice is inside that span there too)
     if(s->vp && s->exact) // node.cpp:761-772 in the reference's arithmetic: exact-fp32 value and Jacobian
     {
-      int rc = vposer_jacobian_device(s->vp, &s->jxw, n, s->theta + 6, TD44, s->theta25 + 6, 75, s->vjac, st);
+      int rc = vposer_jacobian_device(s->vp, s->jxw, n, s->theta + 6, TD44, s->theta25 + 6, 75, s->vjac, st);
       if(rc) return rc;
       th25 = s->theta25;
     }

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void winding_kernel(const float * __restrict__
 int closest_points_device(const smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
                           int64_t * face, float * closest, float * sqdist, hipStream_t st)
 {
-  closest_points_kernel<<<dim3((unsigned)(n * K)), dim3(256), 0, st>>>(verts, m->faces, points, face, closest, sqdist, m->V,
+  closest_points_kernel<<<dim3((unsigned)(n * K)), dim3(256), 0, st>>>(verts, m->faces.get(), points, face, closest, sqdist, m->V,
                                                                       m->F, K);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
@@ -187,9 +187,9 @@ static int normals_common(smplpp_model * m, int64_t n, const float * verts, int6
   HIP_TRY(o.init(normals, (size_t)n * count * 3, space));
   unsigned grid = (unsigned)((n * count + 127) / 128);
   if(vertex)
-    vertex_normals_kernel<<<dim3(grid), dim3(128), 0, st>>>(v.d, m->faces, m->adjOff, m->adjFace, id.d, o.d, m->V, count, n);
+    vertex_normals_kernel<<<dim3(grid), dim3(128), 0, st>>>(v.d, m->faces.get(), m->adjOff.get(), m->adjFace.get(), id.d, o.d, m->V, count, n);
   else
-    face_normals_kernel<<<dim3(grid), dim3(128), 0, st>>>(v.d, m->faces, id.d, o.d, m->V, count, n);
+    face_normals_kernel<<<dim3(grid), dim3(128), 0, st>>>(v.d, m->faces.get(), id.d, o.d, m->V, count, n);
   hipError_t e = hipGetLastError();
   if(e == hipSuccess) e = o.finish(st);
   if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
@@ -249,7 +249,8 @@ extern "C" int smplpp_mesh_vertex_normals(smplpp_model * m, int64_t n, const flo
   Out<float> o;
   HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st));
   HIP_TRY(o.init(normals, (size_t)n * m->V * 3, space));
-  mesh_vertex_normals_kernel<<<dim3((unsigned)((n * m->V + 255) / 256)), dim3(256), 0, st>>>(v.d, m->faces, m->adjOff, m->adjFace, o.d, m->V, n);
+  mesh_vertex_normals_kernel<<<dim3((unsigned)((n * m->V + 255) / 256)), dim3(256), 0, st>>>(v.d, m->faces.get(), m->adjOff.get(), m->adjFace.get(),
+                                                                                            o.d, m->V, n);
   hipError_t e = hipGetLastError();
   if(e == hipSuccess) e = o.finish(st);
   if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
@@ -271,14 +272,14 @@ extern "C" int smplpp_sweep_grid(smplpp_model * m, const float * verts, int32_t 
   hipStream_t st = static_cast<hipStream_t>(stream);
   In<float> v;
   HIP_TRY(v.init(verts, (size_t)m->V * 3, space, st));
-  DevBuf bb;
-  HIP_TRY(bb.reserve(sizeof(float) * 6));
-  bounds_kernel<<<dim3(1), dim3(1024), 0, st>>>(v.d, m->V, bb.as<float>());
+  DevPtr<float> bb;
+  HIP_TRY(dev_alloc(bb, 6));
+  bounds_kernel<<<dim3(1), dim3(1024), 0, st>>>(v.d, m->V, bb.get());
   float h[6];
   hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = hipMemcpyAsync(h, bb.p, sizeof(h), hipMemcpyDeviceToHost, st);
+  if(e == hipSuccess) e = hipMemcpyAsync(h, bb.get(), sizeof(h), hipMemcpyDeviceToHost, st);
   if(e == hipSuccess) e = hipStreamSynchronize(st);
-  bb.release();
+  bb.reset(); // (here, before the sweep's launches: freeing device memory waits for the device)
   HIP_TRY(e);
   const float scale = 0.025f; // GRID_SCALE
   int64_t total = 1;
@@ -302,8 +303,8 @@ extern "C" int smplpp_sweep_grid(smplpp_model * m, const float * verts, int32_t 
   Out<uint8_t> io;
   HIP_TRY(wo.init(winding, (size_t)todo, space));
   HIP_TRY(io.init(inside, (size_t)todo, space));
-  winding_kernel<<<dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, st>>>(v.d, m->faces, m->F, g0[0], g0[1], g0[2], gn[1], gn[2], todo, scale,
-                                                                            wo.d, io.d);
+  winding_kernel<<<dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, st>>>(v.d, m->faces.get(), m->F, g0[0], g0[1], g0[2], gn[1], gn[2], todo,
+                                                                            scale, wo.d, io.d);
   e = hipGetLastError();
   if(e == hipSuccess) e = wo.finish(st);
   if(e == hipSuccess) e = io.finish(st);

@@ -38,16 +38,8 @@ struct NormalsVjpState
   DevBuf ids, verts, gn, gv; // staging for host-space calls
   int maxdeg = -1;  // largest vertex valence of the model (host, measured on the first call)
 };
-void nvjp_release(NormalsVjpState * s)
+void StateDelete::operator()(NormalsVjpState * s) const
 {
-  if(!s) return;
-  s->G.release();
-  s->setup.release();
-  s->lbuf.release();
-  s->ids.release();
-  s->verts.release();
-  s->gn.release();
-  s->gv.release();
   delete s;
 }
 
@@ -347,9 +339,9 @@ static NormalsVjpState * nvjp_state(smplpp_model * m)
     int md = 0;
     for(int64_t v = 0; v < m->V; v++) md = std::max<int>(md, m->h_adjOff[v + 1] - m->h_adjOff[v]);
     s->maxdeg = md;
-    m->nvjp = s;
+    m->nvjp.reset(s);
   }
-  return m->nvjp;
+  return m->nvjp.get();
 }
 
 // all pointers on the device; gv already zeroed or holding what is accumulated into
@@ -363,15 +355,17 @@ static int mesh_vjp_device(smplpp_model * m, NormalsVjpState * s, int64_t n, con
   if(onchip && lds > 64 * 1024 && lds_opt_in(once, m->device, (const void *)mesh_vjp_lds_kernel, lds) != hipSuccess) onchip = false;
   if(onchip)
   {
-    mesh_vjp_lds_kernel<<<dim3((unsigned)n), dim3(1024), lds, st>>>(verts, gn, gv, m->faces, m->adjOff, m->adjFace, V, accumulate);
+    mesh_vjp_lds_kernel<<<dim3((unsigned)n), dim3(1024), lds, st>>>(verts, gn, gv, m->faces.get(), m->adjOff.get(), m->adjFace.get(), V,
+                                                                     accumulate);
     HIP_TRY(hipGetLastError());
     return SMPLPP_OK;
   }
   HIP_TRY(s->G.reserve(sizeof(float) * (size_t)n * V * 3));
   const unsigned grid = (unsigned)((n * V + 255) / 256);
-  mesh_vjp_g_kernel<<<dim3(grid), dim3(256), 0, st>>>(verts, gn, s->G.as<float>(), m->faces, m->adjOff, m->adjFace, V, n);
+  mesh_vjp_g_kernel<<<dim3(grid), dim3(256), 0, st>>>(verts, gn, s->G.as<float>(), m->faces.get(), m->adjOff.get(), m->adjFace.get(), V, n);
   HIP_TRY(hipGetLastError());
-  mesh_vjp_gather_kernel<<<dim3(grid), dim3(256), 0, st>>>(verts, s->G.as<float>(), gv, m->faces, m->adjOff, m->adjFace, V, n, accumulate);
+  mesh_vjp_gather_kernel<<<dim3(grid), dim3(256), 0, st>>>(verts, s->G.as<float>(), gv, m->faces.get(), m->adjOff.get(), m->adjFace.get(), V, n,
+                                                           accumulate);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -386,7 +380,7 @@ static int list_vjp_device(smplpp_model * m, NormalsVjpState * s, int64_t n, con
   HIP_TRY(s->setup.reserve(sizeof(int32_t) * words));
   int32_t * w = s->setup.as<int32_t>();
   ListSetup ls{w, w + 4, w + 4 + Pmax, w + 4 + 2 * Pmax, w + 4 + 2 * Pmax + Rmax, w + 4 + 2 * Pmax + 2 * Rmax, w + 4 + 2 * Pmax + 3 * Rmax};
-  list_pairs_kernel<<<dim3(1), dim3(256), 0, st>>>(ids, count, vertex ? 1 : 0, m->faces, m->adjOff, m->adjFace, m->V, m->F, ls);
+  list_pairs_kernel<<<dim3(1), dim3(256), 0, st>>>(ids, count, vertex ? 1 : 0, m->faces.get(), m->adjOff.get(), m->adjFace.get(), m->V, m->F, ls);
   HIP_TRY(hipGetLastError());
   if(Rmax > 0)
   {
@@ -399,13 +393,13 @@ static int list_vjp_device(smplpp_model * m, NormalsVjpState * s, int64_t n, con
   const int64_t buf_floats = (vertex ? 3 * count : 0) + 6 * Pmax + 2 * Rmax;
   const int64_t bytes = buf_floats * (int64_t)sizeof(float);
   if(bytes <= LIST_LDS_BYTES && !staged_forced())
-    list_vjp_lds_kernel<<<dim3((unsigned)n), dim3(256), (unsigned)bytes, st>>>(verts, gn, gv, ids, count, vertex ? 1 : 0, m->faces, m->adjOff,
-                                                                               m->adjFace, m->V, ls, Pmax, accumulate);
+    list_vjp_lds_kernel<<<dim3((unsigned)n), dim3(256), (unsigned)bytes, st>>>(verts, gn, gv, ids, count, vertex ? 1 : 0, m->faces.get(),
+                                                                               m->adjOff.get(), m->adjFace.get(), m->V, ls, Pmax, accumulate);
   else
   {
     HIP_TRY(s->lbuf.reserve(sizeof(float) * (size_t)n * (size_t)buf_floats + 16));
-    list_vjp_ws_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(verts, gn, gv, ids, count, vertex ? 1 : 0, m->faces, m->adjOff, m->adjFace, m->V,
-                                                                ls, Pmax, accumulate, s->lbuf.as<float>(), buf_floats);
+    list_vjp_ws_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(verts, gn, gv, ids, count, vertex ? 1 : 0, m->faces.get(), m->adjOff.get(),
+                                                                m->adjFace.get(), m->V, ls, Pmax, accumulate, s->lbuf.as<float>(), buf_floats);
   }
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;

@@ -249,11 +249,11 @@ __global__ void pack_regressor_rows_kernel(const float * __restrict__ J0, const 
 }
 
 template<class T>
-static hipError_t upload(T ** dst, const T * src, size_t count)
+static hipError_t upload(DevPtr<T> & dst, const T * src, size_t count)
 {
-  hipError_t e = hipMalloc((void **)dst, sizeof(T) * std::max<size_t>(count, 1));
+  hipError_t e = dev_alloc(dst, count);
   if(e != hipSuccess) return e;
-  if(count) e = hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice);
+  if(count) e = hipMemcpy(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice);
   return e;
 }
 } // namespace smplpp_hip
@@ -280,21 +280,15 @@ extern "C" int smplpp_device_count(int * count)
   return SMPLPP_OK;
 }
 
+smplpp_model::~smplpp_model()
+{
+  (void)hipSetDevice(device);
+  for(hipEvent_t e : prof_events) (void)hipEventDestroy(e);
+}
+
 extern "C" int smplpp_model_destroy(smplpp_model * m)
 {
-  if(!m) return SMPLPP_OK;
-  (void)hipSetDevice(m->device);
-  for(hipEvent_t e : m->prof_events) (void)hipEventDestroy(e);
-  m->prof_events.clear();
-  void * ptrs[] = {m->Bm, m->B3, m->B3e, m->B2h, m->range_flag, m->lvl, m->wIdx, m->wVal, m->wSum, m->J0, m->JS, m->JSp, m->parent, m->faces, m->adjOff, m->adjFace, m->Wdense, m->Pvm, m->Svm, m->faceRing, m->faceMap, m->anc};
-  for(void * p : ptrs)
-    if(p) (void)hipFree(p);
-  Workspace & w = m->ws;
-  for(DevBuf * b : {&w.AT, &w.A3, &w.A2h, &w.G2h, &w.Gp, &w.joints, &w.beta, &w.theta, &w.verts, &w.rest, &w.xf44, &w.dummy}) b->release();
-  vjp_release(m->vjp);
-  nvjp_release(m->nvjp);
-  pd_release(m->pd);
-  delete m;
+  if(m) delete m;
   return SMPLPP_OK;
 }
 
@@ -322,25 +316,13 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
     if(faces1[i] < 1 || faces1[i] > V) return fail(SMPLPP_ERR_INVALID, "face_indices must be 1-based vertex ids");
 
   HIP_TRY(hipSetDevice(device));
-  smplpp_model * m = new smplpp_model();
+  std::unique_ptr<smplpp_model> m(new smplpp_model());
   m->device = device;
   m->V = V;
   m->F = F;
   m->VGn = (V + VG - 1) / VG;
   m->ldB = m->VGn * 3 * VG;
   m->h_parent = parent;
-
-#define TRY_OR_FREE(expr)                                      \
-  do                                                           \
-  {                                                            \
-    hipError_t _e = (expr);                                    \
-    if(_e != hipSuccess)                                       \
-    {                                                          \
-      int _rc = hip_fail(_e, #expr, __FILE__, __LINE__);       \
-      smplpp_model_destroy(m);                                 \
-      return _rc;                                              \
-    }                                                          \
-  } while(0)
 
   // --- blend bases -> Bm, regressor fold (device side; the raw arrays are only needed transiently) ---
   // Form of the fused kernel: read once, here.  Default: smplpp_fk runs e (skin_e.hip: fp32-exact operands, the reference's
@@ -362,37 +344,18 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
     m->pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
   }
   auto uses = [&](char f) { return m->form == f || m->form_ik == f; };
-  // (the vertex-major uploads are owned by the handle from the start, so a failure below frees them with it)
-  TRY_OR_FREE(upload(&m->Pvm, P, (size_t)V * 3 * NP)); // kept: vertex-major copies serve the sparse IK Jacobian (contiguous 2.5 KB per vertex)
-  TRY_OR_FREE(upload(&m->Svm, S, (size_t)V * 3 * NB));
-  DevBuf dT, dJreg;
-  auto free_tmp = [&]() {
-    dT.release();
-    dJreg.release();
-  };
-#define TRY_TMP(expr)                                          \
-  do                                                           \
-  {                                                            \
-    hipError_t _e = (expr);                                    \
-    if(_e != hipSuccess)                                       \
-    {                                                          \
-      int _rc = hip_fail(_e, #expr, __FILE__, __LINE__);       \
-      free_tmp();                                              \
-      smplpp_model_destroy(m);                                 \
-      return _rc;                                              \
-    }                                                          \
-  } while(0)
-  TRY_TMP(dT.reserve(sizeof(float) * (size_t)V * 3));
-  TRY_TMP(dJreg.reserve(sizeof(float) * (size_t)NJ * V));
-  TRY_TMP(hipMemcpy(dT.p, vt, sizeof(float) * (size_t)V * 3, hipMemcpyHostToDevice));
-  TRY_TMP(hipMemcpy(dJreg.p, Jreg, sizeof(float) * (size_t)NJ * V, hipMemcpyHostToDevice));
-  TRY_TMP(hipMalloc((void **)&m->Bm, sizeof(float) * (size_t)KP * m->ldB));
-  TRY_TMP(hipMalloc((void **)&m->J0, sizeof(float) * NJ * 3));
-  TRY_TMP(hipMalloc((void **)&m->JS, sizeof(float) * NJ * 3 * NB));
-  relayout_basis_kernel<<<dim3((unsigned)((m->ldB + 255) / 256)), dim3(256)>>>(m->Pvm, m->Svm, dT.as<float>(), m->Bm, V, m->ldB);
-  fold_regressor_kernel<<<dim3(NJ * 3 * (NB + 1)), dim3(256)>>>(dJreg.as<float>(), m->Svm, dT.as<float>(), m->J0, m->JS, V);
-  TRY_TMP(hipMalloc((void **)&m->JSp, sizeof(float) * NJ * 3 * 12));
-  pack_regressor_rows_kernel<<<dim3(1), dim3(NJ * 3)>>>(m->J0, m->JS, m->JSp);
+  HIP_TRY(upload(m->Pvm, P, (size_t)V * 3 * NP)); // kept: vertex-major copies serve the sparse IK Jacobian (contiguous 2.5 KB per vertex)
+  HIP_TRY(upload(m->Svm, S, (size_t)V * 3 * NB));
+  DevPtr<float> dT, dJreg;
+  HIP_TRY(upload(dT, vt, (size_t)V * 3));
+  HIP_TRY(upload(dJreg, Jreg, (size_t)NJ * V));
+  HIP_TRY(dev_alloc(m->Bm, (size_t)KP * m->ldB));
+  HIP_TRY(dev_alloc(m->J0, NJ * 3));
+  HIP_TRY(dev_alloc(m->JS, NJ * 3 * NB));
+  relayout_basis_kernel<<<dim3((unsigned)((m->ldB + 255) / 256)), dim3(256)>>>(m->Pvm.get(), m->Svm.get(), dT.get(), m->Bm.get(), V, m->ldB);
+  fold_regressor_kernel<<<dim3(NJ * 3 * (NB + 1)), dim3(256)>>>(dJreg.get(), m->Svm.get(), dT.get(), m->J0.get(), m->JS.get(), V);
+  HIP_TRY(dev_alloc(m->JSp, NJ * 3 * 12));
+  pack_regressor_rows_kernel<<<dim3(1), dim3(NJ * 3)>>>(m->J0.get(), m->JS.get(), m->JSp.get());
   m->VGPn = (V + 63) / 64;
   // the split-operand kernels address their basis images with 32-bit buffer offsets: a mesh whose image would reach 2 GiB
   // (more than ~745k vertices for h, ~410k for b) takes the first form (64-bit addressing) from creation on
@@ -404,15 +367,15 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   }
   if(uses('b') || uses('e')) // (e falls back to b for models with 5..8 weights per vertex: decided below, once they are counted)
   {
-    TRY_TMP(hipMalloc((void **)&m->B3, (size_t)m->VGPn * BB_KS * BB_B_BYTES));
+    HIP_TRY(dev_alloc(m->B3, (size_t)m->VGPn * BB_KS * BB_B_BYTES));
     const int64_t cnt = m->VGPn * BB_KS * 6 * 64;
-    relayout_basis_bf16x3_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm, m->ldB, V, m->VGPn,
-                                                                                  reinterpret_cast<uint16_t *>(m->B3));
+    relayout_basis_bf16x3_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm.get(), m->ldB, V, m->VGPn,
+                                                                                  reinterpret_cast<uint16_t *>(m->B3.get()));
   }
-  TRY_TMP(hipGetLastError());
-  TRY_TMP(hipDeviceSynchronize());
-  free_tmp();
-#undef TRY_TMP
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  dT.reset(); // (here, before the launches below: freeing device memory waits for the device)
+  dJreg.reset();
 
   // --- skinning weights: keep the non-zeros (real SMPL has <= 4 per vertex), dense fallback otherwise ---
   int maxnz = 0;
@@ -448,10 +411,10 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
     }
     hSum[v] = s;
   }
-  TRY_OR_FREE(upload(&m->wIdx, hIdx.data(), hIdx.size()));
-  TRY_OR_FREE(upload(&m->wVal, hVal.data(), hVal.size()));
-  TRY_OR_FREE(upload(&m->wSum, hSum.data(), hSum.size()));
-  TRY_OR_FREE(upload(&m->Wdense, W, (size_t)V * NJ));
+  HIP_TRY(upload(m->wIdx, hIdx.data(), hIdx.size()));
+  HIP_TRY(upload(m->wVal, hVal.data(), hVal.size()));
+  HIP_TRY(upload(m->wSum, hSum.data(), hSum.size()));
+  HIP_TRY(upload(m->Wdense, W, (size_t)V * NJ));
   // e keeps at most 4 weights per vertex in registers, b and p at most 8: a model with more takes the next form from here on
   // (decided once, so that the layouts kept below are the ones the launches will read)
   for(char * f : {&m->form, &m->form_ik})
@@ -461,13 +424,14 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   }
   if(uses('e'))
   {
-    TRY_OR_FREE(hipMalloc((void **)&m->B3e, (size_t)m->VGPn * EB_KS * EB_IMG));
-    TRY_OR_FREE(hipMemset(m->B3e, 0, (size_t)m->VGPn * EB_KS * EB_IMG));
+    HIP_TRY(dev_alloc(m->B3e, (size_t)m->VGPn * EB_KS * EB_IMG));
+    HIP_TRY(hipMemset(m->B3e.get(), 0, (size_t)m->VGPn * EB_KS * EB_IMG));
     const int64_t cnt = m->VGPn * EB_KS * 6 * 64;
-    relayout_basis_exact_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm, m->ldB, V, m->VGPn, m->B3e);
-    skin_tables_exact_kernel<<<dim3((unsigned)((m->VGPn * 64 + 255) / 256)), dim3(256)>>>(m->wIdx, m->wVal, m->wSum, m->maxw, V, m->VGPn, m->B3e);
-    TRY_OR_FREE(hipGetLastError());
-    TRY_OR_FREE(hipDeviceSynchronize());
+    relayout_basis_exact_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm.get(), m->ldB, V, m->VGPn, m->B3e.get());
+    skin_tables_exact_kernel<<<dim3((unsigned)((m->VGPn * 64 + 255) / 256)), dim3(256)>>>(m->wIdx.get(), m->wVal.get(), m->wSum.get(), m->maxw, V,
+                                                                                       m->VGPn, m->B3e.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
   }
   if(uses('h'))
   {
@@ -479,14 +443,10 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
     for(int64_t i = 0; i < V * 3 * NB; i++) bmax = std::max(bmax, std::fabs(S[i]));
     for(int64_t i = 0; i < V * 3; i++) tmax = std::max(tmax, std::fabs(vt[i]));
     bmax = std::max(bmax, tmax);
-    if(!(bmax > 0.0f) || !std::isfinite(bmax))
-    {
-      smplpp_model_destroy(m);
-      return fail(SMPLPP_ERR_INVALID, "Cannot initialize a SMPL model!");
-    }
+    if(!(bmax > 0.0f) || !std::isfinite(bmax)) return fail(SMPLPP_ERR_INVALID, "Cannot initialize a SMPL model!");
     m->sB = std::exp2(std::floor(std::log2(32768.0f / bmax)));
     m->sG = std::exp2(std::floor(std::log2(32768.0f / (16.0f * tmax > 1.0f ? 16.0f * tmax : 1.0f))));
-    TRY_OR_FREE(hipMalloc((void **)&m->B2h, (size_t)m->VGPn * HB_SLOTS * HB_IMG));
+    HIP_TRY(dev_alloc(m->B2h, (size_t)m->VGPn * HB_SLOTS * HB_IMG));
     // Vertex groups by skinning class (common.h, HB_PERM_OFF).  (1) A group is 64 CONSECUTIVE vertices and its class what their
     // weights touch — joints 0..15 only, both halves, joints 16..23 only.  (Sorting the VERTICES by class first, which makes 73 of
     // the synthetic model's 108 groups single-class instead of 11, was measured: the step went from 46 to 62 us — a group's 64
@@ -546,34 +506,21 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
         }
       }
     }
-    DevBuf dPerm, dFlags;
-    TRY_OR_FREE(dPerm.reserve(sizeof(int32_t) * hperm.size()));
-    TRY_OR_FREE(dFlags.reserve(sizeof(int32_t) * gflags.size()));
-    TRY_OR_FREE(hipMemcpy(dPerm.p, hperm.data(), sizeof(int32_t) * hperm.size(), hipMemcpyHostToDevice));
-    TRY_OR_FREE(hipMemcpy(dFlags.p, gflags.data(), sizeof(int32_t) * gflags.size(), hipMemcpyHostToDevice));
+    DevPtr<int32_t> dPerm, dFlags;
+    HIP_TRY(upload(dPerm, hperm.data(), hperm.size()));
+    HIP_TRY(upload(dFlags, gflags.data(), gflags.size()));
     const int64_t cnt = m->VGPn * (HB_KS * 6 * 64 + 4 * 64 + 64);
-    relayout_basis_f16x2_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm, m->ldB, m->Wdense, m->wSum, V, m->VGPn,
-                                                                                 m->sB, m->sG, m->B2h, dPerm.as<int32_t>(), dFlags.as<int32_t>());
-    hipError_t le = hipGetLastError();
-    if(le == hipSuccess) le = hipDeviceSynchronize();
-    dPerm.release();
-    dFlags.release();
-    TRY_OR_FREE(le);
+    relayout_basis_f16x2_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm.get(), m->ldB, m->Wdense.get(), m->wSum.get(), V,
+                                                                                 m->VGPn, m->sB, m->sG, m->B2h.get(), dPerm.get(), dFlags.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
   }
-  if(!uses('b') && m->B3)
-  {
-    (void)hipFree(m->B3);
-    m->B3 = nullptr;
-  }
-  if(!uses('p') && !uses('v'))
-  {
-    (void)hipFree(m->Bm); // only the fp32-MFMA forms read the K-major fp32 basis
-    m->Bm = nullptr;
-  }
-  TRY_OR_FREE(upload(&m->parent, parent.data(), parent.size()));
+  if(!uses('b')) m->B3.reset();
+  if(!uses('p') && !uses('v')) m->Bm.reset(); // only the fp32-MFMA forms read the K-major fp32 basis
+  HIP_TRY(upload(m->parent, parent.data(), parent.size()));
   {
     const int zero[RANGE_SLOTS] = {};
-    TRY_OR_FREE(upload(&m->range_flag, zero, RANGE_SLOTS));
+    HIP_TRY(upload(m->range_flag, zero, RANGE_SLOTS));
   }
   {
     // joints by depth: the FK chain advances one tree level per step (SMPL: 9 levels)
@@ -625,7 +572,7 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
         }
       }
     }
-    TRY_OR_FREE(upload(&m->lvl, lv.data(), lv.size()));
+    HIP_TRY(upload(m->lvl, lv.data(), lv.size()));
   }
 
   // --- faces + adjacency (src/SMPL.cpp:620-640; emplace keeps one entry per (vertex, face)) ---
@@ -642,9 +589,9 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   for(int64_t v = 0; v < V; v++) m->h_adjOff[v + 1] = m->h_adjOff[v] + (int32_t)adj[v].size();
   m->h_adjFace.reserve((size_t)m->h_adjOff[V]);
   for(int64_t v = 0; v < V; v++) m->h_adjFace.insert(m->h_adjFace.end(), adj[v].begin(), adj[v].end());
-  TRY_OR_FREE(upload(&m->faces, m->h_faces.data(), m->h_faces.size()));
-  TRY_OR_FREE(upload(&m->adjOff, m->h_adjOff.data(), m->h_adjOff.size()));
-  TRY_OR_FREE(upload(&m->adjFace, m->h_adjFace.data(), m->h_adjFace.size()));
+  HIP_TRY(upload(m->faces, m->h_faces.data(), m->h_faces.size()));
+  HIP_TRY(upload(m->adjOff, m->h_adjOff.data(), m->h_adjOff.size()));
+  HIP_TRY(upload(m->adjFace, m->h_adjFace.data(), m->h_adjFace.size()));
   {
     // tree tables of the IK evaluation (common.h TREE_*); trees deeper than TREE_DMAX keep the masks only (smplpp_ik_create
     // refuses them)
@@ -661,7 +608,7 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
       for(int i = 0; i < NJ && L < TREE_DMAX; i++)
         if(depth[i] == L) tr[TREE_LVLJ + pos++] = i;
     }
-    TRY_OR_FREE(upload(&m->anc, tr.data(), tr.size()));
+    HIP_TRY(upload(m->anc, tr.data(), tr.size()));
   }
   if(V <= 65535 && F > 0)
   {
@@ -703,11 +650,10 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
       }
       rg[0] = (uint16_t)nr;
     }
-    TRY_OR_FREE(upload(&m->faceRing, ring.data(), ring.size()));
-    TRY_OR_FREE(upload(&m->faceMap, map.data(), map.size()));
+    HIP_TRY(upload(m->faceRing, ring.data(), ring.size()));
+    HIP_TRY(upload(m->faceMap, map.data(), map.size()));
   }
-#undef TRY_OR_FREE
-  *out = m;
+  *out = m.release();
   return SMPLPP_OK;
 }
 

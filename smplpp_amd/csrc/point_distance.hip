@@ -43,12 +43,8 @@ struct PointDistState
   int64_t nseed = -1;
   DevBuf verts, points, face, weights, closest, sqdist, gsq, gv, gp; // staging for host-space calls
 };
-void pd_release(PointDistState * s)
+void StateDelete::operator()(PointDistState * s) const
 {
-  if(!s) return;
-  for(DevBuf * b : {&s->tri, &s->perm, &s->rec, &s->seedv, &s->verts, &s->points, &s->face, &s->weights, &s->closest, &s->sqdist, &s->gsq,
-                    &s->gv, &s->gp})
-    b->release();
   delete s;
 }
 
@@ -472,8 +468,8 @@ __global__ __launch_bounds__(256) void pd_vjp_gather_kernel(const PdRecord * __r
 
 static PointDistState * pd_state(smplpp_model * m)
 {
-  if(!m->pd) m->pd = new PointDistState();
-  return m->pd;
+  if(!m->pd) m->pd.reset(new PointDistState());
+  return m->pd.get();
 }
 
 static int pd_seed_setup(smplpp_model * m, PointDistState * s)
@@ -483,7 +479,7 @@ static int pd_seed_setup(smplpp_model * m, PointDistState * s)
   for(int64_t v = 0; v < m->V; v++)
     if(m->h_adjOff[v + 1] > m->h_adjOff[v]) ids.push_back((int32_t)v);
   HIP_TRY(s->seedv.reserve(sizeof(int32_t) * (ids.size() + 1)));
-  if(!ids.empty()) HIP_TRY(hipMemcpy(s->seedv.p, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
+  if(!ids.empty()) HIP_TRY(hipMemcpy(s->seedv.as<int32_t>(), ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
   s->nseed = (int64_t)ids.size();
   return SMPLPP_OK;
 }
@@ -496,7 +492,7 @@ static int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, co
   const int64_t V = m->V, F = m->F;
   if(!tiled)
   {
-    pd_query_kernel<<<dim3((unsigned)(n * K)), dim3(256), 0, st>>>(verts, m->faces, points, face, weights, closest, sqdist, V, F, K);
+    pd_query_kernel<<<dim3((unsigned)(n * K)), dim3(256), 0, st>>>(verts, m->faces.get(), points, face, weights, closest, sqdist, V, F, K);
     HIP_TRY(hipGetLastError());
     return SMPLPP_OK;
   }
@@ -504,7 +500,7 @@ static int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, co
   if(rc) return rc;
   HIP_TRY(s->tri.reserve(sizeof(float4) * (size_t)n * F * 3));
   HIP_TRY(s->perm.reserve(sizeof(int32_t) * (size_t)n * K));
-  pd_tri_image_kernel<<<dim3((unsigned)((n * F + 255) / 256)), dim3(256), 0, st>>>(verts, m->faces, s->tri.as<float4>(), V, F, n);
+  pd_tri_image_kernel<<<dim3((unsigned)((n * F + 255) / 256)), dim3(256), 0, st>>>(verts, m->faces.get(), s->tri.as<float4>(), V, F, n);
   HIP_TRY(hipGetLastError());
   pd_sort_kernel<<<dim3((unsigned)n), dim3(1024), 0, st>>>(points, s->perm.as<int32_t>(), K);
   HIP_TRY(hipGetLastError());
@@ -525,7 +521,7 @@ static int pd_vjp_device(smplpp_model * m, PointDistState * s, int64_t n, const 
     HIP_TRY(s->rec.reserve(sizeof(PdRecord) * (size_t)nk));
     rec = s->rec.as<PdRecord>();
   }
-  pd_vjp_record_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(verts, m->faces, points, face, gsq, rec, gp, accumulate, V,
+  pd_vjp_record_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(verts, m->faces.get(), points, face, gsq, rec, gp, accumulate, V,
                                                                                  m->F, K, nk);
   HIP_TRY(hipGetLastError());
   if(gv)

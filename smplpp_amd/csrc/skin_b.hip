@@ -591,8 +591,8 @@ static hipError_t launch_b(const smplpp_model * m, int64_t n, const float * thet
   }
   // f_off (a multiple of 64): first frame of this launch inside the workspace / caller arrays of a longer batch
   skin_kernel_b<MAXW, WANT_REST><<<dim3(blocks), dim3(256), B_LDS_TOTAL, st>>>(
-      m->ws.A3.as<uint8_t>() + (f_off / 64) * (int64_t)(BB_KS * BB_A_BYTES), m->B3, m->ws.Gp.as<float>() + f_off * (NJ * 12),
-      theta + f_off * ((NJ + 1) * 3), m->wIdx, m->wVal, m->wSum, verts ? verts + f_off * m->V * 3 : nullptr,
+      m->ws.A3.as<uint8_t>() + (f_off / 64) * (int64_t)(BB_KS * BB_A_BYTES), m->B3.get(), m->ws.Gp.as<float>() + f_off * (NJ * 12),
+      theta + f_off * ((NJ + 1) * 3), m->wIdx.get(), m->wVal.get(), m->wSum.get(), verts ? verts + f_off * m->V * 3 : nullptr,
       rest ? rest + f_off * m->V * 3 : nullptr, n, m->V, nvgp, nftp, ipb);
   return hipGetLastError();
 }

@@ -677,7 +677,7 @@ static hipError_t launch_e(const smplpp_model * m, int64_t n, const float * thet
   }
   // f_off (a multiple of 64): first frame of this launch inside the workspace / caller arrays of a longer batch
   skin_kernel_e<MAXW, WANT_REST><<<dim3(nbx * 8), dim3(256), E_LDS_TOTAL, st>>>(
-      m->ws.A3.as<uint8_t>() + (f_off / 64) * (int64_t)(BB_KS * BB_A_BYTES), m->B3e, m->ws.Gp.as<float>() + f_off * (NJ * 12),
+      m->ws.A3.as<uint8_t>() + (f_off / 64) * (int64_t)(BB_KS * BB_A_BYTES), m->B3e.get(), m->ws.Gp.as<float>() + f_off * (NJ * 12),
       theta + f_off * ((NJ + 1) * 3), verts ? verts + f_off * m->V * 3 : nullptr, rest ? rest + f_off * m->V * 3 : nullptr, n, m->V, nvg, nft);
   return hipGetLastError();
 }

@@ -590,9 +590,9 @@ static hipError_t launch_h(const smplpp_model * m, int64_t n, const float * thet
   float * vo = verts ? verts + f_off * m->V * 3 : nullptr;
   float * ro = rest ? rest + f_off * m->V * 3 : nullptr;
   if(wr)
-    skin_kernel_h<true><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h, G2, th, vo, ro, n, m->V, nvg, nft, cAB);
+    skin_kernel_h<true><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h.get(), G2, th, vo, ro, n, m->V, nvg, nft, cAB);
   else
-    skin_kernel_h<false><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h, G2, th, vo, ro, n, m->V, nvg, nft, cAB);
+    skin_kernel_h<false><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h.get(), G2, th, vo, ro, n, m->V, nvg, nft, cAB);
   return hipGetLastError();
 }
 

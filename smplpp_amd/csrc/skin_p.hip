@@ -371,9 +371,9 @@ static hipError_t launch_p(const smplpp_model * m, int64_t n, const float * thet
     hipError_t e = lds_opt_in(once, m->device, reinterpret_cast<const void *>(&skin_kernel_p<MAXW, WANT_REST>), (int)shmem);
     if(e != hipSuccess) return e;
   }
-  skin_kernel_p<MAXW, WANT_REST><<<dim3(blocks), dim3(256), shmem, st>>>(m->ws.AT.as<float>(), m->ws.ldA, m->Bm, m->ldB, Gp_padded, theta,
-                                                                        m->wIdx, m->wVal, m->wSum, verts, rest, m->ws.dummy.as<float>(), n, m->V,
-                                                                        (int)m->VGn, nft, ipb, 0);
+  skin_kernel_p<MAXW, WANT_REST><<<dim3(blocks), dim3(256), shmem, st>>>(m->ws.AT.as<float>(), m->ws.ldA, m->Bm.get(), m->ldB, Gp_padded, theta,
+                                                                        m->wIdx.get(), m->wVal.get(), m->wSum.get(), verts, rest, m->ws.dummy.as<float>(),
+                                                                        n, m->V, (int)m->VGn, nft, ipb, 0);
   return hipGetLastError();
 }
 

@@ -182,7 +182,7 @@ extern "C" int smplpp_stage_blend_shape(int device, int64_t V, int64_t n, const 
   hipStream_t st = static_cast<hipStream_t>(stream);
   In<float> b, t, s, p;
   Out<float> bs, bp, rot;
-  float * rot_tmp = nullptr;
+  DevPtr<float> rot_tmp;
   HIP_TRY(b.init(beta, (size_t)n * NB, space, st));
   HIP_TRY(t.init(theta24, (size_t)n * NJ * 3, space, st));
   HIP_TRY(s.init(S, (size_t)V * 3 * NB, space, st));
@@ -193,8 +193,8 @@ extern "C" int smplpp_stage_blend_shape(int device, int64_t V, int64_t n, const 
   float * rd = rot.d;
   if(!rd)
   {
-    HIP_TRY(hipMalloc((void **)&rot_tmp, sizeof(float) * (size_t)n * NJ * 9));
-    rd = rot_tmp;
+    HIP_TRY(dev_alloc(rot_tmp, (size_t)n * NJ * 9));
+    rd = rot_tmp.get();
   }
   stage_rodrigues_kernel<<<dim3((unsigned)((n * NJ + 255) / 256)), dim3(256), 0, st>>>(t.d, rd, n * NJ);
   if(bs.d || bp.d)
@@ -204,7 +204,6 @@ extern "C" int smplpp_stage_blend_shape(int device, int64_t V, int64_t n, const 
   if(e == hipSuccess) e = bp.finish(st);
   if(e == hipSuccess) e = rot.finish(st);
   if(e == hipSuccess && (space == SMPLPP_HOST || rot_tmp)) e = hipStreamSynchronize(st);
-  if(rot_tmp) (void)hipFree(rot_tmp);
   HIP_TRY(e);
   return SMPLPP_OK;
 }

@@ -11,7 +11,7 @@ template<class T>
 struct In
 {
   const T * d = nullptr;
-  T * tmp = nullptr;
+  DevPtr<T> tmp;
   hipError_t init(const T * p, size_t count, int space, hipStream_t st, DevBuf * buf = nullptr)
   {
     if(!p || count == 0) return hipSuccess;
@@ -20,15 +20,11 @@ struct In
       d = p;
       return hipSuccess;
     }
-    hipError_t e = buf ? buf->reserve(sizeof(T) * count) : hipMalloc((void **)&tmp, sizeof(T) * count);
+    hipError_t e = buf ? buf->reserve(sizeof(T) * count) : dev_alloc(tmp, count);
     if(e != hipSuccess) return e;
-    T * dst = buf ? buf->as<T>() : tmp;
+    T * dst = buf ? buf->as<T>() : tmp.get();
     d = dst;
     return hipMemcpyAsync(dst, p, sizeof(T) * count, hipMemcpyHostToDevice, st);
-  }
-  ~In()
-  {
-    if(tmp) (void)hipFree(tmp);
   }
 };
 
@@ -37,7 +33,7 @@ template<class T>
 struct Out
 {
   T * d = nullptr;
-  T * tmp = nullptr;
+  DevPtr<T> tmp;
   T * host = nullptr;
   size_t count = 0;
   hipError_t init(T * p, size_t cnt, int space, DevBuf * buf = nullptr)
@@ -50,8 +46,8 @@ struct Out
       return hipSuccess;
     }
     host = p;
-    hipError_t e = buf ? buf->reserve(sizeof(T) * cnt) : hipMalloc((void **)&tmp, sizeof(T) * cnt);
-    if(e == hipSuccess) d = buf ? buf->as<T>() : tmp;
+    hipError_t e = buf ? buf->reserve(sizeof(T) * cnt) : dev_alloc(tmp, cnt);
+    if(e == hipSuccess) d = buf ? buf->as<T>() : tmp.get();
     return e;
   }
   // the caller's host values into the device copy (an output the call adds into)
@@ -64,10 +60,6 @@ struct Out
   {
     if(!host) return hipSuccess;
     return hipMemcpyAsync(host, d, sizeof(T) * count, hipMemcpyDeviceToHost, st);
-  }
-  ~Out()
-  {
-    if(tmp) (void)hipFree(tmp);
   }
 };
 

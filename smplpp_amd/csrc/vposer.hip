@@ -667,7 +667,7 @@ __global__ __launch_bounds__(256) void vposer_jac2_kernel(const float * __restri
 }
 
 // weights [out][in] -> fp16x2 pieces in MFMA fragment order: [ceil(out/32)][in/16][piece 2][64 lanes][8 fp16]
-static hipError_t upload_frag(uint8_t ** dst, const float * w, int out, int in, float scale)
+static hipError_t upload_frag(DevPtr<uint8_t> & dst, const float * w, int out, int in, float scale)
 {
   const int tiles = (out + 31) / 32, ksn = in / 16;
   std::vector<_Float16> t((size_t)tiles * ksn * 2 * 64 * 8);
@@ -684,9 +684,9 @@ static hipError_t upload_frag(uint8_t ** dst, const float * w, int out, int in, 
           t[o] = hi;
           t[o + 64 * 8] = lo;
         }
-  hipError_t e = hipMalloc((void **)dst, sizeof(_Float16) * t.size());
+  hipError_t e = dev_alloc(dst, sizeof(_Float16) * t.size());
   if(e != hipSuccess) return e;
-  return hipMemcpy(*dst, t.data(), sizeof(_Float16) * t.size(), hipMemcpyHostToDevice);
+  return hipMemcpy(dst.get(), t.data(), sizeof(_Float16) * t.size(), hipMemcpyHostToDevice);
 }
 
 __global__ void rotmat_to_aa_kernel(const float * __restrict__ rot, float * __restrict__ aa_out, int64_t n)
@@ -720,8 +720,8 @@ int vposer_forward_device(smplpp_vposer * v, int64_t n, const float * z, int64_t
     HIP_TRY(lds_opt_in(once[(NF_ - 1) * 2 + (VO_ ? 1 : 0)], v->device, reinterpret_cast<const void *>(&vposer_jac2_kernel<NF_, VO_>),    \
                        VJ2<NF_>::TOTAL));                                                                                                  \
     vposer_jac2_kernel<NF_, VO_><<<dim3((unsigned)(GRID_)), dim3(256), VJ2<NF_>::TOTAL, st>>>(                                             \
-        z, z_stride, v->w0t, v->b0, v->b1, v->b2, v->w1h, v->w2h, v->w0h, v->c10, v->sD1, v->sD2, 1.0f / v->sW1, 1.0f / v->sW2, out,     \
-        out_stride, jac, n, frame_base, sig_flag, sig_counter, sig_tick);                                                                  \
+        z, z_stride, v->w0t.get(), v->b0.get(), v->b1.get(), v->b2.get(), v->w1h.get(), v->w2h.get(), v->w0h.get(), v->c10.get(), v->sD1,  \
+        v->sD2, 1.0f / v->sW1, 1.0f / v->sW2, out, out_stride, jac, n, frame_base, sig_flag, sig_counter, sig_tick);                       \
   } while(0)
     if(n > device_cus(v->device))
     {
@@ -746,8 +746,8 @@ int vposer_forward_device(smplpp_vposer * v, int64_t n, const float * z, int64_t
   const size_t shmem = sizeof(float) * (size_t)(2 * HID * VS + LAT + HID);
   static PerDeviceOnce once;
   HIP_TRY(lds_opt_in(once, v->device, reinterpret_cast<const void *>(&vposer_kernel<false>), (int)shmem));
-  vposer_kernel<false><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out,
-                                                                   out_stride, nullptr);
+  vposer_kernel<false><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t.get(), v->b0.get(), v->w1t.get(), v->b1.get(),
+                                                                   v->w2t.get(), v->b2.get(), out, out_stride, nullptr);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -760,8 +760,8 @@ int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * o
   const size_t shmem = sizeof(float) * (size_t)(2 * HID * VS + LAT + HID);
   static PerDeviceOnce once;
   HIP_TRY(lds_opt_in(once, v->device, reinterpret_cast<const void *>(&vposer_kernel<true>), (int)shmem));
-  vposer_kernel<true><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2, out,
-                                                                  out_stride, ws);
+  vposer_kernel<true><<<dim3((unsigned)n), dim3(256), shmem, st>>>(z, z_stride, v->w0t.get(), v->b0.get(), v->w1t.get(), v->b1.get(),
+                                                                  v->w2t.get(), v->b2.get(), out, out_stride, ws);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -769,31 +769,25 @@ int vposer_value_device(smplpp_vposer * v, int64_t n, const float * z, float * o
 
 using namespace smplpp_hip;
 
+smplpp_vposer::~smplpp_vposer()
+{
+  (void)hipSetDevice(device);
+}
+
 extern "C" int smplpp_vposer_destroy(smplpp_vposer * v)
 {
-  if(!v) return SMPLPP_OK;
-  (void)hipSetDevice(v->device);
-  for(float * p : {v->w0t, v->b0, v->w1t, v->b1, v->w2t, v->b2})
-    if(p) (void)hipFree(p);
-  if(v->w1h) (void)hipFree(v->w1h);
-  if(v->w2h) (void)hipFree(v->w2h);
-  if(v->w0h) (void)hipFree(v->w0h);
-  if(v->c10) (void)hipFree(v->c10);
-  vposer_vjp_release(v->vjp);
-  if(v->w0r) (void)hipFree(v->w0r);
-  vposer_jx_release(v->jx);
-  delete v;
+  if(v) delete v;
   return SMPLPP_OK;
 }
 
-static hipError_t upload_t(float ** dst, const float * w, int out, int in)
+static hipError_t upload_t(DevPtr<float> & dst, const float * w, int out, int in)
 {
   std::vector<float> t((size_t)out * in);
   for(int o = 0; o < out; o++)
     for(int i = 0; i < in; i++) t[(size_t)i * out + o] = w[(size_t)o * in + i]; // [out,in] -> [in][out]
-  hipError_t e = hipMalloc((void **)dst, sizeof(float) * t.size());
+  hipError_t e = dev_alloc(dst, t.size());
   if(e != hipSuccess) return e;
-  return hipMemcpy(*dst, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice);
+  return hipMemcpy(dst.get(), t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice);
 }
 
 extern "C" int smplpp_vposer_create(int device, const float * w0, const float * b0, const float * w1, const float * b1,
@@ -806,14 +800,14 @@ extern "C" int smplpp_vposer_create(int device, const float * w0, const float * 
   if(rc) return rc;
   if(device < 0 || device >= ndev) return fail(SMPLPP_ERR_INVALID, "Failed to fetch device index!");
   HIP_TRY(hipSetDevice(device));
-  smplpp_vposer * v = new smplpp_vposer();
+  std::unique_ptr<smplpp_vposer> v(new smplpp_vposer());
   v->device = device;
-  hipError_t e = upload_t(&v->w0t, w0, HID, LAT);
-  if(e == hipSuccess) e = upload_t(&v->w1t, w1, HID, HID);
-  if(e == hipSuccess) e = upload_t(&v->w2t, w2, OUT6, HID);
-  if(e == hipSuccess) e = upload_t(&v->b0, b0, 1, HID);
-  if(e == hipSuccess) e = upload_t(&v->b1, b1, 1, HID);
-  if(e == hipSuccess) e = upload_t(&v->b2, b2, 1, OUT6);
+  HIP_TRY(upload_t(v->w0t, w0, HID, LAT));
+  HIP_TRY(upload_t(v->w1t, w1, HID, HID));
+  HIP_TRY(upload_t(v->w2t, w2, OUT6, HID));
+  HIP_TRY(upload_t(v->b0, b0, 1, HID));
+  HIP_TRY(upload_t(v->b1, b1, 1, HID));
+  HIP_TRY(upload_t(v->b2, b2, 1, OUT6));
   {
     // fp16x2 operands of the tangent GEMMs: power-of-two scales that keep every piece inside fp16's range.  Weights: the
     // largest entry just under 2^14.  Tangent blocks: |D1| <= max|W0|; |D2| <= 512 max|W1| max|W0| (every slope <= 1).
@@ -824,18 +818,13 @@ extern "C" int smplpp_vposer_create(int device, const float * w0, const float * 
     };
     auto pow2_under = [](float bound, float m) { return std::exp2(std::floor(std::log2(bound / (m > 1e-30f ? m : 1e-30f)))); };
     const float m0 = amax(w0, (size_t)HID * LAT), m1 = amax(w1, (size_t)HID * HID), m2 = amax(w2, (size_t)OUT6 * HID);
-    if(!std::isfinite(m0) || !std::isfinite(m1) || !std::isfinite(m2))
-    {
-      smplpp_vposer_destroy(v);
-      return fail(SMPLPP_ERR_INVALID, "smplpp_vposer_create: non-finite weights");
-    }
+    if(!std::isfinite(m0) || !std::isfinite(m1) || !std::isfinite(m2)) return fail(SMPLPP_ERR_INVALID, "smplpp_vposer_create: non-finite weights");
     v->sW1 = pow2_under(16384.0f, m1);
     v->sW2 = pow2_under(16384.0f, m2);
     v->sD1 = pow2_under(16384.0f, m0);
     v->sD2 = pow2_under(16384.0f, 512.0f * m1 * m0);
-    if(e == hipSuccess) e = upload_frag(&v->w1h, w1, HID, HID, v->sW1);
-    if(e == hipSuccess) e = upload_frag(&v->w2h, w2, OUT6, HID, v->sW2);
-    if(e == hipSuccess)
+    HIP_TRY(upload_frag(v->w1h, w1, HID, HID, v->sW1));
+    HIP_TRY(upload_frag(v->w2h, w2, OUT6, HID, v->sW2));
     {
       // W0 [512][32] as the B operand of layer 1 (k = row of W0): [32 k-steps][piece 2][64 lanes (32 h + column)][8 fp16]
       std::vector<_Float16> t((size_t)32 * 2 * 64 * 8);
@@ -848,10 +837,9 @@ extern "C" int smplpp_vposer_create(int device, const float * w0, const float * 
           t[o] = hi;
           t[o + 64 * 8] = lo;
         }
-      e = hipMalloc((void **)&v->w0h, sizeof(_Float16) * t.size());
-      if(e == hipSuccess) e = hipMemcpy(v->w0h, t.data(), sizeof(_Float16) * t.size(), hipMemcpyHostToDevice);
+      HIP_TRY(dev_alloc(v->w0h, sizeof(_Float16) * t.size()));
+      HIP_TRY(hipMemcpy(v->w0h.get(), t.data(), sizeof(_Float16) * t.size(), hipMemcpyHostToDevice));
     }
-    if(e == hipSuccess)
     {
       std::vector<float> c((size_t)HID * LAT);
       for(int r = 0; r < HID; r++)
@@ -862,17 +850,11 @@ extern "C" int smplpp_vposer_create(int device, const float * w0, const float * 
           // the layer-1 epilogue's order: row r = 32 tile + 8 g + 4 lh + i of column cc at [tile][g][lh][cc][i]
           c[((((size_t)(r >> 5) * 4 + ((r >> 3) & 3)) * 2 + ((r >> 2) & 1)) * 32 + cc) * 4 + (r & 3)] = (float)sum;
         }
-      e = hipMalloc((void **)&v->c10, sizeof(float) * c.size());
-      if(e == hipSuccess) e = hipMemcpy(v->c10, c.data(), sizeof(float) * c.size(), hipMemcpyHostToDevice);
+      HIP_TRY(dev_alloc(v->c10, c.size()));
+      HIP_TRY(hipMemcpy(v->c10.get(), c.data(), sizeof(float) * c.size(), hipMemcpyHostToDevice));
     }
   }
-  if(e != hipSuccess)
-  {
-    int r = hip_fail(e, "vposer upload", __FILE__, __LINE__);
-    smplpp_vposer_destroy(v);
-    return r;
-  }
-  *out = v;
+  *out = v.release();
   return SMPLPP_OK;
 }
 

@@ -36,21 +36,9 @@ struct VPoserJxWork
   DevBuf t1; // [n][512][32] T1
 };
 
-void vposer_jx_release(VPoserJxWork * w)
+void StateDelete::operator()(VPoserJxWork * w) const
 {
-  if(!w) return;
-  w->ws.release();
-  w->t1.release();
   delete w;
-}
-
-// W0: [in][out] (w0t) -> [out][in] (torch's [512][32]), so that the B operand's lanes read consecutive columns
-__global__ void vposer_jx_w0_kernel(const float * __restrict__ w0t, float * __restrict__ w0r)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if(i >= HID * LAT) return;
-  const int k = i / LAT, c = i % LAT;
-  w0r[i] = w0t[c * HID + k];
 }
 
 // grid (ceil(n / NF), HID / JX_ROWS), block 256.  Lane l of wave w: r = l & 31, h = l >> 5.  At k-step ks (k = 2 ks + h):
@@ -220,31 +208,13 @@ __global__ __launch_bounds__(256) void vposer_jx_tail_kernel(const float * __res
 }
 static_assert(OUT6 <= 4 * 32, "vposer_jx_tail_kernel: four 32-row tiles cover layer 2");
 
-static int jx_weights(smplpp_vposer * v)
-{
-  if(v->w0r) return SMPLPP_OK;
-  float * w = nullptr;
-  hipError_t e = hipMalloc((void **)&w, sizeof(float) * HID * LAT);
-  // built on the null stream and waited for: a later call on any stream finds the copy complete
-  if(e == hipSuccess) vposer_jx_w0_kernel<<<dim3((HID * LAT + 255) / 256), dim3(256), 0, nullptr>>>(v->w0t, w);
-  if(e == hipSuccess) e = hipGetLastError();
-  if(e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if(e != hipSuccess)
-  {
-    if(w) (void)hipFree(w);
-    return hip_fail(e, "smplpp_vposer_jacobian: weight copy", __FILE__, __LINE__);
-  }
-  v->w0r = w;
-  return SMPLPP_OK;
-}
-
-int vposer_jacobian_device(smplpp_vposer * v, VPoserJxWork ** work, int64_t n, const float * z, int64_t z_stride, float * out,
+int vposer_jacobian_device(smplpp_vposer * v, StatePtr<VPoserJxWork> & work, int64_t n, const float * z, int64_t z_stride, float * out,
                            int64_t out_stride, float * jac, hipStream_t st)
 {
-  int rc = jx_weights(v);
+  int rc = vposer_weight_rows(v, false);
   if(rc) return rc;
-  if(!*work) *work = new VPoserJxWork();
-  VPoserJxWork * w = *work;
+  if(!work) work.reset(new VPoserJxWork());
+  VPoserJxWork * w = work.get();
   HIP_TRY(w->ws.reserve(sizeof(float) * (size_t)n * VW_FRAME));
   HIP_TRY(w->t1.reserve(sizeof(float) * (size_t)n * JX_T1));
   float * ws = w->ws.as<float>();
@@ -257,15 +227,15 @@ int vposer_jacobian_device(smplpp_vposer * v, VPoserJxWork ** work, int64_t n, c
   const unsigned groups = (unsigned)((n + nf - 1) / nf);
   const dim3 grid(groups, HID / JX_ROWS), block(256);
   if(nf == 8)
-    vposer_jx_layer1_kernel<8><<<grid, block, 0, st>>>(ws, v->w1t, v->w0r, t1, n);
+    vposer_jx_layer1_kernel<8><<<grid, block, 0, st>>>(ws, v->w1t.get(), v->w0r.get(), t1, n);
   else if(nf == 4)
-    vposer_jx_layer1_kernel<4><<<grid, block, 0, st>>>(ws, v->w1t, v->w0r, t1, n);
+    vposer_jx_layer1_kernel<4><<<grid, block, 0, st>>>(ws, v->w1t.get(), v->w0r.get(), t1, n);
   else if(nf == 2)
-    vposer_jx_layer1_kernel<2><<<grid, block, 0, st>>>(ws, v->w1t, v->w0r, t1, n);
+    vposer_jx_layer1_kernel<2><<<grid, block, 0, st>>>(ws, v->w1t.get(), v->w0r.get(), t1, n);
   else
-    vposer_jx_layer1_kernel<1><<<grid, block, 0, st>>>(ws, v->w1t, v->w0r, t1, n);
+    vposer_jx_layer1_kernel<1><<<grid, block, 0, st>>>(ws, v->w1t.get(), v->w0r.get(), t1, n);
   HIP_TRY(hipGetLastError());
-  vposer_jx_tail_kernel<<<dim3((unsigned)n), block, 0, st>>>(ws, t1, v->w2t, jac);
+  vposer_jx_tail_kernel<<<dim3((unsigned)n), block, 0, st>>>(ws, t1, v->w2t.get(), jac);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -287,7 +257,7 @@ extern "C" int smplpp_vposer_jacobian(smplpp_vposer * v, int64_t n, int64_t fram
   HIP_TRY(zi.init(z, (size_t)n * LAT, space, st));
   HIP_TRY(oo.init(out, (size_t)n * 63, space));
   HIP_TRY(jo.init(jac, (size_t)n * 63 * LAT, space));
-  rc = vposer_jacobian_device(v, &v->jx, n, zi.d, LAT, oo.d, 63, jo.d, st);
+  rc = vposer_jacobian_device(v, v->jx, n, zi.d, LAT, oo.d, 63, jo.d, st);
   if(rc) return rc;
   hipError_t e = jo.finish(st);
   if(e == hipSuccess) e = oo.finish(st);

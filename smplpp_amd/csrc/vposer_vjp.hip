@@ -12,8 +12,8 @@
 //                        also storing s0, s1 and o into the backward's workspace: the masks and the axis-angle branches are the
 //                        ones the caller's loss saw, and `out` is that call's bits.
 //  vposer_vjp_kernel     VV_NF frames per workgroup, exact fp32 on the VALU: every weight the workgroup streams from L2 serves
-//                        VV_NF frames.  Weights are read from copies in [out][in] layout (built by the decoder's first backward
-//                        call, freed by smplpp_vposer_destroy), so that consecutive lanes read consecutive inputs.
+//                        VV_NF frames.  Weights are read from the decoder's copies in [out][in] layout (vposer_weight_rows, built
+//                        by the first backward call that needs them), so that consecutive lanes read consecutive inputs.
 // No atomics; every sum runs in a fixed order that does not depend on the frame's slot in its workgroup, on n or on frame_base:
 // a frame's bits are the same in any batch or shard.
 #include "staging.h"
@@ -27,21 +27,6 @@ namespace smplpp_hip
 {
 constexpr int VV_NF = 8; // frames per workgroup of vposer_vjp_kernel
 
-struct VPoserVjp
-{
-  float *w0 = nullptr, *w1 = nullptr, *w2 = nullptr; // W0 [512][32], W1 [512][512], W2 [126][512] (torch::nn::Linear layout)
-  DevBuf ws;                                         // [n][VW_FRAME] of vposer_kernel<true>
-};
-
-void vposer_vjp_release(VPoserVjp * s)
-{
-  if(!s) return;
-  for(float * p : {s->w0, s->w1, s->w2})
-    if(p) (void)hipFree(p);
-  s->ws.release();
-  delete s;
-}
-
 // [in][out] -> [out][in]
 __global__ void vposer_untranspose_kernel(const float * __restrict__ src, float * __restrict__ dst, int in, int out)
 {
@@ -49,6 +34,31 @@ __global__ void vposer_untranspose_kernel(const float * __restrict__ src, float 
   if(i >= in * out) return;
   const int o = i / in, k = i % in;
   dst[i] = src[k * out + o];
+}
+
+// dst [out][in] from src [in][out] on the null stream (dst null: nothing to build)
+static void untranspose(const float * src, float * dst, int in, int out)
+{
+  if(dst) vposer_untranspose_kernel<<<dim3((in * out + 255) / 256), dim3(256), 0, nullptr>>>(src, dst, in, out);
+}
+
+int vposer_weight_rows(smplpp_vposer * v, bool all3)
+{
+  if(v->w0r && (!all3 || (v->w1r && v->w2r))) return SMPLPP_OK;
+  DevPtr<float> w0, w1, w2; // the missing copies, handed to the decoder once complete
+  if(!v->w0r) HIP_TRY(dev_alloc(w0, (size_t)HID * LAT));
+  if(all3 && !v->w1r) HIP_TRY(dev_alloc(w1, (size_t)HID * HID));
+  if(all3 && !v->w2r) HIP_TRY(dev_alloc(w2, (size_t)OUT6 * HID));
+  untranspose(v->w0t.get(), w0.get(), LAT, HID);
+  untranspose(v->w1t.get(), w1.get(), HID, HID);
+  untranspose(v->w2t.get(), w2.get(), HID, OUT6);
+  // waited for once, here: a later call on any stream finds the copies complete
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  if(w0) v->w0r = std::move(w0);
+  if(w1) v->w1r = std::move(w1);
+  if(w2) v->w2r = std::move(w2);
+  return SMPLPP_OK;
 }
 
 // grid: ceil(n / VV_NF) workgroups of 256.  LDS holds the gradients of the workgroup's frames as [row][VV_NF], so a weight's VV_NF
@@ -184,31 +194,6 @@ __global__ __launch_bounds__(256) void vposer_vjp_kernel(const float * __restric
 }
 static_assert(VV_NF * LAT == 256 && 8 * LAT == 256, "layer 0 of vposer_vjp_kernel maps one thread to each (slice, latent), then to each (frame, latent)");
 static_assert(VV_NF * 21 <= 256, "the rotation tail of vposer_vjp_kernel maps one thread to each (frame, joint)");
-
-static int vjp_state(smplpp_vposer * v)
-{
-  if(v->vjp) return SMPLPP_OK;
-  VPoserVjp * s = new VPoserVjp();
-  hipError_t e = hipMalloc((void **)&s->w0, sizeof(float) * HID * LAT);
-  if(e == hipSuccess) e = hipMalloc((void **)&s->w1, sizeof(float) * HID * HID);
-  if(e == hipSuccess) e = hipMalloc((void **)&s->w2, sizeof(float) * OUT6 * HID);
-  // built on the null stream and waited for: a later call on any stream finds the copies complete
-  if(e == hipSuccess)
-    vposer_untranspose_kernel<<<dim3((HID * LAT + 255) / 256), dim3(256), 0, nullptr>>>(v->w0t, s->w0, LAT, HID);
-  if(e == hipSuccess)
-    vposer_untranspose_kernel<<<dim3((HID * HID + 255) / 256), dim3(256), 0, nullptr>>>(v->w1t, s->w1, HID, HID);
-  if(e == hipSuccess)
-    vposer_untranspose_kernel<<<dim3((HID * OUT6 + 255) / 256), dim3(256), 0, nullptr>>>(v->w2t, s->w2, HID, OUT6);
-  if(e == hipSuccess) e = hipGetLastError();
-  if(e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if(e != hipSuccess)
-  {
-    vposer_vjp_release(s);
-    return hip_fail(e, "smplpp_vposer_vjp: weight copies", __FILE__, __LINE__);
-  }
-  v->vjp = s;
-  return SMPLPP_OK;
-}
 } // namespace smplpp_hip
 
 using namespace smplpp_hip;
@@ -222,20 +207,19 @@ extern "C" int smplpp_vposer_vjp(smplpp_vposer * v, int64_t n, int64_t frame_bas
   if(rc) return rc;
   HIP_TRY(hipSetDevice(v->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = vjp_state(v);
+  rc = vposer_weight_rows(v, true);
   if(rc) return rc;
-  VPoserVjp * s = v->vjp;
-  HIP_TRY(s->ws.reserve(sizeof(float) * (size_t)n * VW_FRAME));
+  HIP_TRY(v->vjp_ws.reserve(sizeof(float) * (size_t)n * VW_FRAME));
   In<float> zi, gi;
   Out<float> gzo, oo;
   HIP_TRY(zi.init(z, (size_t)n * LAT, space, st));
   HIP_TRY(gi.init(grad_out, (size_t)n * 63, space, st));
   HIP_TRY(gzo.init(grad_z, (size_t)n * LAT, space));
   HIP_TRY(oo.init(out, (size_t)n * 63, space));
-  rc = vposer_value_device(v, n, zi.d, oo.d, s->ws.as<float>(), st);
+  rc = vposer_value_device(v, n, zi.d, oo.d, v->vjp_ws.as<float>(), st);
   if(rc) return rc;
-  vposer_vjp_kernel<<<dim3((unsigned)((n + VV_NF - 1) / VV_NF)), dim3(256), 0, st>>>(s->ws.as<float>(), gi.d, s->w0, s->w1, s->w2, gzo.d,
-                                                                                    n);
+  vposer_vjp_kernel<<<dim3((unsigned)((n + VV_NF - 1) / VV_NF)), dim3(256), 0, st>>>(v->vjp_ws.as<float>(), gi.d, v->w0r.get(), v->w1r.get(),
+                                                                                    v->w2r.get(), gzo.d, n);
   hipError_t e = hipGetLastError();
   if(e == hipSuccess) e = gzo.finish(st);
   if(e == hipSuccess) e = oo.finish(st);
