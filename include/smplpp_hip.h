@@ -274,10 +274,18 @@ int smplpp_ik_get_vertices(smplpp_ik * s, float * verts, int space, void * strea
  * (no caller moves on a truncated Jacobian) and smplpp_ik_set_tasks clears the bit (it belongs to the tasks; the next evaluation
  * raises it again where it still applies); position-only tasks are unaffected and any model gets its solver.  Bit 3 = a forward
  * pass inside a loop on this model met an operand outside the fp16x2 form's range since the last smplpp_ik_set_config (one word per
- * model: every frame of the batch carries it).  Host-space eval / iterate / solve_sequence calls return SMPLPP_ERR_NUMERIC
- * (bits 0, 1) or SMPLPP_ERR_INVALID (bit 2) themselves; enqueue-only (SMPLPP_DEVICE) callers have no return value to inspect and
- * read it here (waits for `stream` first). flags [n]. */
+ * model: every frame of the batch carries it).  Bit 4 = the last solve of the frame was a box QP (enable_qp) that used all of its
+ * 4 D + 20 active-set passes without meeting its optimality test; its last iterate was applied as the update.  Host-space eval /
+ * iterate / solve_sequence calls return SMPLPP_ERR_NUMERIC (bits 0, 1) or SMPLPP_ERR_INVALID (bit 2) themselves, and no error for
+ * bit 4; enqueue-only (SMPLPP_DEVICE) callers have no return value to inspect and read it here (waits for `stream` first). flags [n]. */
 int smplpp_ik_get_status(smplpp_ik * s, int32_t * flags, int space, void * stream);
+/* The step of the last solve of every frame, fp64: x [n,D] = (d theta [theta_dim] | phi [2K] | d beta [beta_dim]) as the solve
+ * computed it, before the fp32 update (node/node.cpp:938-968), with D = theta_dim + 2K + beta_dim of that solve (beta_dim 10 when
+ * it optimised beta, else 0); *D receives it, and x may be NULL to ask for D alone (0 before the first solve).  Rows are defined
+ * only for frames whose last solve ran and succeeded: a skipped frame (min_valid) keeps what an earlier solve wrote, and a frame
+ * with status bit 0 holds the values of the failed solve.  Pinned surface coordinates (phi limit 0) read 0.  Waits for `stream`
+ * in host space; in device space the copy is enqueued on it. */
+int smplpp_ik_get_step(smplpp_ik * s, double * x, int64_t * D, int space, void * stream);
 
 /* Streams and sharing.  A model owns ONE workspace (pose coefficients, relative transforms of the last forward pass) that
  * smplpp_fk and every smplpp_ik built on the model write: all work on one model handle must be issued in stream order on

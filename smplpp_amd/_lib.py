@@ -90,6 +90,7 @@ def load():
         "smplpp_ik_solve_sequence_shared": [vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp, C.c_int, vp],
         "smplpp_ik_get_vertices": [vp, vp, C.c_int, vp],
         "smplpp_ik_get_status": [vp, vp, C.c_int, vp],
+        "smplpp_ik_get_step": [vp, vp, vp, C.c_int, vp],
         "smplpp_gather": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int64, vp],
         "smplpp_gather_to_root": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64, vp],
         "smplpp_gather_offsets": [i64p, C.c_int, C.c_int64, i64p],

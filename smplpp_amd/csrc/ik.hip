@@ -43,6 +43,7 @@ struct smplpp_ik
   float * list_d = nullptr;
   std::vector<DevPtr<void>> owned; // what the raw pointers of this struct point to
   bool have_eval = false;
+  int64_t last_D = 0; // unknowns of the last solve (theta_dim + 2K + beta_dim): the row length of xout (smplpp_ik_get_step)
   // re-projection beside the solve: when no task's surface coordinates can move (phiLimit_ <= 0 everywhere, or the
   // motion stage's forced zero, node.cpp:699) the query points are the actual positions the evaluation already wrote,
   // so the face scan does not depend on the solve and runs on a second stream while the solve is in flight
@@ -590,6 +591,7 @@ static int ik_iterate_enqueue(smplpp_ik * s, int iters, int enable_qp, int optim
     const int beta_dim = opt_beta ? NB : 0;
     // LDS plan: packed system + vectors, the rest (up to a 150 KB total) for the J row chunk
     const int D = s->theta_dim + 2 * K + beta_dim, rows = 4 * K;
+    s->last_D = D;
     // the packed system is sized for the unknowns that CAN be free: a pinned phi (zero limit, node.cpp:567,699) never is,
     // which leaves 75 of the 157 unknowns of a 41-marker motion solve and room for its 164 Jacobian rows in two chunks
     const int m_dim = D - ((!phi_live || s->phi_locked) ? 2 * K : 0);
@@ -891,7 +893,9 @@ extern "C" int smplpp_ik_solve_sequence_shared(smplpp_ik * s, int64_t T, const f
 // solve_sequence start failed, bit 2 = an evaluation since the tasks were last set (smplpp_ik_set_tasks clears it; so do set_config
 // and solve_sequence) met a task with a normal term on a vertex of more than 12 adjacent faces: its Jacobian rows are not supported,
 // and the solve skips that frame's update (bit 0 then reads 1 as for any skipped update).  SMPLPP_HOST calls of iterate / solve_sequence report the same condition as an error; a
-// SMPLPP_DEVICE (enqueue-only) caller reads it here once its stream has reached the point of interest.
+// SMPLPP_DEVICE (enqueue-only) caller reads it here once its stream has reached the point of interest.  Bit 4 = the last solve of
+// frame f was a box QP that used all its active-set passes without meeting its optimality test (the update was applied; no call
+// reports it as an error).
 extern "C" int smplpp_ik_get_status(smplpp_ik * s, int32_t * flags, int space, void * stream)
 {
   if(!s || !flags) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_get_status: bad argument");
@@ -910,11 +914,28 @@ extern "C" int smplpp_ik_get_status(smplpp_ik * s, int32_t * flags, int space, v
   if(s->range_word && s->m->form_ik == 'h') HIP_TRY(hipMemcpy(&internal, s->range_word, sizeof(int), hipMemcpyDeviceToHost));
   std::vector<int32_t> h((size_t)s->n);
   for(int64_t f = 0; f < s->n; f++)
-    h[(size_t)f] = (a[(size_t)f] == 1 ? 1 : 0) | ((b[(size_t)f] & 1) ? 2 : 0) | (b[(size_t)f] & 4) | ((internal & 1) ? 8 : 0);
+    h[(size_t)f] = (a[(size_t)f] == 1 ? 1 : 0) | ((b[(size_t)f] & 1) ? 2 : 0) | (b[(size_t)f] & 4) | ((internal & 1) ? 8 : 0) |
+                   (a[(size_t)f] == 2 ? 16 : 0); // bit 4: the box QP ran out of active-set passes (ik_solve_kernel's status 2)
   if(space == SMPLPP_HOST)
     memcpy(flags, h.data(), sizeof(int32_t) * (size_t)s->n);
   else
     HIP_TRY(hipMemcpy(flags, h.data(), sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice));
+  return SMPLPP_OK;
+}
+
+// The step x = (theta, phi, beta) of the last solve of every frame, fp64, as the solve kernel wrote it (xout, [n][last_D])
+extern "C" int smplpp_ik_get_step(smplpp_ik * s, double * x, int64_t * D, int space, void * stream)
+{
+  if(!s || !D) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_get_step: bad argument");
+  int rc = check_space(space, "smplpp_ik_get_step");
+  if(rc) return rc;
+  *D = s->last_D;
+  if(!x || s->last_D == 0) return SMPLPP_OK;
+  HIP_TRY(hipSetDevice(s->m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  HIP_TRY(hipMemcpyAsync(x, s->xout, sizeof(double) * s->n * s->last_D, kind, st));
+  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
   return SMPLPP_OK;
 }
 

@@ -294,10 +294,23 @@ class IkSolver:
 
     def getStatus(self):
         """Per-frame solve outcome (bit 0: the last solve hit "LLT has numerical issue!", node.cpp:934-937; bit 1: some
-        solve did since setConfig / the sequence start) — what an enqueue-only caller checks after synchronising."""
+        solve did since setConfig / the sequence start; bit 4: the last solve was a box QP that ran out of active-set passes
+        without meeting its optimality test) — what an enqueue-only caller checks after synchronising."""
         f = np.zeros(self.n, np.int32)
         check(_lib.load().smplpp_ik_get_status(self._h, _ptr(f), HOST, None))
         return f
+
+    def getStep(self):
+        """The fp64 step x [n, D] of the last solve of every frame (smplpp_ik_get_step): d theta [theta_dim] | phi [2K] |
+        d beta [10 if that solve optimised beta], before the fp32 update.  Defined only for frames whose last solve ran and
+        succeeded (not skipped, getStatus() bit 0 clear).  None before the first solve."""
+        D = C.c_int64(0)
+        check(_lib.load().smplpp_ik_get_step(self._h, None, C.byref(D), HOST, None))
+        if D.value == 0:
+            return None
+        x = np.empty((self.n, D.value), np.float64)
+        check(_lib.load().smplpp_ik_get_step(self._h, _ptr(x), C.byref(D), HOST, None))
+        return x
 
     # ---- configuration g_beta / g_theta (node.cpp:44-45)
     def setConfig(self, beta=None, theta=None):
