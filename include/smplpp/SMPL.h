@@ -366,6 +366,47 @@ public:
           "SMPL");
     return g;
   }
+  // Mesh-to-point distance on the last launch's vertices (the other direction of pointMeshDistance): for points [N,K,3], the nearest
+  // point to each vertex of each frame's mesh (smplpp_mesh_point_distance).  index [N,V] kInt64 (-1: no finite distance), sqdist [N,V].
+  struct MeshPointDistance
+  {
+    Tensor index, sqdist;
+  };
+  MeshPointDistance meshPointDistance(const Tensor & points) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || points.size(1) < 1 || points.size(2) != 3)
+      throw Exception("SMPL", "Cannot compute the mesh-to-point distance!");
+    const int64_t K = points.size(1);
+    MeshPointDistance r{Tensor({n, V_}, kInt64), Tensor({n, V_})};
+    check(smplpp_mesh_point_distance(m_.get(), n, verts_.ptr(), K, points.ptr(), r.index.idata.data(), r.sqdist.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
+  // Its backward pass (smplpp_mesh_point_distance_vjp): dL/dverts [N,V,3] for dL/dsqdist = gradSqdist [N,V] at the points `index` [N,V]
+  // meshPointDistance chose.  `gradPoints` non-null receives dL/dpoints [N,K,3].  `accumulate` non-null: the vertex product is added
+  // into it (and it is returned), and the point product into *gradPoints, which must then hold [N,K,3].
+  Tensor meshPointDistanceBackward(const Tensor & points, const Tensor & index, const Tensor & gradSqdist, Tensor * gradPoints = nullptr,
+                                   Tensor * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const int64_t K = points.dim() == 3 ? points.size(1) : 0;
+    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || K < 1 || points.size(2) != 3 ||
+       (index.dtype != kInt64 && index.dtype != kInt32) || index.numel() != n * V_ || gradSqdist.dtype != kFloat32 ||
+       gradSqdist.numel() != n * V_ || (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3)) ||
+       (accumulate && gradPoints && (gradPoints->dtype != kFloat32 || gradPoints->numel() != n * K * 3)))
+      throw Exception("SMPL", "Cannot back-propagate through the mesh-to-point distance!");
+    Tensor fresh;
+    if(!accumulate) fresh = Tensor(verts_.shape);
+    Tensor & g = accumulate ? *accumulate : fresh;
+    if(gradPoints && !accumulate) *gradPoints = Tensor({n, K, 3});
+    check(smplpp_mesh_point_distance_vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), index.idata.data(), gradSqdist.ptr(), g.ptr(),
+                                         gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return g;
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const

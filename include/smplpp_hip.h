@@ -192,6 +192,33 @@ int smplpp_point_mesh_distance_vjp(smplpp_model * m, int64_t n, const float * ve
                                    const int64_t * face /*[n,K]*/, const float * grad_sqdist /*[n,K]*/,
                                    float * grad_verts /*[n,V,3] nullable*/, float * grad_points /*[n,K,3] nullable*/,
                                    int accumulate, int space, void * stream);
+/* Mesh-to-point distance, the other direction of a two-sided scan registration (Chamfer) loss: for each of n frames, the nearest
+ * of K points [n,K,3] to each vertex of that frame's posed mesh verts [n,V,3].  A brute-force scan; faces are not used, so a
+ * model created without faces is accepted.  Exact rule (a float32 restatement reproduces every bit):
+ *  - sqdist[f,v] is the fp32 value of ((dx*dx + dy*dy) + dz*dz), d = v - p, every operation rounded on its own (no FMA);
+ *  - index[f,v] is the point with the smallest such distance; on equal distances the lowest point index wins;
+ *  - a pair whose distance is not finite (NaN, inf, fp32 overflow of huge coordinates) is never chosen; a vertex with no
+ *    eligible point (a frame of NaN padding) gets index = -1 and sqdist = 0;
+ *  - the bits do not depend on n, on the frame's position in the batch, or on how the call splits K: few frames split K into
+ *    chunks (chosen from n and K alone), each with a partial (d, k), then a lexicographic (d, k) minimum over the chunks.
+ *  - SMPLPP_ERR_INVALID: bad arguments, n * K or n * V beyond int32 indexing. */
+int smplpp_mesh_point_distance(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t K, const float * points /*[n,K,3]*/,
+                               int64_t * index /*[n,V]*/, float * sqdist /*[n,V]*/, int space, void * stream);
+/* Vector-Jacobian product of sqdist above: grad_verts [n,V,3] and grad_points [n,K,3] for dL/dsqdist = grad_sqdist [n,V], at
+ * the points `index` [n,V] the forward chose.  With r = v - p[index] and g = grad_sqdist:
+ *    grad_verts[v] = 2 g_v r_v,    grad_points[k] = sum over the vertices v with index_v == k of -2 g_v r_v.
+ *  - accumulate = 0: both outputs are overwritten (points no vertex chose get 0); accumulate = 1: the product is added.  Either
+ *    output may be NULL, not both.
+ *  - a vertex with index = -1, or with a cotangent of exactly 0, contributes nothing (masking vertices, e.g. back-facing ones for
+ *    a single-view depth cloud, is done with zero cotangents).
+ *  - deterministic: no floating-point atomics; each element of grad_points is one fixed-order sum in ascending v, so a frame's
+ *    bits do not depend on n or on its position in the batch.  No cap on how many vertices one point receives.
+ *  - SMPLPP_ERR_INVALID: bad arguments, n * K or n * V beyond int32 indexing, a host-space index outside [-1, K) (the outputs are
+ *    left untouched); a device-space index out of range contributes nothing. */
+int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
+                                   const int64_t * index /*[n,V]*/, const float * grad_sqdist /*[n,V]*/,
+                                   float * grad_verts /*[n,V,3] nullable*/, float * grad_points /*[n,K,3] nullable*/,
+                                   int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -231,6 +231,7 @@ struct Workspace
 struct VjpState;        // smplpp_fk_vjp's operand image and workspace (fk_vjp.hip)
 struct NormalsVjpState; // the normals' backward pass (mesh_vjp.hip)
 struct PointDistState;  // point-to-mesh distance and its backward pass (point_distance.hip)
+struct MeshPointDistState; // mesh-to-point distance and its backward pass (mesh_point_distance.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -238,6 +239,7 @@ struct StateDelete
   void operator()(VjpState * s) const;
   void operator()(NormalsVjpState * s) const;
   void operator()(PointDistState * s) const;
+  void operator()(MeshPointDistState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -293,5 +295,6 @@ struct smplpp_model
   smplpp_hip::StatePtr<smplpp_hip::NormalsVjpState> nvjp; // backward pass of the normal queries (mesh_vjp.hip): null until its first call
   char pd_form = 0;             // point-to-mesh distance form (SMPLPP_POINT_DISTANCE_FORM, read at model creation): 0 = by K | q | t
   smplpp_hip::StatePtr<smplpp_hip::PointDistState> pd; // point-to-mesh distance workspace (point_distance.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::MeshPointDistState> mpd; // mesh-to-point distance workspace (mesh_point_distance.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

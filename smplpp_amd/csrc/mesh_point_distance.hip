@@ -1,0 +1,390 @@
+// Mesh-to-point distance (the other half of a two-sided scan registration loss): for every posed vertex, the nearest point of the
+// frame's cloud, and its vector-Jacobian product to the vertices and the points.  A brute-force scan over the cloud; faces are not used.
+//
+// Forward:
+//  mpd_scan_kernel    256 lanes, MPD_VPL vertices of one frame per lane in registers (vertex vb 1024 + i 256 + lane), the frame's
+//                     points (or one chunk of them) streamed through LDS MPD_TILE at a time as float4: every lane reads the same
+//                     point, so each LDS read is a broadcast.  Each vertex keeps a running (best_d, best_k), updated on a strict
+//                     d < best_d in ascending k: the lowest k among equal distances, and a NaN or inf distance never chosen
+//                     (best_d starts at +inf).  d = ((dx dx + dy dy) + dz dz), d = v - p, every operation rounded on its own.
+//  mpd_reduce_kernel  when the call splits K (few frames: the grid would not fill the device), each chunk wrote a partial (d, k);
+//                     one thread per (frame, vertex) takes the lexicographic (d, k) minimum over the chunks.  A minimum over a total
+//                     order does not depend on how K was cut, so the bits do not depend on the split, on n or on the frame's slot.
+// Backward (no search: the forward's index is an input), r = v - p[index], g = grad_sqdist:
+//  mpd_vjp_record_kernel  per (frame, vertex): grad_verts = 2 g r, and the record (index, -2 g r) for grad_points.  A zero
+//                         cotangent or an index out of [0, K) gives no record (key -1) and a zero grad_verts.
+//  mpd_vjp_gather_kernel  one thread per (frame, point), 256 points per workgroup: the frame's V records stream through LDS,
+//                         compacted in record order to those whose key falls in the workgroup's points; every thread adds its own in
+//                         ascending vertex.  One fixed-order sum per element, no floating-point atomics, no cap on how many vertices
+//                         reach one point.
+#include "staging.h"
+#include "trace.h"
+
+#include <cmath>
+
+namespace smplpp_hip
+{
+struct MeshPointDistState
+{
+  DevBuf part_d, part_k; // [n][chunks][V] partial (d, k) of a split forward
+  DevBuf rec;            // [n][V] MpdRecord of the backward pass
+  DevBuf verts, points, index, sqdist, gsq, gv, gp; // staging for host-space calls
+};
+void StateDelete::operator()(MeshPointDistState * s) const
+{
+  delete s;
+}
+
+constexpr int MPD_THREADS = 256;
+constexpr int MPD_VPL = 4;                            // vertices per lane
+constexpr int MPD_VBLOCK = MPD_THREADS * MPD_VPL;     // vertices per workgroup
+constexpr int MPD_TILE = 1024;                        // points per LDS tile (float4: 16 KiB)
+constexpr int64_t MPD_TARGET_WG = 2048;               // below this many (frame, vertex block) workgroups the call splits K ...
+constexpr int64_t MPD_MIN_CHUNK = 256;                // ... into chunks of at least this many points
+constexpr int MPD_GATHER_K = 256;                     // points per workgroup of the backward gather
+constexpr int MPD_GATHER_R = 4;                       // records per thread per tile of the backward gather
+
+struct MpdRecord
+{
+  int32_t k;   // the point (-1: no record)
+  float g[3];  // -2 g r
+};
+static_assert(sizeof(MpdRecord) == 16, "MpdRecord: one 16-byte load");
+
+// the contract's distance: ((dx dx + dy dy) + dz dz), no contraction to FMA
+__device__ inline float mpd_sqdist(float vx, float vy, float vz, float px, float py, float pz)
+{
+#pragma clang fp contract(off)
+  const float dx = vx - px, dy = vy - py, dz = vz - pz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// K chunks of one call: from (n, K) alone (the model's V fixes the vertex blocks), so the same call always splits the same way
+static int64_t mpd_chunk_len(int64_t n, int64_t K, int64_t vblocks)
+{
+  const int64_t wg = n * vblocks;
+  if(wg >= MPD_TARGET_WG || K < 2 * MPD_MIN_CHUNK) return K;
+  int64_t s = (MPD_TARGET_WG + wg - 1) / wg;
+  if(s > K / MPD_MIN_CHUNK) s = K / MPD_MIN_CHUNK;
+  return (K + s - 1) / s;
+}
+
+// ---- forward
+__global__ __launch_bounds__(MPD_THREADS) void mpd_scan_kernel(const float * __restrict__ verts, const float * __restrict__ points,
+                                                               int64_t * __restrict__ index_out, float * __restrict__ sq_out,
+                                                               float * __restrict__ part_d, int32_t * __restrict__ part_k, int64_t V,
+                                                               int64_t K, int64_t vblocks, int64_t chunks, int64_t chunk)
+{
+  __shared__ float4 s_p[MPD_TILE];
+  const uint32_t b = blockIdx.x; // (the grid is below 2^31: 32-bit index arithmetic)
+  const int64_t vb = b % (uint32_t)vblocks;
+  const int64_t fc = b / (uint32_t)vblocks; // frame * chunks + c
+  const int64_t c = (uint32_t)fc % (uint32_t)chunks, frame = (uint32_t)fc / (uint32_t)chunks;
+  const int64_t k0 = c * chunk, k1 = k0 + chunk < K ? k0 + chunk : K;
+  const int t = threadIdx.x;
+  const float * vf = verts + frame * V * 3;
+  const float * pf = points + frame * K * 3;
+  float vx[MPD_VPL], vy[MPD_VPL], vz[MPD_VPL], bd[MPD_VPL];
+  int bk[MPD_VPL];
+#pragma unroll
+  for(int i = 0; i < MPD_VPL; i++)
+  {
+    int64_t v = vb * MPD_VBLOCK + i * MPD_THREADS + t;
+    if(v >= V) v = V - 1; // lanes past V repeat the last vertex and write nothing
+    vx[i] = vf[v * 3];
+    vy[i] = vf[v * 3 + 1];
+    vz[i] = vf[v * 3 + 2];
+    bd[i] = INFINITY;
+    bk[i] = -1;
+  }
+  for(int64_t base = k0; base < k1; base += MPD_TILE)
+  {
+    const int cnt = (int)(k1 - base < MPD_TILE ? k1 - base : MPD_TILE);
+    __syncthreads();
+    for(int j = t; j < cnt; j += MPD_THREADS)
+    {
+      const float * p = pf + (base + j) * 3;
+      s_p[j] = make_float4(p[0], p[1], p[2], 0.0f);
+    }
+    __syncthreads();
+#pragma unroll 4
+    for(int j = 0; j < cnt; j++)
+    {
+      const float4 p = s_p[j];
+      const int k = (int)base + j;
+#pragma unroll
+      for(int i = 0; i < MPD_VPL; i++)
+      {
+        const float d = mpd_sqdist(vx[i], vy[i], vz[i], p.x, p.y, p.z);
+        if(d < bd[i])
+        {
+          bd[i] = d;
+          bk[i] = k;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for(int i = 0; i < MPD_VPL; i++)
+  {
+    const int64_t v = vb * MPD_VBLOCK + i * MPD_THREADS + t;
+    if(v >= V) continue;
+    if(chunks == 1)
+    {
+      index_out[frame * V + v] = bk[i];
+      sq_out[frame * V + v] = bk[i] < 0 ? 0.0f : bd[i];
+    }
+    else
+    {
+      part_d[fc * V + v] = bd[i];
+      part_k[fc * V + v] = bk[i];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void mpd_reduce_kernel(const float * __restrict__ part_d, const int32_t * __restrict__ part_k,
+                                                         int64_t * __restrict__ index_out, float * __restrict__ sq_out, int64_t V,
+                                                         int64_t chunks, int64_t nv)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= nv) return;
+  const int64_t frame = i / V, v = i % V;
+  float bd = INFINITY;
+  int bk = -1;
+#pragma unroll 8
+  for(int64_t c = 0; c < chunks; c++) // (unrolled: the partials' loads are independent and go out together)
+  {
+    const int64_t j = (frame * chunks + c) * V + v;
+    const int k = part_k[j];
+    const float d = part_d[j];
+    if(k >= 0 && (bk < 0 || d < bd || (d == bd && k < bk)))
+    {
+      bd = d;
+      bk = k;
+    }
+  }
+  index_out[i] = bk;
+  sq_out[i] = bk < 0 ? 0.0f : bd;
+}
+
+// ---- backward
+__global__ __launch_bounds__(256) void mpd_vjp_record_kernel(const float * __restrict__ verts, const float * __restrict__ points,
+                                                             const int64_t * __restrict__ index, const float * __restrict__ gsq,
+                                                             MpdRecord * __restrict__ rec, float * __restrict__ gv, int accumulate,
+                                                             int64_t V, int64_t K, int64_t nv)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= nv) return;
+  const float g = gsq[i];
+  const int64_t k = index[i];
+  MpdRecord r;
+  r.k = -1;
+  r.g[0] = r.g[1] = r.g[2] = 0.0f;
+  float gvt[3] = {0.0f, 0.0f, 0.0f};
+  if(g != 0.0f && k >= 0 && k < K)
+  {
+    const float * p = points + ((i / V) * K + k) * 3;
+    const float rr[3] = {verts[i * 3] - p[0], verts[i * 3 + 1] - p[1], verts[i * 3 + 2] - p[2]};
+    const float s = 2.0f * g, sn = -2.0f * g;
+    r.k = (int32_t)k;
+    for(int x = 0; x < 3; x++)
+    {
+      gvt[x] = s * rr[x];
+      r.g[x] = sn * rr[x];
+    }
+  }
+  if(rec) rec[i] = r;
+  if(gv)
+    for(int x = 0; x < 3; x++) gv[i * 3 + x] = accumulate ? gv[i * 3 + x] + gvt[x] : gvt[x];
+}
+
+__global__ __launch_bounds__(256) void mpd_vjp_gather_kernel(const MpdRecord * __restrict__ rec, float * __restrict__ gp, int accumulate,
+                                                             int64_t V, int64_t K, int64_t blocks_per_frame)
+{
+  constexpr int RT = 256 * MPD_GATHER_R; // records per tile
+  __shared__ float4 s_r[RT];
+  __shared__ int s_cnt[MPD_GATHER_R][4];
+  const int64_t frame = blockIdx.x / blocks_per_frame;
+  const int lo = (int)(blockIdx.x % blocks_per_frame) * MPD_GATHER_K;
+  const int hi = (int)(lo + MPD_GATHER_K < K ? lo + MPD_GATHER_K : K);
+  const int k = lo + (int)threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float4 * rf = reinterpret_cast<const float4 *>(rec + frame * V);
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  for(int64_t base = 0; base < V; base += RT)
+  {
+    float4 rr[MPD_GATHER_R];
+    bool hit[MPD_GATHER_R];
+    int pos[MPD_GATHER_R];
+#pragma unroll
+    for(int r = 0; r < MPD_GATHER_R; r++)
+    {
+      const int64_t i = base + r * 256 + threadIdx.x;
+      rr[r] = i < V ? rf[i] : make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
+      const int key = __float_as_int(rr[r].x);
+      hit[r] = key >= lo && key < hi;
+      const uint64_t mask = __ballot(hit[r]);
+      pos[r] = (int)__popcll(mask & ((1ull << lane) - 1ull));
+      if(lane == 0) s_cnt[r][wave] = (int)__popcll(mask);
+    }
+    __syncthreads();
+    int total = 0;
+#pragma unroll
+    for(int r = 0; r < MPD_GATHER_R; r++)
+      for(int w = 0; w < 4; w++)
+      {
+        if(w == wave) pos[r] += total; // records before this one: earlier rows, then earlier wavefronts of this row
+        total += s_cnt[r][w];
+      }
+#pragma unroll
+    for(int r = 0; r < MPD_GATHER_R; r++)
+      if(hit[r]) s_r[pos[r]] = rr[r];
+    __syncthreads();
+    if(k < hi)
+#pragma unroll 8
+      for(int h = 0; h < total; h++) // (unrolled: independent LDS reads in flight; the adds keep their order)
+      {
+        // branch-free: adding +0 for another point's record leaves acc's bits (it starts at +0, so it is never -0)
+        const float4 R = s_r[h];
+        const bool mine = __float_as_int(R.x) == k;
+        acc[0] += mine ? R.y : 0.0f;
+        acc[1] += mine ? R.z : 0.0f;
+        acc[2] += mine ? R.w : 0.0f;
+      }
+    __syncthreads();
+  }
+  if(k >= hi) return;
+  float * o = gp + (frame * K + k) * 3;
+  for(int x = 0; x < 3; x++) o[x] = accumulate ? o[x] + acc[x] : acc[x];
+}
+
+static MeshPointDistState * mpd_state(smplpp_model * m)
+{
+  if(!m->mpd) m->mpd.reset(new MeshPointDistState());
+  return m->mpd.get();
+}
+
+// all pointers on the device
+static int mpd_forward_device(smplpp_model * m, MeshPointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
+                              int64_t * index, float * sqdist, hipStream_t st)
+{
+  const int64_t V = m->V;
+  const int64_t vblocks = (V + MPD_VBLOCK - 1) / MPD_VBLOCK;
+  const int64_t chunk = mpd_chunk_len(n, K, vblocks);
+  const int64_t chunks = (K + chunk - 1) / chunk;
+  float * pd = nullptr;
+  int32_t * pk = nullptr;
+  if(chunks > 1)
+  {
+    HIP_TRY(s->part_d.reserve(sizeof(float) * (size_t)(n * chunks * V)));
+    HIP_TRY(s->part_k.reserve(sizeof(int32_t) * (size_t)(n * chunks * V)));
+    pd = s->part_d.as<float>();
+    pk = s->part_k.as<int32_t>();
+  }
+  mpd_scan_kernel<<<dim3((unsigned)(n * chunks * vblocks)), dim3(MPD_THREADS), 0, st>>>(verts, points, index, sqdist, pd, pk, V, K, vblocks,
+                                                                                        chunks, chunk);
+  HIP_TRY(hipGetLastError());
+  if(chunks > 1)
+  {
+    mpd_reduce_kernel<<<dim3((unsigned)((n * V + 255) / 256)), dim3(256), 0, st>>>(pd, pk, index, sqdist, V, chunks, n * V);
+    HIP_TRY(hipGetLastError());
+  }
+  return SMPLPP_OK;
+}
+
+static int mpd_vjp_device(smplpp_model * m, MeshPointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
+                          const int64_t * index, const float * gsq, float * gv, float * gp, int accumulate, hipStream_t st)
+{
+  const int64_t V = m->V, nv = n * V;
+  MpdRecord * rec = nullptr;
+  if(gp)
+  {
+    HIP_TRY(s->rec.reserve(sizeof(MpdRecord) * (size_t)nv));
+    rec = s->rec.as<MpdRecord>();
+  }
+  mpd_vjp_record_kernel<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st>>>(verts, points, index, gsq, rec, gv, accumulate, V, K, nv);
+  HIP_TRY(hipGetLastError());
+  if(gp)
+  {
+    const int64_t bpf = (K + MPD_GATHER_K - 1) / MPD_GATHER_K;
+    mpd_vjp_gather_kernel<<<dim3((unsigned)(n * bpf)), dim3(256), 0, st>>>(rec, gp, accumulate, V, K, bpf);
+    HIP_TRY(hipGetLastError());
+  }
+  return SMPLPP_OK;
+}
+} // namespace smplpp_hip
+
+using namespace smplpp_hip;
+
+static int mpd_check(const char * fn, smplpp_model * m, int64_t n, int64_t K, int space)
+{
+  // every [n,K] and [n,V] index, every partial [n][chunks][V] index and every grid below stays in int32
+  if(n > 0x7fffffffLL || K > 0x7fffffffLL || n * K > 0x7fffffffLL || n * m->V > 0x7fffffffLL)
+    return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": n * K or n * V beyond int32 indexing");
+  return check_space(space, fn);
+}
+
+extern "C" int smplpp_mesh_point_distance(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points, int64_t * index,
+                                          float * sqdist, int space, void * stream)
+{
+  const char * fn = "smplpp_mesh_point_distance";
+  if(!m || n <= 0 || K <= 0 || !verts || !points || !index || !sqdist) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
+  int rc = mpd_check(fn, m, n, K, space);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceRange tr("mesh-point distance");
+  MeshPointDistState * s = mpd_state(m);
+  In<float> v, p;
+  Out<int64_t> io;
+  Out<float> so;
+  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
+  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->points));
+  HIP_TRY(io.init(index, (size_t)n * m->V, space, &s->index));
+  HIP_TRY(so.init(sqdist, (size_t)n * m->V, space, &s->sqdist));
+  rc = mpd_forward_device(m, s, n, v.d, K, p.d, io.d, so.d, st);
+  if(rc) return rc;
+  HIP_TRY(io.finish(st));
+  HIP_TRY(so.finish(st));
+  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
+                                              const int64_t * index, const float * grad_sqdist, float * grad_verts, float * grad_points,
+                                              int accumulate, int space, void * stream)
+{
+  const char * fn = "smplpp_mesh_point_distance_vjp";
+  if(!m || n <= 0 || K <= 0 || !verts || !points || !index || !grad_sqdist || (!grad_verts && !grad_points))
+    return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
+  if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
+  int rc = mpd_check(fn, m, n, K, space);
+  if(rc) return rc;
+  if(space == SMPLPP_HOST)
+    for(int64_t i = 0; i < n * m->V; i++)
+      if(index[i] < -1 || index[i] >= K) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": point index out of range");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceRange tr("mesh-point distance VJP");
+  MeshPointDistState * s = mpd_state(m);
+  In<float> v, p, g;
+  In<int64_t> ii;
+  Out<float> gv, gp;
+  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
+  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->points));
+  HIP_TRY(ii.init(index, (size_t)n * m->V, space, st, &s->index));
+  HIP_TRY(g.init(grad_sqdist, (size_t)n * m->V, space, st, &s->gsq));
+  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
+  HIP_TRY(gp.init(grad_points, (size_t)n * K * 3, space, &s->gp));
+  if(accumulate)
+  {
+    HIP_TRY(gv.load(st));
+    HIP_TRY(gp.load(st));
+  }
+  rc = mpd_vjp_device(m, s, n, v.d, K, p.d, ii.d, g.d, gv.d, gp.d, accumulate, st);
+  if(rc) return rc;
+  HIP_TRY(gv.finish(st));
+  HIP_TRY(gp.finish(st));
+  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
+  return SMPLPP_OK;
+}

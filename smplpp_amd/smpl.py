@@ -466,6 +466,62 @@ class SMPL:
             raise SmplppError(1, "point_mesh_distance_differentiable needs torch")
         return _PointDistanceFunction.apply(verts, points, self)
 
+    # ---- mesh-to-point distance (smplpp_mesh_point_distance / smplpp_mesh_point_distance_vjp)
+    def _mpd(self, c, verts, points, K):
+        n, V = len(verts), self.vertex_num
+        index, sq = c.empty((n, V), "int64"), c.empty((n, V))
+        check(_lib.load().smplpp_mesh_point_distance(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(index), _ptr(sq), c.space, c.stream))
+        return index, sq
+
+    def _mpd_vjp(self, c, verts, points, K, index, grad_sqdist, out, grad_points, want_verts=True, want_points=True):
+        n, V = len(verts), self.vertex_num
+        idx = c.ids(index)
+        if idx.shape[0] != n * V:
+            c.refuse("expected index of shape (%d, %d)" % (n, V))
+        g = c.input(grad_sqdist, (n, V))
+        acc = out is not None or grad_points is not None
+
+        def buf(a, shape, want):
+            if a is not None:
+                return c.inout(a, shape)
+            if not want:
+                return None
+            if not acc:
+                return c.empty(shape)
+            return torch.zeros(shape, dtype=torch.float32, device=c.device) if c.dev else np.zeros(shape, np.float32)
+
+        gv, gp = buf(out, (n, V, 3), want_verts), buf(grad_points, (n, K, 3), want_points)
+        check(_lib.load().smplpp_mesh_point_distance_vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(idx), _ptr(g), _ptr(gv), _ptr(gp),
+                                                         int(acc), c.space, c.stream))
+        return gv, gp
+
+    def meshPointDistance(self, verts, points):
+        """The nearest of K points [N,K,3] to each vertex of each frame's mesh verts [N,V,3] (smplpp_mesh_point_distance): returns
+        (index [N,V] int64, sqdist [N,V]).  sqdist is the fp32 ((dx*dx + dy*dy) + dz*dz) of d = v - p without FMA; the lowest
+        index wins ties; non-finite distances are never chosen, and a vertex with no eligible point gets (-1, 0).  The other
+        direction of pointMeshDistance.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("meshPointDistance", verts, points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        return self._mpd(c, verts, points, K)
+
+    def meshPointDistanceBackward(self, verts, points, index, grad_sqdist, out=None, grad_points=None):
+        """Vector-Jacobian product of meshPointDistance's sqdist at the points `index` [N,V] it chose: (grad_verts [N,V,3],
+        grad_points [N,K,3]) for dL/dsqdist = grad_sqdist [N,V] (smplpp_mesh_point_distance_vjp).  `out` [N,V,3] and / or
+        `grad_points` [N,K,3] given: the product is added into them (and they are returned); an array not given is then
+        returned holding the product alone.  A zero cotangent masks a vertex out."""
+        c = _Call("meshPointDistanceBackward", verts, points, grad_sqdist, out, grad_points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        return self._mpd_vjp(c, verts, points, K, index, grad_sqdist, out, grad_points)
+
+    def mesh_point_distance_differentiable(self, verts, points):
+        """(index [N,V], sqdist [N,V]) of device vertices verts [N,V,3] against device points [N,K,3] (the bits of
+        meshPointDistance), with sqdist differentiable in both verts and points through torch.autograd: smplpp_mesh_point_distance
+        forward, smplpp_mesh_point_distance_vjp backward, on torch's current stream.  index is not differentiable.  With
+        point_mesh_distance_differentiable, the two halves of a two-sided (Chamfer) scan registration loss."""
+        if torch is None:
+            raise SmplppError(1, "mesh_point_distance_differentiable needs torch")
+        return _MeshPointDistanceFunction.apply(verts, points, self)
+
     def out(self, index: int, path: str):
         """SMPL::out (src/SMPL.cpp:757-790): Wavefront OBJ of frame `index` (v lines, then 1-based f lines)."""
         verts = self._need("verts")
@@ -539,6 +595,29 @@ if torch is not None:
                 return None, None, None
             c = _Call("point_mesh_distance_differentiable", verts, device_only=True)
             gv, gp = ctx.smpl._pmd_vjp(c, verts, points, ctx.K, face, grad_sqdist.contiguous(), None, None, want_v, want_p)
+            return gv, gp, None
+
+    class _MeshPointDistanceFunction(torch.autograd.Function):
+        """smplpp_mesh_point_distance forward / smplpp_mesh_point_distance_vjp backward (SMPL.mesh_point_distance_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, points, smpl):
+            c = _Call("mesh_point_distance_differentiable", verts, points, device_only=True)
+            verts, points, K = smpl._pmd_inputs(c, verts, points)
+            index, sq = smpl._mpd(c, verts, points, K)
+            ctx.mark_non_differentiable(index)
+            ctx.smpl, ctx.K = smpl, K
+            ctx.save_for_backward(verts, points, index)
+            return index, sq
+
+        @staticmethod
+        def backward(ctx, grad_index, grad_sqdist):
+            verts, points, index = ctx.saved_tensors
+            want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if grad_sqdist is None or not (want_v or want_p):
+                return None, None, None
+            c = _Call("mesh_point_distance_differentiable", verts, device_only=True)
+            gv, gp = ctx.smpl._mpd_vjp(c, verts, points, ctx.K, index, grad_sqdist.contiguous(), None, None, want_v, want_p)
             return gv, gp, None
 
 
