@@ -349,22 +349,8 @@ public:
   Tensor pointMeshDistanceBackward(const Tensor & points, const Tensor & face, const Tensor & gradSqdist, Tensor * gradPoints = nullptr,
                                    Tensor * accumulate = nullptr) const
   {
-    need(verts_);
-    const int64_t n = verts_.size(0);
-    const int64_t K = points.dim() == 3 ? points.size(1) : 0;
-    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || K < 1 || points.size(2) != 3 ||
-       (face.dtype != kInt64 && face.dtype != kInt32) || face.numel() != n * K || gradSqdist.dtype != kFloat32 || gradSqdist.numel() != n * K ||
-       (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3)) ||
-       (accumulate && gradPoints && (gradPoints->dtype != kFloat32 || gradPoints->numel() != n * K * 3)))
-      throw Exception("SMPL", "Cannot back-propagate through the point-to-mesh distance!");
-    Tensor fresh;
-    if(!accumulate) fresh = Tensor(verts_.shape);
-    Tensor & g = accumulate ? *accumulate : fresh;
-    if(gradPoints && !accumulate) *gradPoints = Tensor({n, K, 3});
-    check(smplpp_point_mesh_distance_vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), face.idata.data(), gradSqdist.ptr(), g.ptr(),
-                                         gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
-          "SMPL");
-    return g;
+    return distanceBackward(smplpp_point_mesh_distance_vjp, false, points, face, gradSqdist, gradPoints, accumulate,
+                            "Cannot back-propagate through the point-to-mesh distance!");
   }
   // Mesh-to-point distance on the last launch's vertices (the other direction of pointMeshDistance): for points [N,K,3], the nearest
   // point to each vertex of each frame's mesh (smplpp_mesh_point_distance).  index [N,V] kInt64 (-1: no finite distance), sqdist [N,V].
@@ -390,22 +376,8 @@ public:
   Tensor meshPointDistanceBackward(const Tensor & points, const Tensor & index, const Tensor & gradSqdist, Tensor * gradPoints = nullptr,
                                    Tensor * accumulate = nullptr) const
   {
-    need(verts_);
-    const int64_t n = verts_.size(0);
-    const int64_t K = points.dim() == 3 ? points.size(1) : 0;
-    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || K < 1 || points.size(2) != 3 ||
-       (index.dtype != kInt64 && index.dtype != kInt32) || index.numel() != n * V_ || gradSqdist.dtype != kFloat32 ||
-       gradSqdist.numel() != n * V_ || (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3)) ||
-       (accumulate && gradPoints && (gradPoints->dtype != kFloat32 || gradPoints->numel() != n * K * 3)))
-      throw Exception("SMPL", "Cannot back-propagate through the mesh-to-point distance!");
-    Tensor fresh;
-    if(!accumulate) fresh = Tensor(verts_.shape);
-    Tensor & g = accumulate ? *accumulate : fresh;
-    if(gradPoints && !accumulate) *gradPoints = Tensor({n, K, 3});
-    check(smplpp_mesh_point_distance_vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), index.idata.data(), gradSqdist.ptr(), g.ptr(),
-                                         gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
-          "SMPL");
-    return g;
+    return distanceBackward(smplpp_mesh_point_distance_vjp, true, points, index, gradSqdist, gradPoints, accumulate,
+                            "Cannot back-propagate through the mesh-to-point distance!");
   }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
@@ -466,6 +438,27 @@ private:
       check((kind == 1 ? smplpp_vertex_normals_vjp : smplpp_face_normals_vjp)(m_.get(), n, verts_.ptr(), rows, ids.data(), gradNormal.ptr(),
                                                                              g.ptr(), acc, SMPLPP_HOST, nullptr),
             "SMPL");
+    return g;
+  }
+  // the two *DistanceBackward: ids and gradSqdist hold one entry per vertex (perVertex) or per point
+  Tensor distanceBackward(decltype(&smplpp_point_mesh_distance_vjp) vjp, bool perVertex, const Tensor & points, const Tensor & ids,
+                          const Tensor & gradSqdist, Tensor * gradPoints, Tensor * accumulate, const char * what) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const int64_t K = points.dim() == 3 ? points.size(1) : 0, rows = n * (perVertex ? V_ : K);
+    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || K < 1 || points.size(2) != 3 ||
+       (ids.dtype != kInt64 && ids.dtype != kInt32) || ids.numel() != rows || gradSqdist.dtype != kFloat32 || gradSqdist.numel() != rows ||
+       (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3)) ||
+       (accumulate && gradPoints && (gradPoints->dtype != kFloat32 || gradPoints->numel() != n * K * 3)))
+      throw Exception("SMPL", what);
+    Tensor fresh;
+    if(!accumulate) fresh = Tensor(verts_.shape);
+    Tensor & g = accumulate ? *accumulate : fresh;
+    if(gradPoints && !accumulate) *gradPoints = Tensor({n, K, 3});
+    check(vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), ids.idata.data(), gradSqdist.ptr(), g.ptr(),
+              gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
     return g;
   }
   std::shared_ptr<smplpp_model> m_;

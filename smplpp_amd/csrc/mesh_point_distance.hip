@@ -13,12 +13,8 @@
 // Backward (no search: the forward's index is an input), r = v - p[index], g = grad_sqdist:
 //  mpd_vjp_record_kernel  per (frame, vertex): grad_verts = 2 g r, and the record (index, -2 g r) for grad_points.  A zero
 //                         cotangent or an index out of [0, K) gives no record (key -1) and a zero grad_verts.
-//  mpd_vjp_gather_kernel  one thread per (frame, point), 256 points per workgroup: the frame's V records stream through LDS,
-//                         compacted in record order to those whose key falls in the workgroup's points; every thread adds its own in
-//                         ascending vertex.  One fixed-order sum per element, no floating-point atomics, no cap on how many vertices
-//                         reach one point.
-#include "staging.h"
-#include "trace.h"
+//  record_gather_kernel<MpdRecord>  (distance_vjp.h) grad_points: one fixed-order sum per point, ascending vertex.
+#include "distance_vjp.h"
 
 #include <cmath>
 
@@ -28,7 +24,8 @@ struct MeshPointDistState
 {
   DevBuf part_d, part_k; // [n][chunks][V] partial (d, k) of a split forward
   DevBuf rec;            // [n][V] MpdRecord of the backward pass
-  DevBuf verts, points, index, sqdist, gsq, gv, gp; // staging for host-space calls
+  DistanceStaging io;    // staging for host-space calls (index in io.ids) ...
+  DevBuf sqdist;         // ... and the forward's distances
 };
 void StateDelete::operator()(MeshPointDistState * s) const
 {
@@ -41,13 +38,30 @@ constexpr int MPD_VBLOCK = MPD_THREADS * MPD_VPL;     // vertices per workgroup
 constexpr int MPD_TILE = 1024;                        // points per LDS tile (float4: 16 KiB)
 constexpr int64_t MPD_TARGET_WG = 2048;               // below this many (frame, vertex block) workgroups the call splits K ...
 constexpr int64_t MPD_MIN_CHUNK = 256;                // ... into chunks of at least this many points
-constexpr int MPD_GATHER_K = 256;                     // points per workgroup of the backward gather
-constexpr int MPD_GATHER_R = 4;                       // records per thread per tile of the backward gather
 
 struct MpdRecord
 {
   int32_t k;   // the point (-1: no record)
   float g[3];  // -2 g r
+
+  // record_gather_kernel's pieces: the record staged whole, as float4 (with int4 the loop branched round the reads: 2-4x slower)
+  struct Tile
+  {
+    float4 r[GATHER_TILE];
+  };
+  __device__ static bool touches(const int4 & R, int lo, int hi) { return R.x >= lo && R.x < hi; }
+  __device__ static void stage(Tile & t, int pos, const int4 & R, const MpdRecord &)
+  {
+    t.r[pos] = make_float4(__int_as_float(R.x), __int_as_float(R.y), __int_as_float(R.z), __int_as_float(R.w));
+  }
+  __device__ static void add(float * acc, const Tile & t, int h, int u)
+  {
+    const float4 R = t.r[h];
+    const bool mine = __float_as_int(R.x) == u;
+    acc[0] += mine ? R.y : 0.0f;
+    acc[1] += mine ? R.z : 0.0f;
+    acc[2] += mine ? R.w : 0.0f;
+  }
 };
 static_assert(sizeof(MpdRecord) == 16, "MpdRecord: one 16-byte load");
 
@@ -198,66 +212,6 @@ __global__ __launch_bounds__(256) void mpd_vjp_record_kernel(const float * __res
     for(int x = 0; x < 3; x++) gv[i * 3 + x] = accumulate ? gv[i * 3 + x] + gvt[x] : gvt[x];
 }
 
-__global__ __launch_bounds__(256) void mpd_vjp_gather_kernel(const MpdRecord * __restrict__ rec, float * __restrict__ gp, int accumulate,
-                                                             int64_t V, int64_t K, int64_t blocks_per_frame)
-{
-  constexpr int RT = 256 * MPD_GATHER_R; // records per tile
-  __shared__ float4 s_r[RT];
-  __shared__ int s_cnt[MPD_GATHER_R][4];
-  const int64_t frame = blockIdx.x / blocks_per_frame;
-  const int lo = (int)(blockIdx.x % blocks_per_frame) * MPD_GATHER_K;
-  const int hi = (int)(lo + MPD_GATHER_K < K ? lo + MPD_GATHER_K : K);
-  const int k = lo + (int)threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float4 * rf = reinterpret_cast<const float4 *>(rec + frame * V);
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  for(int64_t base = 0; base < V; base += RT)
-  {
-    float4 rr[MPD_GATHER_R];
-    bool hit[MPD_GATHER_R];
-    int pos[MPD_GATHER_R];
-#pragma unroll
-    for(int r = 0; r < MPD_GATHER_R; r++)
-    {
-      const int64_t i = base + r * 256 + threadIdx.x;
-      rr[r] = i < V ? rf[i] : make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
-      const int key = __float_as_int(rr[r].x);
-      hit[r] = key >= lo && key < hi;
-      const uint64_t mask = __ballot(hit[r]);
-      pos[r] = (int)__popcll(mask & ((1ull << lane) - 1ull));
-      if(lane == 0) s_cnt[r][wave] = (int)__popcll(mask);
-    }
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for(int r = 0; r < MPD_GATHER_R; r++)
-      for(int w = 0; w < 4; w++)
-      {
-        if(w == wave) pos[r] += total; // records before this one: earlier rows, then earlier wavefronts of this row
-        total += s_cnt[r][w];
-      }
-#pragma unroll
-    for(int r = 0; r < MPD_GATHER_R; r++)
-      if(hit[r]) s_r[pos[r]] = rr[r];
-    __syncthreads();
-    if(k < hi)
-#pragma unroll 8
-      for(int h = 0; h < total; h++) // (unrolled: independent LDS reads in flight; the adds keep their order)
-      {
-        // branch-free: adding +0 for another point's record leaves acc's bits (it starts at +0, so it is never -0)
-        const float4 R = s_r[h];
-        const bool mine = __float_as_int(R.x) == k;
-        acc[0] += mine ? R.y : 0.0f;
-        acc[1] += mine ? R.z : 0.0f;
-        acc[2] += mine ? R.w : 0.0f;
-      }
-    __syncthreads();
-  }
-  if(k >= hi) return;
-  float * o = gp + (frame * K + k) * 3;
-  for(int x = 0; x < 3; x++) o[x] = accumulate ? o[x] + acc[x] : acc[x];
-}
-
 static MeshPointDistState * mpd_state(smplpp_model * m)
 {
   if(!m->mpd) m->mpd.reset(new MeshPointDistState());
@@ -304,13 +258,7 @@ static int mpd_vjp_device(smplpp_model * m, MeshPointDistState * s, int64_t n, c
   }
   mpd_vjp_record_kernel<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st>>>(verts, points, index, gsq, rec, gv, accumulate, V, K, nv);
   HIP_TRY(hipGetLastError());
-  if(gp)
-  {
-    const int64_t bpf = (K + MPD_GATHER_K - 1) / MPD_GATHER_K;
-    mpd_vjp_gather_kernel<<<dim3((unsigned)(n * bpf)), dim3(256), 0, st>>>(rec, gp, accumulate, V, K, bpf);
-    HIP_TRY(hipGetLastError());
-  }
-  return SMPLPP_OK;
+  return gp ? record_gather(rec, gp, accumulate, n, V, K, st) : SMPLPP_OK;
 }
 } // namespace smplpp_hip
 
@@ -338,9 +286,9 @@ extern "C" int smplpp_mesh_point_distance(smplpp_model * m, int64_t n, const flo
   In<float> v, p;
   Out<int64_t> io;
   Out<float> so;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->points));
-  HIP_TRY(io.init(index, (size_t)n * m->V, space, &s->index));
+  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->io.verts));
+  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->io.points));
+  HIP_TRY(io.init(index, (size_t)n * m->V, space, &s->io.ids));
   HIP_TRY(so.init(sqdist, (size_t)n * m->V, space, &s->sqdist));
   rc = mpd_forward_device(m, s, n, v.d, K, p.d, io.d, so.d, st);
   if(rc) return rc;
@@ -363,28 +311,6 @@ extern "C" int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const
   if(space == SMPLPP_HOST)
     for(int64_t i = 0; i < n * m->V; i++)
       if(index[i] < -1 || index[i] >= K) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": point index out of range");
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("mesh-point distance VJP");
-  MeshPointDistState * s = mpd_state(m);
-  In<float> v, p, g;
-  In<int64_t> ii;
-  Out<float> gv, gp;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->points));
-  HIP_TRY(ii.init(index, (size_t)n * m->V, space, st, &s->index));
-  HIP_TRY(g.init(grad_sqdist, (size_t)n * m->V, space, st, &s->gsq));
-  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
-  HIP_TRY(gp.init(grad_points, (size_t)n * K * 3, space, &s->gp));
-  if(accumulate)
-  {
-    HIP_TRY(gv.load(st));
-    HIP_TRY(gp.load(st));
-  }
-  rc = mpd_vjp_device(m, s, n, v.d, K, p.d, ii.d, g.d, gv.d, gp.d, accumulate, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  HIP_TRY(gp.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  return distance_vjp(mpd_vjp_device, m, mpd_state(m), "mesh-point distance VJP", n, verts, K, points, index, n * m->V, grad_sqdist,
+                      grad_verts, grad_points, accumulate, space, stream);
 }

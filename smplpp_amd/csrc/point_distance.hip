@@ -22,13 +22,9 @@
 //  pd_vjp_record_kernel  per query: c and w recomputed with the forward's evaluation, r = p - c; grad_points = 2 g r and the record
 //                        (the face's three vertex ids, -2 g w_j r for j = 0..2).  A zero cotangent or an out-of-range face gives no
 //                        record (ids -1) and a zero grad_points.
-//  pd_vjp_gather_kernel  one thread per (frame, vertex), 256 vertices per workgroup: the frame's records stream through LDS 1024 at a
-//                        time, compacted in record order to those that touch the workgroup's vertices; every thread adds its own
-//                        corners in ascending record index, then corner.  One fixed-order sum per element, no floating-point
-//                        atomics, no cap on how many records reach one vertex, and a frame's bits do not depend on n.
+//  record_gather_kernel<PdRecord>  (distance_vjp.h) grad_verts: one fixed-order sum per vertex, ascending record index, then corner.
+#include "distance_vjp.h"
 #include "mesh_device.h"
-#include "staging.h"
-#include "trace.h"
 
 #include <cmath>
 
@@ -41,7 +37,8 @@ struct PointDistState
   DevBuf rec;          // [n][K] PdRecord of the backward pass
   DevBuf seedv;        // [nseed] int32 vertices that have a face (model constant, set up by the first call)
   int64_t nseed = -1;
-  DevBuf verts, points, face, weights, closest, sqdist, gsq, gv, gp; // staging for host-space calls
+  DistanceStaging io;                // staging for host-space calls (face in io.ids) ...
+  DevBuf weights, closest, sqdist;   // ... and the forward's other outputs
 };
 void StateDelete::operator()(PointDistState * s) const
 {
@@ -54,14 +51,38 @@ constexpr int PD_THREADS = 64 * PD_WAVES;
 constexpr int PD_TILE = 64 * PD_WAVES;        // faces per LDS tile (64 per wavefront)
 constexpr int PD_VTILE = 3 * PD_TILE;         // seed vertices per LDS tile (the same 48 KiB)
 constexpr int PD_MORTON_BITS = 4;  // per axis: 4096 cells
-constexpr int PD_GATHER_V = 256;   // vertices per workgroup of the backward gather
-constexpr int PD_GATHER_R = 4;     // records per thread per tile of the backward gather
 
 struct PdRecord
 {
   int32_t u[4];   // the face's vertex ids (-1: no record), pad
   float g[3][3];  // -2 g w_j r per corner j
   float pad[3];
+
+  // record_gather_kernel's pieces: the ids and the nine shares staged apart (no padding in LDS)
+  struct Tile
+  {
+    int4 u[GATHER_TILE];
+    float g[GATHER_TILE][9];
+  };
+  __device__ static bool touches(const int4 & U, int lo, int hi)
+  {
+    return (U.x >= lo && U.x < hi) || (U.y >= lo && U.y < hi) || (U.z >= lo && U.z < hi);
+  }
+  __device__ static void stage(Tile & t, int pos, const int4 & U, const PdRecord & r)
+  {
+    t.u[pos] = U;
+    for(int e = 0; e < 9; e++) t.g[pos][e] = r.g[0][e];
+  }
+  __device__ static void add(float * acc, const Tile & t, int h, int u)
+  {
+    const int4 U = t.u[h];
+    if(U.x == u)
+      for(int x = 0; x < 3; x++) acc[x] += t.g[h][x];
+    if(U.y == u)
+      for(int x = 0; x < 3; x++) acc[x] += t.g[h][3 + x];
+    if(U.z == u)
+      for(int x = 0; x < 3; x++) acc[x] += t.g[h][6 + x];
+  }
 };
 static_assert(sizeof(PdRecord) == 64, "PdRecord: four 16-byte loads");
 
@@ -401,71 +422,6 @@ __global__ __launch_bounds__(256) void pd_vjp_record_kernel(const float * __rest
     for(int x = 0; x < 3; x++) gp[i * 3 + x] = accumulate ? gp[i * 3 + x] + gpt[x] : gpt[x];
 }
 
-__global__ __launch_bounds__(256) void pd_vjp_gather_kernel(const PdRecord * __restrict__ rec, float * __restrict__ gv, int accumulate,
-                                                            int64_t V, int64_t K, int64_t blocks_per_frame)
-{
-  constexpr int RT = 256 * PD_GATHER_R; // records per tile
-  __shared__ int4 s_u[RT];
-  __shared__ float s_g[RT][9];
-  __shared__ int s_cnt[PD_GATHER_R][4];
-  const int64_t frame = blockIdx.x / blocks_per_frame;
-  const int lo = (int)(blockIdx.x % blocks_per_frame) * PD_GATHER_V;
-  const int hi = (int)(lo + PD_GATHER_V < V ? lo + PD_GATHER_V : V);
-  const int u = lo + (int)threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const PdRecord * rf = rec + frame * K;
-  float acc[3] = {0.0f, 0.0f, 0.0f};
-  for(int64_t base = 0; base < K; base += RT)
-  {
-    int4 ru[PD_GATHER_R];
-    bool hit[PD_GATHER_R];
-    int pos[PD_GATHER_R];
-#pragma unroll
-    for(int r = 0; r < PD_GATHER_R; r++)
-    {
-      const int64_t i = base + r * 256 + threadIdx.x;
-      ru[r] = i < K ? *reinterpret_cast<const int4 *>(rf[i].u) : make_int4(-1, -1, -1, 0);
-      hit[r] = (ru[r].x >= lo && ru[r].x < hi) || (ru[r].y >= lo && ru[r].y < hi) || (ru[r].z >= lo && ru[r].z < hi);
-      const uint64_t mask = __ballot(hit[r]);
-      pos[r] = (int)__popcll(mask & ((1ull << lane) - 1ull));
-      if(lane == 0) s_cnt[r][wave] = (int)__popcll(mask);
-    }
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for(int r = 0; r < PD_GATHER_R; r++)
-      for(int w = 0; w < 4; w++)
-      {
-        if(w == wave) pos[r] += total; // records before this one: earlier rows, then earlier wavefronts of this row
-        total += s_cnt[r][w];
-      }
-#pragma unroll
-    for(int r = 0; r < PD_GATHER_R; r++)
-      if(hit[r])
-      {
-        const float * src = rf[base + r * 256 + threadIdx.x].g[0];
-        s_u[pos[r]] = ru[r];
-        for(int e = 0; e < 9; e++) s_g[pos[r]][e] = src[e];
-      }
-    __syncthreads();
-    if(u < hi)
-      for(int h = 0; h < total; h++)
-      {
-        const int4 U = s_u[h];
-        if(U.x == u)
-          for(int x = 0; x < 3; x++) acc[x] += s_g[h][x];
-        if(U.y == u)
-          for(int x = 0; x < 3; x++) acc[x] += s_g[h][3 + x];
-        if(U.z == u)
-          for(int x = 0; x < 3; x++) acc[x] += s_g[h][6 + x];
-      }
-    __syncthreads();
-  }
-  if(u >= hi) return;
-  float * o = gv + (frame * V + u) * 3;
-  for(int x = 0; x < 3; x++) o[x] = accumulate ? o[x] + acc[x] : acc[x];
-}
-
 static PointDistState * pd_state(smplpp_model * m)
 {
   if(!m->pd) m->pd.reset(new PointDistState());
@@ -524,13 +480,7 @@ static int pd_vjp_device(smplpp_model * m, PointDistState * s, int64_t n, const 
   pd_vjp_record_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(verts, m->faces.get(), points, face, gsq, rec, gp, accumulate, V,
                                                                                  m->F, K, nk);
   HIP_TRY(hipGetLastError());
-  if(gv)
-  {
-    const int64_t bpf = (V + PD_GATHER_V - 1) / PD_GATHER_V;
-    pd_vjp_gather_kernel<<<dim3((unsigned)(n * bpf)), dim3(256), 0, st>>>(rec, gv, accumulate, V, K, bpf);
-    HIP_TRY(hipGetLastError());
-  }
-  return SMPLPP_OK;
+  return gv ? record_gather(rec, gv, accumulate, n, K, V, st) : SMPLPP_OK;
 }
 } // namespace smplpp_hip
 
@@ -541,7 +491,7 @@ static int pd_check(const char * fn, smplpp_model * m, int64_t n, int64_t K, int
   const std::string name(fn);
   if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, name + ": model has no faces");
   // every [n,K] index and every grid below stays in int32 (the tiled form's grid is n * ceil(K / 64), the gather's n * ceil(V / 256))
-  if(n > 0x7fffffffLL || K > 0x7fffffffLL || n * K > 0x7fffffffLL || n * ((m->V + PD_GATHER_V - 1) / PD_GATHER_V) > 0x7fffffffLL)
+  if(n > 0x7fffffffLL || K > 0x7fffffffLL || n * K > 0x7fffffffLL || n * ((m->V + GATHER_T - 1) / GATHER_T) > 0x7fffffffLL)
     return fail(SMPLPP_ERR_INVALID, name + ": n * K beyond int32 indexing");
   return check_space(space, fn);
 }
@@ -560,9 +510,9 @@ extern "C" int smplpp_point_mesh_distance(smplpp_model * m, int64_t n, const flo
   In<float> v, p;
   Out<int64_t> fo;
   Out<float> wo, co, so;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->points));
-  HIP_TRY(fo.init(face, (size_t)n * K, space, &s->face));
+  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->io.verts));
+  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->io.points));
+  HIP_TRY(fo.init(face, (size_t)n * K, space, &s->io.ids));
   HIP_TRY(wo.init(weights, (size_t)n * K * 3, space, &s->weights));
   HIP_TRY(co.init(closest, (size_t)n * K * 3, space, &s->closest));
   HIP_TRY(so.init(sqdist, (size_t)n * K, space, &s->sqdist));
@@ -589,28 +539,6 @@ extern "C" int smplpp_point_mesh_distance_vjp(smplpp_model * m, int64_t n, const
   if(space == SMPLPP_HOST)
     for(int64_t i = 0; i < n * K; i++)
       if(face[i] < 0 || face[i] >= m->F) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": face id out of range");
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("point-mesh distance VJP");
-  PointDistState * s = pd_state(m);
-  In<float> v, p, g;
-  In<int64_t> fi;
-  Out<float> gv, gp;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->points));
-  HIP_TRY(fi.init(face, (size_t)n * K, space, st, &s->face));
-  HIP_TRY(g.init(grad_sqdist, (size_t)n * K, space, st, &s->gsq));
-  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
-  HIP_TRY(gp.init(grad_points, (size_t)n * K * 3, space, &s->gp));
-  if(accumulate)
-  {
-    HIP_TRY(gv.load(st));
-    HIP_TRY(gp.load(st));
-  }
-  rc = pd_vjp_device(m, s, n, v.d, K, p.d, fi.d, g.d, gv.d, gp.d, accumulate, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  HIP_TRY(gp.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  return distance_vjp(pd_vjp_device, m, pd_state(m), "point-mesh distance VJP", n, verts, K, points, face, n * K, grad_sqdist, grad_verts,
+                      grad_points, accumulate, space, stream);
 }

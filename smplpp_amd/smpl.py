@@ -416,12 +416,15 @@ class SMPL:
                                                      c.space, c.stream))
         return face, w, closest, sq
 
-    def _pmd_vjp(self, c, verts, points, K, face, grad_sqdist, out, grad_points, want_verts=True, want_points=True):
+    def _distance_vjp(self, mesh_to_point, c, verts, points, K, ids, grad_sqdist, out, grad_points, want_verts=True, want_points=True):
+        """smplpp_point_mesh_distance_vjp (ids = the forward's face [N,K]) or, mesh_to_point, smplpp_mesh_point_distance_vjp (ids =
+        the forward's index [N,V]); grad_sqdist has the shape of ids."""
         n, V = len(verts), self.vertex_num
-        fid = c.ids(face)
-        if fid.shape[0] != n * K:
-            c.refuse("expected face of shape (%d, %d)" % (n, K))
-        g = c.input(grad_sqdist, (n, K))
+        name, rows = ("index", V) if mesh_to_point else ("face", K)
+        idt = c.ids(ids)
+        if idt.shape[0] != n * rows:
+            c.refuse("expected %s of shape (%d, %d)" % (name, n, rows))
+        g = c.input(grad_sqdist, (n, rows))
         acc = out is not None or grad_points is not None
 
         def buf(a, shape, want):
@@ -434,8 +437,9 @@ class SMPL:
             return torch.zeros(shape, dtype=torch.float32, device=c.device) if c.dev else np.zeros(shape, np.float32)
 
         gv, gp = buf(out, (n, V, 3), want_verts), buf(grad_points, (n, K, 3), want_points)
-        check(_lib.load().smplpp_point_mesh_distance_vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(fid), _ptr(g), _ptr(gv), _ptr(gp),
-                                                         int(acc), c.space, c.stream))
+        L = _lib.load()
+        vjp = L.smplpp_mesh_point_distance_vjp if mesh_to_point else L.smplpp_point_mesh_distance_vjp
+        check(vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(idt), _ptr(g), _ptr(gv), _ptr(gp), int(acc), c.space, c.stream))
         return gv, gp
 
     def pointMeshDistance(self, verts, points):
@@ -454,7 +458,7 @@ class SMPL:
         returned holding the product alone."""
         c = _Call("pointMeshDistanceBackward", verts, points, grad_sqdist, out, grad_points)
         verts, points, K = self._pmd_inputs(c, verts, points)
-        return self._pmd_vjp(c, verts, points, K, face, grad_sqdist, out, grad_points)
+        return self._distance_vjp(False, c, verts, points, K, face, grad_sqdist, out, grad_points)
 
     def point_mesh_distance_differentiable(self, verts, points):
         """(face [N,K], weights [N,K,3], sqdist [N,K]) of device points [N,K,3] against device vertices verts [N,V,3] (the bits of
@@ -473,28 +477,6 @@ class SMPL:
         check(_lib.load().smplpp_mesh_point_distance(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(index), _ptr(sq), c.space, c.stream))
         return index, sq
 
-    def _mpd_vjp(self, c, verts, points, K, index, grad_sqdist, out, grad_points, want_verts=True, want_points=True):
-        n, V = len(verts), self.vertex_num
-        idx = c.ids(index)
-        if idx.shape[0] != n * V:
-            c.refuse("expected index of shape (%d, %d)" % (n, V))
-        g = c.input(grad_sqdist, (n, V))
-        acc = out is not None or grad_points is not None
-
-        def buf(a, shape, want):
-            if a is not None:
-                return c.inout(a, shape)
-            if not want:
-                return None
-            if not acc:
-                return c.empty(shape)
-            return torch.zeros(shape, dtype=torch.float32, device=c.device) if c.dev else np.zeros(shape, np.float32)
-
-        gv, gp = buf(out, (n, V, 3), want_verts), buf(grad_points, (n, K, 3), want_points)
-        check(_lib.load().smplpp_mesh_point_distance_vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(idx), _ptr(g), _ptr(gv), _ptr(gp),
-                                                         int(acc), c.space, c.stream))
-        return gv, gp
-
     def meshPointDistance(self, verts, points):
         """The nearest of K points [N,K,3] to each vertex of each frame's mesh verts [N,V,3] (smplpp_mesh_point_distance): returns
         (index [N,V] int64, sqdist [N,V]).  sqdist is the fp32 ((dx*dx + dy*dy) + dz*dz) of d = v - p without FMA; the lowest
@@ -511,7 +493,7 @@ class SMPL:
         returned holding the product alone.  A zero cotangent masks a vertex out."""
         c = _Call("meshPointDistanceBackward", verts, points, grad_sqdist, out, grad_points)
         verts, points, K = self._pmd_inputs(c, verts, points)
-        return self._mpd_vjp(c, verts, points, K, index, grad_sqdist, out, grad_points)
+        return self._distance_vjp(True, c, verts, points, K, index, grad_sqdist, out, grad_points)
 
     def mesh_point_distance_differentiable(self, verts, points):
         """(index [N,V], sqdist [N,V]) of device vertices verts [N,V,3] against device points [N,K,3] (the bits of
@@ -574,12 +556,29 @@ if torch is not None:
             gv = ctx.smpl._normals_vjp(ctx.kind, verts, ctx.idt, grad, None)
             return gv, None, None, None
 
-    class _PointDistanceFunction(torch.autograd.Function):
+    class _DistanceFunction(torch.autograd.Function):
+        """The backward of both scan distances: a subclass's forward saves (verts, points, the chosen ids) and sets ctx.smpl,
+        ctx.K, ctx.call_name and ctx.mesh_to_point; sqdist is its last output."""
+
+        @staticmethod
+        def backward(ctx, *grads):
+            verts, points, ids = ctx.saved_tensors
+            grad_sqdist = grads[-1]
+            want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if grad_sqdist is None or not (want_v or want_p):
+                return None, None, None
+            c = _Call(ctx.call_name, verts, device_only=True)
+            gv, gp = ctx.smpl._distance_vjp(ctx.mesh_to_point, c, verts, points, ctx.K, ids, grad_sqdist.contiguous(), None, None, want_v,
+                                            want_p)
+            return gv, gp, None
+
+    class _PointDistanceFunction(_DistanceFunction):
         """smplpp_point_mesh_distance forward / smplpp_point_mesh_distance_vjp backward (SMPL.point_mesh_distance_differentiable)."""
 
         @staticmethod
         def forward(ctx, verts, points, smpl):
-            c = _Call("point_mesh_distance_differentiable", verts, points, device_only=True)
+            ctx.call_name, ctx.mesh_to_point = "point_mesh_distance_differentiable", False
+            c = _Call(ctx.call_name, verts, points, device_only=True)
             verts, points, K = smpl._pmd_inputs(c, verts, points)
             face, w, _, sq = smpl._pmd(c, verts, points, K, want_closest=False)
             ctx.mark_non_differentiable(face, w)
@@ -587,38 +586,19 @@ if torch is not None:
             ctx.save_for_backward(verts, points, face)
             return face, w, sq
 
-        @staticmethod
-        def backward(ctx, grad_face, grad_weights, grad_sqdist):
-            verts, points, face = ctx.saved_tensors
-            want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if grad_sqdist is None or not (want_v or want_p):
-                return None, None, None
-            c = _Call("point_mesh_distance_differentiable", verts, device_only=True)
-            gv, gp = ctx.smpl._pmd_vjp(c, verts, points, ctx.K, face, grad_sqdist.contiguous(), None, None, want_v, want_p)
-            return gv, gp, None
-
-    class _MeshPointDistanceFunction(torch.autograd.Function):
+    class _MeshPointDistanceFunction(_DistanceFunction):
         """smplpp_mesh_point_distance forward / smplpp_mesh_point_distance_vjp backward (SMPL.mesh_point_distance_differentiable)."""
 
         @staticmethod
         def forward(ctx, verts, points, smpl):
-            c = _Call("mesh_point_distance_differentiable", verts, points, device_only=True)
+            ctx.call_name, ctx.mesh_to_point = "mesh_point_distance_differentiable", True
+            c = _Call(ctx.call_name, verts, points, device_only=True)
             verts, points, K = smpl._pmd_inputs(c, verts, points)
             index, sq = smpl._mpd(c, verts, points, K)
             ctx.mark_non_differentiable(index)
             ctx.smpl, ctx.K = smpl, K
             ctx.save_for_backward(verts, points, index)
             return index, sq
-
-        @staticmethod
-        def backward(ctx, grad_index, grad_sqdist):
-            verts, points, index = ctx.saved_tensors
-            want_v, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            if grad_sqdist is None or not (want_v or want_p):
-                return None, None, None
-            c = _Call("mesh_point_distance_differentiable", verts, device_only=True)
-            gv, gp = ctx.smpl._mpd_vjp(c, verts, points, ctx.K, index, grad_sqdist.contiguous(), None, None, want_v, want_p)
-            return gv, gp, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)

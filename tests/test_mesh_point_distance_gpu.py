@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import closest_ref as cr  # noqa: E402
 import mesh_point_distance_oracle as O  # noqa: E402
+from distance_cases import _rel, _same_bits, _surface_points, _verts  # noqa: E402
 
 torch = O.torch
 pytestmark = pytest.mark.gpu
@@ -33,31 +33,6 @@ def smpl(synth_model):
 @pytest.fixture(scope="module")
 def faces(synth_model):
     return synth_model["face_indices"].astype(np.int64) - 1
-
-
-def _verts(s, n, seed):
-    from smplpp_amd import model_io
-
-    beta, theta = model_io.synthetic_inputs(n, seed=seed)
-    return s.launch(beta, theta, want=("verts",))["verts"]
-
-
-def _surface_points(v, faces, K, rng, off=0.015):
-    """K points per frame sampled on the posed surface and moved up to +-off along the face normal (the scan-like case)."""
-    n = len(v)
-    out = np.empty((n, K, 3), np.float32)
-    for f in range(n):
-        fid = rng.integers(0, len(faces), K)
-        w = rng.dirichlet(np.ones(3), K)
-        tri = v[f].astype(np.float64)[faces[fid]]
-        nrm = cr.face_normals(v[f], faces)[fid]
-        out[f] = (np.einsum("ki,kix->kx", w, tri) + rng.uniform(-off, off, (K, 1)) * nrm).astype(np.float32)
-    return out
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def _assert_oracle_bits(index, sq, v, P):
@@ -176,10 +151,6 @@ def test_model_without_faces(synth_model):
 
 
 # ---------------------------------------------------------------------------------------------------- backward
-def _rel(a, b):
-    return np.linalg.norm((np.asarray(a, np.float64) - b).ravel()) / max(np.linalg.norm(np.asarray(b).ravel()), 1e-30)
-
-
 def _check_vjp(v, P, index, g, gv, gp):
     """House tolerance: within 4x the error of an fp32 autograd of the same graph, or 1e-5 relative, per frame."""
     for f in range(len(v)):
@@ -224,6 +195,44 @@ def test_hot_point(smpl, faces):
         assert _same_bits(gv, gv2) and _same_bits(gp, gp2)
     assert (gp[0, np.arange(K) != 17] == 0).all() and (gp[1, :63] == 0).all()
     _check_vjp(v, P, index, g, gv, gp)
+
+
+def _fp32_vjp(v, P, index, g):
+    """The backward's fp32 arithmetic and order: r = v - p[index], grad_verts = (2 g) r; grad_points a sum from +0 per point, in
+    ascending vertex, of (-2 g) r over the vertices with g != 0 and an index in [0, K)."""
+    n, V = index.shape
+    f = np.arange(n)
+    live = (g != 0) & (index >= 0) & (index < P.shape[1])
+    r = v - P[f[:, None], np.where(live, index, 0)]
+    gv = np.where(live[..., None], (2 * g)[..., None] * r, np.float32(0))
+    c = (-2 * g)[..., None] * r
+    gp = np.zeros(P.shape, np.float32)
+    for u in range(V):
+        m = live[:, u]
+        gp[f[m], index[m, u]] += c[m, u]
+    return gv, gp
+
+
+@pytest.mark.parametrize("case", ["surface", "hot_point"])
+def test_backward_bits_vs_fp32_restatement(smpl, faces, case):
+    """Every bit: 6890 records (several LDS tiles), 3000 points (several target blocks), a hot point; zero g and index -1."""
+    rng = np.random.default_rng(97)
+    if case == "surface":
+        v = _verts(smpl, 3, seed=97)
+        P = _surface_points(v, faces, 3000, rng)
+    else:
+        v = _verts(smpl, 2, seed=41)
+        P = np.full((2, 64, 3), np.nan, np.float32)
+        P[0, 17] = (0.05, 0.3, 0.1)
+        P[1, 63] = (-0.2, 0.0, 0.4)
+    index, _ = smpl.meshPointDistance(v, P)
+    g = rng.normal(size=index.shape).astype(np.float32)
+    g[rng.random(g.shape) < 0.1] = 0
+    index[rng.random(index.shape) < 0.05] = -1
+    gv, gp = smpl.meshPointDistanceBackward(v, P, index, g)
+    rv, rp = _fp32_vjp(v, P, index, g)
+    assert _same_bits(gv, rv)
+    assert _same_bits(gp, rp), np.nonzero(gp != rp)[:2]
 
 
 # ---------------------------------------------------------------------------------------------------- call semantics

@@ -11,6 +11,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import closest_ref as cr  # noqa: E402
 import point_distance_oracle as O  # noqa: E402
+from distance_cases import _rel, _same_bits, _surface_points, _verts  # noqa: E402
 
 torch = O.torch
 pytestmark = pytest.mark.gpu
@@ -50,26 +51,6 @@ def faces(synth_model):
     return synth_model["face_indices"].astype(np.int64) - 1
 
 
-def _verts(s, n, seed):
-    from smplpp_amd import model_io
-
-    beta, theta = model_io.synthetic_inputs(n, seed=seed)
-    return s.launch(beta, theta, want=("verts",))["verts"]
-
-
-def _surface_points(v, faces, K, rng, off=0.015):
-    """K points per frame sampled on the posed surface and moved up to +-off along the face normal (the scan-like case)."""
-    n = len(v)
-    out = np.empty((n, K, 3), np.float32)
-    for f in range(n):
-        fid = rng.integers(0, len(faces), K)
-        w = rng.dirichlet(np.ones(3), K)
-        tri = v[f].astype(np.float64)[faces[fid]]
-        nrm = cr.face_normals(v[f], faces)[fid]
-        out[f] = (np.einsum("ki,kix->kx", w, tri) + rng.uniform(-off, off, (K, 1)) * nrm).astype(np.float32)
-    return out
-
-
 def _closest_points(s, verts, points):
     from smplpp_amd import _lib
     from smplpp_amd._lib import HOST, check
@@ -80,11 +61,6 @@ def _closest_points(s, verts, points):
     face, closest, sq = np.empty((n, K), np.int64), np.empty((n, K, 3), np.float32), np.empty((n, K), np.float32)
     check(_lib.load().smplpp_closest_points(s.handle, n, _ptr(verts), K, _ptr(points), _ptr(face), _ptr(closest), _ptr(sq), HOST, None))
     return face, closest, sq
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def _assert_forward_bits(s, v, P):
@@ -161,10 +137,6 @@ def test_weights(smpl, faces):
 
 
 # ---------------------------------------------------------------------------------------------------- backward
-def _rel(a, b):
-    return np.linalg.norm((np.asarray(a, np.float64) - b).ravel()) / max(np.linalg.norm(np.asarray(b).ravel()), 1e-30)
-
-
 def _check_vjp(v, faces, P, face, g, gv, gp):
     """House tolerance: within 4x the error of an fp32 autograd of the same graph, or 1e-5 relative, per frame."""
     for f in range(len(v)):
@@ -254,6 +226,44 @@ def test_hot_vertex(forms, faces):
     gv, gp = s.pointMeshDistanceBackward(v, P, face, g)
     assert _same_bits(gv, s.pointMeshDistanceBackward(v, P, face, g)[0])
     _check_vjp(v, faces, P, face, g, gv, gp)
+
+
+def _fp32_vjp(faces, P, face, closest, w, g, V):
+    """The backward's fp32 arithmetic and order, from the forward's closest and weights: rr = p - closest, grad_points = (2 g) rr,
+    corner j gets ((-2 g) w_j) rr; grad_verts a sum from +0 per vertex, in ascending query, then corner, over the g != 0."""
+    n, K = face.shape
+    f = np.arange(n)
+    live = g != 0
+    rr = P - closest
+    gp = np.where(live[..., None], (2 * g)[..., None] * rr, np.float32(0))
+    c = ((-2 * g)[..., None] * w)[..., None] * rr[:, :, None, :]
+    corner = faces[face]
+    gv = np.zeros((n, V, 3), np.float32)
+    for k in range(K):
+        m = live[:, k]
+        for j in range(3):
+            gv[f[m], corner[m, k, j]] += c[m, k, j]
+    return gv, gp
+
+
+@pytest.mark.parametrize("case", ["surface", "hot_vertex"])
+def test_backward_bits_vs_fp32_restatement(forms, faces, case):
+    """Every bit (tiled form): K > 1024 records (several LDS tiles), 6890 vertices (several target blocks), a hot vertex; zero g."""
+    s = forms["tiled"]
+    rng = np.random.default_rng(97)
+    if case == "surface":
+        v = _verts(s, 3, seed=97)
+        P = _surface_points(v, faces, 3000, rng)
+    else:
+        v = _verts(s, 2, seed=41)
+        P = (v[:, int(faces[100, 0])][:, None, :] + rng.normal(0, 1e-3, (2, 4096, 3))).astype(np.float32)
+    face, w, closest, _ = s.pointMeshDistance(v, P)
+    g = rng.normal(size=face.shape).astype(np.float32)
+    g[rng.random(g.shape) < 0.1] = 0
+    gv, gp = s.pointMeshDistanceBackward(v, P, face, g)
+    rv, rp = _fp32_vjp(faces, P, face, closest, w, g, s.vertex_num)
+    assert _same_bits(gp, rp)
+    assert _same_bits(gv, rv), np.nonzero(gv != rv)[:2]
 
 
 # ---------------------------------------------------------------------------------------------------- call semantics
