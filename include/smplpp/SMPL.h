@@ -379,6 +379,49 @@ public:
     return distanceBackward(smplpp_mesh_point_distance_vjp, true, points, index, gradSqdist, gradPoints, accumulate,
                             "Cannot back-propagate through the mesh-to-point distance!");
   }
+  // Generalized winding numbers of each frame's mesh at points [N,K,3] on the last launch's vertices (smplpp_point_mesh_winding):
+  // winding [N,K] (the bits calcSweepGrid's cells have at the same position), inside [N,K] kInt64 0 / 1 (winding > 0.5).
+  struct PointMeshWinding
+  {
+    Tensor winding, inside;
+  };
+  PointMeshWinding pointMeshWinding(const Tensor & points) const
+  {
+    const int64_t n = pointsFor(points, "Cannot compute the winding numbers!"), K = points.size(1);
+    std::vector<uint8_t> in((size_t)(n * K));
+    PointMeshWinding r{Tensor({n, K}), Tensor({n, K}, kInt64)};
+    check(smplpp_point_mesh_winding(m_.get(), n, verts_.ptr(), K, points.ptr(), r.winding.ptr(), in.data(), SMPLPP_HOST, nullptr), "SMPL");
+    for(size_t i = 0; i < in.size(); i++) r.inside.idata[i] = in[i];
+    return r;
+  }
+  // Signed point-to-mesh distance on the last launch's vertices (smplpp_point_mesh_signed_distance): pointMeshDistance's face,
+  // weights and closest, pointMeshWinding's winding and inside, and signedSqdist [N,K] = -sqdist where inside, else sqdist.
+  struct PointMeshSignedDistance
+  {
+    Tensor face, weights, closest, winding, inside, signedSqdist;
+  };
+  PointMeshSignedDistance pointMeshSignedDistance(const Tensor & points) const
+  {
+    const int64_t n = pointsFor(points, "Cannot compute the signed point-to-mesh distance!"), K = points.size(1);
+    std::vector<uint8_t> in((size_t)(n * K));
+    PointMeshSignedDistance r{Tensor({n, K}, kInt64), Tensor({n, K, 3}), Tensor({n, K, 3}), Tensor({n, K}), Tensor({n, K}, kInt64), Tensor({n, K})};
+    check(smplpp_point_mesh_signed_distance(m_.get(), n, verts_.ptr(), K, points.ptr(), r.face.idata.data(), r.weights.ptr(), r.closest.ptr(),
+                                            r.winding.ptr(), in.data(), r.signedSqdist.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    for(size_t i = 0; i < in.size(); i++) r.inside.idata[i] = in[i];
+    return r;
+  }
+  // Its backward pass (smplpp_point_mesh_signed_distance_vjp) at the faces `face` and flags `inside` [N,K] (nonzero = inside) it
+  // gave: pointMeshDistanceBackward at the cotangent gradSignedSqdist * (inside ? -1 : 1), with the same gradPoints / accumulate rules.
+  Tensor pointMeshSignedDistanceBackward(const Tensor & points, const Tensor & face, const Tensor & inside, const Tensor & gradSignedSqdist,
+                                         Tensor * gradPoints = nullptr, Tensor * accumulate = nullptr) const
+  {
+    const char * what = "Cannot back-propagate through the signed point-to-mesh distance!";
+    if((inside.dtype != kInt64 && inside.dtype != kInt32) || inside.numel() != face.numel()) throw Exception("SMPL", what);
+    std::vector<uint8_t> in((size_t)inside.numel());
+    for(size_t i = 0; i < in.size(); i++) in[i] = inside.idata[i] != 0 ? 1 : 0;
+    return distanceBackward(smplpp_point_mesh_distance_vjp, false, points, face, gradSignedSqdist, gradPoints, accumulate, what, in.data());
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const
@@ -440,9 +483,18 @@ private:
             "SMPL");
     return g;
   }
-  // the two *DistanceBackward: ids and gradSqdist hold one entry per vertex (perVertex) or per point
+  int64_t pointsFor(const Tensor & points, const char * what) const // frames of the last launch, checked against points [N,K,3]
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || points.size(1) < 1 || points.size(2) != 3)
+      throw Exception("SMPL", what);
+    return n;
+  }
+  // the *DistanceBackward: ids and gradSqdist hold one entry per vertex (perVertex) or per point; inside non-null: the signed distance's
   Tensor distanceBackward(decltype(&smplpp_point_mesh_distance_vjp) vjp, bool perVertex, const Tensor & points, const Tensor & ids,
-                          const Tensor & gradSqdist, Tensor * gradPoints, Tensor * accumulate, const char * what) const
+                          const Tensor & gradSqdist, Tensor * gradPoints, Tensor * accumulate, const char * what,
+                          const uint8_t * inside = nullptr) const
   {
     need(verts_);
     const int64_t n = verts_.size(0);
@@ -456,9 +508,14 @@ private:
     if(!accumulate) fresh = Tensor(verts_.shape);
     Tensor & g = accumulate ? *accumulate : fresh;
     if(gradPoints && !accumulate) *gradPoints = Tensor({n, K, 3});
-    check(vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), ids.idata.data(), gradSqdist.ptr(), g.ptr(),
-              gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
-          "SMPL");
+    if(inside)
+      check(smplpp_point_mesh_signed_distance_vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), ids.idata.data(), inside, gradSqdist.ptr(), g.ptr(),
+                                                  gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+            "SMPL");
+    else
+      check(vjp(m_.get(), n, verts_.ptr(), K, points.ptr(), ids.idata.data(), gradSqdist.ptr(), g.ptr(),
+                gradPoints ? gradPoints->ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+            "SMPL");
     return g;
   }
   std::shared_ptr<smplpp_model> m_;

@@ -219,6 +219,39 @@ int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const float * ve
                                    const int64_t * index /*[n,V]*/, const float * grad_sqdist /*[n,V]*/,
                                    float * grad_verts /*[n,V,3] nullable*/, float * grad_points /*[n,K,3] nullable*/,
                                    int accumulate, int space, void * stream);
+/* Generalized winding numbers at K query points per frame (which points lie inside the body: penetration and one-sided scan
+ * terms): for each of n frames, igl::winding_number of that frame's posed mesh verts [n,V,3] at each of K points [n,K,3].
+ *  - winding [n,K] has exactly the bits smplpp_sweep_grid gives at a cell of the same fp32 position: the same per-face term
+ *    atan2f(det, den), summed in fp32 in ascending face order within each 256-face chunk, the chunk partials summed in fp64 in
+ *    ascending chunk order, then (float)(acc / (2 pi)).  On a closed, outward-oriented mesh w ~ 1 inside, ~ 0 outside, ~ 2 where
+ *    the posed mesh overlaps itself.
+ *  - inside [n,K] (nullable) = w > 0.5f.  A NaN point or vertex gives w = NaN and inside = 0 (no refusal of device data).
+ *  - the bits do not depend on n, on the frame's position in the batch, or on how the call splits the faces over workgroups (few
+ *    frames: at 256-face chunk boundaries, chosen from n and K alone).
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, n * K beyond int32 indexing. */
+int smplpp_point_mesh_winding(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t K, const float * points /*[n,K,3]*/,
+                              float * winding /*[n,K]*/, uint8_t * inside /*[n,K] nullable*/, int space, void * stream);
+/* Signed point-to-mesh distance: smplpp_point_mesh_distance and smplpp_point_mesh_winding in one call.
+ *  - face, weights, closest have exactly the bits of smplpp_point_mesh_distance; winding and inside those of
+ *    smplpp_point_mesh_winding, on the same inputs.
+ *  - signed_sqdist = inside ? -sqdist : sqdist.  The SQUARED distance on purpose: sigma d^2 is continuous and C1 across the surface
+ *    (both sides reach 0 with zero slope), so a penetration loss such as relu(-signed_sqdist) has no step there.
+ *  - weights, closest and winding are nullable; face, inside and signed_sqdist are not.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, n * K beyond int32 indexing. */
+int smplpp_point_mesh_signed_distance(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t K, const float * points /*[n,K,3]*/,
+                                      int64_t * face /*[n,K]*/, float * weights /*[n,K,3] nullable*/, float * closest /*[n,K,3] nullable*/,
+                                      float * winding /*[n,K] nullable*/, uint8_t * inside /*[n,K]*/, float * signed_sqdist /*[n,K]*/,
+                                      int space, void * stream);
+/* Vector-Jacobian product of signed_sqdist above, at the faces `face` and the flags `inside` the forward gave.  The sign is
+ * piecewise constant, so this is smplpp_point_mesh_distance_vjp at the cotangent g * (inside ? -1 : 1), bit for bit (the
+ * multiplication by -1 is exact), with all of its rules: accumulate = 0 overwrites, 1 adds; either output may be NULL, not both; a
+ * zero cotangent contributes nothing, even on a NaN row; deterministic, no floating-point atomics.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, n * K beyond int32 indexing, host-space face ids out of range (a
+ *    device-space face id out of range contributes nothing). */
+int smplpp_point_mesh_signed_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
+                                          const int64_t * face /*[n,K]*/, const uint8_t * inside /*[n,K]*/,
+                                          const float * grad_signed_sqdist /*[n,K]*/, float * grad_verts /*[n,V,3] nullable*/,
+                                          float * grad_points /*[n,K,3] nullable*/, int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -232,6 +232,7 @@ struct VjpState;        // smplpp_fk_vjp's operand image and workspace (fk_vjp.h
 struct NormalsVjpState; // the normals' backward pass (mesh_vjp.hip)
 struct PointDistState;  // point-to-mesh distance and its backward pass (point_distance.hip)
 struct MeshPointDistState; // mesh-to-point distance and its backward pass (mesh_point_distance.hip)
+struct WindingState;    // batched winding numbers and the signed point-to-mesh distance (winding.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -240,6 +241,7 @@ struct StateDelete
   void operator()(NormalsVjpState * s) const;
   void operator()(PointDistState * s) const;
   void operator()(MeshPointDistState * s) const;
+  void operator()(WindingState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -296,5 +298,6 @@ struct smplpp_model
   char pd_form = 0;             // point-to-mesh distance form (SMPLPP_POINT_DISTANCE_FORM, read at model creation): 0 = by K | q | t
   smplpp_hip::StatePtr<smplpp_hip::PointDistState> pd; // point-to-mesh distance workspace (point_distance.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::MeshPointDistState> mpd; // mesh-to-point distance workspace (mesh_point_distance.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::WindingState> wn; // winding-number and signed-distance workspace (winding.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

@@ -2,6 +2,7 @@
 // the closest-point projection the IK loop does through igl::point_mesh_squared_distance (node/node.cpp:970-989).
 #include "mesh_device.h"
 #include "staging.h"
+#include "winding_device.h"
 
 #include <cmath>
 
@@ -104,10 +105,9 @@ __global__ __launch_bounds__(1024) void bounds_kernel(const float * __restrict__
   }
 }
 
-// generalized winding number of the closed mesh at every grid point (igl::winding_number as called at node/node.cpp:1052):
-// w(p) = sum_f Omega_f(p) / (4 pi), Omega_f = 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) with
-// a, b, c = the face's vertices minus p.  One thread per grid point; the faces pass through LDS 256 at a time; fp32 terms
-// like the reference's float matrices, fp64 sum.  Cell order: x outermost, z innermost (the reference's triple loop).
+// generalized winding number of the closed mesh at every grid point (igl::winding_number as called at node/node.cpp:1052; the
+// terms and sums of winding_device.h).  One thread per grid point; the faces pass through LDS 256 at a time; fp32 terms like the
+// reference's float matrices, fp64 sum.  Cell order: x outermost, z innermost (the reference's triple loop).
 __global__ __launch_bounds__(256) void winding_kernel(const float * __restrict__ verts, const int32_t * __restrict__ faces, int64_t F,
                                                       int gx0, int gy0, int gz0, int ny, int nz, int64_t cells, float scale,
                                                       float * __restrict__ winding, uint8_t * __restrict__ inside)
@@ -135,16 +135,7 @@ __global__ __launch_bounds__(256) void winding_kernel(const float * __restrict__
     __syncthreads();
     const int cnt = (int)(F - f0 < 256 ? F - f0 : 256);
     float part = 0.0f;
-    for(int t = 0; t < cnt; t++)
-    {
-      const float ax = tri[t][0] - px, ay = tri[t][1] - py, az = tri[t][2] - pz;
-      const float bx = tri[t][3] - px, by = tri[t][4] - py, bz = tri[t][5] - pz;
-      const float cx = tri[t][6] - px, cy = tri[t][7] - py, cz = tri[t][8] - pz;
-      const float la = sqrtf(ax * ax + ay * ay + az * az), lb = sqrtf(bx * bx + by * by + bz * bz), lc = sqrtf(cx * cx + cy * cy + cz * cz);
-      const float det = ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx);
-      const float den = la * lb * lc + (ax * bx + ay * by + az * bz) * lc + (bx * cx + by * cy + bz * cz) * la + (cx * ax + cy * ay + cz * az) * lb;
-      part += atan2f(det, den);
-    }
+    for(int t = 0; t < cnt; t++) part += winding_term(tri[t], px, py, pz);
     acc += (double)part;
     __syncthreads();
   }

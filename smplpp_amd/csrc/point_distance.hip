@@ -23,23 +23,13 @@
 //                        (the face's three vertex ids, -2 g w_j r for j = 0..2).  A zero cotangent or an out-of-range face gives no
 //                        record (ids -1) and a zero grad_points.
 //  record_gather_kernel<PdRecord>  (distance_vjp.h) grad_verts: one fixed-order sum per vertex, ascending record index, then corner.
-#include "distance_vjp.h"
 #include "mesh_device.h"
+#include "point_distance.h"
 
 #include <cmath>
 
 namespace smplpp_hip
 {
-struct PointDistState
-{
-  DevBuf tri;          // [n][F][3] float4 triangle image of the tiled form
-  DevBuf perm;         // [n][K] int32 query order of the tiled form
-  DevBuf rec;          // [n][K] PdRecord of the backward pass
-  DevBuf seedv;        // [nseed] int32 vertices that have a face (model constant, set up by the first call)
-  int64_t nseed = -1;
-  DistanceStaging io;                // staging for host-space calls (face in io.ids) ...
-  DevBuf weights, closest, sqdist;   // ... and the forward's other outputs
-};
 void StateDelete::operator()(PointDistState * s) const
 {
   delete s;
@@ -441,8 +431,8 @@ static int pd_seed_setup(smplpp_model * m, PointDistState * s)
 }
 
 // all pointers on the device
-static int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
-                             int64_t * face, float * weights, float * closest, float * sqdist, hipStream_t st)
+int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
+                      int64_t * face, float * weights, float * closest, float * sqdist, hipStream_t st)
 {
   const bool tiled = m->pd_form == 't' || (m->pd_form != 'q' && n * K >= PD_TILED_MIN_NK);
   const int64_t V = m->V, F = m->F;
@@ -467,8 +457,8 @@ static int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, co
   return SMPLPP_OK;
 }
 
-static int pd_vjp_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
-                         const int64_t * face, const float * gsq, float * gv, float * gp, int accumulate, hipStream_t st)
+int pd_vjp_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
+                  const int64_t * face, const float * gsq, float * gv, float * gp, int accumulate, hipStream_t st)
 {
   const int64_t V = m->V, nk = n * K;
   PdRecord * rec = nullptr;

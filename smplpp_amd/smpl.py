@@ -94,6 +94,13 @@ class _Call:
         ids = np.ascontiguousarray(ids.detach().cpu().numpy() if _is_torch(ids) else np.atleast_1d(ids), np.int64).reshape(-1)
         return torch.from_numpy(ids).to(self.device) if self.dev else ids
 
+    def flags(self, flags):
+        """Flat uint8 flags (nonzero = set) in this call's space."""
+        if self.dev and _is_torch(flags) and flags.is_cuda:
+            return flags.detach().to(dtype=torch.uint8).contiguous().reshape(-1)
+        flags = np.ascontiguousarray(flags.detach().cpu().numpy() if _is_torch(flags) else np.atleast_1d(flags), np.uint8).reshape(-1)
+        return torch.from_numpy(flags).to(self.device) if self.dev else flags
+
     def empty(self, shape, dtype="float32"):
         if self.dev:
             return torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
@@ -416,9 +423,10 @@ class SMPL:
                                                      c.space, c.stream))
         return face, w, closest, sq
 
-    def _distance_vjp(self, mesh_to_point, c, verts, points, K, ids, grad_sqdist, out, grad_points, want_verts=True, want_points=True):
-        """smplpp_point_mesh_distance_vjp (ids = the forward's face [N,K]) or, mesh_to_point, smplpp_mesh_point_distance_vjp (ids =
-        the forward's index [N,V]); grad_sqdist has the shape of ids."""
+    def _distance_vjp(self, mesh_to_point, c, verts, points, K, ids, grad_sqdist, out, grad_points, want_verts=True, want_points=True,
+                      inside=None):
+        """smplpp_point_mesh_distance_vjp (ids = the forward's face [N,K]), with `inside` [N,K] smplpp_point_mesh_signed_distance_vjp,
+        or, mesh_to_point, smplpp_mesh_point_distance_vjp (ids = the forward's index [N,V]); grad_sqdist has the shape of ids."""
         n, V = len(verts), self.vertex_num
         name, rows = ("index", V) if mesh_to_point else ("face", K)
         idt = c.ids(ids)
@@ -438,6 +446,13 @@ class SMPL:
 
         gv, gp = buf(out, (n, V, 3), want_verts), buf(grad_points, (n, K, 3), want_points)
         L = _lib.load()
+        if inside is not None:
+            ins = c.flags(inside)
+            if ins.shape[0] != n * rows:
+                c.refuse("expected inside of shape (%d, %d)" % (n, rows))
+            check(L.smplpp_point_mesh_signed_distance_vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(idt), _ptr(ins), _ptr(g), _ptr(gv),
+                                                          _ptr(gp), int(acc), c.space, c.stream))
+            return gv, gp
         vjp = L.smplpp_mesh_point_distance_vjp if mesh_to_point else L.smplpp_point_mesh_distance_vjp
         check(vjp(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(idt), _ptr(g), _ptr(gv), _ptr(gp), int(acc), c.space, c.stream))
         return gv, gp
@@ -504,6 +519,56 @@ class SMPL:
             raise SmplppError(1, "mesh_point_distance_differentiable needs torch")
         return _MeshPointDistanceFunction.apply(verts, points, self)
 
+    # ---- winding numbers and the signed point-to-mesh distance (smplpp_point_mesh_winding / smplpp_point_mesh_signed_distance[_vjp])
+    def pointMeshWinding(self, verts, points):
+        """Generalized winding numbers of each frame's mesh verts [N,V,3] at K points [N,K,3] (smplpp_point_mesh_winding): returns
+        (winding [N,K], inside [N,K] bool).  winding has the bits calcSweepGrid gives at a cell of the same fp32 position; inside =
+        winding > 0.5 (~1 inside the closed body, ~0 outside, ~2 where the posed mesh overlaps itself).  A NaN point gives NaN and
+        False.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("pointMeshWinding", verts, points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        n = len(verts)
+        w, ins = c.empty((n, K)), c.empty((n, K), "uint8")
+        check(_lib.load().smplpp_point_mesh_winding(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(w), _ptr(ins), c.space, c.stream))
+        return w, ins.bool() if c.dev else ins.astype(bool)
+
+    def _psd(self, c, verts, points, K, want_closest=True, want_winding=True):
+        n = len(verts)
+        face, w, sq, ins = c.empty((n, K), "int64"), c.empty((n, K, 3)), c.empty((n, K)), c.empty((n, K), "uint8")
+        closest = c.empty((n, K, 3)) if want_closest else None
+        wn = c.empty((n, K)) if want_winding else None
+        check(_lib.load().smplpp_point_mesh_signed_distance(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(face), _ptr(w), _ptr(closest),
+                                                            _ptr(wn), _ptr(ins), _ptr(sq), c.space, c.stream))
+        return face, w, closest, wn, ins, sq
+
+    def pointMeshSignedDistance(self, verts, points):
+        """pointMeshDistance and pointMeshWinding in one call (smplpp_point_mesh_signed_distance): returns (face [N,K] int64,
+        weights [N,K,3], closest [N,K,3], winding [N,K], inside [N,K] bool, signed_sqdist [N,K]) with signed_sqdist = -sqdist where
+        inside, else sqdist (squared on purpose: continuous and C1 across the surface).  The other outputs have the bits of the two
+        calls.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("pointMeshSignedDistance", verts, points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        face, w, closest, wn, ins, sq = self._psd(c, verts, points, K)
+        return face, w, closest, wn, ins.bool() if c.dev else ins.astype(bool), sq
+
+    def pointMeshSignedDistanceBackward(self, verts, points, face, inside, grad, out=None, grad_points=None):
+        """Vector-Jacobian product of pointMeshSignedDistance's signed_sqdist at the faces `face` [N,K] and flags `inside` [N,K] it
+        gave: (grad_verts [N,V,3], grad_points [N,K,3]) for dL/dsigned_sqdist = grad [N,K] (smplpp_point_mesh_signed_distance_vjp):
+        the bits of pointMeshDistanceBackward at grad * (inside ? -1 : 1).  `out` and / or `grad_points` as in
+        pointMeshDistanceBackward."""
+        c = _Call("pointMeshSignedDistanceBackward", verts, points, grad, out, grad_points)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        return self._distance_vjp(False, c, verts, points, K, face, grad, out, grad_points, inside=inside)
+
+    def point_mesh_signed_distance_differentiable(self, verts, points):
+        """(face [N,K], weights [N,K,3], inside [N,K] bool, signed_sqdist [N,K]) of device points [N,K,3] against device vertices
+        verts [N,V,3] (the bits of pointMeshSignedDistance), with signed_sqdist differentiable in both verts and points through
+        torch.autograd: smplpp_point_mesh_signed_distance forward, smplpp_point_mesh_signed_distance_vjp backward, on torch's current
+        stream.  A penetration term is e.g. relu(-signed_sqdist).sum()."""
+        if torch is None:
+            raise SmplppError(1, "point_mesh_signed_distance_differentiable needs torch")
+        return _SignedDistanceFunction.apply(verts, points, self)
+
     def out(self, index: int, path: str):
         """SMPL::out (src/SMPL.cpp:757-790): Wavefront OBJ of frame `index` (v lines, then 1-based f lines)."""
         verts = self._need("verts")
@@ -558,7 +623,7 @@ if torch is not None:
 
     class _DistanceFunction(torch.autograd.Function):
         """The backward of both scan distances: a subclass's forward saves (verts, points, the chosen ids) and sets ctx.smpl,
-        ctx.K, ctx.call_name and ctx.mesh_to_point; sqdist is its last output."""
+        ctx.K, ctx.call_name and ctx.mesh_to_point (and ctx.inside, the flags of the signed distance); sqdist is its last output."""
 
         @staticmethod
         def backward(ctx, *grads):
@@ -569,7 +634,7 @@ if torch is not None:
                 return None, None, None
             c = _Call(ctx.call_name, verts, device_only=True)
             gv, gp = ctx.smpl._distance_vjp(ctx.mesh_to_point, c, verts, points, ctx.K, ids, grad_sqdist.contiguous(), None, None, want_v,
-                                            want_p)
+                                            want_p, inside=getattr(ctx, "inside", None))
             return gv, gp, None
 
     class _PointDistanceFunction(_DistanceFunction):
@@ -599,6 +664,23 @@ if torch is not None:
             ctx.smpl, ctx.K = smpl, K
             ctx.save_for_backward(verts, points, index)
             return index, sq
+
+
+    class _SignedDistanceFunction(_DistanceFunction):
+        """smplpp_point_mesh_signed_distance forward / smplpp_point_mesh_signed_distance_vjp backward
+        (SMPL.point_mesh_signed_distance_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, points, smpl):
+            ctx.call_name, ctx.mesh_to_point = "point_mesh_signed_distance_differentiable", False
+            c = _Call(ctx.call_name, verts, points, device_only=True)
+            verts, points, K = smpl._pmd_inputs(c, verts, points)
+            face, w, _, _, ins, sq = smpl._psd(c, verts, points, K, want_closest=False, want_winding=False)
+            inside = ins.bool()
+            ctx.mark_non_differentiable(face, w, inside)
+            ctx.smpl, ctx.K, ctx.inside = smpl, K, ins
+            ctx.save_for_backward(verts, points, face)
+            return face, w, inside, sq
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
