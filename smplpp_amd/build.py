@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import glob
 import os
+import shlex
 import shutil
 import subprocess
 import sys
@@ -11,10 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsmplpp_hip.so")
 ARCH = "gfx950"
+FLAGS = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # skin_h.hip: accumulators in arch VGPRs (its VALU epilogue reads them; the A operand takes the AGPRs).
-# skin_p.hip places its VALU work by hand in MFMA shadows: SLP-packing adjacent f32 FMAs into v_pk_fma_f32 (+ the v_mov
-# shuffles that feeds them) is an anti-lever beside MFMAs (cdna_hip_programming.md, per-instruction constants).
-PER_FILE_FLAGS = {"skin_p.hip": ["-fno-slp-vectorize"], "skin_b.hip": ["-fno-slp-vectorize"], "skin_e.hip": ["-fno-slp-vectorize"], "skin_h.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"], "fk.hip": ["-fno-slp-vectorize"], "ik.hip": ["-fno-slp-vectorize"]}
+PER_FILE_FLAGS = {"skin_b.hip": ["-fno-slp-vectorize"], "skin_e.hip": ["-fno-slp-vectorize"], "skin_h.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"], "fk.hip": ["-fno-slp-vectorize"], "ik.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:
@@ -22,6 +22,11 @@ def _hipcc() -> str:
         if cand and os.path.exists(cand):
             return cand
     raise RuntimeError("hipcc not found (ROCm toolchain required to build libsmplpp_hip.so)")
+
+
+def compile_cmd(src: str, obj: str, extra=()) -> list:
+    """The hipcc command that compiles `src` to `obj` as the library build does, with `extra` flags added."""
+    return [_hipcc()] + FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + list(extra) + ["-c", src, "-o", obj]
 
 
 def sources():
@@ -43,7 +48,6 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
-    flags = ["-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
     procs = []
     for src in sources():
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
@@ -51,8 +55,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(obj)
         if not force and os.path.exists(obj) and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in [src] + hdrs):
             continue
-        extra = PER_FILE_FLAGS.get(os.path.basename(src), [])
-        cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
+        cmd = compile_cmd(src, obj)
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
@@ -70,4 +73,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    # --compile-cmd SRC OBJ [FLAGS...]: print the command that builds SRC (for development scripts that rebuild one file)
+    if sys.argv[1:2] == ["--compile-cmd"]:
+        print(shlex.join(compile_cmd(sys.argv[2], sys.argv[3], sys.argv[4:])))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

@@ -225,7 +225,6 @@ struct Workspace
   DevBuf joints;  // [n][24][3]
   DevBuf beta, theta, verts, rest, xf44; // staging for host-pointer calls
   int64_t ldA = 0;
-  DevBuf dummy;   // write-only sink for masked-off lanes of branch-free epilogues (skin_p.hip)
 };
 // Per-feature state of a handle, created by the feature's first call on it and owned by the handle
 struct VjpState;        // smplpp_fk_vjp's operand image and workspace (fk_vjp.hip)
@@ -263,7 +262,7 @@ struct smplpp_model
   float sB = 1.0f, sG = 1.0f;  // power-of-two scales of the basis operand and of the relative transforms (fp16 range)
   smplpp_hip::DevPtr<int> range_flag; // device words [RANGE_SLOTS]: bit 0 = a launch of the fp16x2 form met an operand outside fp16's range
   smplpp_hip::DevPtr<uint8_t> B3e; // bases + skinning tables of the exact form, one 20 KiB image per (vertex group, k-step) (layout above, EB_*)
-  char form = 'e';             // fused-kernel form of smplpp_fk (SMPLPP_SKIN, read once at model creation): e | h | b | p | v
+  char form = 'e';             // fused-kernel form of smplpp_fk (SMPLPP_SKIN, read once at model creation): e | h | b | v
   char form_ik = 'h';          // ... of the IK / VPoser loops' internal launches (h unless SMPLPP_SKIN chose one form for everything)
   smplpp_hip::DevPtr<uint8_t> wIdx; // [VGn*32][maxw]
   smplpp_hip::DevPtr<float> wVal; // [VGn*32][maxw]

@@ -241,8 +241,6 @@ static hipError_t launch_skin_w(const smplpp_model * m, int64_t n, const float *
   }
 }
 
-hipError_t launch_skin_persistent(const smplpp_model * m, int64_t n, const float * theta, const float * Gp_padded, float * verts,
-                                  float * rest, hipStream_t st); // skin_p.hip (fp32 MFMA, one wave/SIMD, epilogue in the MFMA shadow)
 hipError_t launch_skin_bf16x3(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st); // skin_b.hip
 hipError_t launch_skin_f16x2(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st);  // skin_h.hip
 hipError_t launch_skin_exact(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st);  // skin_e.hip
@@ -283,16 +281,13 @@ PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const flo
 // Form of the fused kernel a launch runs (decided once per launch, here, for both halves of the forward pass).  m->form (from
 // SMPLPP_SKIN at model creation; default e) is what smplpp_fk runs: e (skin_e.hip) carries every fp32 operand exactly (bf16x3
 // pieces, six MFMA products per fp32 product, fp32 VALU skinning) — the reference's arithmetic; h (skin_h.hip): fp16x2 pieces,
-// 22-bit operands, skinning on the matrix pipe too; b (skin_b.hip): round 1's bf16x3 kernel; p (skin_p.hip): fp32 MFMA; v: the
-// first form.  The IK / VPoser loops' internal launches (range_slot RANGE_INTERNAL: intermediate iterates whose mesh feeds the
-// residual's few vertices and the re-projection's face scan) run m->form_ik: h unless SMPLPP_SKIN chose a form for everything.
-// p (32-bit output offsets) falls back to v for outputs of 2 GiB and more.
+// 22-bit operands, skinning on the matrix pipe too; b (skin_b.hip): round 1's bf16x3 kernel; v: the first form (fp32 MFMA).
+// The IK / VPoser loops' internal launches (range_slot RANGE_INTERNAL: intermediate iterates whose mesh feeds the residual's few
+// vertices and the re-projection's face scan) run m->form_ik: h unless SMPLPP_SKIN chose a form for everything.
 // form_override (0: none): the form the caller chose for this launch (an IK solver in exact-arithmetic mode runs m->form).
-static char launch_form(const smplpp_model * m, int64_t n, int range_slot, char form_override)
+static char launch_form(const smplpp_model * m, int range_slot, char form_override)
 {
-  char form = form_override ? form_override : range_slot == RANGE_INTERNAL ? m->form_ik : m->form;
-  if(form == 'p' && n * m->V * 12 >= 0x7fffff00LL) form = 'v';
-  return form;
+  return form_override ? form_override : range_slot == RANGE_INTERNAL ? m->form_ik : m->form;
 }
 
 // range_slot: which word of the model's range status a launch of the fp16x2 form reports to (common.h RANGE_*): enqueue-only user
@@ -305,7 +300,7 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
 {
   Workspace & ws = m->ws;
   const int64_t n64 = ((n + 63) / 64) * 64;
-  HIP_TRY(ws.Gp.reserve(sizeof(float) * (size_t)n64 * NJ * 12)); // e / b / p stage whole frame tiles of G' (padding never stored)
+  HIP_TRY(ws.Gp.reserve(sizeof(float) * (size_t)n64 * NJ * 12)); // e / b stage whole frame tiles of G' (padding never stored)
   if(form == 'h')
   {
     HIP_TRY(ws.A2h.reserve((size_t)(n64 / 64) * HB_KS * HB_A_BYTES));
@@ -349,7 +344,6 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
 // (theta[f, 0, :], stride 75).
 static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st)
 {
-  Workspace & ws = m->ws;
   if(verts || rest)
   {
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -373,8 +367,6 @@ static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * 
       HIP_TRY(launch_skin_f16x2(m, n, theta, verts, rest, st));
     else if(form == 'b')
       HIP_TRY(launch_skin_bf16x3(m, n, theta, verts, rest, st));
-    else if(form == 'p' && ws.dummy.reserve(4096) == hipSuccess)
-      HIP_TRY(launch_skin_persistent(m, n, theta, ws.Gp.as<float>(), verts, rest, st));
     else if(n <= 32)
       HIP_TRY(launch_skin_w<1>(m, n, theta, verts, rest, st));
     else
@@ -389,7 +381,7 @@ static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * 
 int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * verts, float * joints,
               float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word, char form_override = 0)
 {
-  const char form = launch_form(m, n, range_slot, form_override);
+  const char form = launch_form(m, range_slot, form_override);
   int rc = fk_pose_device(m, form, n, beta, theta, joints, xforms44, poserot, st, range_word ? range_word : m->range_flag.get() + range_slot,
                           verts || rest);
   if(rc) return rc;
@@ -486,6 +478,6 @@ extern "C" int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const 
   if(ranged) HIP_TRY(hipMemcpy(&bits, m->range_flag.get() + RANGE_HOST, sizeof(int), hipMemcpyDeviceToHost));
   if(bits & 1)
     return fail(SMPLPP_ERR_NUMERIC, "smplpp_fk: an operand left the range of the fp16x2 form (|beta| < 1023, relative transforms within 16 x the "
-                                    "template's extent): the vertices of such frames are not finite; create the model under SMPLPP_SKIN=b or p");
+                                    "template's extent): the vertices of such frames are not finite; create the model under SMPLPP_SKIN=e or b");
   return SMPLPP_OK;
 }

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <tuple>
 
 namespace smplpp_hip
 {
@@ -256,6 +257,28 @@ static hipError_t upload(DevPtr<T> & dst, const T * src, size_t count)
   if(count) e = hipMemcpy(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice);
   return e;
 }
+
+// Forms of the fused kernel, {smplpp_fk's, the IK / VPoser loops' internal launches'}, decided once at model creation.  Default:
+// smplpp_fk runs e (skin_e.hip: fp32-exact operands, the reference's arithmetic) and the loops h (skin_h.hip: fp16x2 operands,
+// 3e-7 m); SMPLPP_SKIN = e | h | b | v puts every launch on that form.  The split-operand kernels address their basis images
+// with 32-bit buffer offsets: a mesh whose image would reach 2 GiB (more than ~745k vertices for h, ~410k for b) takes the
+// first form (64-bit addressing).  e keeps at most 4 skinning weights per vertex in registers and b at most 8: a model with
+// more takes the next form.
+static std::pair<char, char> choose_forms(const char * env, int maxw, int64_t VGPn)
+{
+  const char e = env ? env[0] : 0;
+  char forms[2] = {'e', 'h'};
+  if(e == 'e' || e == 'h' || e == 'b' || e == 'v') forms[0] = forms[1] = e;
+  for(char & f : forms)
+  {
+    if(f == 'h' && VGPn * HB_SLOTS * HB_IMG > 0x7fffff00LL) f = 'v';
+    if(f == 'e' && VGPn * EB_KS * EB_IMG > 0x7fffff00LL) f = 'v';
+    if(f == 'b' && VGPn * BB_KS * BB_B_BYTES > 0x7fffff00LL) f = 'v';
+    if(f == 'e' && maxw > 4) f = 'b';
+    if(f == 'b' && maxw > 8) f = 'v';
+  }
+  return {forms[0], forms[1]};
+}
 } // namespace smplpp_hip
 
 using namespace smplpp_hip;
@@ -314,6 +337,14 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   }
   for(int64_t i = 0; i < F * 3; i++)
     if(faces1[i] < 1 || faces1[i] > V) return fail(SMPLPP_ERR_INVALID, "face_indices must be 1-based vertex ids");
+  // skinning weights: the non-zeros are kept (real SMPL has <= 4 per vertex), a dense table otherwise
+  int maxnz = 0;
+  for(int64_t v = 0; v < V; v++)
+  {
+    int nz = 0;
+    for(int j = 0; j < NJ; j++) nz += (W[v * NJ + j] != 0.0f);
+    maxnz = std::max(maxnz, nz);
+  }
 
   HIP_TRY(hipSetDevice(device));
   std::unique_ptr<smplpp_model> m(new smplpp_model());
@@ -322,23 +353,13 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   m->F = F;
   m->VGn = (V + VG - 1) / VG;
   m->ldB = m->VGn * 3 * VG;
+  m->VGPn = (V + 63) / 64;
+  m->maxw = maxnz <= 4 ? 4 : (maxnz <= 8 ? 8 : NJ);
   m->h_parent = parent;
+  std::tie(m->form, m->form_ik) = choose_forms(getenv("SMPLPP_SKIN"), m->maxw, m->VGPn);
 
-  // --- blend bases -> Bm, regressor fold (device side; the raw arrays are only needed transiently) ---
-  // Form of the fused kernel: read once, here.  Default: smplpp_fk runs e (skin_e.hip: fp32-exact operands, the reference's
-  // arithmetic) and the IK / VPoser loops' internal launches h (skin_h.hip: fp16x2 operands, 3e-7 m); SMPLPP_SKIN = e | h | b | p | v
-  // puts every launch on that form.  Only the operand layouts the chosen forms need stay resident.
-  {
-    const char * form_env = getenv("SMPLPP_SKIN");
-    const char f = form_env ? form_env[0] : 0;
-    if(f == 'e' || f == 'h' || f == 'b' || f == 'p' || f == 'v')
-      m->form = m->form_ik = f;
-    else
-    {
-      m->form = 'e';
-      m->form_ik = 'h';
-    }
-  }
+  // --- blend bases -> Bm, regressor fold (device side; the raw arrays are only needed transiently).  Only the operand layouts
+  // the chosen forms read are built.
   {
     const char * pd_env = getenv("SMPLPP_POINT_DISTANCE_FORM"); // query | tiled: one form of smplpp_point_mesh_distance for every K
     m->pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
@@ -356,16 +377,7 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   fold_regressor_kernel<<<dim3(NJ * 3 * (NB + 1)), dim3(256)>>>(dJreg.get(), m->Svm.get(), dT.get(), m->J0.get(), m->JS.get(), V);
   HIP_TRY(dev_alloc(m->JSp, NJ * 3 * 12));
   pack_regressor_rows_kernel<<<dim3(1), dim3(NJ * 3)>>>(m->J0.get(), m->JS.get(), m->JSp.get());
-  m->VGPn = (V + 63) / 64;
-  // the split-operand kernels address their basis images with 32-bit buffer offsets: a mesh whose image would reach 2 GiB
-  // (more than ~745k vertices for h, ~410k for b) takes the first form (64-bit addressing) from creation on
-  for(char * f : {&m->form, &m->form_ik})
-  {
-    if(*f == 'h' && (int64_t)m->VGPn * HB_SLOTS * HB_IMG > 0x7fffff00LL) *f = 'v';
-    if(*f == 'e' && (int64_t)m->VGPn * EB_KS * EB_IMG > 0x7fffff00LL) *f = 'v';
-    if(*f == 'b' && (int64_t)m->VGPn * BB_KS * BB_B_BYTES > 0x7fffff00LL) *f = 'v';
-  }
-  if(uses('b') || uses('e')) // (e falls back to b for models with 5..8 weights per vertex: decided below, once they are counted)
+  if(uses('b'))
   {
     HIP_TRY(dev_alloc(m->B3, (size_t)m->VGPn * BB_KS * BB_B_BYTES));
     const int64_t cnt = m->VGPn * BB_KS * 6 * 64;
@@ -377,15 +389,7 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   dT.reset(); // (here, before the launches below: freeing device memory waits for the device)
   dJreg.reset();
 
-  // --- skinning weights: keep the non-zeros (real SMPL has <= 4 per vertex), dense fallback otherwise ---
-  int maxnz = 0;
-  for(int64_t v = 0; v < V; v++)
-  {
-    int nz = 0;
-    for(int j = 0; j < NJ; j++) nz += (W[v * NJ + j] != 0.0f);
-    maxnz = std::max(maxnz, nz);
-  }
-  m->maxw = maxnz <= 4 ? 4 : (maxnz <= 8 ? 8 : NJ);
+  // --- skinning weights (m->maxw per vertex) ---
   const int64_t Vpad = m->VGn * VG;
   std::vector<uint8_t> hIdx((size_t)Vpad * m->maxw, 0);
   std::vector<float> hVal((size_t)Vpad * m->maxw, 0.0f), hSum((size_t)Vpad, 1.0f);
@@ -415,13 +419,6 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   HIP_TRY(upload(m->wVal, hVal.data(), hVal.size()));
   HIP_TRY(upload(m->wSum, hSum.data(), hSum.size()));
   HIP_TRY(upload(m->Wdense, W, (size_t)V * NJ));
-  // e keeps at most 4 weights per vertex in registers, b and p at most 8: a model with more takes the next form from here on
-  // (decided once, so that the layouts kept below are the ones the launches will read)
-  for(char * f : {&m->form, &m->form_ik})
-  {
-    if(*f == 'e' && m->maxw > 4) *f = 'b';
-    if(m->maxw > 8 && (*f == 'b' || *f == 'p')) *f = 'v';
-  }
   if(uses('e'))
   {
     HIP_TRY(dev_alloc(m->B3e, (size_t)m->VGPn * EB_KS * EB_IMG));
@@ -515,8 +512,7 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
   }
-  if(!uses('b')) m->B3.reset();
-  if(!uses('p') && !uses('v')) m->Bm.reset(); // only the fp32-MFMA forms read the K-major fp32 basis
+  if(!uses('v')) m->Bm.reset(); // only the fp32-MFMA form reads the K-major fp32 basis
   HIP_TRY(upload(m->parent, parent.data(), parent.size()));
   {
     const int zero[RANGE_SLOTS] = {};

@@ -1,11 +1,11 @@
 // skin_kernel_b — the fused blend-shape GEMM + linear blend skinning kernel on the bf16 matrix pipe, fp32-exact operands.
 //
-// Why: v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 MFMA rate, and the fp32 forms of this kernel (fk.hip, skin_p.hip) are
+// Why: v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 MFMA rate, and the fp32 form of this kernel (fk.hip) is
 // bound by it.  Here every fp32 operand is carried as THREE bf16 pieces, x = x1 + x2 + x3 exactly (8 + 8 + 8 significant
 // bits), and a product a.b is evaluated as the six bf16 MFMAs a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1 accumulated in
 // fp32 — the three dropped cross terms are below 2^-24 |a||b|, the size of one fp32 rounding.  6 MFMAs of 32 cycles do the
 // work of 8 fp32 MFMAs of 64 cycles: 2.6x fewer matrix-pipe cycles at fp32-level accuracy (the parity tests compare it
-// with the fp32-MFMA forms against an fp64-accumulating CPU restatement: tests/test_fk_gpu.py).
+// with the fp32-MFMA form against an fp64-accumulating CPU restatement: tests/test_fk_gpu.py).
 //
 // Work item: 64 frames x 64 vertices (x 3 coordinates), one 256-thread workgroup (one wavefront per SIMD, 2 x 2
 // wavefronts of 32 frames x 32 vertices each), 14 k-steps of 16.  Operands are stored in HBM in MFMA FRAGMENT ORDER — a
@@ -18,15 +18,14 @@
 // arrives the same way.  hipcc does not order LDS reads behind LDS-DMA writes: every barrier that publishes DMA data
 // carries an explicit counted s_waitcnt vmcnt(N), N = the vector-memory instructions issued after the last DMA it needs.
 //
-// Software pipeline (as skin_p.hip): the instruction stream of an item is 252 hand-placed "slots", one per MFMA; the
+// Software pipeline: the instruction stream of an item is 252 hand-placed "slots", one per MFMA; the
 // skinning epilogue of the PREVIOUS item (16 accumulator rows at a pitch of 13 slots), the DMA of the operands three
 // k-steps ahead, the fragment reads of the next coordinates and the G' tile of the current item all issue in the MFMA
 // shadows.  One raw s_barrier per k-step (slot 6) orders the LDS images; DMAs stay in flight across it.
 #include "common.h"
+#include "slot_pipe.h"
 
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
 namespace smplpp_hip
 {
@@ -58,21 +57,6 @@ constexpr int B_ROOT_P = 9;                            // row slot that reads th
 constexpr int B_ROOT_KS = 11;                          // k-step whose slot 14 loads the root translations into a register
 constexpr int B_GCHUNKS = B_LDS_G / (256 * 16);        // 18 DMAs of 1 KiB per wavefront
 constexpr int B_GDMA0 = 12 * B_SLOTS + B_BAR + 1;      // 223: first slot of the G' DMAs (one per slot, 223..240)
-
-template<class F, int... I>
-__device__ __forceinline__ void bstatic_for_impl(F && f, std::integer_sequence<int, I...>)
-{
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template<int N, class F>
-__device__ __forceinline__ void bstatic_for(F && f)
-{
-  bstatic_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// piece products in issue order (index into the A pieces, index into the B pieces): small terms first
-constexpr int B_PA[6] = {2, 0, 1, 1, 0, 0};
-constexpr int B_PB[6] = {0, 2, 1, 0, 1, 0};
 
 // ---- compile-time bookkeeping of what each slot issues (the counted waits of the barriers are derived from it)
 // LDS instructions the epilogue of the previous item issues in slot S BEHIND the slot's sched_barrier line
@@ -161,19 +145,6 @@ static_assert(sum_epilogue_lds_ops(4) == 16 * (4 * 3 + 1) && sum_epilogue_lds_op
 static_assert(B_ROW_END < 12 * B_SLOTS + B_BAR, "the rows must end before the barrier after which the G' image is overwritten");
 static_assert(B_ROW0 - B_RD_AHEAD > B_BAR, "the first G' read of an item must follow the barrier that publishes the tile");
 static_assert(B_GDMA0 + B_GCHUNKS <= B_NSLOT, "the G' DMAs must fit the item");
-
-// Barrier of a k-step: LGKM = LDS instructions of this wavefront that may stay in flight (epilogue reads issued behind
-// slot 5's sched_barrier line), VM = vector-memory instructions that may stay in flight (see barrier_vmcnt).
-template<int LGKM, int VM>
-__device__ __forceinline__ void kstep_barrier()
-{
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(VM), "n"(LGKM) : "memory");
-}
-
-__device__ __forceinline__ void full_barrier()
-{
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 #if SKINB_ABL & 256
 // slot timestamps (development only): wavefront 0 of workgroup 0 stamps s_memtime at every slot of its first 8 items
@@ -422,7 +393,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
       }
     };
 
-    bstatic_for<B_NSLOT>([&](auto ss) {
+    static_for<B_NSLOT>([&](auto ss) {
       constexpr int S = decltype(ss)::value;
       constexpr int KS = S / B_SLOTS, M = S % B_SLOTS;
       constexpr int X = M / 6, Q = M % 6;
@@ -431,9 +402,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
       if(blockIdx.x == 0 && tid == 0 && dbg_item < 8) g_slot_times[dbg_item * 256 + S] = __builtin_readcyclecounter();
 #endif
       if constexpr(!(SKINB_ABL & 4))
-        acc[X] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afr[AP][B_PA[Q]]),
-                                                         __builtin_bit_cast(bf16x8, bfr[AP][X][B_PB[Q]]), acc[X], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
+        acc[X] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afr[AP][PIECE_A[Q]]),
+                                                         __builtin_bit_cast(bf16x8, bfr[AP][X][PIECE_B[Q]]), acc[X], 0, 0, 0);
+      SCHED_BARRIER();
 
       if constexpr(M == B_BAR && !(SKINB_ABL & 8))
       {
@@ -444,7 +415,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
         // the previous k-step); for k-step 0 those after the root translation write of slot 5.
         constexpr int LG = !EPI || KS == 12 ? 0 : (KS == 0 ? epilogue_lds_ops(S - 1, MAXW) : lds_ops_since_frag_reads(S, MAXW));
         constexpr int VM = barrier_vmcnt(KS, EPI, WANT_REST);
-        kstep_barrier<(LG < 15 ? LG : 15), (VM < 63 ? VM : 63)>();
+        waitcnt_barrier<(VM < 63 ? VM : 63), (LG < 15 ? LG : 15)>();
       }
       // ---- operand fragments of the NEXT k-step, all twelve behind this k-step's barrier (slots 6..14): their image has
       // landed, they are >= 6 slots old at the next barrier (whose LDS wait is then free) and >= 6 slots ahead of their MFMAs
@@ -456,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
       }
       // ---- root translations of the PREVIOUS item: register -> LDS, published by the barrier of k-step 0
       if constexpr(EPI && KS == 0 && M == B_BAR - 1) *rootWr = rstage;
-      __builtin_amdgcn_sched_barrier(0); // (the LDS instructions above are the ones the k-step barrier has to wait for)
+      SCHED_BARRIER(); // (the LDS instructions above are the ones the k-step barrier has to wait for)
 
       // ---- operand DMA: k-step KS + 3 into the image this k-step has just finished with (slots 7..12, one chunk each)
       if constexpr(M > B_BAR && M <= B_BAR + 6 && !(SKINB_ABL & 2))
@@ -500,7 +471,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
           if constexpr(S1 - R * B_PITCH <= 13) row_piece(std::integral_constant<int, R>{}, std::integral_constant<int, S1 - R * B_PITCH>{});
         }
       }
-      __builtin_amdgcn_sched_barrier(0);
+      SCHED_BARRIER();
     });
 
     // the current item becomes the previous one; the images rotate (14 k-steps per item, 14 mod 3 = 2)
@@ -529,7 +500,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
   // ---- drain: the epilogue of the last item with nothing to hide behind (its G' tile was DMA'd in its own slots 223..240)
   *rootWr = rstage;
   full_barrier();
-  bstatic_for<16>([&](auto rr) {
+  static_for<16>([&](auto rr) {
     constexpr int R = decltype(rr)::value;
     constexpr int ROWC = (R & 3) + 8 * (R >> 2);
     const float rx = accp[0][R], ry = accp[1][R], rz = accp[2][R];
@@ -538,9 +509,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
     {
       v3f ov = {rx, ry, rz};
       __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(v3u, ov), rsR, prev.voff, soff, 2);
-      __builtin_amdgcn_sched_barrier(0);
+      SCHED_BARRIER();
       asm volatile("s_nop 1");
-      __builtin_amdgcn_sched_barrier(0);
+      SCHED_BARRIER();
     }
     v4f m0 = {0.f, 0.f, 0.f, 0.f}, m1 = m0, m2 = m0;
 #pragma unroll
@@ -563,9 +534,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
     // HAZARD (measured on gfx950, not covered by hipcc's hazard recogniser when soffset is an SGPR): a VALU write to the
     // data registers of a 96-bit buffer store in the very next instruction lands before the store has read dword 1 of
     // lanes 12-15 of each 16.  In the slot stream above an MFMA always follows a store; here keep one instruction of distance.
-    __builtin_amdgcn_sched_barrier(0);
+    SCHED_BARRIER();
     asm volatile("s_nop 1");
-    __builtin_amdgcn_sched_barrier(0);
+    SCHED_BARRIER();
   });
 }
 

@@ -20,9 +20,7 @@
 //  * one raw s_barrier per k-step; every barrier that publishes DMA data carries a counted s_waitcnt vmcnt(N), N derived at
 //    compile time from a table of what each slot issues (hipcc does not order LDS reads behind LDS-DMA writes).
 #include "common.h"
-
-#include <type_traits>
-#include <utility>
+#include "slot_pipe.h"
 
 namespace smplpp_hip
 {
@@ -69,21 +67,6 @@ constexpr int E_A_SLOT = 13;                         // fragments of k-step KS +
 #ifndef SKINE_LGKM
 #define SKINE_LGKM 1 // 1: the k-step barriers let the epilogue's youngest LDS reads stay in flight (counted lgkmcnt); 0: lgkmcnt(0)
 #endif
-
-template<class F, int... I>
-__device__ __forceinline__ void estatic_for_impl(F && f, std::integer_sequence<int, I...>)
-{
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template<int N, class F>
-__device__ __forceinline__ void estatic_for(F && f)
-{
-  estatic_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// piece products in issue order (index into the A pieces, index into the B pieces): small terms first
-constexpr int E_PA[6] = {2, 0, 1, 1, 0, 0};
-constexpr int E_PB[6] = {0, 2, 1, 0, 1, 0};
 
 // ---- compile-time bookkeeping of what each slot issues.  Order inside a slot: MFMA, [barrier], fragment / table reads, ring DMA,
 // G' DMA, epilogue (its LDS reads, then its stores).
@@ -170,20 +153,6 @@ static_assert(e_barrier_vmcnt(0, true, false) == 5 && (E_A_PRE != 4 || (e_barrie
                   e_barrier_vmcnt(3, true, false) == 10 + 3 && e_barrier_vmcnt(5, true, false) == 10 + 4,
               "window bookkeeping");
 
-template<int LGKM, int VM>
-__device__ __forceinline__ void e_barrier()
-{
-#if SKINE_ABL & 8
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)" ::"n"(VM), "n"(LGKM) : "memory");
-#else
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)\n\ts_barrier" ::"n"(VM), "n"(LGKM) : "memory");
-#endif
-}
-__device__ __forceinline__ void e_full_barrier()
-{
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-#define ESB() __builtin_amdgcn_sched_barrier(0)
 #if SKINE_ABL & 512
 __device__ unsigned long long g_ewg_times[256 * 8];
 #endif
@@ -287,7 +256,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
   // 0..3 into images 0..3; only k-step 0 is waited for.
   auto load_frame_tile = [&](int ft, auto first_tag) {
     constexpr bool FIRST = decltype(first_tag)::value;
-    e_full_barrier(); // (later runs: every wavefront is done with the previous tile's G' image and root translations)
+    full_barrier(); // (later runs: every wavefront is done with the previous tile's G' image and root translations)
     float tval = 0.0f;
     if(tid < 192)
     {
@@ -296,7 +265,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
     }
     const int vgF = (vg0 + i0 % nvx) * (EB_KS * EB_IMG);
     if constexpr(FIRST)
-      estatic_for<E_NDMA>([&](auto ii) { dma(ii, vgF, 0, imgS[0]); });
+      static_for<E_NDMA>([&](auto ii) { dma(ii, vgF, 0, imgS[0]); });
     const uint8_t * ap = A3 + ((int64_t)ft * EB_KS * 2 + wf) * 3072 + lane * 16;
     // (the first four k-steps only: every CU starts at the same time and what a workgroup pulls before its first MFMA is served at
     // ~20 B/clk; the run's first item loads the rest, three fragments per k-step, four k-steps ahead of their first use)
@@ -306,11 +275,11 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
       for(int s = 0; s < 3; s++) areg[ks][s] = *reinterpret_cast<const v4f *>(ap + ks * BB_A_BYTES + s * 1024);
     if constexpr(FIRST)
     {
-      estatic_for<E_R - 1>([&](auto dd) {
+      static_for<E_R - 1>([&](auto dd) {
         constexpr int D = decltype(dd)::value + 1;
-        estatic_for<E_NDMA>([&](auto ii) { dma(ii, vgF, D, imgS[D]); });
+        static_for<E_NDMA>([&](auto ii) { dma(ii, vgF, D, imgS[D]); });
       });
-      e_barrier<0, E_A_PRE * 3 + (E_R - 1) * E_NDMA>(); // behind k-step 0: the A loads and k-steps 1..3 may stay in flight
+      waitcnt_barrier<E_A_PRE * 3 + (E_R - 1) * E_NDMA, 0, !(SKINE_ABL & 8)>(); // behind k-step 0: the A loads and k-steps 1..3 may stay in flight
 #pragma unroll
       for(int q = 0; q < 9; q++) bfr[0][q / 3][q % 3] = *reinterpret_cast<const v4f *>(imgV[0] + q * 1024);
       read_tables(lds + imgS[0]);
@@ -429,7 +398,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
       }
     };
 
-    estatic_for<E_NSLOT>([&](auto ss) {
+    static_for<E_NSLOT>([&](auto ss) {
       constexpr int S = decltype(ss)::value;
       constexpr int KS = S / E_SLOTS, M = S % E_SLOTS;
       constexpr int X = M / 6, Q = M % 6;
@@ -440,18 +409,18 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
       if constexpr(SKINE_ABL & 4)
       {
         if constexpr(KS == 0 && Q == 0) acc[X] = zero16;
-        asm volatile("" ::"v"(areg[KS][E_PA[Q]]), "v"(bfr[AP][X][E_PB[Q]]));
+        asm volatile("" ::"v"(areg[KS][PIECE_A[Q]]), "v"(bfr[AP][X][PIECE_B[Q]]));
       }
       else if constexpr(KS == 0 && Q == 0)
-        acc[X] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, areg[KS][E_PA[Q]]), __builtin_bit_cast(bf16x8, bfr[AP][X][E_PB[Q]]), zero16, 0, 0, 0);
+        acc[X] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, areg[KS][PIECE_A[Q]]), __builtin_bit_cast(bf16x8, bfr[AP][X][PIECE_B[Q]]), zero16, 0, 0, 0);
       else
-        acc[X] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, areg[KS][E_PA[Q]]), __builtin_bit_cast(bf16x8, bfr[AP][X][E_PB[Q]]), acc[X], 0, 0, 0);
-      ESB();
+        acc[X] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, areg[KS][PIECE_A[Q]]), __builtin_bit_cast(bf16x8, bfr[AP][X][PIECE_B[Q]]), acc[X], 0, 0, 0);
+      SCHED_BARRIER();
 
       // Barrier of the k-step.  Behind it image (KS + 1) % 4 holds k-step KS + 1 (its DMAs have landed: vmcnt) and image KS % 4 is
       // free for the DMAs of k-step KS + 4 (every wavefront's reads of it have completed: lgkmcnt).  k-step 0 also publishes the G'
       // image and the root translations of a new run.
-      if constexpr(M == E_BAR) e_barrier<e_barrier_lgkm(KS, EPI, MAXW), e_barrier_vmcnt(KS, EPI, WANT_REST)>();
+      if constexpr(M == E_BAR) waitcnt_barrier<e_barrier_vmcnt(KS, EPI, WANT_REST), e_barrier_lgkm(KS, EPI, MAXW), !(SKINE_ABL & 8)>();
       // ---- operand fragments of the NEXT k-step, all nine behind this k-step's barrier (slots 6..14)
       if constexpr(M >= E_BAR && M < E_BAR + 9 && !(SKINE_ABL & 16))
       {
@@ -471,7 +440,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
         const v4f jv = *reinterpret_cast<const v4f *>(lds + imgS[EB_KS % E_R] + tabLane + 1024);
         nx_jw[0] = jv.x; nx_jw[1] = jv.y; nx_jw[2] = jv.z; nx_jw[3] = jv.w;
       }
-      ESB(); // (the LDS instructions above are the ones the k-step barriers count from)
+      SCHED_BARRIER(); // (the LDS instructions above are the ones the k-step barriers count from)
 
       // ---- ring DMA: k-step KS + 4 into the image this k-step has just finished with (slots 7..11, one piece each)
       if constexpr(M > E_BAR && M <= E_BAR + E_NDMA)
@@ -508,7 +477,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
           if constexpr(S1 - R * E_PITCH <= 13) row_piece(std::integral_constant<int, R>{}, std::integral_constant<int, S1 - R * E_PITCH>{});
         }
       }
-      ESB();
+      SCHED_BARRIER();
     });
 
     // the current item becomes the previous one; the images rotate (14 k-steps per item, 14 mod 4 = 2)
@@ -531,7 +500,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
 
   // ---- the epilogue of a run's last item with nothing to hide behind (the G' tile may still be on its way: a run of one item)
   auto drain = [&]() {
-    e_full_barrier();
+    full_barrier();
     // the twelve matrix rows of accumulator row R + 1 are requested before row R is computed (two register sets)
     v4f gd[2][12], rtd[2];
     auto request = [&](auto rtag) {
@@ -542,7 +511,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
       for(int g = 0; g < 12; g++) gd[R & 1][g] = *reinterpret_cast<const v4f *>(gLane + ROWC * (NJ * 48) + (g / 4) * 16 + prev.jofs[g % 4]);
     };
     request(std::integral_constant<int, 0>{});
-    estatic_for<16>([&](auto rr) {
+    static_for<16>([&](auto rr) {
       constexpr int R = decltype(rr)::value;
       constexpr int ROWC = (R & 3) + 8 * (R >> 2);
       const v4f rt = rtd[R & 1];
@@ -552,9 +521,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
       {
         v3f ov = {rx, ry, rz};
         __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(v3u, ov), rsR, prev.voff, prev.sb + ROWC * frameB, 0);
-        ESB();
+        SCHED_BARRIER();
         asm volatile("s_nop 1");
-        ESB();
+        SCHED_BARRIER();
       }
       // (no MFMA is in flight here: packed fp32 math, two FMAs per instruction — the same products and sums as the slot stream's)
       typedef float v2f __attribute__((ext_vector_type(2)));
@@ -599,9 +568,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
       __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(v3u, ov), rsV, prev.voff, prev.sb + ROWC * frameB, SKINE_STORE_AUX);
       // HAZARD (measured on gfx950, see skin_b.hip): keep one instruction between a 96-bit buffer store and the next VALU write
       // to its data registers
-      ESB();
+      SCHED_BARRIER();
       asm volatile("s_nop 1");
-      ESB();
+      SCHED_BARRIER();
     });
   };
 

@@ -27,9 +27,7 @@
 // carries the group's vertex ids and its flags).  A group whose weights live in one k-step runs the skinning phase in the instantiation that issues only that k-step's
 // MFMAs and G' fragment reads — 3 (joints 0..15 only) or 2 (joints 16..23 only) MFMAs per entry instead of 5; exact zeros skipped.
 #include "common.h"
-
-#include <type_traits>
-#include <utility>
+#include "slot_pipe.h"
 
 namespace smplpp_hip
 {
@@ -43,17 +41,6 @@ constexpr int H_R = 7;                                  // ring images (15 slots
 constexpr int H_LDS_RING = HB_G_BYTES;                  // [0, 72 KiB): G' operand of the frame tile
 constexpr int H_LDS_TR = H_LDS_RING + H_R * HB_IMG;     // root translations of the 64 frames, (x, y, z, -) each
 constexpr int H_LDS_TOTAL = H_LDS_TR + 64 * 16;         // 160768 <= 163840
-
-template<class F, int... I>
-__device__ __forceinline__ void hstatic_for_impl(F && f, std::integer_sequence<int, I...>)
-{
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template<int N, class F>
-__device__ __forceinline__ void hstatic_for(F && f)
-{
-  hstatic_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // ---- the tail of an item (its last 16 vertex stores) is spread over the 14 GEMM slots of the NEXT item: all workgroups
 // run in step, so stores issued together arrive together — 16 stores per wavefront inside two slots were a 12.6 MB burst
@@ -108,20 +95,6 @@ static_assert(h_barrier_vmcnt(0, false, true) == 15 && h_barrier_vmcnt(1, false,
                   h_barrier_vmcnt(1, true, false) == 5 * 3 + 1 && h_barrier_vmcnt(8, true, false) == 15 + 7 && h_barrier_vmcnt(14, false, false) == 2 + 15,
               "window bookkeeping");
 
-template<int VM>
-__device__ __forceinline__ void h_barrier()
-{
-#if SKINH_ABL & 1
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(VM) : "memory");
-#else
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM) : "memory");
-#endif
-}
-__device__ __forceinline__ void h_full_barrier()
-{
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-#define HSB() __builtin_amdgcn_sched_barrier(0)
 #ifndef SKINH_STORE_AUX
 #define SKINH_STORE_AUX 0 // cache policy of the output stores (bit 0 sc0, bit 1 nt, bit 4 sc1)
 #endif
@@ -248,9 +221,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
     tail_store(rtag);
   };
   auto standalone_tail = [&]() {
-    hstatic_for<16>([&](auto rr) {
+    static_for<16>([&](auto rr) {
       tail_row(rr);
-      HSB();
+      SCHED_BARRIER();
     });
   };
 
@@ -261,7 +234,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
   // FIRST (the workgroup's first item): also the ring's prologue, slots 0..6 into images 0..6; only slot 0 is waited for.
   auto load_frame_tile = [&](int ft, auto first_tag) {
     constexpr bool FIRST = decltype(first_tag)::value;
-    h_full_barrier();
+    full_barrier();
 #if SKINH_ABL & 512
     if(FIRST && blockIdx.x == 8 && tid == 0) g_hslot_times[70] = __builtin_amdgcn_s_memtime();
 #endif
@@ -284,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
 #pragma unroll
       for(int p = 0; p < 2; p++) areg[ks][p] = *reinterpret_cast<const v4f *>(ap + ks * HB_A_BYTES + p * 1024);
     if constexpr(FIRST)
-      hstatic_for<H_R - 1>([&](auto dd) {
+      static_for<H_R - 1>([&](auto dd) {
         constexpr int D = decltype(dd)::value + 1;
         dma(std::integral_constant<int, 0>{}, vgF * (HB_SLOTS * HB_IMG), D, imgS[D]);
         dma(std::integral_constant<int, 1>{}, vgF * (HB_SLOTS * HB_IMG), D, imgS[D]);
@@ -292,7 +265,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
       });
     if constexpr(FIRST)
     {
-      h_barrier<28 + 18>(); // behind slot 0: the A loads and slots 1..6 may stay in flight
+      waitcnt_barrier<28 + 18, 0, !(SKINH_ABL & 1)>(); // behind slot 0: the A loads and slots 1..6 may stay in flight
 #pragma unroll
       for(int q = 0; q < 6; q++) bfr[0][q / 2][q % 2] = *reinterpret_cast<const v4f *>(imgV[0] + q * 1024);
     }
@@ -324,9 +297,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
 #endif
     // ---- blend-shape GEMM: 14 k-steps of 9 MFMAs.  Per coordinate: hi.hi, hi.lo, lo.hi; the two B fragments of a coordinate
     // are re-read (for the next k-step) right behind their last MFMA, six MFMAs ahead of their next use.
-    hstatic_for<HB_KS>([&](auto ss) {
+    static_for<HB_KS>([&](auto ss) {
       constexpr int S = decltype(ss)::value;
-      hstatic_for<9>([&](auto mm) {
+      static_for<9>([&](auto mm) {
         constexpr int M = decltype(mm)::value, X = M / 3, Q = M % 3; // Q: 0 hi.hi, 1 Ahi.Blo, 2 Alo.Bhi
         const v4f & a = areg[S][Q == 2 ? 1 : 0];
         const v4f & b = bfr[S & 1][X][Q == 1 ? 1 : 0];
@@ -345,10 +318,10 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
           acc[X] = mfma(a, b, zero16);
         else
           acc[X] = mfma(a, b, acc[X]);
-        HSB();
+        SCHED_BARRIER();
         // barrier of the slot: behind it image (S + 1) % 7 holds slot S + 1 (its DMAs have landed: vmcnt) and image S % 7 is
         // free for slot S + 7 (every wavefront's reads of it completed: lgkmcnt)
-        if constexpr(M == 1) h_barrier<h_barrier_vmcnt(S, HT, WANT_REST)>();
+        if constexpr(M == 1) waitcnt_barrier<h_barrier_vmcnt(S, HT, WANT_REST), 0, !(SKINH_ABL & 1)>();
         if constexpr(M >= 2 && M <= 4)
           dma(std::integral_constant<int, M - 2>{}, S + 7 < HB_SLOTS ? Bcur : Bnext, S + 7 < HB_SLOTS ? S + 7 : S + 7 - HB_SLOTS,
               imgS[S % H_R]);
@@ -359,12 +332,12 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
                                                    ft * HB_G_BYTES + (PC + wave) * 1024, 0, 0);
         }
         if constexpr(HT && (M == 5 || M == 7)) // a tail row placed at MFMA 5 / 8: arithmetic behind MFMA 5 / 7 ...
-          hstatic_for<16>([&](auto kk) {
+          static_for<16>([&](auto kk) {
             constexpr int K = decltype(kk)::value;
             if constexpr(h_tail_slot(K) == S && h_tail_m(K) == (M == 5 ? 5 : 8)) tail_prep(kk);
           });
         if constexpr(HT && (M == 6 || M == 8)) // ... store behind MFMA 6 / 8
-          hstatic_for<16>([&](auto kk) {
+          static_for<16>([&](auto kk) {
             constexpr int K = decltype(kk)::value;
             if constexpr(h_tail_slot(K) == S && h_tail_m(K) == (M == 6 ? 5 : 8)) tail_store(kk);
           });
@@ -396,7 +369,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
             gfr[0][3] = *reinterpret_cast<const v4f *>(gLane1 + 512);
           }
         }
-        HSB();
+        SCHED_BARRIER();
       });
     });
 
@@ -414,9 +387,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
     auto skin_phase = [&](auto ctag) {
     constexpr int CLS = decltype(ctag)::value;
     constexpr bool K0 = (CLS & 1) != 0, K1 = (CLS & 2) != 0;
-    hstatic_for<12>([&](auto ee) {
+    static_for<12>([&](auto ee) {
       constexpr int E = decltype(ee)::value, MPE = E & 1, ME = E % 3;
-      hstatic_for<5>([&](auto bb) {
+      static_for<5>([&](auto bb) {
         constexpr int B = decltype(bb)::value;
         constexpr bool LIVE = (B == 0 || B == 1 || B == 3) ? K0 : K1; // this position's MFMA belongs to a k-step the group uses
         constexpr int FIRST = K0 ? 0 : 2;                             // the entry's first MFMA (starts from zero)
@@ -437,8 +410,8 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
           macc[ME] = mfma(gfr[MPE][GI], wfr[WI], zero16);
         else
           macc[ME] = mfma(gfr[MPE][GI], wfr[WI], macc[ME]);
-        HSB();
-        if constexpr(E == 0 && B == 0) h_barrier<h_barrier_vmcnt(HB_KS, HT, WANT_REST)>(); // slot 14: publishes slot 0 of the next item
+        SCHED_BARRIER();
+        if constexpr(E == 0 && B == 0) waitcnt_barrier<h_barrier_vmcnt(HB_KS, HT, WANT_REST), 0, !(SKINH_ABL & 1)>(); // slot 14: publishes slot 0 of the next item
         if constexpr(E == 0 && B >= 1 && B <= 3) dma(std::integral_constant<int, B - 1>{}, Bnext, HB_KS + 7 - HB_SLOTS, imgS[HB_KS % H_R]);
         if constexpr(E == 1) // operand fragments of the next item's first k-step (image (14 + 1) % 7)
         {
@@ -484,7 +457,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
           __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(v3u, ov), rsR, cur.voff, cur.sb + ROWC * frameB, SKINH_STORE_AUX);
           asm volatile("s_nop 1");
         }
-        HSB();
+        SCHED_BARRIER();
       });
     });
     };

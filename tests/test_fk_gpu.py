@@ -92,10 +92,10 @@ def test_fk_batch1024_properties_and_sample(smpl, oracle_synth):
     assert np.isfinite(o).all()
 
 
-@pytest.mark.parametrize("form", ["e", "h", "b", "p", "v"])
+@pytest.mark.parametrize("form", ["e", "h", "b", "v"])
 def test_fk_dense_weights_and_ragged_vertex_count(form, monkeypatch):
     """61-vertex model with all 24 skinning weights non-zero (dense path) — golden from the reference build.  Under every
-    SMPLPP_SKIN: h takes dense weights as they are; e (at most 4 weights per vertex), b and p (at most 8) must hand such a
+    SMPLPP_SKIN: h takes dense weights as they are; e (at most 4 weights per vertex) and b (at most 8) must hand such a
     model to the first form when it is CREATED, with the operand layout that form reads kept resident."""
     from smplpp_amd import model_io
     from smplpp_amd.smpl import SMPL
@@ -111,10 +111,10 @@ def test_fk_dense_weights_and_ragged_vertex_count(form, monkeypatch):
         assert np.abs(o[k] - g[k]).max() < VERT_TOL, k
 
 
-@pytest.mark.parametrize("form", ["e", "h", "b", "p"])
+@pytest.mark.parametrize("form", ["e", "h", "b"])
 def test_fk_eight_weights_per_vertex(synth_model, form, monkeypatch):
-    """Models with 5..8 skinning weights per vertex: h skins on the matrix pipe with dense weights, the b / p forms take their
-    MAXW = 8 instantiations, and the default form (e: four weights per vertex in registers) hands such a model to b when it is
+    """Models with 5..8 skinning weights per vertex: h skins on the matrix pipe with dense weights, the b form takes its
+    MAXW = 8 instantiation, and the default form (e: four weights per vertex in registers) hands such a model to b when it is
     created (real SMPL has at most 4); ragged frame counts exercise partial frame tiles and the single-item / multi-item
     paths.  (The form is read from SMPLPP_SKIN when a model is created.)"""
     from smplpp_amd.smpl import SMPL
@@ -268,7 +268,7 @@ def test_fk_split_operand_forms_are_fp32_exact(synth_model, oracle_synth, monkey
     """The default fused kernel (e, skin_e.hip) and round 1's b (skin_b.hip) carry every fp32 operand as three bf16 pieces
     (fp32's 24 bits, six MFMA products) and skin in fp32 on the vector ALU; h (skin_h.hip) carries two fp16 pieces on the f16
     matrix pipe and skins there too.  Their error against the fp64-accumulating oracle must be of the same size as that of the
-    exact fp32-MFMA form (p, skin_p.hip), far inside the 1e-5 m parity bar, on shaped vertices and skinned vertices alike;
+    exact fp32-MFMA form (v, fk.hip), far inside the 1e-5 m parity bar, on shaped vertices and skinned vertices alike;
     and e, which issues b's piece products and b's skinning operations in b's order, must reproduce b's bits."""
     from smplpp_amd import model_io
     from smplpp_amd.smpl import SMPL
@@ -278,7 +278,7 @@ def test_fk_split_operand_forms_are_fp32_exact(synth_model, oracle_synth, monkey
     r = oracle_synth.fk(beta, theta)
     err = {}
     outs = {}
-    for form in ("e", "h", "b", "p"):
+    for form in ("e", "h", "b", "v"):
         monkeypatch.setenv("SMPLPP_SKIN", form)
         s = SMPL()
         s.setDevice("cuda:0")
@@ -291,7 +291,7 @@ def test_fk_split_operand_forms_are_fp32_exact(synth_model, oracle_synth, monkey
     for form in ("e", "h", "b"):
         for k in ("verts", "rest"):
             assert err[form][k] < 2e-6, err
-            assert err[form][k] <= 3.0 * err["p"][k] + 2e-7, err
+            assert err[form][k] <= 3.0 * err["v"][k] + 2e-7, err
 
 
 @pytest.mark.parametrize("form", ["h", "e"])

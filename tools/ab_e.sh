@@ -9,7 +9,7 @@ MASKS="1 2 8 16 32 26 59"
 if [ "$1" = build ]; then
   shift; mkdir -p ab
   for m in $MASKS; do
-    /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -fno-slp-vectorize "$@" -DSKINE_ABL=$m -c smplpp_amd/csrc/skin_e.hip -o /tmp/variant_e$m.o || exit 1
+    eval "$(python3 smplpp_amd/build.py --compile-cmd smplpp_amd/csrc/skin_e.hip /tmp/variant_e$m.o "$@" -DSKINE_ABL=$m)" || exit 1
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ab/e$m.so /tmp/variant_e$m.o $(ls smplpp_amd/build/*.o | grep -v "/skin_e.hip.o") || exit 1
   done
   ls ab/e*.so; exit 0
