@@ -422,6 +422,61 @@ public:
     for(size_t i = 0; i < in.size(); i++) in[i] = inside.idata[i] != 0 ? 1 : 0;
     return distanceBackward(smplpp_point_mesh_distance_vjp, false, points, face, gradSignedSqdist, gradPoints, accumulate, what, in.data());
   }
+  // Self-intersections of the last launch's meshes (smplpp_self_intersections): pairs [N,maxPairs,2] kInt64 in ascending (f, g),
+  // -1 past count, and count [N] kInt64, the true totals (a frame with more than maxPairs pairs keeps the lowest maxPairs).
+  struct SelfIntersections
+  {
+    Tensor pairs, count;
+  };
+  SelfIntersections selfIntersections(int64_t maxPairs = 32768) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    SelfIntersections r{Tensor({n, maxPairs, 2}, kInt64), Tensor({n}, kInt64)};
+    check(smplpp_self_intersections(m_.get(), n, verts_.ptr(), maxPairs, r.pairs.idata.data(), r.count.idata.data(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
+  // selfIntersections and the self-penetration energy of each stored pair (smplpp_self_penetration): pairEnergy [N,maxPairs], 0 past count
+  struct SelfPenetration
+  {
+    Tensor pairs, count, pairEnergy;
+  };
+  SelfPenetration selfPenetration(float sigma = 2.0f, int64_t maxPairs = 32768) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    SelfPenetration r{Tensor({n, maxPairs, 2}, kInt64), Tensor({n}, kInt64), Tensor({n, maxPairs})};
+    check(smplpp_self_penetration(m_.get(), n, verts_.ptr(), maxPairs, sigma, r.pairs.idata.data(), r.count.idata.data(), r.pairEnergy.ptr(),
+                                  SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
+  // Its backward pass (smplpp_self_penetration_vjp) at the pairs and count selfPenetration gave: dL/dverts [N,V,3] for
+  // dL/dpairEnergy = gradPairEnergy [N,maxPairs].  `accumulate` non-null: the product is added into it (and it is returned).
+  Tensor selfPenetrationBackward(const SelfPenetration & fwd, const Tensor & gradPairEnergy, float sigma = 2.0f,
+                                 Tensor * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const char * what = "Cannot back-propagate through the self-penetration energy!";
+    if(fwd.pairs.dim() != 3 || fwd.pairs.size(0) != n || fwd.count.numel() != n || gradPairEnergy.dtype != kFloat32 ||
+       gradPairEnergy.numel() != fwd.pairEnergy.numel())
+      throw Exception("SMPL", what);
+    const int64_t maxPairs = fwd.pairs.size(1);
+    Tensor local;
+    Tensor & out = accumulate ? *accumulate : local;
+    if(accumulate)
+    {
+      if(accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3) throw Exception("SMPL", what);
+    }
+    else
+      out = Tensor({n, V_, 3});
+    check(smplpp_self_penetration_vjp(m_.get(), n, verts_.ptr(), maxPairs, sigma, fwd.pairs.idata.data(), fwd.count.idata.data(),
+                                      gradPairEnergy.ptr(), out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return out;
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const

@@ -252,6 +252,42 @@ int smplpp_point_mesh_signed_distance_vjp(smplpp_model * m, int64_t n, const flo
                                           const int64_t * face /*[n,K]*/, const uint8_t * inside /*[n,K]*/,
                                           const float * grad_signed_sqdist /*[n,K]*/, float * grad_verts /*[n,V,3] nullable*/,
                                           float * grad_points /*[n,K,3] nullable*/, int accumulate, int space, void * stream);
+/* Self-intersections of each frame's posed mesh verts [n,V,3]: every pair of the model's faces (f, g), f < g, that share no vertex
+ * and intersect under this exact fp32 rule (every operation rounded on its own, no FMA):
+ *  - orient(a,b,c,d): u = b-a, v = c-a, w = d-a; cx = u.y v.z - u.z v.y, cy = u.z v.x - u.x v.z, cz = u.x v.y - u.y v.x;
+ *    (cx w.x + cy w.y) + cz w.z.
+ *  - edge pq crosses triangle abc iff orient(a,b,c,p) and orient(a,b,c,q) have strictly opposite signs and orient(p,q,a,b),
+ *    orient(p,q,b,c), orient(p,q,c,a) are all > 0 or all < 0.  A triangle's edges are (c0,c1), (c1,c2), (c2,c0) of its stored
+ *    corners.
+ *  - f and g intersect iff their closed fp32 AABBs overlap and some edge of either crosses the other.  Coplanar and merely
+ *    touching pairs are not reported; a face with a non-finite coordinate intersects nothing.
+ *  - pairs [n,max_pairs,2] (nullable when max_pairs = 0) in ascending (f, g); count [n] the true total, also beyond max_pairs
+ *    (then the lowest max_pairs pairs are stored); rows past min(count, max_pairs) are -1.
+ *  - the bits do not depend on n or on the frame's position in the batch; no floating-point atomics.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, max_pairs < 0, n * max_pairs, n * F or n * V beyond int32
+ *    indexing. */
+int smplpp_self_intersections(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t max_pairs,
+                              int64_t * pairs /*[n,max_pairs,2]*/, int64_t * count /*[n]*/, int space, void * stream);
+/* smplpp_self_intersections, then one self-penetration energy per stored pair (0 past min(count, max_pairs)): each pair is scored
+ * both ways, receiver f with g's corners, then receiver g with f's.  For a receiver (a, b, c): o = (a+b+c)/3,
+ * n = normalize((b-a) x (c-a)), rho^2 = (|a-o|^2 + |b-o|^2 + |c-o|^2)/3; an intruder corner x gives h = (x-o).n,
+ * q^2 = |x-o|^2 - h^2, phi = max(0, 1 - q^2 / (sigma^2 rho^2)) and contributes phi^2 h^2 if h < 0, else 0.  C1 in all six corners;
+ * a receiver of zero area contributes 0.  sigma (default 2) must be finite and > 0.  pairs and count as smplpp_self_intersections. */
+int smplpp_self_penetration(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t max_pairs, float sigma,
+                            int64_t * pairs /*[n,max_pairs,2]*/, int64_t * count /*[n]*/, float * pair_energy /*[n,max_pairs]*/,
+                            int space, void * stream);
+/* Vector-Jacobian product of pair_energy above to the vertices, at the pairs the forward gave (held fixed): accumulate = 0
+ * overwrites grad_verts, 1 adds; rows past min(count, max_pairs) and a zero cotangent contribute nothing, even on a NaN row;
+ * deterministic, no floating-point atomics.
+ *  - SMPLPP_ERR_INVALID: as the forward, host-space face ids out of range in the rows below min(count, max_pairs) (a device-space
+ *    pair with an id out of range contributes nothing).
+ *  - the handle keeps a record workspace of 384 bytes per (frame, row): n * max_pairs * 384 bytes (the counts are on the device
+ *    when the call is enqueued), grown to the largest call and held until the model is destroyed; pass a max_pairs near the counts
+ *    the forward returned to keep it small. */
+int smplpp_self_penetration_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t max_pairs, float sigma,
+                                const int64_t * pairs /*[n,max_pairs,2]*/, const int64_t * count /*[n]*/,
+                                const float * grad_pair_energy /*[n,max_pairs]*/, float * grad_verts /*[n,V,3]*/, int accumulate,
+                                int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

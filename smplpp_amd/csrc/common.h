@@ -232,6 +232,7 @@ struct NormalsVjpState; // the normals' backward pass (mesh_vjp.hip)
 struct PointDistState;  // point-to-mesh distance and its backward pass (point_distance.hip)
 struct MeshPointDistState; // mesh-to-point distance and its backward pass (mesh_point_distance.hip)
 struct WindingState;    // batched winding numbers and the signed point-to-mesh distance (winding.hip)
+struct SelfPenState;    // self-intersections, the self-penetration energy and its backward pass (self_penetration.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -241,6 +242,7 @@ struct StateDelete
   void operator()(PointDistState * s) const;
   void operator()(MeshPointDistState * s) const;
   void operator()(WindingState * s) const;
+  void operator()(SelfPenState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -298,5 +300,6 @@ struct smplpp_model
   smplpp_hip::StatePtr<smplpp_hip::PointDistState> pd; // point-to-mesh distance workspace (point_distance.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::MeshPointDistState> mpd; // mesh-to-point distance workspace (mesh_point_distance.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::WindingState> wn; // winding-number and signed-distance workspace (winding.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::SelfPenState> sp; // self-intersection and self-penetration workspace (self_penetration.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

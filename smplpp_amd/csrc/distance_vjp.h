@@ -4,7 +4,8 @@
 // record order (__ballot / __popcll, then a prefix over rows and wavefronts) to those that touch the workgroup's targets [lo, hi),
 // and each thread adds its shares in ascending record, then key: one fixed-order sum per target, no floating-point atomics.  An add
 // may be branch-free: +0 added for another target's share leaves acc's bits (acc starts at +0; a sum is -0 only if both terms are).
-// A record type supplies its LDS image Tile and touches(head, lo, hi), stage(tile, pos, head, rec), add(acc, tile, h, u).
+// A record type supplies its LDS image Tile and touches(head, lo, hi), stage(tile, pos, head, rec), add(acc, tile, h, u).  With
+// `nvalid` (device, [n]) a frame's records past nvalid[frame] are not read.
 #pragma once
 #include "staging.h"
 #include "trace.h"
@@ -17,7 +18,8 @@ constexpr int GATHER_TILE = GATHER_T * GATHER_R; // records per LDS tile
 
 template<class Rec>
 __global__ __launch_bounds__(GATHER_T) void record_gather_kernel(const Rec * __restrict__ rec, float * __restrict__ out, int accumulate,
-                                                                 int64_t nrec, int64_t ntarget, int64_t blocks_per_frame)
+                                                                 int64_t nrec, int64_t ntarget, int64_t blocks_per_frame,
+                                                                 const int64_t * __restrict__ nvalid)
 {
   __shared__ typename Rec::Tile s_tile;
   __shared__ int s_cnt[GATHER_R][GATHER_T / 64];
@@ -27,6 +29,7 @@ __global__ __launch_bounds__(GATHER_T) void record_gather_kernel(const Rec * __r
   const int u = lo + (int)threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const Rec * rf = rec + frame * nrec;
+  if(nvalid) nrec = nvalid[frame] < nrec ? nvalid[frame] : nrec;
   float acc[3] = {0.0f, 0.0f, 0.0f};
   for(int64_t base = 0; base < nrec; base += GATHER_TILE)
   {
@@ -66,12 +69,13 @@ __global__ __launch_bounds__(GATHER_T) void record_gather_kernel(const Rec * __r
   for(int x = 0; x < 3; x++) o[x] = accumulate ? o[x] + acc[x] : acc[x];
 }
 
-// n frames of nrec records each into [n][ntarget][3] floats
+// n frames of nrec records each (the first nvalid[frame] of them, with nvalid) into [n][ntarget][3] floats
 template<class Rec>
-int record_gather(const Rec * rec, float * out, int accumulate, int64_t n, int64_t nrec, int64_t ntarget, hipStream_t st)
+int record_gather(const Rec * rec, float * out, int accumulate, int64_t n, int64_t nrec, int64_t ntarget, hipStream_t st,
+                  const int64_t * nvalid = nullptr)
 {
   const int64_t bpf = (ntarget + GATHER_T - 1) / GATHER_T;
-  record_gather_kernel<Rec><<<dim3((unsigned)(n * bpf)), dim3(GATHER_T), 0, st>>>(rec, out, accumulate, nrec, ntarget, bpf);
+  record_gather_kernel<Rec><<<dim3((unsigned)(n * bpf)), dim3(GATHER_T), 0, st>>>(rec, out, accumulate, nrec, ntarget, bpf, nvalid);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }

@@ -44,6 +44,9 @@ def _stream():
     return None
 
 
+SELF_PAIRS_DEFAULT = 32768  # default max_pairs of the self-intersection calls
+
+
 class _Call:
     """The memory space of one ABI call, decided by its first array argument: numpy arrays are host space (converted to float32; the
     call stages and synchronises), torch tensors device space (CUDA float32 only; enqueued on torch's current stream).  `fail` is
@@ -569,6 +572,71 @@ class SMPL:
             raise SmplppError(1, "point_mesh_signed_distance_differentiable needs torch")
         return _SignedDistanceFunction.apply(verts, points, self)
 
+    # ---- self-intersections and the self-penetration energy (smplpp_self_intersections / smplpp_self_penetration[_vjp])
+    def _sp_forward(self, name, verts, max_pairs, sigma, check_count, energy, device_only=False):
+        c = _Call(name, verts, device_only=device_only)
+        n = verts.shape[0] if c.dev else len(verts)
+        verts = c.input(verts, (n, self.vertex_num, 3))
+        max_pairs = SELF_PAIRS_DEFAULT if max_pairs is None else int(max_pairs)
+        if max_pairs < 0:
+            c.refuse("max_pairs must be >= 0")
+        pairs, count = c.empty((n, max_pairs, 2), "int64"), c.empty((n,), "int64")
+        L = _lib.load()
+        if energy:
+            e = c.empty((n, max_pairs))
+            check(L.smplpp_self_penetration(self.handle, n, _ptr(verts), max_pairs, float(sigma), _ptr(pairs), _ptr(count), _ptr(e), c.space,
+                                            c.stream))
+        else:
+            e = None
+            check(L.smplpp_self_intersections(self.handle, n, _ptr(verts), max_pairs, _ptr(pairs), _ptr(count), c.space, c.stream))
+        if check_count:
+            most = int(count.max().item()) if c.dev else int(count.max())  # one read of count on the device
+            if most > max_pairs:
+                raise SmplppError(1, "%s: %d intersecting face pairs in a frame, more than max_pairs = %d" % (name, most, max_pairs))
+        return pairs, count, e
+
+    def selfIntersections(self, verts, max_pairs=None, check=True):
+        """The intersecting face pairs of each frame's posed mesh verts [N,V,3] (smplpp_self_intersections): returns (pairs
+        [N,max_pairs,2] int64, count [N] int64).  Pairs (f, g), f < g, share no vertex and intersect under the exact fp32 edge-crossing
+        rule of the C header, in ascending (f, g); rows past count are -1.  max_pairs defaults to 32768; a frame with more pairs
+        raises (one read of count) unless check=False, when count holds the true total and the lowest max_pairs pairs are stored.
+        numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        pairs, count, _ = self._sp_forward("selfIntersections", verts, max_pairs, 1.0, check, False)
+        return pairs, count
+
+    def selfPenetration(self, verts, sigma=2.0, max_pairs=None, check=True):
+        """selfIntersections and one self-penetration energy per stored pair (smplpp_self_penetration): returns (pairs, count,
+        pair_energy [N,max_pairs], 0 past count).  Each pair is scored both ways: the intruding corners below the receiver's plane,
+        phi^2 h^2 with phi = max(0, 1 - q^2 / (sigma^2 rho^2)) (the C header states the field)."""
+        return self._sp_forward("selfPenetration", verts, max_pairs, sigma, check, True)
+
+    def selfPenetrationBackward(self, verts, pairs, count, grad_pair_energy, sigma=2.0, out=None):
+        """Vector-Jacobian product of selfPenetration's pair_energy at the pairs [N,max_pairs,2] and count [N] it gave (the pair set
+        held fixed): grad_verts [N,V,3] for dL/dpair_energy = grad_pair_energy [N,max_pairs] (smplpp_self_penetration_vjp).  With
+        `out` [N,V,3] the gradient is added into it and it is returned.  The model keeps a workspace of N * max_pairs * 384 bytes
+        (max_pairs from the shape of `pairs`), grown to the largest call."""
+        c = _Call("selfPenetrationBackward", verts, grad_pair_energy, out)
+        n = verts.shape[0] if c.dev else len(verts)
+        verts = c.input(verts, (n, self.vertex_num, 3))
+        pr, cn = c.ids(pairs), c.ids(count)
+        if pr.shape[0] % (2 * n) or cn.shape[0] != n:
+            c.refuse("expected pairs of shape (%d, max_pairs, 2) and count of shape (%d,)" % (n, n))
+        max_pairs = pr.shape[0] // (2 * n)
+        g = c.input(grad_pair_energy, (n, max_pairs))
+        acc = out is not None
+        gv = c.inout(out, (n, self.vertex_num, 3)) if acc else c.empty((n, self.vertex_num, 3))
+        check(_lib.load().smplpp_self_penetration_vjp(self.handle, n, _ptr(verts), max_pairs, float(sigma), _ptr(pr), _ptr(cn), _ptr(g),
+                                                      _ptr(gv), int(acc), c.space, c.stream))
+        return gv
+
+    def self_penetration_differentiable(self, verts, sigma=2.0, max_pairs=None, check=True):
+        """(pairs [N,max_pairs,2], count [N], pair_energy [N,max_pairs]) of device vertices verts [N,V,3] (the bits of
+        selfPenetration), with pair_energy differentiable in verts through torch.autograd: smplpp_self_penetration forward,
+        smplpp_self_penetration_vjp backward at the same pairs, on torch's current stream.  A loss is e.g. pair_energy.sum()."""
+        if torch is None:
+            raise SmplppError(1, "self_penetration_differentiable needs torch")
+        return _SelfPenetrationFunction.apply(verts, self, float(sigma), max_pairs, check)
+
     def out(self, index: int, path: str):
         """SMPL::out (src/SMPL.cpp:757-790): Wavefront OBJ of frame `index` (v lines, then 1-based f lines)."""
         verts = self._need("verts")
@@ -681,6 +749,28 @@ if torch is not None:
             ctx.smpl, ctx.K, ctx.inside = smpl, K, ins
             ctx.save_for_backward(verts, points, face)
             return face, w, inside, sq
+
+
+    class _SelfPenetrationFunction(torch.autograd.Function):
+        """smplpp_self_penetration forward / smplpp_self_penetration_vjp backward (SMPL.self_penetration_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, smpl, sigma, max_pairs, check_count):
+            verts = verts.detach().contiguous()
+            pairs, count, e = smpl._sp_forward("self_penetration_differentiable", verts, max_pairs, sigma, check_count, True,
+                                               device_only=True)
+            ctx.mark_non_differentiable(pairs, count)
+            ctx.smpl, ctx.sigma = smpl, sigma
+            ctx.save_for_backward(verts, pairs, count)
+            return pairs, count, e
+
+        @staticmethod
+        def backward(ctx, _gp, _gc, grad_e):
+            verts, pairs, count = ctx.saved_tensors
+            if grad_e is None or not ctx.needs_input_grad[0]:
+                return None, None, None, None, None
+            gv = ctx.smpl.selfPenetrationBackward(verts, pairs, count, grad_e.contiguous(), ctx.sigma)
+            return gv, None, None, None, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
