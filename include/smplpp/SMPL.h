@@ -477,6 +477,52 @@ public:
           "SMPL");
     return out;
   }
+  // The last launch's meshes through a pinhole camera into an H x W image (smplpp_depth_raster): face [N,H,W] kInt64 (-1 =
+  // background), depth [N,H,W] (0 at background), bary [N,H,W,3], visible [N,V] kInt64 0 / 1, culled [N] kInt64.  camera [N,16] or
+  // [16] (one camera for every frame): R row-major (world -> camera), t, fx, fy, cx, cy.
+  struct DepthRaster
+  {
+    Tensor face, depth, bary, visible, culled;
+  };
+  DepthRaster depthRaster(const Tensor & camera, int64_t H, int64_t W, float near = 0.05f) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const char * what = "Cannot rasterise the mesh!";
+    const std::vector<float> cam = cameraRows(camera, n, what);
+    if(H < 1 || W < 1) throw Exception("SMPL", what);
+    std::vector<uint8_t> vis((size_t)(n * V_));
+    DepthRaster r{Tensor({n, H, W}, kInt64), Tensor({n, H, W}), Tensor({n, H, W, 3}), Tensor({n, V_}, kInt64), Tensor({n}, kInt64)};
+    check(smplpp_depth_raster(m_.get(), n, verts_.ptr(), cam.data(), H, W, near, r.face.idata.data(), r.depth.ptr(), r.bary.ptr(), vis.data(),
+                              r.culled.idata.data(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    for(size_t i = 0; i < vis.size(); i++) r.visible.idata[i] = vis[i];
+    return r;
+  }
+  // Its backward pass (smplpp_depth_raster_vjp) at the faces `face` [N,H,W] it gave: dL/dverts [N,V,3] for dL/ddepth = gradDepth
+  // [N,H,W].  `accumulate` non-null: the product is added into it (and it is returned).
+  Tensor depthRasterBackward(const Tensor & camera, const Tensor & face, const Tensor & gradDepth, Tensor * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const char * what = "Cannot back-propagate through the depth image!";
+    const std::vector<float> cam = cameraRows(camera, n, what);
+    if(face.dim() != 3 || face.size(0) != n || (face.dtype != kInt64 && face.dtype != kInt32) || gradDepth.dtype != kFloat32 ||
+       gradDepth.numel() != face.numel())
+      throw Exception("SMPL", what);
+    Tensor local;
+    Tensor & out = accumulate ? *accumulate : local;
+    if(accumulate)
+    {
+      if(accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3) throw Exception("SMPL", what);
+    }
+    else
+      out = Tensor({n, V_, 3});
+    check(smplpp_depth_raster_vjp(m_.get(), n, verts_.ptr(), cam.data(), face.size(1), face.size(2), face.idata.data(), gradDepth.ptr(),
+                                  out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return out;
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const
@@ -537,6 +583,14 @@ private:
                                                                              g.ptr(), acc, SMPLPP_HOST, nullptr),
             "SMPL");
     return g;
+  }
+  std::vector<float> cameraRows(const Tensor & camera, int64_t n, const char * what) const // camera [16] or [N,16] as N rows
+  {
+    if(camera.dtype != kFloat32 || !(camera.numel() == 16 || (camera.dim() == 2 && camera.size(0) == n && camera.size(1) == 16)))
+      throw Exception("SMPL", what);
+    std::vector<float> rows((size_t)(n * 16));
+    for(size_t i = 0; i < rows.size(); i++) rows[i] = camera.data[camera.numel() == 16 ? i % 16 : i];
+    return rows;
   }
   int64_t pointsFor(const Tensor & points, const char * what) const // frames of the last launch, checked against points [N,K,3]
   {

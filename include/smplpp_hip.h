@@ -288,6 +288,53 @@ int smplpp_self_penetration_vjp(smplpp_model * m, int64_t n, const float * verts
                                 const int64_t * pairs /*[n,max_pairs,2]*/, const int64_t * count /*[n]*/,
                                 const float * grad_pair_energy /*[n,max_pairs]*/, float * grad_verts /*[n,V,3]*/, int accumulate,
                                 int space, void * stream);
+/* Depth rasteriser: each frame's posed mesh verts [n,V,3] through a pinhole camera into a face-id + depth image of H rows and W
+ * columns.  camera [n,16] per frame: R (9, row-major, world -> camera), t (3), fx, fy, cx, cy; the camera looks along +z, x right,
+ * y down; pixel (row j, column i) has its centre at (i + 0.5, j + 0.5).  The rule, in fp32 with every operation rounded on its own
+ * (no FMA; correctly rounded divisions) unless it says integer:
+ *  - vertex: xc.k = ((R[3k] x + R[3k+1] y) + R[3k+2] z) + t[k]; u = (fx xc.x) / xc.z + cx, v = (fy xc.y) / xc.z + cy;
+ *    su = rintf(u * 256), sv = rintf(v * 256) (ties to even).  The vertex is refused unless xc is finite, xc.z > near and
+ *    |su|, |sv| <= 2^23 (a guard band of 32768 px: edge functions below stay under 2^51).  X = (int) su, Y = (int) sv.
+ *  - a face (a, b, c) of the model with a refused corner is skipped, and counted in culled[frame] (no clipping).  Otherwise, in
+ *    int64: A2 = (Xb-Xa)(Yc-Ya) - (Yb-Ya)(Xc-Xa); A2 = 0 covers nothing; s = sign(A2).  For each corner k, with p, q the next two
+ *    corners in cyclic order: ex = s (Xq-Xp), ey = s (Yq-Yp), E = ex (Py-Yp) - ey (Px-Xp) at the pixel centre
+ *    (Px, Py) = (256 i + 128, 256 j + 128).  The pixel is covered iff for all three E > 0, or E = 0 and (ey < 0, or ey = 0 and
+ *    ex > 0) (top-left rule: a centre on an edge two faces share belongs to exactly one of them).  Both orientations are drawn.
+ *  - depth of a covered pixel: in camera space e1 = b-a, e2 = c-a, n = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *    e1.x e2.y - e1.y e2.x), na = (n.x a.x + n.y a.y) + n.z a.z; the centre's ray d = ((((float) i + 0.5) - cx) / fx,
+ *    (((float) j + 0.5) - cy) / fy, 1); nd = (n.x d.x + n.y d.y) + n.z; depth = na / nd.  A candidate whose depth is not finite or
+ *    <= near is dropped.
+ *  - depth test: the smallest depth wins, on equal depth bits the lowest face id (the minimum of depth bits << 32 | face id).
+ *  - face [n,H,W]: the winner, -1 at background.  depth [n,H,W]: its depth, 0 at background.  bary [n,H,W,3] (nullable): with
+ *    w = (depth d.x - a.x, depth d.y - a.y, depth - a.z), nn = (n.x n.x + n.y n.y) + n.z n.z, dot(p, q) = (p.x q.x + p.y q.y) +
+ *    p.z q.z and cross() as n above: beta_b = dot(cross(w, e2), n) / nn, beta_c = dot(cross(e1, w), n) / nn,
+ *    beta_a = (1 - beta_b) - beta_c; stored (beta_a, beta_b, beta_c), 0 at background.  They are the weights of the hit point
+ *    depth d in 3-D, consistent with depth; a pixel the snap put just outside the true triangle has one a little below 0.
+ *  - visible [n,V] (nullable): 1 iff the vertex is a corner of a face that owns at least one pixel of the frame, else 0.  Exact and
+ *    parameter-free; it depends on the resolution (a face that falls between pixel centres is not seen), and a corner of a partly
+ *    hidden face counts as seen.  culled [n] (nullable): the skipped faces.
+ *  - the bits of a frame do not depend on n, on its position in the batch, on the memory space or on how the work is split
+ *    (SMPLPP_DEPTH_RASTER_INLINE, read at model creation); no floating-point atomics.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, H or W outside [1, 8192], near not finite or <= 0, n H W, n V or n F
+ *    beyond int32 indexing.  Device data is never refused: NaN vertices give skipped faces. */
+int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H,
+                        int64_t W, float near, int64_t * face /*[n,H,W]*/, float * depth /*[n,H,W]*/,
+                        float * bary /*[n,H,W,3] nullable*/, uint8_t * visible /*[n,V] nullable*/, int64_t * culled /*[n] nullable*/,
+                        int space, void * stream);
+/* Vector-Jacobian product of depth above to the world-space vertices, at the faces the forward chose (face [n,H,W], held fixed;
+ * coverage is not differentiated): with g = grad_depth at a pixel, beta, n, nd as above, corner i of the pixel's face receives
+ * R^T (g beta_i n / nd).  In fp32: per face, s_i = sum of beta_i * (g / nd) over the pixel centres of its snapped bounding box
+ * (clipped to the image, row-major) that name the face and have g != 0, entry r of the box summed by lane r mod 8 in ascending r,
+ * the eight partial sums combined as ((l0+l4)+(l2+l6)) + ((l1+l5)+(l3+l7)); the face's vector for corner i is s_i n; a vertex sums
+ * the vectors of its faces in ascending face id, and R^T is applied once.  accumulate = 0 overwrites grad_verts (untouched
+ * vertices get 0), 1 adds.  A pixel with face = -1 or a cotangent of exactly 0 contributes nothing, even when its data is NaN;
+ * so does a pixel outside its face's snapped bounding box and a face with a non-finite or out-of-band projection (the forward
+ * names neither).  Deterministic, no floating-point atomics.  No gradient to camera.
+ *  - SMPLPP_ERR_INVALID: as the forward, accumulate not 0 or 1, a host-space face id outside [-1, F) (the output is untouched; a
+ *    device-space id out of range contributes nothing). */
+int smplpp_depth_raster_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H,
+                            int64_t W, const int64_t * face /*[n,H,W]*/, const float * grad_depth /*[n,H,W]*/,
+                            float * grad_verts /*[n,V,3]*/, int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -1,0 +1,502 @@
+// Depth rasteriser: each frame's posed mesh through a pinhole camera into a face-id + depth image, with vertex visibility, and the
+// vector-Jacobian product of the depth image to the vertices.  The rule is in include/smplpp_hip.h; every fp32
+// operation below is rounded on its own (no contraction to FMA), and coverage is decided in integers, so a numpy restatement
+// reproduces every bit.
+//
+// Forward:
+//  dr_vertex_kernel   per (frame, vertex): camera-space position (float4, w unused) and the snapped projection (int2; x = DR_BAD
+//                     for a vertex the rule refuses).
+//  dr_face_kernel     per (frame, face): skipped faces counted (integer atomics), the snapped bounding box clipped to the image; a
+//                     box of at most `inline` pixels is walked by the face's own thread, a larger one is queued (an integer
+//                     atomic takes the slot; the order of the queue cannot matter, see below).
+//  dr_large_kernel    a fixed grid of wavefronts takes the queued faces in turn, 64 lanes striding one box: no lane ever owns a
+//                     large face's whole box.
+//                     Both apply the integer edge functions at the pixel centre, the ray-plane depth, and a 64-bit unsigned
+//                     minimum on the pixel's key, depth bits << 32 | face id (depths are positive, so their bits order like their
+//                     values): a minimum over a set does not depend on the order the set is met in.  A plain load of the key
+//                     first skips the atomic for a candidate that has already lost (keys only fall).
+//  dr_resolve_kernel  per pixel: key -> face, depth, the 3-D barycentrics of the hit point, and a plain byte store of 1 into
+//                     `visible` for the three corners (every writer stores the same value).
+// Backward (the face image is an input and held fixed):
+//  dr_vjp_face_kernel   per (frame, face), DR_SPLIT lanes: the face's clipped box in row-major order, lane l taking entries l,
+//                       l + DR_SPLIT, ...; a pixel that names the face and has a nonzero cotangent adds beta_i * (g / (n.d)) to
+//                       corner i's sum; the lanes' sums meet in a fixed xor tree (4, 2, 1) and lane 0 stores n times each.
+//  dr_vjp_vertex_kernel per (frame, vertex): its faces' vectors in ascending face id (the adjacency of the normals' backward pass),
+//                       then R^T once.  One fixed-order sum per vertex, no floating-point atomics.
+#include "staging.h"
+#include "trace.h"
+
+#include <algorithm>
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+namespace smplpp_hip
+{
+constexpr int DR_T = 256;                   // threads of every kernel here
+constexpr int DR_SPLIT = 8;                 // lanes per face in the backward walk
+constexpr int DR_BAD = INT32_MIN;           // snapped x of a refused vertex
+constexpr float DR_GUARD = 8388608.0f;      // guard band in snapped units (1/256 px): 32768 px; |edge function| < 2^51
+constexpr int64_t DR_MAX_SIDE = 8192;       // largest H or W
+constexpr int DR_INLINE_DEFAULT = 16;       // box pixels a face's own thread walks (SMPLPP_DEPTH_RASTER_INLINE)
+constexpr int DR_INLINE_MAX = 4096;
+constexpr unsigned DR_LARGE_BLOCKS = 2048;  // grid of dr_large_kernel: 8192 wavefronts
+constexpr unsigned long long DR_EMPTY = ~0ull;
+
+__host__ __device__ inline int64_t dr_min(int64_t a, int64_t b) { return a < b ? a : b; }
+__host__ __device__ inline int64_t dr_max(int64_t a, int64_t b) { return a > b ? a : b; }
+
+struct DepthRasterState
+{
+  DevBuf cam, snap;   // [n][V] float4 camera-space vertex, int2 snapped projection
+  DevBuf keys;        // [n][H][W] uint64
+  DevBuf queue, qn;   // [n][F] int32 queued (frame, face) items and their count
+  DevBuf fgrad;       // [n][F][9] per-face corner vectors of the backward pass
+  DevBuf verts, camera, face, depth, bary, visible, culled, grad, gv; // staging of host-space calls
+  int inline_px = DR_INLINE_DEFAULT;
+};
+void StateDelete::operator()(DepthRasterState * s) const
+{
+  delete s;
+}
+
+struct DrCamera
+{
+  float R[9], t[3], fx, fy, cx, cy;
+};
+__device__ inline DrCamera dr_camera(const float * __restrict__ camera, int64_t frame)
+{
+  DrCamera c;
+  const float * p = camera + frame * 16;
+  for(int k = 0; k < 9; k++) c.R[k] = p[k];
+  for(int k = 0; k < 3; k++) c.t[k] = p[9 + k];
+  c.fx = p[12], c.fy = p[13], c.cx = p[14], c.cy = p[15];
+  return c;
+}
+
+__global__ __launch_bounds__(DR_T) void dr_vertex_kernel(const float * __restrict__ verts, const float * __restrict__ camera,
+                                                         float4 * __restrict__ cam, int2 * __restrict__ snap, float near, int64_t V,
+                                                         int64_t nv)
+{
+  const int64_t idx = (int64_t)blockIdx.x * DR_T + threadIdx.x;
+  if(idx >= nv) return;
+  const DrCamera c = dr_camera(camera, idx / V);
+  const float x = verts[idx * 3], y = verts[idx * 3 + 1], z = verts[idx * 3 + 2];
+  float xc[3];
+  for(int k = 0; k < 3; k++) xc[k] = ((c.R[3 * k] * x + c.R[3 * k + 1] * y) + c.R[3 * k + 2] * z) + c.t[k];
+  const float u = (c.fx * xc[0]) / xc[2] + c.cx;
+  const float v = (c.fy * xc[1]) / xc[2] + c.cy;
+  const float su = rintf(u * 256.0f), sv = rintf(v * 256.0f);
+  const bool ok = fabsf(xc[0]) < INFINITY && fabsf(xc[1]) < INFINITY && fabsf(xc[2]) < INFINITY && xc[2] > near && fabsf(su) <= DR_GUARD &&
+                  fabsf(sv) <= DR_GUARD; // (a NaN fails every comparison)
+  cam[idx] = make_float4(xc[0], xc[1], xc[2], 0.0f);
+  snap[idx] = ok ? make_int2((int)su, (int)sv) : make_int2(DR_BAD, DR_BAD);
+}
+
+// one (frame, face) ready to be walked: snapped corners, the clipped box, the plane
+struct DrFace
+{
+  int64_t x[3], y[3];
+  int sgn;
+  int i0, i1, j0, j1;
+  float ax, ay, az, nx, ny, nz, na;
+  float e1[3], e2[3];
+};
+enum
+{
+  DR_FACE_OK = 0,
+  DR_FACE_SKIPPED = 1, // a refused corner
+  DR_FACE_EMPTY = 2    // zero snapped area, or a box that holds no pixel centre of the image
+};
+__device__ inline int dr_face_setup(DrFace & t, const float4 * __restrict__ cam, const int2 * __restrict__ snap,
+                                    const int32_t * __restrict__ faces, int64_t frame, int64_t f, int64_t V, int64_t H, int64_t W)
+{
+  int32_t c[3];
+  int2 s[3];
+  for(int k = 0; k < 3; k++)
+  {
+    c[k] = faces[f * 3 + k];
+    s[k] = snap[frame * V + c[k]];
+  }
+  if(s[0].x == DR_BAD || s[1].x == DR_BAD || s[2].x == DR_BAD) return DR_FACE_SKIPPED;
+  for(int k = 0; k < 3; k++) t.x[k] = s[k].x, t.y[k] = s[k].y;
+  const int64_t A2 = (t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (t.y[1] - t.y[0]) * (t.x[2] - t.x[0]);
+  if(A2 == 0) return DR_FACE_EMPTY;
+  t.sgn = A2 > 0 ? 1 : -1;
+  const int64_t xmin = dr_min(t.x[0], dr_min(t.x[1], t.x[2])), xmax = dr_max(t.x[0], dr_max(t.x[1], t.x[2]));
+  const int64_t ymin = dr_min(t.y[0], dr_min(t.y[1], t.y[2])), ymax = dr_max(t.y[0], dr_max(t.y[1], t.y[2]));
+  // pixel centres 256 i + 128 inside [min, max]
+  t.i0 = (int)dr_max(0, (xmin + 127) >> 8), t.i1 = (int)dr_min(W - 1, (xmax - 128) >> 8);
+  t.j0 = (int)dr_max(0, (ymin + 127) >> 8), t.j1 = (int)dr_min(H - 1, (ymax - 128) >> 8);
+  if(t.i0 > t.i1 || t.j0 > t.j1) return DR_FACE_EMPTY;
+  const float4 a = cam[frame * V + c[0]], b = cam[frame * V + c[1]], cc = cam[frame * V + c[2]];
+  t.ax = a.x, t.ay = a.y, t.az = a.z;
+  t.e1[0] = b.x - a.x, t.e1[1] = b.y - a.y, t.e1[2] = b.z - a.z;
+  t.e2[0] = cc.x - a.x, t.e2[1] = cc.y - a.y, t.e2[2] = cc.z - a.z;
+  t.nx = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1];
+  t.ny = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2];
+  t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
+  t.na = (t.nx * t.ax + t.ny * t.ay) + t.nz * t.az;
+  return DR_FACE_OK;
+}
+
+// the pixel-centre ray's x and y (z = 1)
+__device__ inline void dr_ray(const DrCamera & c, int i, int j, float & dx, float & dy)
+{
+  dx = (((float)i + 0.5f) - c.cx) / c.fx;
+  dy = (((float)j + 0.5f) - c.cy) / c.fy;
+}
+
+// barycentrics of p = depth * d in (a, a + e1, a + e2) with normal n
+__device__ inline void dr_bary(const DrFace & t, float depth, float dx, float dy, float & ba, float & bb, float & bc)
+{
+  const float wx = depth * dx - t.ax, wy = depth * dy - t.ay, wz = depth - t.az;
+  const float nn = (t.nx * t.nx + t.ny * t.ny) + t.nz * t.nz;
+  const float px = wy * t.e2[2] - wz * t.e2[1], py = wz * t.e2[0] - wx * t.e2[2], pz = wx * t.e2[1] - wy * t.e2[0]; // w x e2
+  const float qx = t.e1[1] * wz - t.e1[2] * wy, qy = t.e1[2] * wx - t.e1[0] * wz, qz = t.e1[0] * wy - t.e1[1] * wx; // e1 x w
+  bb = ((px * t.nx + py * t.ny) + pz * t.nz) / nn;
+  bc = ((qx * t.nx + qy * t.ny) + qz * t.nz) / nn;
+  ba = (1.0f - bb) - bc;
+}
+
+// coverage of pixel (row j, column i) by the face, its depth, the depth test
+__device__ inline void dr_pixel(const DrFace & t, const DrCamera & c, float near, int i, int j, unsigned f,
+                                unsigned long long * __restrict__ keys, int64_t W)
+{
+  const int64_t px = 256 * (int64_t)i + 128, py = 256 * (int64_t)j + 128;
+#pragma unroll
+  for(int e = 0; e < 3; e++)
+  {
+    const int p = (e + 1) % 3, q = (e + 2) % 3;
+    const int64_t ex = t.sgn * (t.x[q] - t.x[p]), ey = t.sgn * (t.y[q] - t.y[p]);
+    const int64_t E = ex * (py - t.y[p]) - ey * (px - t.x[p]);
+    if(!(E > 0 || (E == 0 && (ey < 0 || (ey == 0 && ex > 0))))) return;
+  }
+  float dx, dy;
+  dr_ray(c, i, j, dx, dy);
+  const float nd = (t.nx * dx + t.ny * dy) + t.nz;
+  const float depth = t.na / nd;
+  if(!(depth > near && depth < INFINITY)) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | f;
+  unsigned long long * k = keys + (int64_t)j * W + i;
+  if(key < __atomic_load_n(k, __ATOMIC_RELAXED)) atomicMin(k, key);
+}
+
+__global__ __launch_bounds__(DR_T) void dr_face_kernel(const float4 * __restrict__ cam, const int2 * __restrict__ snap,
+                                                       const int32_t * __restrict__ faces, const float * __restrict__ camera,
+                                                       unsigned long long * __restrict__ keys, int32_t * __restrict__ queue,
+                                                       int32_t * __restrict__ qn, unsigned long long * __restrict__ culled, float near,
+                                                       int64_t H, int64_t W, int64_t V, int64_t F, int64_t nf, int inline_px)
+{
+  const int64_t idx = (int64_t)blockIdx.x * DR_T + threadIdx.x;
+  if(idx >= nf) return;
+  const int64_t frame = idx / F, f = idx % F;
+  DrFace t;
+  const int rc = dr_face_setup(t, cam, snap, faces, frame, f, V, H, W);
+  if(rc == DR_FACE_SKIPPED && culled) atomicAdd(culled + frame, 1ull);
+  if(rc != DR_FACE_OK) return;
+  const int w = t.i1 - t.i0 + 1, h = t.j1 - t.j0 + 1;
+  if((int64_t)w * h > inline_px)
+  {
+    queue[atomicAdd(qn, 1)] = (int32_t)idx;
+    return;
+  }
+  const DrCamera c = dr_camera(camera, frame);
+  unsigned long long * kf = keys + frame * H * W;
+  for(int j = t.j0; j <= t.j1; j++)
+    for(int i = t.i0; i <= t.i1; i++) dr_pixel(t, c, near, i, j, (unsigned)f, kf, W);
+}
+
+__global__ __launch_bounds__(DR_T) void dr_large_kernel(const float4 * __restrict__ cam, const int2 * __restrict__ snap,
+                                                        const int32_t * __restrict__ faces, const float * __restrict__ camera,
+                                                        unsigned long long * __restrict__ keys, const int32_t * __restrict__ queue,
+                                                        const int32_t * __restrict__ qn, float near, int64_t H, int64_t W, int64_t V,
+                                                        int64_t F)
+{
+  const int lane = threadIdx.x & 63;
+  const int count = *qn;
+  const int waves = (int)gridDim.x * (DR_T / 64);
+  for(int e = (int)blockIdx.x * (DR_T / 64) + (int)(threadIdx.x >> 6); e < count; e += waves)
+  {
+    const int64_t idx = queue[e], frame = idx / F, f = idx % F;
+    DrFace t;
+    if(dr_face_setup(t, cam, snap, faces, frame, f, V, H, W) != DR_FACE_OK) continue; // (queued faces are OK)
+    const DrCamera c = dr_camera(camera, frame);
+    unsigned long long * kf = keys + frame * H * W;
+    const int w = t.i1 - t.i0 + 1;
+    const int64_t area = (int64_t)w * (t.j1 - t.j0 + 1);
+    for(int64_t r = lane; r < area; r += 64) dr_pixel(t, c, near, t.i0 + (int)(r % w), t.j0 + (int)(r / w), (unsigned)f, kf, W);
+  }
+}
+
+__global__ __launch_bounds__(DR_T) void dr_resolve_kernel(const float4 * __restrict__ cam, const int32_t * __restrict__ faces,
+                                                          const float * __restrict__ camera,
+                                                          const unsigned long long * __restrict__ keys, int64_t * __restrict__ face,
+                                                          float * __restrict__ depth, float * __restrict__ bary,
+                                                          uint8_t * __restrict__ visible, int64_t H, int64_t W, int64_t V, int64_t np)
+{
+  const int64_t idx = (int64_t)blockIdx.x * DR_T + threadIdx.x;
+  if(idx >= np) return;
+  const unsigned long long key = keys[idx];
+  if(key == DR_EMPTY)
+  {
+    face[idx] = -1;
+    depth[idx] = 0.0f;
+    if(bary) bary[idx * 3] = 0.0f, bary[idx * 3 + 1] = 0.0f, bary[idx * 3 + 2] = 0.0f;
+    return;
+  }
+  const int64_t frame = idx / (H * W), pix = idx % (H * W);
+  const int64_t f = (int64_t)(key & 0xffffffffull);
+  const float z = __uint_as_float((unsigned)(key >> 32));
+  face[idx] = f;
+  depth[idx] = z;
+  const int32_t c0 = faces[f * 3], c1 = faces[f * 3 + 1], c2 = faces[f * 3 + 2];
+  if(visible) visible[frame * V + c0] = 1, visible[frame * V + c1] = 1, visible[frame * V + c2] = 1;
+  if(!bary) return;
+  const DrCamera c = dr_camera(camera, frame);
+  const float4 a = cam[frame * V + c0], b = cam[frame * V + c1], cc = cam[frame * V + c2];
+  DrFace t;
+  t.ax = a.x, t.ay = a.y, t.az = a.z;
+  t.e1[0] = b.x - a.x, t.e1[1] = b.y - a.y, t.e1[2] = b.z - a.z;
+  t.e2[0] = cc.x - a.x, t.e2[1] = cc.y - a.y, t.e2[2] = cc.z - a.z;
+  t.nx = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1];
+  t.ny = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2];
+  t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
+  float dx, dy, ba, bb, bc;
+  dr_ray(c, (int)(pix % W), (int)(pix / W), dx, dy);
+  dr_bary(t, z, dx, dy, ba, bb, bc);
+  bary[idx * 3] = ba, bary[idx * 3 + 1] = bb, bary[idx * 3 + 2] = bc;
+}
+
+__global__ __launch_bounds__(DR_T) void dr_vjp_face_kernel(const float4 * __restrict__ cam, const int2 * __restrict__ snap,
+                                                           const int32_t * __restrict__ faces, const float * __restrict__ camera,
+                                                           const int64_t * __restrict__ face, const float * __restrict__ gd,
+                                                           float * __restrict__ fgrad, int64_t H, int64_t W, int64_t V, int64_t F,
+                                                           int64_t nf)
+{
+  const int64_t tid = (int64_t)blockIdx.x * DR_T + threadIdx.x;
+  const int64_t idx = tid / DR_SPLIT;
+  const int part = (int)(tid % DR_SPLIT);
+  const bool in = idx < nf;
+  const int64_t frame = in ? idx / F : 0, f = in ? idx % F : 0;
+  DrFace t;
+  const bool live = in && dr_face_setup(t, cam, snap, faces, frame, f, V, H, W) == DR_FACE_OK;
+  float s[3] = {0.0f, 0.0f, 0.0f};
+  if(live)
+  {
+    const DrCamera c = dr_camera(camera, frame);
+    const int64_t * ff = face + frame * H * W;
+    const float * gf = gd + frame * H * W;
+    const int w = t.i1 - t.i0 + 1;
+    const int64_t area = (int64_t)w * (t.j1 - t.j0 + 1);
+    for(int64_t r = part; r < area; r += DR_SPLIT)
+    {
+      const int i = t.i0 + (int)(r % w), j = t.j0 + (int)(r / w);
+      const int64_t pix = (int64_t)j * W + i;
+      if(ff[pix] != f) continue;
+      const float g = gf[pix];
+      if(g == 0.0f) continue;
+      float dx, dy, b[3];
+      dr_ray(c, i, j, dx, dy);
+      const float nd = (t.nx * dx + t.ny * dy) + t.nz;
+      const float depth = t.na / nd;
+      dr_bary(t, depth, dx, dy, b[0], b[1], b[2]);
+      const float coef = g / nd;
+      for(int k = 0; k < 3; k++) s[k] = s[k] + b[k] * coef;
+    }
+  }
+  for(int m = DR_SPLIT / 2; m >= 1; m >>= 1)
+    for(int k = 0; k < 3; k++) s[k] = s[k] + __shfl_xor(s[k], m);
+  if(!in || part != 0) return;
+  float * o = fgrad + idx * 9;
+  for(int k = 0; k < 3; k++)
+  {
+    o[3 * k] = live ? s[k] * t.nx : 0.0f;
+    o[3 * k + 1] = live ? s[k] * t.ny : 0.0f;
+    o[3 * k + 2] = live ? s[k] * t.nz : 0.0f;
+  }
+}
+
+__global__ __launch_bounds__(DR_T) void dr_vjp_vertex_kernel(const float * __restrict__ fgrad, const int32_t * __restrict__ faces,
+                                                             const int32_t * __restrict__ adjOff, const int32_t * __restrict__ adjFace,
+                                                             const float * __restrict__ camera, float * __restrict__ gv, int accumulate,
+                                                             int64_t V, int64_t F, int64_t nv)
+{
+  const int64_t idx = (int64_t)blockIdx.x * DR_T + threadIdx.x;
+  if(idx >= nv) return;
+  const int64_t frame = idx / V;
+  const int32_t v = (int32_t)(idx % V);
+  float g[3] = {0.0f, 0.0f, 0.0f};
+  for(int32_t q = adjOff[v]; q < adjOff[v + 1]; q++)
+  {
+    const int64_t f = adjFace[q];
+    for(int k = 0; k < 3; k++)
+      if(faces[f * 3 + k] == v)
+      {
+        const float * p = fgrad + ((frame * F + f) * 3 + k) * 3;
+        for(int x = 0; x < 3; x++) g[x] = g[x] + p[x];
+      }
+  }
+  const float * R = camera + frame * 16;
+  float * o = gv + idx * 3;
+  for(int x = 0; x < 3; x++)
+  {
+    const float w = (R[x] * g[0] + R[3 + x] * g[1]) + R[6 + x] * g[2];
+    o[x] = accumulate ? o[x] + w : w;
+  }
+}
+
+static DepthRasterState * dr_state(smplpp_model * m)
+{
+  if(!m->dr)
+  {
+    m->dr.reset(new DepthRasterState());
+    m->dr->inline_px = m->dr_inline < 0 ? DR_INLINE_DEFAULT : m->dr_inline > DR_INLINE_MAX ? DR_INLINE_MAX : m->dr_inline;
+  }
+  return m->dr.get();
+}
+
+static unsigned dr_grid(int64_t items)
+{
+  return (unsigned)((items + DR_T - 1) / DR_T);
+}
+
+static int dr_vertex_pass(smplpp_model * m, DepthRasterState * s, int64_t n, const float * verts, const float * camera, float near,
+                          hipStream_t st)
+{
+  const int64_t nv = n * m->V;
+  HIP_TRY(s->cam.reserve(sizeof(float4) * (size_t)nv));
+  HIP_TRY(s->snap.reserve(sizeof(int2) * (size_t)nv));
+  dr_vertex_kernel<<<dim3(dr_grid(nv)), dim3(DR_T), 0, st>>>(verts, camera, s->cam.as<float4>(), s->snap.as<int2>(), near, m->V, nv);
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+
+// all pointers on the device
+static int dr_forward_device(smplpp_model * m, DepthRasterState * s, int64_t n, const float * verts, const float * camera, int64_t H,
+                             int64_t W, float near, int64_t * face, float * depth, float * bary, uint8_t * visible, int64_t * culled,
+                             hipStream_t st)
+{
+  const int64_t V = m->V, F = m->F, nf = n * F, np = n * H * W;
+  int rc = dr_vertex_pass(m, s, n, verts, camera, near, st);
+  if(rc) return rc;
+  HIP_TRY(s->keys.reserve(sizeof(unsigned long long) * (size_t)np));
+  HIP_TRY(s->queue.reserve(sizeof(int32_t) * (size_t)nf));
+  HIP_TRY(s->qn.reserve(sizeof(int32_t)));
+  unsigned long long * keys = s->keys.as<unsigned long long>();
+  HIP_TRY(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)np, st));
+  HIP_TRY(hipMemsetAsync(s->qn.as<int32_t>(), 0, sizeof(int32_t), st));
+  if(culled) HIP_TRY(hipMemsetAsync(culled, 0, sizeof(int64_t) * (size_t)n, st));
+  if(visible) HIP_TRY(hipMemsetAsync(visible, 0, (size_t)(n * V), st));
+  dr_face_kernel<<<dim3(dr_grid(nf)), dim3(DR_T), 0, st>>>(s->cam.as<float4>(), s->snap.as<int2>(), m->faces.get(), camera, keys,
+                                                           s->queue.as<int32_t>(), s->qn.as<int32_t>(),
+                                                           reinterpret_cast<unsigned long long *>(culled), near, H, W, V, F, nf,
+                                                           s->inline_px);
+  HIP_TRY(hipGetLastError());
+  const unsigned blocks = (unsigned)std::min<int64_t>(DR_LARGE_BLOCKS, (nf + DR_T / 64 - 1) / (DR_T / 64));
+  dr_large_kernel<<<dim3(blocks), dim3(DR_T), 0, st>>>(s->cam.as<float4>(), s->snap.as<int2>(), m->faces.get(), camera, keys,
+                                                       s->queue.as<int32_t>(), s->qn.as<int32_t>(), near, H, W, V, F);
+  HIP_TRY(hipGetLastError());
+  dr_resolve_kernel<<<dim3(dr_grid(np)), dim3(DR_T), 0, st>>>(s->cam.as<float4>(), m->faces.get(), camera, keys, face, depth, bary,
+                                                              visible, H, W, V, np);
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+
+static int dr_vjp_device(smplpp_model * m, DepthRasterState * s, int64_t n, const float * verts, const float * camera, int64_t H,
+                         int64_t W, const int64_t * face, const float * gd, float * gv, int accumulate, hipStream_t st)
+{
+  const int64_t V = m->V, F = m->F, nf = n * F;
+  // no near plane here: the face image names the faces; a vertex is refused for a non-finite or out-of-band projection only
+  int rc = dr_vertex_pass(m, s, n, verts, camera, -INFINITY, st);
+  if(rc) return rc;
+  HIP_TRY(s->fgrad.reserve(sizeof(float) * 9 * (size_t)nf));
+  dr_vjp_face_kernel<<<dim3(dr_grid(nf * DR_SPLIT)), dim3(DR_T), 0, st>>>(s->cam.as<float4>(), s->snap.as<int2>(), m->faces.get(), camera,
+                                                                          face, gd, s->fgrad.as<float>(), H, W, V, F, nf);
+  HIP_TRY(hipGetLastError());
+  dr_vjp_vertex_kernel<<<dim3(dr_grid(n * V)), dim3(DR_T), 0, st>>>(s->fgrad.as<float>(), m->faces.get(), m->adjOff.get(),
+                                                                    m->adjFace.get(), camera, gv, accumulate, V, F, n * V);
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+} // namespace smplpp_hip
+
+using namespace smplpp_hip;
+
+static int dr_check(const char * fn, smplpp_model * m, int64_t n, int64_t H, int64_t W, int space)
+{
+  if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": the model has no faces");
+  if(H < 1 || W < 1 || H > DR_MAX_SIDE || W > DR_MAX_SIDE) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": H and W must be in [1, 8192]");
+  // every [n,H,W], [n,V] and [n,F] index stays in int32 (and the 8 lanes per face of the backward walk in its grid)
+  if(n > 0x7fffffffLL || n * H * W > 0x7fffffffLL || n * m->V > 0x7fffffffLL || n * m->F > 0x7fffffffLL)
+    return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": n * H * W, n * V or n * F beyond int32 indexing");
+  return check_space(space, fn);
+}
+
+extern "C" int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * verts, const float * camera, int64_t H, int64_t W,
+                                   float near, int64_t * face, float * depth, float * bary, uint8_t * visible, int64_t * culled,
+                                   int space, void * stream)
+{
+  const char * fn = "smplpp_depth_raster";
+  if(!m || n <= 0 || !verts || !camera || !face || !depth) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
+  if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
+  int rc = dr_check(fn, m, n, H, W, space);
+  if(rc) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceRange tr("depth raster");
+  DepthRasterState * s = dr_state(m);
+  In<float> v, c;
+  Out<int64_t> fo, co;
+  Out<float> zo, bo;
+  Out<uint8_t> vo;
+  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
+  HIP_TRY(c.init(camera, (size_t)n * 16, space, st, &s->camera));
+  HIP_TRY(fo.init(face, (size_t)(n * H * W), space, &s->face));
+  HIP_TRY(zo.init(depth, (size_t)(n * H * W), space, &s->depth));
+  HIP_TRY(bo.init(bary, (size_t)(n * H * W * 3), space, &s->bary));
+  HIP_TRY(vo.init(visible, (size_t)(n * m->V), space, &s->visible));
+  HIP_TRY(co.init(culled, (size_t)n, space, &s->culled));
+  rc = dr_forward_device(m, s, n, v.d, c.d, H, W, near, fo.d, zo.d, bo.d, vo.d, co.d, st);
+  if(rc) return rc;
+  HIP_TRY(fo.finish(st));
+  HIP_TRY(zo.finish(st));
+  HIP_TRY(bo.finish(st));
+  HIP_TRY(vo.finish(st));
+  HIP_TRY(co.finish(st));
+  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_depth_raster_vjp(smplpp_model * m, int64_t n, const float * verts, const float * camera, int64_t H, int64_t W,
+                                       const int64_t * face, const float * grad_depth, float * grad_verts, int accumulate, int space,
+                                       void * stream)
+{
+  const char * fn = "smplpp_depth_raster_vjp";
+  if(!m || n <= 0 || !verts || !camera || !face || !grad_depth || !grad_verts)
+    return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
+  if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
+  int rc = dr_check(fn, m, n, H, W, space);
+  if(rc) return rc;
+  if(space == SMPLPP_HOST)
+    for(int64_t i = 0; i < n * H * W; i++)
+      if(face[i] < -1 || face[i] >= m->F) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": face id out of range");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceRange tr("depth raster VJP");
+  DepthRasterState * s = dr_state(m);
+  In<float> v, c, g;
+  In<int64_t> f;
+  Out<float> gv;
+  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
+  HIP_TRY(c.init(camera, (size_t)n * 16, space, st, &s->camera));
+  HIP_TRY(f.init(face, (size_t)(n * H * W), space, st, &s->face));
+  HIP_TRY(g.init(grad_depth, (size_t)(n * H * W), space, st, &s->grad));
+  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
+  if(accumulate) HIP_TRY(gv.load(st));
+  rc = dr_vjp_device(m, s, n, v.d, c.d, H, W, f.d, g.d, gv.d, accumulate, st);
+  if(rc) return rc;
+  HIP_TRY(gv.finish(st));
+  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
+  return SMPLPP_OK;
+}

@@ -363,6 +363,8 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   {
     const char * pd_env = getenv("SMPLPP_POINT_DISTANCE_FORM"); // query | tiled: one form of smplpp_point_mesh_distance for every K
     m->pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
+    const char * dr_env = getenv("SMPLPP_DEPTH_RASTER_INLINE"); // 0..4096: the largest box a face's own thread walks in smplpp_depth_raster
+    m->dr_inline = dr_env && dr_env[0] >= '0' && dr_env[0] <= '9' ? atoi(dr_env) : -1;
   }
   auto uses = [&](char f) { return m->form == f || m->form_ik == f; };
   HIP_TRY(upload(m->Pvm, P, (size_t)V * 3 * NP)); // kept: vertex-major copies serve the sparse IK Jacobian (contiguous 2.5 KB per vertex)

@@ -47,6 +47,29 @@ def _stream():
 SELF_PAIRS_DEFAULT = 32768  # default max_pairs of the self-intersection calls
 
 
+def pinhole_camera(R, t, fx, fy, cx, cy, n=None):
+    """The camera rows smplpp_depth_raster reads, [n,16] float32: R (world -> camera, row-major), t, fx, fy, cx, cy.  The camera looks
+    along +z, x right, y down; pixel (row j, column i) has its centre at (i + 0.5, j + 0.5).  R [3,3] or [n,3,3], t [3] or [n,3],
+    scalars or [n]; one camera is broadcast to n frames."""
+    R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
+    k = n if n is not None else max([1] + [len(a) for a, d in ((R, 3), (t, 2)) if a.ndim == d] +
+                                    [np.size(a) for a in (fx, fy, cx, cy) if np.ndim(a) > 0])
+    cam = np.empty((k, 16), np.float32)
+    cam[:, :9] = R.reshape(-1, 9)
+    cam[:, 9:12] = t.reshape(-1, 3)
+    for j, a in enumerate((fx, fy, cx, cy)):
+        cam[:, 12 + j] = np.asarray(a, np.float64).reshape(-1)
+    return cam
+
+
+def pinhole_camera_rows(camera, n):
+    """camera [16] or [n,16] as contiguous float32 [n,16]."""
+    camera = np.asarray(camera, np.float32)
+    if camera.ndim == 1:
+        camera = np.broadcast_to(camera, (n,) + camera.shape)
+    return np.ascontiguousarray(camera)
+
+
 class _Call:
     """The memory space of one ABI call, decided by its first array argument: numpy arrays are host space (converted to float32; the
     call stages and synchronises), torch tensors device space (CUDA float32 only; enqueued on torch's current stream).  `fail` is
@@ -637,6 +660,70 @@ class SMPL:
             raise SmplppError(1, "self_penetration_differentiable needs torch")
         return _SelfPenetrationFunction.apply(verts, self, float(sigma), max_pairs, check)
 
+    # ---- depth rasteriser (smplpp_depth_raster / smplpp_depth_raster_vjp)
+    def _dr_inputs(self, c, verts, camera, H, W):
+        n = verts.shape[0] if c.dev else len(verts)
+        verts = c.input(verts, (n, self.vertex_num, 3))
+        if c.dev and not _is_torch(camera):
+            camera = torch.from_numpy(pinhole_camera_rows(camera, n)).to(c.device)
+        elif c.dev and camera.dim() == 1:
+            camera = camera.expand(n, 16)
+        elif not c.dev:
+            camera = pinhole_camera_rows(camera, n)
+        camera = c.input(camera, (n, 16))
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            c.refuse("H and W must be >= 1")
+        return n, verts, camera, H, W
+
+    def _depth_raster(self, name, verts, camera, H, W, near, want=("bary", "visible", "culled"), device_only=False):
+        c = _Call(name, verts, device_only=device_only)
+        n, verts, camera, H, W = self._dr_inputs(c, verts, camera, H, W)
+        r = {"face": c.empty((n, H, W), "int64"), "depth": c.empty((n, H, W))}
+        if "bary" in want:
+            r["bary"] = c.empty((n, H, W, 3))
+        if "visible" in want:
+            r["visible"] = c.empty((n, self.vertex_num), "uint8")
+        if "culled" in want:
+            r["culled"] = c.empty((n,), "int64")
+        check(_lib.load().smplpp_depth_raster(self.handle, n, _ptr(verts), _ptr(camera), H, W, float(near), _ptr(r["face"]),
+                                              _ptr(r["depth"]), _ptr(r.get("bary")), _ptr(r.get("visible")), _ptr(r.get("culled")),
+                                              c.space, c.stream))
+        return r
+
+    def depthRaster(self, verts, camera, H, W, near=0.05, want=("bary", "visible", "culled")):
+        """Each frame's posed mesh verts [N,V,3] through a pinhole camera into an H x W image (smplpp_depth_raster): a dict of face
+        [N,H,W] int64 (-1 = background), depth [N,H,W] (camera-space z of the pixel-centre ray's hit, 0 at background), bary [N,H,W,3]
+        (3-D barycentrics of the hit in the face's corners), visible [N,V] uint8 (1 iff the vertex is a corner of a face that owns a
+        pixel) and culled [N] int64 (faces skipped: a corner at or behind `near`, non-finite, or beyond the guard band).  camera
+        [N,16] or [16] as pinhole_camera packs it.  The rule is exact and stated in the C header.  numpy (the call synchronises) or
+        float32 device tensors (torch's current stream); `want` drops optional outputs."""
+        return self._depth_raster("depthRaster", verts, camera, H, W, near, want)
+
+    def depthRasterBackward(self, verts, camera, H, W, face, grad_depth, out=None):
+        """Vector-Jacobian product of depthRaster's depth at the faces it gave (held fixed; coverage is not differentiated):
+        grad_verts [N,V,3] for dL/ddepth = grad_depth [N,H,W] (smplpp_depth_raster_vjp).  A pixel with face -1 or a cotangent of
+        exactly 0 contributes nothing.  With `out` [N,V,3] the gradient is added into it and it is returned."""
+        c = _Call("depthRasterBackward", verts, grad_depth, out)
+        n, verts, camera, H, W = self._dr_inputs(c, verts, camera, H, W)
+        f = c.ids(face)
+        if f.shape[0] != n * H * W:
+            c.refuse("expected face of shape (%d, %d, %d)" % (n, H, W))
+        g = c.input(grad_depth, (n, H, W))
+        acc = out is not None
+        gv = c.inout(out, (n, self.vertex_num, 3)) if acc else c.empty((n, self.vertex_num, 3))
+        check(_lib.load().smplpp_depth_raster_vjp(self.handle, n, _ptr(verts), _ptr(camera), H, W, _ptr(f), _ptr(g), _ptr(gv), int(acc),
+                                                  c.space, c.stream))
+        return gv
+
+    def depth_raster_differentiable(self, verts, camera, H, W, near=0.05):
+        """(depth [N,H,W], face [N,H,W], visible [N,V]) of device vertices verts [N,V,3] (the bits of depthRaster), with depth
+        differentiable in verts through torch.autograd: smplpp_depth_raster forward, smplpp_depth_raster_vjp backward at the same
+        faces, on torch's current stream.  A projective-ICP term is e.g. ((depth - target)[(face >= 0) & (target > 0)] ** 2).sum()."""
+        if torch is None:
+            raise SmplppError(1, "depth_raster_differentiable needs torch")
+        return _DepthRasterFunction.apply(verts, self, camera, int(H), int(W), float(near))
+
     def out(self, index: int, path: str):
         """SMPL::out (src/SMPL.cpp:757-790): Wavefront OBJ of frame `index` (v lines, then 1-based f lines)."""
         verts = self._need("verts")
@@ -771,6 +858,28 @@ if torch is not None:
                 return None, None, None, None, None
             gv = ctx.smpl.selfPenetrationBackward(verts, pairs, count, grad_e.contiguous(), ctx.sigma)
             return gv, None, None, None, None
+
+
+    class _DepthRasterFunction(torch.autograd.Function):
+        """smplpp_depth_raster forward / smplpp_depth_raster_vjp backward (SMPL.depth_raster_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, smpl, camera, H, W, near):
+            verts = verts.detach().contiguous()
+            camera = torch.from_numpy(pinhole_camera_rows(camera, verts.shape[0])).to(verts.device) if not _is_torch(camera) else camera
+            r = smpl._depth_raster("depth_raster_differentiable", verts, camera, H, W, near, want=("visible",), device_only=True)
+            ctx.mark_non_differentiable(r["face"], r["visible"])
+            ctx.smpl, ctx.size = smpl, (H, W)
+            ctx.save_for_backward(verts, camera, r["face"])
+            return r["depth"], r["face"], r["visible"]
+
+        @staticmethod
+        def backward(ctx, grad_depth, _gf, _gv):
+            verts, camera, face = ctx.saved_tensors
+            if grad_depth is None or not ctx.needs_input_grad[0]:
+                return None, None, None, None, None, None
+            gv = ctx.smpl.depthRasterBackward(verts, camera, ctx.size[0], ctx.size[1], face, grad_depth.contiguous())
+            return gv, None, None, None, None, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
