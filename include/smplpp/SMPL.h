@@ -523,6 +523,77 @@ public:
           "SMPL");
     return out;
   }
+  // Exact Euclidean feature transform of binary images mask [N,H,W] (integer tensor, nonzero = set; smplpp_mask_distance_transform):
+  // nearest [N,H,W] kInt64 (the linear index of the nearest set pixel of the frame, the lowest among equal distances; -1 without a
+  // set pixel) and sqdist [N,H,W] kInt64 (px^2).
+  struct MaskDistance
+  {
+    Tensor nearest, sqdist;
+  };
+  MaskDistance maskDistanceTransform(const Tensor & mask) const
+  {
+    const char * what = "Cannot transform the mask!";
+    const std::vector<uint8_t> mk = maskBytes(mask, what);
+    const int64_t n = mask.size(0), H = mask.size(1), W = mask.size(2);
+    MaskDistance r{Tensor({n, H, W}, kInt64), Tensor({n, H, W}, kInt64)};
+    std::vector<int32_t> sq(mk.size());
+    check(smplpp_mask_distance_transform(m_.get(), n, mk.data(), H, W, r.nearest.idata.data(), sq.data(), SMPLPP_HOST, nullptr), "SMPL");
+    for(size_t i = 0; i < sq.size(); i++) r.sqdist.idata[i] = sq[i];
+    return r;
+  }
+  // The silhouette residuals of the last launch's meshes against the target mask [N,H,W] (smplpp_silhouette), at the face image
+  // `face` [N,H,W] depthRaster gave for the same camera and near: vertTarget [N,V] kInt64 and vertSq [N,V] (model -> mask, px^2),
+  // pixSource [N,H,W] kInt64 and pixSq [N,H,W] (mask -> model); -1 and 0 where there is no residual.
+  struct Silhouette
+  {
+    Tensor vertTarget, vertSq, pixSource, pixSq;
+  };
+  Silhouette silhouette(const Tensor & camera, const Tensor & face, const Tensor & mask, float near = 0.05f) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const char * what = "Cannot evaluate the silhouette term!";
+    const std::vector<float> cam = cameraRows(camera, n, what);
+    const std::vector<uint8_t> mk = maskBytes(mask, what);
+    if(face.dim() != 3 || face.size(0) != n || (face.dtype != kInt64 && face.dtype != kInt32) || mask.shape != face.shape)
+      throw Exception("SMPL", what);
+    const int64_t H = face.size(1), W = face.size(2);
+    Silhouette r{Tensor({n, V_}, kInt64), Tensor({n, V_}), Tensor({n, H, W}, kInt64), Tensor({n, H, W})};
+    check(smplpp_silhouette(m_.get(), n, verts_.ptr(), cam.data(), H, W, near, face.idata.data(), mk.data(), r.vertTarget.idata.data(),
+                            r.vertSq.ptr(), r.pixSource.idata.data(), r.pixSq.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
+  // Its backward pass (smplpp_silhouette_vjp) at the correspondences `fwd` and the face image: dL/dverts [N,V,3] for dL/dvertSq =
+  // gradVertSq [N,V] and dL/dpixSq = gradPixSq [N,H,W]; an undefined (default-constructed) cotangent is left out.  `accumulate`
+  // non-null: the product is added into it (and it is returned).
+  Tensor silhouetteBackward(const Tensor & camera, const Tensor & face, const Silhouette & fwd, const Tensor & gradVertSq,
+                            const Tensor & gradPixSq, float near = 0.05f, Tensor * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const char * what = "Cannot back-propagate through the silhouette term!";
+    const std::vector<float> cam = cameraRows(camera, n, what);
+    const bool gv = gradVertSq.defined(), gp = gradPixSq.defined();
+    if(face.dim() != 3 || face.size(0) != n || (face.dtype != kInt64 && face.dtype != kInt32) || (!gv && !gp) ||
+       (gv && (gradVertSq.dtype != kFloat32 || gradVertSq.numel() != n * V_ || fwd.vertTarget.numel() != n * V_)) ||
+       (gp && (gradPixSq.dtype != kFloat32 || gradPixSq.numel() != face.numel() || fwd.pixSource.numel() != face.numel())))
+      throw Exception("SMPL", what);
+    Tensor local;
+    Tensor & out = accumulate ? *accumulate : local;
+    if(accumulate)
+    {
+      if(accumulate->dtype != kFloat32 || accumulate->numel() != n * V_ * 3) throw Exception("SMPL", what);
+    }
+    else
+      out = Tensor({n, V_, 3});
+    check(smplpp_silhouette_vjp(m_.get(), n, verts_.ptr(), cam.data(), face.size(1), face.size(2), near, face.idata.data(),
+                                gv ? fwd.vertTarget.idata.data() : nullptr, gp ? fwd.pixSource.idata.data() : nullptr,
+                                gv ? gradVertSq.ptr() : nullptr, gp ? gradPixSq.ptr() : nullptr, out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST,
+                                nullptr),
+          "SMPL");
+    return out;
+  }
   // The sweep grid of node/node.cpp:1023-1073 for frame `index`: the grid indices (cell position = 0.025 m x index) whose
   // winding number exceeds 0.5 — the keys the reference enters into g_sweepGridList
   std::vector<std::array<int32_t, 3>> calcSweepGrid(int64_t index = 0) const
@@ -560,6 +631,14 @@ public:
   int64_t faceNum() const { return F_; }
 
 private:
+  // an integer mask tensor [N,H,W] as bytes (nonzero = set)
+  static std::vector<uint8_t> maskBytes(const Tensor & mask, const char * what)
+  {
+    if(mask.dim() != 3 || (mask.dtype != kInt64 && mask.dtype != kInt32) || mask.numel() < 1) throw Exception("SMPL", what);
+    std::vector<uint8_t> b(mask.idata.size());
+    for(size_t i = 0; i < b.size(); i++) b[i] = mask.idata[i] != 0;
+    return b;
+  }
   static const Tensor & need(const Tensor & t)
   {
     if(t.data.empty()) throw Exception("LinearBlendSknning", "Failed to get vertices of new pose!"); // LinearBlendSkinning.cpp:413

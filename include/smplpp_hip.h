@@ -335,6 +335,65 @@ int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * verts /*[n,V,
 int smplpp_depth_raster_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H,
                             int64_t W, const int64_t * face /*[n,H,W]*/, const float * grad_depth /*[n,H,W]*/,
                             float * grad_verts /*[n,V,3]*/, int accumulate, int space, void * stream);
+/* Exact Euclidean feature transform of n binary images mask [n,H,W] (a nonzero byte = set), all in integers.  For pixel p = (row j,
+ * column i) and the set pixels q = (j', i') of the same frame, d2(p, q) = (i-i')^2 + (j-j')^2: sqdist[p] is the minimum and
+ * nearest[p] the linear index j' W + i' of the set pixel that attains it; among equal distances the lowest linear index wins (the
+ * minimum of the key d2 << 32 | linear index).  A set pixel names itself with 0; a frame without a set pixel gives nearest = -1 and
+ * sqdist = 0 everywhere.  Either output may be NULL, not both.  The bits do not depend on n, on the frame's position in the batch
+ * or on the memory space.  (Computed separably: each column's nearest set pixel per row, the upper one on a tie, then the minimum
+ * key over a row's columns; a pixel that is not its column's nearest can never tie for the minimum.)
+ *  - SMPLPP_ERR_INVALID: bad arguments, H or W outside [1, 8192], n H W beyond int32 indexing (the outputs are untouched).
+ *  - the handle keeps 2 bytes per (frame, pixel) of workspace, grown to the largest call and shared with smplpp_silhouette. */
+int smplpp_mask_distance_transform(smplpp_model * m, int64_t n, const uint8_t * mask /*[n,H,W]*/, int64_t H, int64_t W,
+                                   int64_t * nearest /*[n,H,W] nullable*/, int32_t * sqdist /*[n,H,W] nullable*/, int space,
+                                   void * stream);
+/* Silhouette residuals of each frame's posed mesh against a target mask [n,H,W] (a nonzero byte = set).  verts, camera, H, W, near as
+ * smplpp_depth_raster; face [n,H,W] is that call's output for the same arguments (coverage is face >= 0).  With T_mask and T_cov
+ * the transform above of the mask and of the coverage, in fp32 with every operation rounded on its own:
+ *  - model -> mask, per vertex (every vertex, seen or hidden, should project into the target): the vertex is projected by the
+ *    rasteriser's vertex rule (same operations, same refusal; the unsnapped u, v).  A refused vertex gives vert_target = -1,
+ *    vert_sq = 0.  Else pixel (i, j) = (floorf(u), floorf(v)), each clamped into the image; if that pixel is set in the mask, or the
+ *    frame's mask is empty: (-1, 0); else t = T_mask.nearest there = j_t W + i_t, r = (u - ((float) i_t + 0.5), v - ((float) j_t +
+ *    0.5)), vert_sq = r.x r.x + r.y r.y, vert_target = t.  Units: px^2.
+ *  - mask -> model, per pixel (the body should cover the target): for a pixel q that is set in the mask and not covered,
+ *    pix_source = s = T_cov.nearest at q and pix_sq = (float) T_cov.sqdist at q; every other pixel, and every pixel of a frame without
+ *    coverage: (-1, 0).
+ *  - vert_target [n,V] int64, vert_sq [n,V], pix_source [n,H,W] int64, pix_sq [n,H,W]: each may be NULL, not all four.  The bits do
+ *    not depend on n, on the frame's position in the batch, on the memory space or on how the work is split.
+ *  - SMPLPP_ERR_INVALID: as smplpp_depth_raster, and a host-space face id outside [-1, F) (the outputs are untouched).  Device data
+ *    is never refused: NaN vertices are refused vertices.
+ *  - the handle keeps 4 bytes per (frame, pixel) of workspace (the two column passes), grown to the largest call. */
+int smplpp_silhouette(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H, int64_t W,
+                      float near, const int64_t * face /*[n,H,W]*/, const uint8_t * mask /*[n,H,W]*/,
+                      int64_t * vert_target /*[n,V] nullable*/, float * vert_sq /*[n,V] nullable*/,
+                      int64_t * pix_source /*[n,H,W] nullable*/, float * pix_sq /*[n,H,W] nullable*/, int space, void * stream);
+/* Vector-Jacobian product of vert_sq and pix_sq above to the world-space vertices at the correspondences the forward chose
+ * (vert_target, pix_source and face held fixed; the mask itself is not read: the correspondences carry what it decided).  With
+ * pull(x, k) = R^T J^T k at the camera-space point x, in fp32: jx = (fx k.x) / x.z, jy = (fy k.y) / x.z, jz = -((jx x.x + jy x.y) /
+ * x.z), world component a = (R[a] jx + R[3+a] jy) + R[6+a] jz:
+ *  - vertex term: vertex v with target t >= 0 and g = grad_vert_sq != 0, not refused by the vertex rule: r as in the forward, its
+ *    term is pull(xc_v, ((2 g) r.x, (2 g) r.y)).
+ *  - pixel term: pixel q with source s >= 0 and g = grad_pix_sq != 0, f = face[s]: the corners of f in camera space, the plane n,
+ *    na, the ray d of pixel s, depth = na / nd and the barycentrics beta of the hit point y = (depth d.x, depth d.y, depth) as the
+ *    rasteriser states them; the function differentiated is |pi(sum_i beta_i x_i) - c_q|^2 with beta, f, s held fixed (pix_sq at
+ *    the point of evaluation, up to the rounding of beta); w = pull(y, ((2 g) (float)(i_s - i_q), (2 g) (float)(j_s - j_q))) and
+ *    corner i of f receives beta_i w (each component one product).
+ *  - each element of grad_verts is one fixed-order sum: the vertex's pixel shares in ascending linear index of q, then corner,
+ *    starting from +0; then its own term is added; then accumulate = 0 stores the sum (untouched vertices get 0), 1 adds it to
+ *    grad_verts.  No floating-point atomics; the bits do not depend on n or on the frame's position in the batch.
+ *  - a cotangent of exactly 0 or an id of -1 contributes nothing, even on NaN data; in device space a target or source outside
+ *    [0, H W), or a source whose face is -1 or outside [0, F), contributes nothing.  grad_vert_sq [n,V] (with vert_target) or
+ *    grad_pix_sq [n,H,W] (with pix_source) may be NULL, not both.  No gradient to camera or mask.
+ *  - SMPLPP_ERR_INVALID: as the forward, accumulate not 0 or 1, a host-space face id outside [-1, F), a host-space vert_target or
+ *    pix_source outside [-1, H W) (the output is untouched).
+ *  - with grad_pix_sq the handle keeps a record workspace of 64 bytes per (frame, pixel) (the live records are compacted per frame
+ *    in pixel order; their count is on the device when the call is enqueued) and 12 bytes per (frame, vertex), grown to the largest
+ *    call and held until the model is destroyed. */
+int smplpp_silhouette_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H,
+                          int64_t W, float near, const int64_t * face /*[n,H,W]*/, const int64_t * vert_target /*[n,V] nullable*/,
+                          const int64_t * pix_source /*[n,H,W] nullable*/, const float * grad_vert_sq /*[n,V] nullable*/,
+                          const float * grad_pix_sq /*[n,H,W] nullable*/, float * grad_verts /*[n,V,3]*/, int accumulate, int space,
+                          void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -84,6 +84,9 @@ def load():
         "smplpp_self_penetration_vjp": [vp, C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_depth_raster": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_depth_raster_vjp": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_mask_distance_transform": [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int, vp],
+        "smplpp_silhouette": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_silhouette_vjp": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],

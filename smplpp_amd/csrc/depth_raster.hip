@@ -23,11 +23,10 @@
 //                       corner i's sum; the lanes' sums meet in a fixed xor tree (4, 2, 1) and lane 0 stores n times each.
 //  dr_vjp_vertex_kernel per (frame, vertex): its faces' vectors in ascending face id (the adjacency of the normals' backward pass),
 //                       then R^T once.  One fixed-order sum per vertex, no floating-point atomics.
-#include "staging.h"
+#include "depth_raster_device.h"
 #include "trace.h"
 
 #include <algorithm>
-#include <cmath>
 
 #pragma clang fp contract(off)
 
@@ -35,9 +34,6 @@ namespace smplpp_hip
 {
 constexpr int DR_T = 256;                   // threads of every kernel here
 constexpr int DR_SPLIT = 8;                 // lanes per face in the backward walk
-constexpr int DR_BAD = INT32_MIN;           // snapped x of a refused vertex
-constexpr float DR_GUARD = 8388608.0f;      // guard band in snapped units (1/256 px): 32768 px; |edge function| < 2^51
-constexpr int64_t DR_MAX_SIDE = 8192;       // largest H or W
 constexpr int DR_INLINE_DEFAULT = 16;       // box pixels a face's own thread walks (SMPLPP_DEPTH_RASTER_INLINE)
 constexpr int DR_INLINE_MAX = 4096;
 constexpr unsigned DR_LARGE_BLOCKS = 2048;  // grid of dr_large_kernel: 8192 wavefronts
@@ -60,20 +56,6 @@ void StateDelete::operator()(DepthRasterState * s) const
   delete s;
 }
 
-struct DrCamera
-{
-  float R[9], t[3], fx, fy, cx, cy;
-};
-__device__ inline DrCamera dr_camera(const float * __restrict__ camera, int64_t frame)
-{
-  DrCamera c;
-  const float * p = camera + frame * 16;
-  for(int k = 0; k < 9; k++) c.R[k] = p[k];
-  for(int k = 0; k < 3; k++) c.t[k] = p[9 + k];
-  c.fx = p[12], c.fy = p[13], c.cx = p[14], c.cy = p[15];
-  return c;
-}
-
 __global__ __launch_bounds__(DR_T) void dr_vertex_kernel(const float * __restrict__ verts, const float * __restrict__ camera,
                                                          float4 * __restrict__ cam, int2 * __restrict__ snap, float near, int64_t V,
                                                          int64_t nv)
@@ -81,27 +63,12 @@ __global__ __launch_bounds__(DR_T) void dr_vertex_kernel(const float * __restric
   const int64_t idx = (int64_t)blockIdx.x * DR_T + threadIdx.x;
   if(idx >= nv) return;
   const DrCamera c = dr_camera(camera, idx / V);
-  const float x = verts[idx * 3], y = verts[idx * 3 + 1], z = verts[idx * 3 + 2];
-  float xc[3];
-  for(int k = 0; k < 3; k++) xc[k] = ((c.R[3 * k] * x + c.R[3 * k + 1] * y) + c.R[3 * k + 2] * z) + c.t[k];
-  const float u = (c.fx * xc[0]) / xc[2] + c.cx;
-  const float v = (c.fy * xc[1]) / xc[2] + c.cy;
-  const float su = rintf(u * 256.0f), sv = rintf(v * 256.0f);
-  const bool ok = fabsf(xc[0]) < INFINITY && fabsf(xc[1]) < INFINITY && fabsf(xc[2]) < INFINITY && xc[2] > near && fabsf(su) <= DR_GUARD &&
-                  fabsf(sv) <= DR_GUARD; // (a NaN fails every comparison)
+  float xc[3], u, v, su, sv;
+  const bool ok = dr_project(c, verts[idx * 3], verts[idx * 3 + 1], verts[idx * 3 + 2], near, xc, u, v, su, sv);
   cam[idx] = make_float4(xc[0], xc[1], xc[2], 0.0f);
   snap[idx] = ok ? make_int2((int)su, (int)sv) : make_int2(DR_BAD, DR_BAD);
 }
 
-// one (frame, face) ready to be walked: snapped corners, the clipped box, the plane
-struct DrFace
-{
-  int64_t x[3], y[3];
-  int sgn;
-  int i0, i1, j0, j1;
-  float ax, ay, az, nx, ny, nz, na;
-  float e1[3], e2[3];
-};
 enum
 {
   DR_FACE_OK = 0,
@@ -138,25 +105,6 @@ __device__ inline int dr_face_setup(DrFace & t, const float4 * __restrict__ cam,
   t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
   t.na = (t.nx * t.ax + t.ny * t.ay) + t.nz * t.az;
   return DR_FACE_OK;
-}
-
-// the pixel-centre ray's x and y (z = 1)
-__device__ inline void dr_ray(const DrCamera & c, int i, int j, float & dx, float & dy)
-{
-  dx = (((float)i + 0.5f) - c.cx) / c.fx;
-  dy = (((float)j + 0.5f) - c.cy) / c.fy;
-}
-
-// barycentrics of p = depth * d in (a, a + e1, a + e2) with normal n
-__device__ inline void dr_bary(const DrFace & t, float depth, float dx, float dy, float & ba, float & bb, float & bc)
-{
-  const float wx = depth * dx - t.ax, wy = depth * dy - t.ay, wz = depth - t.az;
-  const float nn = (t.nx * t.nx + t.ny * t.ny) + t.nz * t.nz;
-  const float px = wy * t.e2[2] - wz * t.e2[1], py = wz * t.e2[0] - wx * t.e2[2], pz = wx * t.e2[1] - wy * t.e2[0]; // w x e2
-  const float qx = t.e1[1] * wz - t.e1[2] * wy, qy = t.e1[2] * wx - t.e1[0] * wz, qz = t.e1[0] * wy - t.e1[1] * wx; // e1 x w
-  bb = ((px * t.nx + py * t.ny) + pz * t.nz) / nn;
-  bc = ((qx * t.nx + qy * t.ny) + qz * t.nz) / nn;
-  ba = (1.0f - bb) - bc;
 }
 
 // coverage of pixel (row j, column i) by the face, its depth, the depth test
@@ -422,16 +370,6 @@ static int dr_vjp_device(smplpp_model * m, DepthRasterState * s, int64_t n, cons
 } // namespace smplpp_hip
 
 using namespace smplpp_hip;
-
-static int dr_check(const char * fn, smplpp_model * m, int64_t n, int64_t H, int64_t W, int space)
-{
-  if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": the model has no faces");
-  if(H < 1 || W < 1 || H > DR_MAX_SIDE || W > DR_MAX_SIDE) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": H and W must be in [1, 8192]");
-  // every [n,H,W], [n,V] and [n,F] index stays in int32 (and the 8 lanes per face of the backward walk in its grid)
-  if(n > 0x7fffffffLL || n * H * W > 0x7fffffffLL || n * m->V > 0x7fffffffLL || n * m->F > 0x7fffffffLL)
-    return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": n * H * W, n * V or n * F beyond int32 indexing");
-  return check_space(space, fn);
-}
 
 extern "C" int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * verts, const float * camera, int64_t H, int64_t W,
                                    float near, int64_t * face, float * depth, float * bary, uint8_t * visible, int64_t * culled,

@@ -724,6 +724,95 @@ class SMPL:
             raise SmplppError(1, "depth_raster_differentiable needs torch")
         return _DepthRasterFunction.apply(verts, self, camera, int(H), int(W), float(near))
 
+    # ---- silhouette term (smplpp_mask_distance_transform / smplpp_silhouette / smplpp_silhouette_vjp)
+    def maskDistanceTransform(self, mask, want=("nearest", "sqdist")):
+        """Exact Euclidean feature transform of binary images mask [N,H,W] (nonzero = set; smplpp_mask_distance_transform): returns
+        (nearest [N,H,W] int64, sqdist [N,H,W] int32): the linear index j' W + i' of the nearest set pixel of the same frame (the lowest
+        index among equal distances) and the squared distance in px^2; a frame without a set pixel gives -1 and 0.  numpy (the call
+        synchronises) or device tensors (torch's current stream); an output missing from `want` is returned as None."""
+        c = _Call("maskDistanceTransform", mask)
+        if len(mask.shape) != 3 or min(mask.shape) < 1:
+            c.refuse("expected a mask of shape (N, H, W)")
+        n, H, W = (int(x) for x in mask.shape)
+        mk = c.flags(mask)
+        nearest = c.empty((n, H, W), "int64") if "nearest" in want else None
+        sqdist = c.empty((n, H, W), "int32") if "sqdist" in want else None
+        check(_lib.load().smplpp_mask_distance_transform(self.handle, n, _ptr(mk), H, W, _ptr(nearest), _ptr(sqdist), c.space, c.stream))
+        return nearest, sqdist
+
+    def _sil_images(self, c, n, H, W, face, mask):
+        f, mk = c.ids(face), c.flags(mask)
+        if f.shape[0] != n * H * W or mk.shape[0] != n * H * W:
+            c.refuse("expected face and mask of shape (%d, %d, %d)" % (n, H, W))
+        return f, mk
+
+    def _silhouette(self, name, verts, camera, H, W, mask, near, face, want, device_only=False):
+        c = _Call(name, verts, device_only=device_only)
+        n, verts, camera, H, W = self._dr_inputs(c, verts, camera, H, W)
+        if face is None:
+            r = {"face": c.empty((n, H, W), "int64"), "depth": c.empty((n, H, W))}
+            check(_lib.load().smplpp_depth_raster(self.handle, n, _ptr(verts), _ptr(camera), H, W, float(near), _ptr(r["face"]),
+                                                  _ptr(r["depth"]), None, None, None, c.space, c.stream))
+            face = r["face"]
+        f, mk = self._sil_images(c, n, H, W, face, mask)
+        shapes = {"vert_target": ((n, self.vertex_num), "int64"), "vert_sq": ((n, self.vertex_num), "float32"),
+                  "pix_source": ((n, H, W), "int64"), "pix_sq": ((n, H, W), "float32")}
+        out = {k: c.empty(*shapes[k]) for k in shapes if k in want}
+        check(_lib.load().smplpp_silhouette(self.handle, n, _ptr(verts), _ptr(camera), H, W, float(near), _ptr(f), _ptr(mk),
+                                            _ptr(out.get("vert_target")), _ptr(out.get("vert_sq")), _ptr(out.get("pix_source")),
+                                            _ptr(out.get("pix_sq")), c.space, c.stream))
+        out["face"] = face
+        return out
+
+    def silhouette(self, verts, camera, H, W, mask, near=0.05, face=None, want=("vert_target", "vert_sq", "pix_source", "pix_sq")):
+        """The two silhouette residual sets of each frame's posed mesh verts [N,V,3] against a target mask [N,H,W] (nonzero = set;
+        smplpp_silhouette): a dict of vert_target [N,V] int64 and vert_sq [N,V] (a vertex that projects outside the mask: the nearest
+        mask pixel's linear index and the squared distance of the projection to its centre, px^2; else -1 and 0), pix_source [N,H,W]
+        int64 and pix_sq [N,H,W] (a mask pixel the body does not cover: the nearest covered pixel and the squared distance; else -1
+        and 0), and `face`, the rasteriser's face image the coverage was read from: the `face` given (depthRaster's output for the
+        same arguments), or a rasterisation the call runs itself.  camera [N,16] or [16] as pinhole_camera packs it.  numpy (the call
+        synchronises) or device tensors (torch's current stream); `want` drops outputs."""
+        return self._silhouette("silhouette", verts, camera, H, W, mask, near, face, want)
+
+    def silhouetteBackward(self, verts, camera, H, W, face, vert_target=None, pix_source=None, grad_vert_sq=None, grad_pix_sq=None,
+                           near=0.05, out=None):
+        """Vector-Jacobian product of silhouette's vert_sq and pix_sq at the correspondences it gave (vert_target, pix_source and face
+        held fixed): grad_verts [N,V,3] for dL/dvert_sq = grad_vert_sq [N,V] and dL/dpix_sq = grad_pix_sq [N,H,W], either of which
+        may be None (smplpp_silhouette_vjp).  A cotangent of exactly 0 or an id of -1 contributes nothing.  With `out` [N,V,3] the
+        gradient is added into it and it is returned.  With grad_pix_sq the model keeps a workspace of N * H * W * 64 bytes."""
+        c = _Call("silhouetteBackward", verts, grad_vert_sq, grad_pix_sq, out)
+        n, verts, camera, H, W = self._dr_inputs(c, verts, camera, H, W)
+        if grad_vert_sq is None and grad_pix_sq is None:
+            c.refuse("grad_vert_sq or grad_pix_sq must be given")
+        if (grad_vert_sq is not None and vert_target is None) or (grad_pix_sq is not None and pix_source is None):
+            c.refuse("a cotangent needs its correspondences (vert_target, pix_source)")
+        f = c.ids(face)
+        if f.shape[0] != n * H * W:
+            c.refuse("expected face of shape (%d, %d, %d)" % (n, H, W))
+        vt = ps = gs = gp = None
+        if grad_vert_sq is not None:
+            vt, gs = c.ids(vert_target), c.input(grad_vert_sq, (n, self.vertex_num))
+            if vt.shape[0] != n * self.vertex_num:
+                c.refuse("expected vert_target of shape (%d, %d)" % (n, self.vertex_num))
+        if grad_pix_sq is not None:
+            ps, gp = c.ids(pix_source), c.input(grad_pix_sq, (n, H, W))
+            if ps.shape[0] != n * H * W:
+                c.refuse("expected pix_source of shape (%d, %d, %d)" % (n, H, W))
+        acc = out is not None
+        gv = c.inout(out, (n, self.vertex_num, 3)) if acc else c.empty((n, self.vertex_num, 3))
+        check(_lib.load().smplpp_silhouette_vjp(self.handle, n, _ptr(verts), _ptr(camera), H, W, float(near), _ptr(f), _ptr(vt), _ptr(ps),
+                                                _ptr(gs), _ptr(gp), _ptr(gv), int(acc), c.space, c.stream))
+        return gv
+
+    def silhouette_differentiable(self, verts, camera, H, W, mask, near=0.05):
+        """(vert_sq [N,V], pix_sq [N,H,W]) of device vertices verts [N,V,3] against the target mask [N,H,W] (the bits of silhouette,
+        which rasterises the frame itself), differentiable in verts through torch.autograd: smplpp_silhouette forward,
+        smplpp_silhouette_vjp backward at the same correspondences, on torch's current stream.  A silhouette term is e.g.
+        vert_sq.mean() + pix_sq.sum() / (pix_sq > 0).sum()."""
+        if torch is None:
+            raise SmplppError(1, "silhouette_differentiable needs torch")
+        return _SilhouetteFunction.apply(verts, self, camera, int(H), int(W), mask, float(near))
+
     def out(self, index: int, path: str):
         """SMPL::out (src/SMPL.cpp:757-790): Wavefront OBJ of frame `index` (v lines, then 1-based f lines)."""
         verts = self._need("verts")
@@ -880,6 +969,32 @@ if torch is not None:
                 return None, None, None, None, None, None
             gv = ctx.smpl.depthRasterBackward(verts, camera, ctx.size[0], ctx.size[1], face, grad_depth.contiguous())
             return gv, None, None, None, None, None
+
+
+    class _SilhouetteFunction(torch.autograd.Function):
+        """smplpp_depth_raster + smplpp_silhouette forward / smplpp_silhouette_vjp backward (SMPL.silhouette_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, smpl, camera, H, W, mask, near):
+            verts = verts.detach().contiguous()
+            camera = torch.from_numpy(pinhole_camera_rows(camera, verts.shape[0])).to(verts.device) if not _is_torch(camera) else camera
+            r = smpl._silhouette("silhouette_differentiable", verts, camera, H, W, mask, near, None,
+                                 ("vert_target", "vert_sq", "pix_source", "pix_sq"), device_only=True)
+            ctx.smpl, ctx.size, ctx.near = smpl, (H, W), near
+            ctx.set_materialize_grads(False)  # an output the loss does not use: None, and its half of the backward is skipped
+            ctx.save_for_backward(verts, camera, r["face"], r["vert_target"], r["pix_source"])
+            return r["vert_sq"], r["pix_sq"]
+
+        @staticmethod
+        def backward(ctx, grad_vert_sq, grad_pix_sq):
+            verts, camera, face, vt, ps = ctx.saved_tensors
+            if (grad_vert_sq is None and grad_pix_sq is None) or not ctx.needs_input_grad[0]:
+                return None, None, None, None, None, None, None
+            gv = ctx.smpl.silhouetteBackward(verts, camera, ctx.size[0], ctx.size[1], face, vt if grad_vert_sq is not None else None,
+                                             ps if grad_pix_sq is not None else None,
+                                             None if grad_vert_sq is None else grad_vert_sq.contiguous(),
+                                             None if grad_pix_sq is None else grad_pix_sq.contiguous(), near=ctx.near)
+            return gv, None, None, None, None, None, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
