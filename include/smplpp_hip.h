@@ -17,6 +17,7 @@
  *  - face ids are 0-based in this ABI (IkTask::faceIdx_ is 0-based; the model FILE is 1-based and is converted at
  *    create time like src/SMPL.cpp:520 does at every use).
  *  - one caller thread per handle (the reference is single-threaded, node/node.cpp:1414).
+ *  - a handle keeps the staging of its largest host-space call (device copies of that call's arguments) until it is destroyed.
  */
 #ifndef SMPLPP_HIP_H
 #define SMPLPP_HIP_H

@@ -215,6 +215,13 @@ struct DevBuf
   }
 };
 
+// The staging slots of a handle's host-space calls (staging.h): slot k holds the k-th staged argument of whichever call is running
+constexpr int ARENA_SLOTS = 8; // the widest calls stage 8 arguments: smplpp_silhouette, smplpp_point_mesh_signed_distance, smplpp_ik_set_tasks
+struct Arena
+{
+  DevBuf slot[ARENA_SLOTS];
+};
+
 struct Workspace
 {
   DevBuf AT;      // [KP][ldA] fp32, K-major A operand (pose coefficients | beta | 1)
@@ -222,8 +229,6 @@ struct Workspace
   DevBuf A2h;     // the same coefficients as fp16x2 pieces in fragment order (skin_h.hip)
   DevBuf G2h;     // relative transforms as fp16x2 pieces, the A operand of the blend MFMAs (skin_h.hip)
   DevBuf Gp;      // [n][24][12] relative transforms, 3x4 row-major
-  DevBuf joints;  // [n][24][3]
-  DevBuf beta, theta, verts, rest, xf44; // staging for host-pointer calls
   int64_t ldA = 0;
 };
 // Per-feature state of a handle, created by the feature's first call on it and owned by the handle
@@ -298,6 +303,7 @@ struct smplpp_model
   bool profiling = false;
   std::vector<hipEvent_t> prof_events; // begin/end pairs around the fused kernel
   smplpp_hip::Workspace ws;
+  smplpp_hip::Arena arena;      // staging of the host-space calls on this model
   smplpp_hip::StatePtr<smplpp_hip::VjpState> vjp; // backward pass (smplpp_fk_vjp): null until its first call on the model
   smplpp_hip::StatePtr<smplpp_hip::NormalsVjpState> nvjp; // backward pass of the normal queries (mesh_vjp.hip): null until its first call
   char pd_form = 0;             // point-to-mesh distance form (SMPLPP_POINT_DISTANCE_FORM, read at model creation): 0 = by K | q | t

@@ -48,7 +48,6 @@ struct DepthRasterState
   DevBuf keys;        // [n][H][W] uint64
   DevBuf queue, qn;   // [n][F] int32 queued (frame, face) items and their count
   DevBuf fgrad;       // [n][F][9] per-face corner vectors of the backward pass
-  DevBuf verts, camera, face, depth, bary, visible, culled, grad, gv; // staging of host-space calls
   int inline_px = DR_INLINE_DEFAULT;
 };
 void StateDelete::operator()(DepthRasterState * s) const
@@ -380,30 +379,16 @@ extern "C" int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * ve
   if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
   int rc = dr_check(fn, m, n, H, W, space);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("depth raster");
+  Frame fr(m->device, &m->arena, space, stream, "depth raster");
   DepthRasterState * s = dr_state(m);
-  In<float> v, c;
-  Out<int64_t> fo, co;
-  Out<float> zo, bo;
-  Out<uint8_t> vo;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(c.init(camera, (size_t)n * 16, space, st, &s->camera));
-  HIP_TRY(fo.init(face, (size_t)(n * H * W), space, &s->face));
-  HIP_TRY(zo.init(depth, (size_t)(n * H * W), space, &s->depth));
-  HIP_TRY(bo.init(bary, (size_t)(n * H * W * 3), space, &s->bary));
-  HIP_TRY(vo.init(visible, (size_t)(n * m->V), space, &s->visible));
-  HIP_TRY(co.init(culled, (size_t)n, space, &s->culled));
-  rc = dr_forward_device(m, s, n, v.d, c.d, H, W, near, fo.d, zo.d, bo.d, vo.d, co.d, st);
-  if(rc) return rc;
-  HIP_TRY(fo.finish(st));
-  HIP_TRY(zo.finish(st));
-  HIP_TRY(bo.finish(st));
-  HIP_TRY(vo.finish(st));
-  HIP_TRY(co.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * c = fr.in(camera, (size_t)n * 16);
+  int64_t * fo = fr.out(face, (size_t)(n * H * W));
+  float * zo = fr.out(depth, (size_t)(n * H * W));
+  float * bo = fr.out(bary, (size_t)(n * H * W * 3));
+  uint8_t * vo = fr.out(visible, (size_t)(n * m->V));
+  int64_t * co = fr.out(culled, (size_t)n);
+  return fr.run([&] { return dr_forward_device(m, s, n, v, c, H, W, near, fo, zo, bo, vo, co, fr.st); });
 }
 
 extern "C" int smplpp_depth_raster_vjp(smplpp_model * m, int64_t n, const float * verts, const float * camera, int64_t H, int64_t W,
@@ -416,25 +401,13 @@ extern "C" int smplpp_depth_raster_vjp(smplpp_model * m, int64_t n, const float 
   if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
   int rc = dr_check(fn, m, n, H, W, space);
   if(rc) return rc;
-  if(space == SMPLPP_HOST)
-    for(int64_t i = 0; i < n * H * W; i++)
-      if(face[i] < -1 || face[i] >= m->F) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": face id out of range");
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("depth raster VJP");
+  if(space == SMPLPP_HOST && (rc = ids_in(fn, "face id", face, n * H * W, -1, m->F))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "depth raster VJP");
   DepthRasterState * s = dr_state(m);
-  In<float> v, c, g;
-  In<int64_t> f;
-  Out<float> gv;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(c.init(camera, (size_t)n * 16, space, st, &s->camera));
-  HIP_TRY(f.init(face, (size_t)(n * H * W), space, st, &s->face));
-  HIP_TRY(g.init(grad_depth, (size_t)(n * H * W), space, st, &s->grad));
-  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
-  if(accumulate) HIP_TRY(gv.load(st));
-  rc = dr_vjp_device(m, s, n, v.d, c.d, H, W, f.d, g.d, gv.d, accumulate, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * c = fr.in(camera, (size_t)n * 16);
+  const int64_t * f = fr.in(face, (size_t)(n * H * W));
+  const float * g = fr.in(grad_depth, (size_t)(n * H * W));
+  float * gv = fr.out(grad_verts, (size_t)n * m->V * 3, accumulate);
+  return fr.run([&] { return dr_vjp_device(m, s, n, v, c, H, W, f, g, gv, accumulate, fr.st); });
 }

@@ -5,10 +5,11 @@
 // and each thread adds its shares in ascending record, then key: one fixed-order sum per target, no floating-point atomics.  An add
 // may be branch-free: +0 added for another target's share leaves acc's bits (acc starts at +0; a sum is -0 only if both terms are).
 // A record type supplies its LDS image Tile and touches(head, lo, hi), stage(tile, pos, head, rec), add(acc, tile, h, u).  With
-// `nvalid` (device, [n]) a frame's records past nvalid[frame] are not read.
+// `nvalid` (device, [n]) a frame's records past nvalid[frame] are not read.  distance_vjp() is the host side the VJP entries of
+// the scan distances share; it runs on its caller's call frame (staging.h), so an entry point that stages an argument of its own
+// first (the signed distance's `inside`) still has one frame, and one run of arena slots, for the whole call.
 #pragma once
 #include "staging.h"
-#include "trace.h"
 
 namespace smplpp_hip
 {
@@ -80,41 +81,19 @@ int record_gather(const Rec * rec, float * out, int accumulate, int64_t n, int64
   return SMPLPP_OK;
 }
 
-// The staging buffers of a distance VJP's host-space calls (the forward reuses verts, points and ids)
-struct DistanceStaging
-{
-  DevBuf verts, points, ids, gsq, gv, gp;
-};
-
-// The host side of both VJP entries after their own checks: the arguments staged (through s->io in host space), the outputs loaded
+// The host side of both VJP entries after their own checks, on the entry point's frame: the arguments staged, the outputs loaded
 // when the call adds into them, device() on device pointers, the outputs copied back.  ids and gsq hold nids entries.
 template<class State, class Device>
-int distance_vjp(const Device & device, smplpp_model * m, State * s, const char * trace, int64_t n, const float * verts, int64_t K,
+int distance_vjp(Frame & fr, const Device & device, smplpp_model * m, State * s, int64_t n, const float * verts, int64_t K,
                  const float * points, const int64_t * ids, int64_t nids, const float * grad_sqdist, float * grad_verts,
-                 float * grad_points, int accumulate, int space, void * stream)
+                 float * grad_points, int accumulate)
 {
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr(trace);
-  In<float> v, p, g;
-  In<int64_t> id;
-  Out<float> gv, gp;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->io.verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->io.points));
-  HIP_TRY(id.init(ids, (size_t)nids, space, st, &s->io.ids));
-  HIP_TRY(g.init(grad_sqdist, (size_t)nids, space, st, &s->io.gsq));
-  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->io.gv));
-  HIP_TRY(gp.init(grad_points, (size_t)n * K * 3, space, &s->io.gp));
-  if(accumulate)
-  {
-    HIP_TRY(gv.load(st));
-    HIP_TRY(gp.load(st));
-  }
-  const int rc = device(m, s, n, v.d, K, p.d, id.d, g.d, gv.d, gp.d, accumulate, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  HIP_TRY(gp.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  const int64_t * id = fr.in(ids, (size_t)nids);
+  const float * g = fr.in(grad_sqdist, (size_t)nids);
+  float * gv = fr.out(grad_verts, (size_t)n * m->V * 3, accumulate);
+  float * gp = fr.out(grad_points, (size_t)n * K * 3, accumulate);
+  return fr.run([&] { return device(m, s, n, v, K, p, id, g, gv, gp, accumulate, fr.st); });
 }
 } // namespace smplpp_hip

@@ -447,33 +447,26 @@ extern "C" int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const 
   if(!m) return fail(SMPLPP_ERR_INVALID, "Cannot launch a SMPL model!"); // src/SMPL.cpp:676
   if(n <= 0 || !beta || !theta) return fail(SMPLPP_ERR_INVALID, "Cannot launch a SMPL model!");
   if(int rc = check_space(space, "smplpp_fk")) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr_fwd("forward SMPL"); // the reference's span around SMPL::launch (node/node.cpp:752-781)
-  if(space == SMPLPP_DEVICE) return fk_device(m, n, beta, theta, verts, joints, xforms, rest, nullptr, st, RANGE_DEVICE, nullptr);
+  Frame fr(m->device, &m->arena, space, stream, "forward SMPL"); // the reference's span around SMPL::launch (node/node.cpp:752-781)
+  if(space == SMPLPP_DEVICE)
+    return fr.run([&] { return fk_device(m, n, beta, theta, verts, joints, xforms, rest, nullptr, fr.st, RANGE_DEVICE, nullptr); });
 
-  Workspace & ws = m->ws;
   const size_t nv = (size_t)n * m->V * 3;
-  In<float> b, t;
-  Out<float> v, j, x, r;
-  HIP_TRY(b.init(beta, (size_t)n * NB, space, st, &ws.beta));
-  HIP_TRY(t.init(theta, (size_t)n * (NJ + 1) * 3, space, st, &ws.theta));
-  HIP_TRY(v.init(verts, nv, space, &ws.verts));
-  HIP_TRY(r.init(rest, nv, space, &ws.rest));
-  HIP_TRY(j.init(joints, (size_t)n * NJ * 3, space, &ws.joints));
-  HIP_TRY(x.init(xforms, (size_t)n * NJ * 16, space, &ws.xf44));
+  const float * b = fr.in(beta, (size_t)n * NB);
+  const float * t = fr.in(theta, (size_t)n * (NJ + 1) * 3);
+  float * v = fr.out(verts, nv);
+  float * r = fr.out(rest, nv);
+  float * j = fr.out(joints, (size_t)n * NJ * 3);
+  float * x = fr.out(xforms, (size_t)n * NJ * 16);
   // this call's own range word: cleared in front of the launch, read back on the launch stream beside the results
   const bool ranged = m->range_flag && m->form == 'h';
-  if(ranged) HIP_TRY(hipMemsetAsync(m->range_flag.get() + RANGE_HOST, 0, sizeof(int), st));
-  int rc = fk_device(m, n, b.d, t.d, v.d, j.d, x.d, r.d, nullptr, st, RANGE_HOST, nullptr);
+  int rc = fr.run([&]() -> int {
+    if(ranged) HIP_TRY(hipMemsetAsync(m->range_flag.get() + RANGE_HOST, 0, sizeof(int), fr.st));
+    return fk_device(m, n, b, t, v, j, x, r, nullptr, fr.st, RANGE_HOST, nullptr);
+  });
   if(rc) return rc;
-  HIP_TRY(v.finish(st));
-  HIP_TRY(r.finish(st));
-  HIP_TRY(j.finish(st));
-  HIP_TRY(x.finish(st));
-  HIP_TRY(hipStreamSynchronize(st));
-  // (read AFTER the synchronisation, synchronously: an asynchronous copy into this frame's stack could still be pending when one of
-  // the copies above fails and the function returns)
+  // (read AFTER the synchronisation, synchronously: an asynchronous copy into this function's stack could still be pending when one
+  // of the copies back fails and the function returns)
   int bits = 0;
   if(ranged) HIP_TRY(hipMemcpy(&bits, m->range_flag.get() + RANGE_HOST, sizeof(int), hipMemcpyDeviceToHost));
   if(bits & 1)

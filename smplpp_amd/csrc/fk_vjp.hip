@@ -54,8 +54,8 @@ struct VjpState
   DevPtr<float> BT;     // operand image (above)
   Workspace fws;        // the forward's workspace while smplpp_fk_vjp recomputes `rest` (smplpp_fk's own stays untouched)
   DevPtr<int> range_word; // where that recomputation reports an fp16x2 range miss (not smplpp_fk's words)
-  DevBuf Gp, joints, rot, slab, rest;
-  DevBuf beta, theta, gv, gj, gbeta, gtheta; // staging for host-space calls
+  DevBuf Gp, joints, rot, slab;
+  DevBuf rest;          // the rest shape recomputed when the caller passes none
 };
 
 void StateDelete::operator()(VjpState * s) const
@@ -486,9 +486,8 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
   if(n <= 0 || !beta || !theta) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: needs n > 0, beta and theta");
   if(int rc = check_space(space, "smplpp_fk_vjp")) return rc;
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: too many frames");
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("backward SMPL");
+  Frame fr(m->device, &m->arena, space, stream, "backward SMPL");
+  if(!fr.ok()) return fr.finish();
   if(!m->vjp)
   {
     StatePtr<VjpState> s(new VjpState());
@@ -497,23 +496,16 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
     m->vjp = std::move(s);
   }
   if(!grad_beta && !grad_theta) return SMPLPP_OK;
-  if(space == SMPLPP_DEVICE) return vjp_device(m, n, beta, theta, rest, grad_verts, grad_joints, grad_beta, grad_theta, st);
+  if(space == SMPLPP_DEVICE)
+    return fr.run([&] { return vjp_device(m, n, beta, theta, rest, grad_verts, grad_joints, grad_beta, grad_theta, fr.st); });
 
-  VjpState * s = m->vjp.get();
   const size_t nb = (size_t)n * NB, nt = (size_t)n * (NJ + 1) * 3, nv = (size_t)n * m->V * 3;
-  In<float> b, t, r, gv, gj;
-  Out<float> gb, gt;
-  HIP_TRY(b.init(beta, nb, space, st, &s->beta));
-  HIP_TRY(t.init(theta, nt, space, st, &s->theta));
-  if(grad_verts) HIP_TRY(r.init(rest, nv, space, st, &s->rest));
-  HIP_TRY(gv.init(grad_verts, nv, space, st, &s->gv));
-  HIP_TRY(gj.init(grad_joints, (size_t)n * NJ * 3, space, st, &s->gj));
-  HIP_TRY(gb.init(grad_beta, nb, space, &s->gbeta));
-  HIP_TRY(gt.init(grad_theta, nt, space, &s->gtheta));
-  int rc = vjp_device(m, n, b.d, t.d, r.d, gv.d, gj.d, gb.d, gt.d, st);
-  if(rc) return rc;
-  HIP_TRY(gb.finish(st));
-  HIP_TRY(gt.finish(st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * b = fr.in(beta, nb);
+  const float * t = fr.in(theta, nt);
+  const float * r = grad_verts ? fr.in(rest, nv) : nullptr;
+  const float * gv = fr.in(grad_verts, nv);
+  const float * gj = fr.in(grad_joints, (size_t)n * NJ * 3);
+  float * gb = fr.out(grad_beta, nb);
+  float * gt = fr.out(grad_theta, nt);
+  return fr.run([&] { return vjp_device(m, n, b, t, r, gv, gj, gb, gt, fr.st); });
 }

@@ -86,6 +86,7 @@ struct smplpp_ik
   int scan_form = -1; // development switch SMPLPP_SCAN_FORM (read at creation): 0 forces the K > 8 instantiations of the face scan
   float * vbuf[2] = {nullptr, nullptr};
   int vcur = 0;
+  Arena arena; // staging of the host-space calls on this solver (its own: the model is another handle, maybe another thread's)
   ~smplpp_ik()
   {
     (void)hipSetDevice(m->device);
@@ -314,12 +315,12 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
 
 // copy caller array -> solver array with optional conversion
 template<class Src, class Dst, class Conv>
-static int set_array(const Src * src, Dst * dst, size_t count, int space, Conv conv)
+static int set_array(Frame & fr, const Src * src, Dst * dst, size_t count, Conv conv)
 {
   if(!src) return SMPLPP_OK;
-  In<Src> in;
-  HIP_TRY(in.init(src, count, space, nullptr));
-  conv(in.d, dst, (int64_t)count);
+  const Src * d = fr.in(src, count);
+  if(!d) return fr.finish(); // (the staging failed)
+  conv(d, dst, (int64_t)count);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   return SMPLPP_OK;
@@ -332,11 +333,10 @@ extern "C" int smplpp_ik_set_tasks(smplpp_ik * s, const int64_t * face_idx, cons
   if(!s) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_tasks: null solver");
   int rc = check_space(space, "smplpp_ik_set_tasks");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
   const size_t nk = (size_t)s->n * s->K;
-  if(face_idx && space == SMPLPP_HOST)
-    for(size_t i = 0; i < nk; i++)
-      if(face_idx[i] < 0 || face_idx[i] >= s->m->F) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_tasks: face index out of range");
+  if(face_idx && space == SMPLPP_HOST && (rc = ids_in("smplpp_ik_set_tasks", "face index", face_idx, (int64_t)nk, 0, s->m->F))) return rc;
+  static_assert(ARENA_SLOTS >= 8, "smplpp_ik_set_tasks stages one slot per array given: up to 8");
+  Frame fr(s->m->device, &s->arena, space, nullptr, nullptr);
   auto g = [](int64_t c) { return dim3((unsigned)((c + 255) / 256)); };
   auto cpf = [](const float * a, float * b, int64_t c) { (void)hipMemcpy(b, a, sizeof(float) * c, hipMemcpyDeviceToDevice); };
   auto cvd = [&](const double * a, float * b, int64_t c) { f64_to_f32_kernel<<<g(c), 256>>>(a, b, c); };
@@ -348,14 +348,14 @@ extern "C" int smplpp_ik_set_tasks(smplpp_ik * s, const int64_t * face_idx, cons
     clear_bits_kernel<<<g((int64_t)s->n), 256>>>(s->sticky, 4, (int64_t)s->n);
     HIP_TRY(hipGetLastError());
   }
-  if((rc = set_array(face_idx, s->ta.face, nk, space, cvi))) return rc;
-  if((rc = set_array(vertex_weights, s->ta.vw, nk * 3, space, cpf))) return rc;
-  if((rc = set_array(target_pos, s->ta.tpos, nk * 3, space, cpf))) return rc;
-  if((rc = set_array(target_normal, s->ta.tnrm, nk * 3, space, cpf))) return rc;
-  if((rc = set_array(pos_task_weight, s->ta.posw, nk, space, cvd))) return rc;
-  if((rc = set_array(normal_task_weight, s->ta.nrmw, nk, space, cvd))) return rc;
-  if((rc = set_array(phi_limit, s->ta.philim, nk, space, cvd))) return rc;
-  if((rc = set_array(normal_offset, s->ta.noff, nk, space, cvd))) return rc;
+  if((rc = set_array(fr, face_idx, s->ta.face, nk, cvi))) return rc;
+  if((rc = set_array(fr, vertex_weights, s->ta.vw, nk * 3, cpf))) return rc;
+  if((rc = set_array(fr, target_pos, s->ta.tpos, nk * 3, cpf))) return rc;
+  if((rc = set_array(fr, target_normal, s->ta.tnrm, nk * 3, cpf))) return rc;
+  if((rc = set_array(fr, pos_task_weight, s->ta.posw, nk, cvd))) return rc;
+  if((rc = set_array(fr, normal_task_weight, s->ta.nrmw, nk, cvd))) return rc;
+  if((rc = set_array(fr, phi_limit, s->ta.philim, nk, cvd))) return rc;
+  if((rc = set_array(fr, normal_offset, s->ta.noff, nk, cvd))) return rc;
   if(phi_limit)
   {
     std::vector<float> h(nk);
@@ -364,7 +364,7 @@ extern "C" int smplpp_ik_set_tasks(smplpp_ik * s, const int64_t * face_idx, cons
     for(size_t i = 0; i < nk && locked; i++) locked = !(h[i] > 0.0f);
     s->phi_locked = locked;
   }
-  return SMPLPP_OK;
+  return fr.finish();
 }
 
 extern "C" int smplpp_ik_set_config(smplpp_ik * s, const float * beta, const float * theta, int space)
@@ -409,19 +409,18 @@ extern "C" int smplpp_ik_get_tasks(smplpp_ik * s, int64_t * face_idx, float * ve
   if(!s) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_get_tasks: null solver");
   int rc = check_space(space, "smplpp_ik_get_tasks");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
+  Frame fr(s->m->device, &s->arena, space, nullptr, nullptr);
   HIP_TRY(hipDeviceSynchronize());
   const size_t nk = (size_t)s->n * s->K;
   hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if(face_idx)
-  {
-    Out<int64_t> o;
-    HIP_TRY(o.init(face_idx, nk, space));
-    i32_to_i64_kernel<<<dim3((unsigned)((nk + 255) / 256)), 256>>>(s->ta.face, o.d, (int64_t)nk);
+  int64_t * fo = fr.out(face_idx, nk);
+  rc = fr.run([&]() -> int { // (the frame ends here: the face indices are back before the copies below)
+    if(fo) i32_to_i64_kernel<<<dim3((unsigned)((nk + 255) / 256)), 256>>>(s->ta.face, fo, (int64_t)nk);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(o.finish(nullptr));
-    HIP_TRY(hipDeviceSynchronize());
-  }
+    return SMPLPP_OK;
+  });
+  if(rc) return rc;
+  if(face_idx) HIP_TRY(hipDeviceSynchronize());
   if(vertex_weights) HIP_TRY(hipMemcpy(vertex_weights, s->ta.vw, sizeof(float) * nk * 3, kind));
   if(tangents) HIP_TRY(hipMemcpy(tangents, s->ta.tang, sizeof(float) * nk * 6, kind));
   if(actual_pos) HIP_TRY(hipMemcpy(actual_pos, s->ta.apos, sizeof(float) * nk * 3, kind));
@@ -817,55 +816,53 @@ static int ik_solve_sequence_impl(smplpp_ik * s, int64_t T, const float * target
     return fail(SMPLPP_ERR_INVALID, "smplpp_ik_solve_sequence: bad argument");
   int rc = check_space(space, "smplpp_ik_solve_sequence");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Frame fr(s->m->device, &s->arena, space, stream, nullptr);
+  hipStream_t st = fr.st;
   const int64_t nk = s->n * s->K, ntheta = s->n * s->theta_dim;
   const int64_t tk = shared ? s->K : nk; // targets per frame of the sequence as the caller holds them
-  In<float> tp;
-  In<uint8_t> vl;
-  Out<float> th;
-  HIP_TRY(tp.init(target_pos, (size_t)(T * tk * 3), space, st));
-  HIP_TRY(vl.init(valid, (size_t)(T * tk), space, st));
-  HIP_TRY(th.init(theta_out, (size_t)(T * ntheta), space));
-  HIP_TRY(hipMemsetAsync(s->sticky, 0, sizeof(int) * s->n, st));
-  const int64_t cnt = nk > ntheta ? nk : ntheta;
-  const dim3 grid((unsigned)((cnt + 255) / 256));
-  // frame 0's targets go in here; every later switch and every frame's record ride on the iterations themselves (SeqHook): no
-  // kernel of its own between one frame's solve and the next frame's pose step
-  ik_seq_frame_kernel<<<grid, 256, 0, st>>>(tp.d, vl.d, s->ta.tpos, s->ta.posw, nk, nullptr, nullptr, 0, shared ? s->K : 0);
-  HIP_TRY(hipGetLastError());
-  const auto enq_t0 = std::chrono::steady_clock::now();
-  for(int64_t t = 0; t < T; t++)
-  {
-    const int iters = t == 0 ? warmup_iters : iters_per_frame;
-    SeqHook hook;
-    hook.theta_record = th.d + t * ntheta;
-    if(t + 1 < T)
+  const float * tp = fr.in(target_pos, (size_t)(T * tk * 3));
+  const uint8_t * vl = fr.in(valid, (size_t)(T * tk));
+  float * th = fr.out(theta_out, (size_t)(T * ntheta));
+  rc = fr.run([&]() -> int {
+    HIP_TRY(hipMemsetAsync(s->sticky, 0, sizeof(int) * s->n, st));
+    const int64_t cnt = nk > ntheta ? nk : ntheta;
+    const dim3 grid((unsigned)((cnt + 255) / 256));
+    // frame 0's targets go in here; every later switch and every frame's record ride on the iterations themselves (SeqHook): no
+    // kernel of its own between one frame's solve and the next frame's pose step
+    ik_seq_frame_kernel<<<grid, 256, 0, st>>>(tp, vl, s->ta.tpos, s->ta.posw, nk, nullptr, nullptr, 0, shared ? s->K : 0);
+    HIP_TRY(hipGetLastError());
+    const auto enq_t0 = std::chrono::steady_clock::now();
+    int rc = SMPLPP_OK;
+    for(int64_t t = 0; t < T; t++)
     {
-      hook.next_tpos = tp.d + (t + 1) * tk * 3;
-      hook.next_valid = vl.d + (t + 1) * tk;
-      hook.shared = shared ? 1 : 0;
+      const int iters = t == 0 ? warmup_iters : iters_per_frame;
+      SeqHook hook;
+      hook.theta_record = th + t * ntheta;
+      if(t + 1 < T)
+      {
+        hook.next_tpos = tp + (t + 1) * tk * 3;
+        hook.next_valid = vl + (t + 1) * tk;
+        hook.shared = shared ? 1 : 0;
+      }
+      if(iters > 0)
+        rc = ik_iterate_enqueue(s, iters, enable_qp, -1, min_valid, st, &hook, /*more_follows=*/t + 1 < T && iters_per_frame > 0);
+      else // (no iteration to carry the hook)
+      {
+        ik_seq_frame_kernel<<<grid, 256, 0, st>>>(hook.next_tpos, hook.next_valid, s->ta.tpos, s->ta.posw, nk, s->theta, hook.theta_record,
+                                                  ntheta, shared ? s->K : 0);
+        HIP_TRY(hipGetLastError());
+      }
+      if(rc) break;
     }
-    if(iters > 0)
-      rc = ik_iterate_enqueue(s, iters, enable_qp, -1, min_valid, st, &hook, /*more_follows=*/t + 1 < T && iters_per_frame > 0);
-    else // (no iteration to carry the hook)
-    {
-      ik_seq_frame_kernel<<<grid, 256, 0, st>>>(hook.next_tpos, hook.next_valid, s->ta.tpos, s->ta.posw, nk, s->theta, hook.theta_record, ntheta,
-                                                shared ? s->K : 0);
-      HIP_TRY(hipGetLastError());
-    }
-    if(rc) break;
-  }
-  const int jrc = ik_join(s, st);
-  // (development figure, smplpp_debug_ik_enqueue_us: what the HOST spent handing the T frames' launches to the two streams — when
-  // it approaches the frames' time on the GPU, the chains wait for the host)
-  s->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - enq_t0).count();
+    const int jrc = ik_join(s, st);
+    // (development figure, smplpp_debug_ik_enqueue_us: what the HOST spent handing the T frames' launches to the two streams — when
+    // it approaches the frames' time on the GPU, the chains wait for the host)
+    s->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - enq_t0).count();
+    return rc ? rc : jrc;
+  });
   if(rc) return rc;
-  if(jrc) return jrc;
-  HIP_TRY(th.finish(st));
   if(space == SMPLPP_HOST)
   {
-    HIP_TRY(hipStreamSynchronize(st));
     if((rc = ik_check_valence(s))) return rc;
     if((rc = ik_check_status(s, s->sticky))) return rc;
   }

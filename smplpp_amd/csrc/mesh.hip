@@ -164,28 +164,21 @@ static int normals_common(smplpp_model * m, int64_t n, const float * verts, int6
   if(!m || n <= 0 || count <= 0 || !verts || !ids || !normals) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
   int rc = check_space(space, fn);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
   // ids are validated on the host when they are host memory
-  if(space == SMPLPP_HOST)
-    for(int64_t i = 0; i < count; i++)
-      if(ids[i] < 0 || ids[i] >= (vertex ? m->V : m->F)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": id out of range");
-  In<float> v;
-  In<int64_t> id;
-  Out<float> o;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st));
-  HIP_TRY(id.init(ids, (size_t)count, space, st));
-  HIP_TRY(o.init(normals, (size_t)n * count * 3, space));
-  unsigned grid = (unsigned)((n * count + 127) / 128);
-  if(vertex)
-    vertex_normals_kernel<<<dim3(grid), dim3(128), 0, st>>>(v.d, m->faces.get(), m->adjOff.get(), m->adjFace.get(), id.d, o.d, m->V, count, n);
-  else
-    face_normals_kernel<<<dim3(grid), dim3(128), 0, st>>>(v.d, m->faces.get(), id.d, o.d, m->V, count, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = o.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  if(space == SMPLPP_HOST && (rc = ids_in(fn, "id", ids, count, 0, vertex ? m->V : m->F))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, nullptr);
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const int64_t * id = fr.in(ids, (size_t)count);
+  float * o = fr.out(normals, (size_t)n * count * 3);
+  return fr.run([&]() -> int {
+    unsigned grid = (unsigned)((n * count + 127) / 128);
+    if(vertex)
+      vertex_normals_kernel<<<dim3(grid), dim3(128), 0, fr.st>>>(v, m->faces.get(), m->adjOff.get(), m->adjFace.get(), id, o, m->V, count, n);
+    else
+      face_normals_kernel<<<dim3(grid), dim3(128), 0, fr.st>>>(v, m->faces.get(), id, o, m->V, count, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }
 
 extern "C" int smplpp_face_normals(smplpp_model * m, int64_t n, const float * verts, int64_t count, const int64_t * face_ids,
@@ -207,24 +200,13 @@ extern "C" int smplpp_closest_points(smplpp_model * m, int64_t n, const float * 
   if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, "smplpp_closest_points: model has no faces");
   int rc = check_space(space, "smplpp_closest_points");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> v, p;
-  Out<int64_t> fo;
-  Out<float> co, so;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st));
-  HIP_TRY(fo.init(face, (size_t)n * K, space));
-  HIP_TRY(co.init(closest, (size_t)n * K * 3, space));
-  HIP_TRY(so.init(sqdist, (size_t)n * K, space));
-  rc = closest_points_device(m, n, v.d, K, p.d, fo.d, co.d, so.d, st);
-  if(rc) return rc;
-  hipError_t e = fo.finish(st);
-  if(e == hipSuccess) e = co.finish(st);
-  if(e == hipSuccess) e = so.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(m->device, &m->arena, space, stream, nullptr);
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  int64_t * fo = fr.out(face, (size_t)n * K);
+  float * co = fr.out(closest, (size_t)n * K * 3);
+  float * so = fr.out(sqdist, (size_t)n * K);
+  return fr.run([&] { return closest_points_device(m, n, v, K, p, fo, co, so, fr.st); });
 }
 
 // SMPL::calcVertexNormal (src/SMPL.cpp:527-535) for every vertex of every frame: normals [n,V,3]
@@ -234,19 +216,15 @@ extern "C" int smplpp_mesh_vertex_normals(smplpp_model * m, int64_t n, const flo
   if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, "smplpp_mesh_vertex_normals: model has no faces");
   int rc = check_space(space, "smplpp_mesh_vertex_normals");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> v;
-  Out<float> o;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st));
-  HIP_TRY(o.init(normals, (size_t)n * m->V * 3, space));
-  mesh_vertex_normals_kernel<<<dim3((unsigned)((n * m->V + 255) / 256)), dim3(256), 0, st>>>(v.d, m->faces.get(), m->adjOff.get(), m->adjFace.get(),
-                                                                                            o.d, m->V, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = o.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(m->device, &m->arena, space, stream, nullptr);
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  float * o = fr.out(normals, (size_t)n * m->V * 3);
+  return fr.run([&]() -> int {
+    mesh_vertex_normals_kernel<<<dim3((unsigned)((n * m->V + 255) / 256)), dim3(256), 0, fr.st>>>(v, m->faces.get(), m->adjOff.get(),
+                                                                                                 m->adjFace.get(), o, m->V, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }
 
 // The sweep grid of node/node.cpp:1023-1073 for one frame of posed vertices: grid cells of GRID_SCALE = 2.5 cm
@@ -259,19 +237,16 @@ extern "C" int smplpp_sweep_grid(smplpp_model * m, const float * verts, int32_t 
   if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, "smplpp_sweep_grid: model has no faces");
   int rc = check_space(space, "smplpp_sweep_grid");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> v;
-  HIP_TRY(v.init(verts, (size_t)m->V * 3, space, st));
-  DevPtr<float> bb;
-  HIP_TRY(dev_alloc(bb, 6));
-  bounds_kernel<<<dim3(1), dim3(1024), 0, st>>>(v.d, m->V, bb.get());
+  Frame fr(m->device, &m->arena, space, stream, nullptr);
+  const float * v = fr.in(verts, (size_t)m->V * 3);
+  float * bb = fr.scratch<float>(6);
+  if(!bb) return fr.finish();
+  // the bounds, read here in mid-call: they size the sweep
   float h[6];
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = hipMemcpyAsync(h, bb.get(), sizeof(h), hipMemcpyDeviceToHost, st);
-  if(e == hipSuccess) e = hipStreamSynchronize(st);
-  bb.reset(); // (here, before the sweep's launches: freeing device memory waits for the device)
-  HIP_TRY(e);
+  bounds_kernel<<<dim3(1), dim3(1024), 0, fr.st>>>(v, m->V, bb);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, bb, sizeof(h), hipMemcpyDeviceToHost, fr.st));
+  if(!fr.sync()) return fr.finish();
   const float scale = 0.025f; // GRID_SCALE
   int64_t total = 1;
   int g0[3], gn[3];
@@ -290,16 +265,12 @@ extern "C" int smplpp_sweep_grid(smplpp_model * m, const float * verts, int32_t 
   *cells = total;
   const int64_t todo = total < cap ? total : cap;
   if(todo <= 0 || (!winding && !inside)) return SMPLPP_OK;
-  Out<float> wo;
-  Out<uint8_t> io;
-  HIP_TRY(wo.init(winding, (size_t)todo, space));
-  HIP_TRY(io.init(inside, (size_t)todo, space));
-  winding_kernel<<<dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, st>>>(v.d, m->faces.get(), m->F, g0[0], g0[1], g0[2], gn[1], gn[2], todo,
-                                                                            scale, wo.d, io.d);
-  e = hipGetLastError();
-  if(e == hipSuccess) e = wo.finish(st);
-  if(e == hipSuccess) e = io.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  float * wo = fr.out(winding, (size_t)todo);
+  uint8_t * io = fr.out(inside, (size_t)todo);
+  return fr.run([&]() -> int {
+    winding_kernel<<<dim3((unsigned)((todo + 255) / 256)), dim3(256), 0, fr.st>>>(v, m->faces.get(), m->F, g0[0], g0[1], g0[2], gn[1], gn[2],
+                                                                                 todo, scale, wo, io);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }

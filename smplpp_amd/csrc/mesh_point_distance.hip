@@ -24,8 +24,6 @@ struct MeshPointDistState
 {
   DevBuf part_d, part_k; // [n][chunks][V] partial (d, k) of a split forward
   DevBuf rec;            // [n][V] MpdRecord of the backward pass
-  DistanceStaging io;    // staging for host-space calls (index in io.ids) ...
-  DevBuf sqdist;         // ... and the forward's distances
 };
 void StateDelete::operator()(MeshPointDistState * s) const
 {
@@ -279,23 +277,13 @@ extern "C" int smplpp_mesh_point_distance(smplpp_model * m, int64_t n, const flo
   if(!m || n <= 0 || K <= 0 || !verts || !points || !index || !sqdist) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
   int rc = mpd_check(fn, m, n, K, space);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("mesh-point distance");
+  Frame fr(m->device, &m->arena, space, stream, "mesh-point distance");
   MeshPointDistState * s = mpd_state(m);
-  In<float> v, p;
-  Out<int64_t> io;
-  Out<float> so;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->io.verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->io.points));
-  HIP_TRY(io.init(index, (size_t)n * m->V, space, &s->io.ids));
-  HIP_TRY(so.init(sqdist, (size_t)n * m->V, space, &s->sqdist));
-  rc = mpd_forward_device(m, s, n, v.d, K, p.d, io.d, so.d, st);
-  if(rc) return rc;
-  HIP_TRY(io.finish(st));
-  HIP_TRY(so.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  int64_t * io = fr.out(index, (size_t)n * m->V);
+  float * so = fr.out(sqdist, (size_t)n * m->V);
+  return fr.run([&] { return mpd_forward_device(m, s, n, v, K, p, io, so, fr.st); });
 }
 
 extern "C" int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
@@ -308,9 +296,8 @@ extern "C" int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const
   if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
   int rc = mpd_check(fn, m, n, K, space);
   if(rc) return rc;
-  if(space == SMPLPP_HOST)
-    for(int64_t i = 0; i < n * m->V; i++)
-      if(index[i] < -1 || index[i] >= K) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": point index out of range");
-  return distance_vjp(mpd_vjp_device, m, mpd_state(m), "mesh-point distance VJP", n, verts, K, points, index, n * m->V, grad_sqdist,
-                      grad_verts, grad_points, accumulate, space, stream);
+  if(space == SMPLPP_HOST && (rc = ids_in(fn, "point index", index, n * m->V, -1, K))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "mesh-point distance VJP");
+  return distance_vjp(fr, mpd_vjp_device, m, mpd_state(m), n, verts, K, points, index, n * m->V, grad_sqdist, grad_verts, grad_points,
+                      accumulate);
 }

@@ -35,7 +35,6 @@ struct NormalsVjpState
   DevBuf G;         // staged whole-mesh form: [n][V][3]
   DevBuf setup;     // list set-up: int32 hdr[4] | pairId[Pmax] | pairFace[Pmax] | tgt[Rmax] | pos[Rmax] | order[Rmax] | stgt[Rmax]
   DevBuf lbuf;      // list form whose per-frame buffer exceeds LDS: [n][buffer]
-  DevBuf ids, verts, gn, gv; // staging for host-space calls
   int maxdeg = -1;  // largest vertex valence of the model (host, measured on the first call)
 };
 void StateDelete::operator()(NormalsVjpState * s) const
@@ -420,31 +419,21 @@ static int normals_vjp_common(const char * fn, smplpp_model * m, int64_t n, cons
   if(n > 0x7fffffffLL || count > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, name + ": too many frames or ids");
   int rc = check_space(space, fn);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if(kind != 2 && space == SMPLPP_HOST)
-    for(int64_t i = 0; i < count; i++)
-      if(ids[i] < 0 || ids[i] >= (kind == 1 ? m->V : m->F)) return fail(SMPLPP_ERR_INVALID, name + ": id out of range");
-  TraceRange tr("normals VJP");
+  if(kind != 2 && space == SMPLPP_HOST && (rc = ids_in(fn, "id", ids, count, 0, kind == 1 ? m->V : m->F))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "normals VJP");
   NormalsVjpState * s = nvjp_state(m);
   const int64_t V = m->V, rows = kind == 2 ? V : count;
   const size_t nv = (size_t)n * V * 3;
-  In<float> v, g;
-  In<int64_t> id;
-  Out<float> gv;
-  HIP_TRY(v.init(verts, nv, space, st, &s->verts));
-  HIP_TRY(g.init(grad_normals, (size_t)n * rows * 3, space, st, &s->gn));
-  HIP_TRY(gv.init(grad_verts, nv, space, &s->gv));
-  if(accumulate) HIP_TRY(gv.load(st));
-  HIP_TRY(id.init(ids, (size_t)count, space, st, &s->ids));
-  // a list form writes only the vertices it touches: without accumulate the rest is zeroed first
-  if(kind != 2 && !accumulate) HIP_TRY(hipMemsetAsync(gv.d, 0, sizeof(float) * nv, st));
-  rc = kind == 2 ? mesh_vjp_device(m, s, n, v.d, g.d, gv.d, accumulate, st)
-                 : list_vjp_device(m, s, n, v.d, count, id.d, g.d, gv.d, accumulate, kind == 1, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, nv);
+  const float * g = fr.in(grad_normals, (size_t)n * rows * 3);
+  float * gv = fr.out(grad_verts, nv, accumulate);
+  const int64_t * id = fr.in(ids, (size_t)count);
+  return fr.run([&]() -> int {
+    // a list form writes only the vertices it touches: without accumulate the rest is zeroed first
+    if(kind != 2 && !accumulate) HIP_TRY(hipMemsetAsync(gv, 0, sizeof(float) * nv, fr.st));
+    return kind == 2 ? mesh_vjp_device(m, s, n, v, g, gv, accumulate, fr.st)
+                     : list_vjp_device(m, s, n, v, count, id, g, gv, accumulate, kind == 1, fr.st);
+  });
 }
 
 extern "C" int smplpp_face_normals_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t count, const int64_t * face_ids,

@@ -12,8 +12,6 @@ struct PointDistState
   DevBuf rec;          // [n][K] PdRecord of the backward pass
   DevBuf seedv;        // [nseed] int32 vertices that have a face (model constant, set up by the first call)
   int64_t nseed = -1;
-  DistanceStaging io;                // staging for host-space calls (face in io.ids) ...
-  DevBuf weights, closest, sqdist;   // ... and the forward's other outputs
 };
 // smplpp_point_mesh_distance's forward and smplpp_point_mesh_distance_vjp's product, all pointers on the device
 int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points, int64_t * face,

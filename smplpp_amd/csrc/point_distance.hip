@@ -493,27 +493,15 @@ extern "C" int smplpp_point_mesh_distance(smplpp_model * m, int64_t n, const flo
   if(!m || n <= 0 || K <= 0 || !verts || !points || !face || !sqdist) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
   int rc = pd_check(fn, m, n, K, space);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("point-mesh distance");
+  Frame fr(m->device, &m->arena, space, stream, "point-mesh distance");
   PointDistState * s = pd_state(m);
-  In<float> v, p;
-  Out<int64_t> fo;
-  Out<float> wo, co, so;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->io.verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->io.points));
-  HIP_TRY(fo.init(face, (size_t)n * K, space, &s->io.ids));
-  HIP_TRY(wo.init(weights, (size_t)n * K * 3, space, &s->weights));
-  HIP_TRY(co.init(closest, (size_t)n * K * 3, space, &s->closest));
-  HIP_TRY(so.init(sqdist, (size_t)n * K, space, &s->sqdist));
-  rc = pd_forward_device(m, s, n, v.d, K, p.d, fo.d, wo.d, co.d, so.d, st);
-  if(rc) return rc;
-  HIP_TRY(fo.finish(st));
-  HIP_TRY(wo.finish(st));
-  HIP_TRY(co.finish(st));
-  HIP_TRY(so.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  int64_t * fo = fr.out(face, (size_t)n * K);
+  float * wo = fr.out(weights, (size_t)n * K * 3);
+  float * co = fr.out(closest, (size_t)n * K * 3);
+  float * so = fr.out(sqdist, (size_t)n * K);
+  return fr.run([&] { return pd_forward_device(m, s, n, v, K, p, fo, wo, co, so, fr.st); });
 }
 
 extern "C" int smplpp_point_mesh_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
@@ -526,9 +514,7 @@ extern "C" int smplpp_point_mesh_distance_vjp(smplpp_model * m, int64_t n, const
   if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
   int rc = pd_check(fn, m, n, K, space);
   if(rc) return rc;
-  if(space == SMPLPP_HOST)
-    for(int64_t i = 0; i < n * K; i++)
-      if(face[i] < 0 || face[i] >= m->F) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": face id out of range");
-  return distance_vjp(pd_vjp_device, m, pd_state(m), "point-mesh distance VJP", n, verts, K, points, face, n * K, grad_sqdist, grad_verts,
-                      grad_points, accumulate, space, stream);
+  if(space == SMPLPP_HOST && (rc = ids_in(fn, "face id", face, n * K, 0, m->F))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "point-mesh distance VJP");
+  return distance_vjp(fr, pd_vjp_device, m, pd_state(m), n, verts, K, points, face, n * K, grad_sqdist, grad_verts, grad_points, accumulate);
 }

@@ -53,7 +53,6 @@ struct SelfPenState
   DevBuf fill, strad;     // [n][F] slots taken per face in the write pass, and the partners of the range straddling max_pairs
   DevBuf seg, temp;       // large F: segment offsets [n + 1] and hipcub's workspace
   DevBuf rec, nrec;       // [n][max_pairs][6] SpRecord and [n] records per frame
-  DevBuf verts, pairs, count, energy, grad, gv; // staging of host-space calls
 };
 void StateDelete::operator()(SelfPenState * s) const
 {
@@ -677,24 +676,13 @@ static int sp_forward(const char * fn, const char * trace, smplpp_model * m, int
 {
   int rc = sp_check(fn, m, n, max_pairs, space);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr(trace);
+  Frame fr(m->device, &m->arena, space, stream, trace);
   SelfPenState * s = sp_state(m);
-  In<float> v;
-  Out<int64_t> po, co;
-  Out<float> eo;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(po.init(pairs, (size_t)(n * max_pairs * 2), space, &s->pairs));
-  HIP_TRY(co.init(count, (size_t)n, space, &s->count));
-  HIP_TRY(eo.init(energy, (size_t)(n * max_pairs), space, &s->energy));
-  rc = sp_forward_device(m, s, n, v.d, max_pairs, sigma * sigma, po.d, co.d, eo.d, st);
-  if(rc) return rc;
-  HIP_TRY(po.finish(st));
-  HIP_TRY(co.finish(st));
-  HIP_TRY(eo.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  int64_t * po = fr.out(pairs, (size_t)(n * max_pairs * 2));
+  int64_t * co = fr.out(count, (size_t)n);
+  float * eo = fr.out(energy, (size_t)(n * max_pairs));
+  return fr.run([&] { return sp_forward_device(m, s, n, v, max_pairs, sigma * sigma, po, co, eo, fr.st); });
 }
 
 extern "C" int smplpp_self_intersections(smplpp_model * m, int64_t n, const float * verts, int64_t max_pairs, int64_t * pairs,
@@ -728,32 +716,17 @@ extern "C" int smplpp_self_penetration_vjp(smplpp_model * m, int64_t n, const fl
   if(!rc) rc = sp_check(fn, m, n, max_pairs, space);
   if(rc) return rc;
   if(space == SMPLPP_HOST)
-    for(int64_t i = 0; i < n; i++)
+    for(int64_t i = 0; i < n; i++) // the rows of a frame that its count makes live
     {
       const int64_t rows = count[i] < 0 ? 0 : count[i] > max_pairs ? max_pairs : count[i];
-      for(int64_t r = 0; r < rows; r++)
-        for(int j = 0; j < 2; j++)
-        {
-          const int64_t id = pairs[(i * max_pairs + r) * 2 + j];
-          if(id < 0 || id >= m->F) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": face id out of range");
-        }
+      if((rc = ids_in(fn, "face id", pairs + i * max_pairs * 2, rows * 2, 0, m->F))) return rc;
     }
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("self penetration VJP");
+  Frame fr(m->device, &m->arena, space, stream, "self penetration VJP");
   SelfPenState * s = sp_state(m);
-  In<float> v, g;
-  In<int64_t> p, c;
-  Out<float> gv;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(p.init(pairs, (size_t)(n * max_pairs * 2), space, st, &s->pairs));
-  HIP_TRY(c.init(count, (size_t)n, space, st, &s->count));
-  HIP_TRY(g.init(grad_pair_energy, (size_t)(n * max_pairs), space, st, &s->grad));
-  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
-  if(accumulate) HIP_TRY(gv.load(st));
-  rc = sp_vjp_device(m, s, n, v.d, max_pairs, sigma * sigma, p.d, c.d, g.d, gv.d, accumulate, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const int64_t * p = fr.in(pairs, (size_t)(n * max_pairs * 2));
+  const int64_t * c = fr.in(count, (size_t)n);
+  const float * g = fr.in(grad_pair_energy, (size_t)(n * max_pairs));
+  float * gv = fr.out(grad_verts, (size_t)n * m->V * 3, accumulate);
+  return fr.run([&] { return sp_vjp_device(m, s, n, v, max_pairs, sigma * sigma, p, c, g, gv, accumulate, fr.st); });
 }

@@ -70,7 +70,6 @@ struct SilhouetteState
   DevBuf cnt, off, nvalid; // [n][blocks] int32 live records per 256 pixels, their exclusive prefix; [n] int64 records per frame
   DevBuf rec;             // [n][H W] SilRecord, the first nvalid[frame] of a frame live
   DevBuf gpix;            // [n][V][3] the pixel term's sums
-  DevBuf mask, nearest, sqdist, verts, camera, face, vt, vsq, ps, psq, gvs, gps, gv; // staging of host-space calls
 };
 void StateDelete::operator()(SilhouetteState * s) const
 {
@@ -489,13 +488,6 @@ static int sil_vjp_device(smplpp_model * m, SilhouetteState * s, int64_t n, cons
 
 using namespace smplpp_hip;
 
-static int sil_ids_in(const char * fn, const char * what, const int64_t * ids, int64_t count, int64_t bound)
-{
-  for(int64_t i = 0; i < count; i++)
-    if(ids[i] < -1 || ids[i] >= bound) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + what + " out of range");
-  return SMPLPP_OK;
-}
-
 extern "C" int smplpp_mask_distance_transform(smplpp_model * m, int64_t n, const uint8_t * mask, int64_t H, int64_t W, int64_t * nearest,
                                               int32_t * sqdist, int space, void * stream)
 {
@@ -505,22 +497,12 @@ extern "C" int smplpp_mask_distance_transform(smplpp_model * m, int64_t n, const
   if(n > 0x7fffffffLL || n * H * W > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": n * H * W beyond int32 indexing");
   int rc = check_space(space, fn);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("mask distance transform");
+  Frame fr(m->device, &m->arena, space, stream, "mask distance transform");
   SilhouetteState * s = sil_state(m);
-  In<uint8_t> mk;
-  Out<int64_t> no;
-  Out<int32_t> so;
-  HIP_TRY(mk.init(mask, (size_t)(n * H * W), space, st, &s->mask));
-  HIP_TRY(no.init(nearest, (size_t)(n * H * W), space, &s->nearest));
-  HIP_TRY(so.init(sqdist, (size_t)(n * H * W), space, &s->sqdist));
-  rc = sil_transform_device(s, n, mk.d, H, W, no.d, so.d, st);
-  if(rc) return rc;
-  HIP_TRY(no.finish(st));
-  HIP_TRY(so.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const uint8_t * mk = fr.in(mask, (size_t)(n * H * W));
+  int64_t * no = fr.out(nearest, (size_t)(n * H * W));
+  int32_t * so = fr.out(sqdist, (size_t)(n * H * W));
+  return fr.run([&] { return sil_transform_device(s, n, mk, H, W, no, so, fr.st); });
 }
 
 extern "C" int smplpp_silhouette(smplpp_model * m, int64_t n, const float * verts, const float * camera, int64_t H, int64_t W, float near,
@@ -533,32 +515,18 @@ extern "C" int smplpp_silhouette(smplpp_model * m, int64_t n, const float * vert
   if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
   int rc = dr_check(fn, m, n, H, W, space);
   if(rc) return rc;
-  if(space == SMPLPP_HOST && (rc = sil_ids_in(fn, "face id", face, n * H * W, m->F))) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("silhouette");
+  if(space == SMPLPP_HOST && (rc = ids_in(fn, "face id", face, n * H * W, -1, m->F))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "silhouette");
   SilhouetteState * s = sil_state(m);
-  In<float> v, c;
-  In<int64_t> f;
-  In<uint8_t> mk;
-  Out<int64_t> vt, ps;
-  Out<float> vs, pq;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(c.init(camera, (size_t)n * 16, space, st, &s->camera));
-  HIP_TRY(f.init(face, (size_t)(n * H * W), space, st, &s->face));
-  HIP_TRY(mk.init(mask, (size_t)(n * H * W), space, st, &s->mask));
-  HIP_TRY(vt.init(vert_target, (size_t)(n * m->V), space, &s->vt));
-  HIP_TRY(vs.init(vert_sq, (size_t)(n * m->V), space, &s->vsq));
-  HIP_TRY(ps.init(pix_source, (size_t)(n * H * W), space, &s->ps));
-  HIP_TRY(pq.init(pix_sq, (size_t)(n * H * W), space, &s->psq));
-  rc = sil_forward_device(m, s, n, v.d, c.d, H, W, near, f.d, mk.d, vt.d, vs.d, ps.d, pq.d, st);
-  if(rc) return rc;
-  HIP_TRY(vt.finish(st));
-  HIP_TRY(vs.finish(st));
-  HIP_TRY(ps.finish(st));
-  HIP_TRY(pq.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * c = fr.in(camera, (size_t)n * 16);
+  const int64_t * f = fr.in(face, (size_t)(n * H * W));
+  const uint8_t * mk = fr.in(mask, (size_t)(n * H * W));
+  int64_t * vt = fr.out(vert_target, (size_t)(n * m->V));
+  float * vs = fr.out(vert_sq, (size_t)(n * m->V));
+  int64_t * ps = fr.out(pix_source, (size_t)(n * H * W));
+  float * pq = fr.out(pix_sq, (size_t)(n * H * W));
+  return fr.run([&] { return sil_forward_device(m, s, n, v, c, H, W, near, f, mk, vt, vs, ps, pq, fr.st); });
 }
 
 extern "C" int smplpp_silhouette_vjp(smplpp_model * m, int64_t n, const float * verts, const float * camera, int64_t H, int64_t W,
@@ -576,35 +544,20 @@ extern "C" int smplpp_silhouette_vjp(smplpp_model * m, int64_t n, const float * 
   if(rc) return rc;
   if(space == SMPLPP_HOST)
   {
-    if((rc = sil_ids_in(fn, "face id", face, n * H * W, m->F))) return rc;
-    if(grad_vert_sq && (rc = sil_ids_in(fn, "vert_target", vert_target, n * m->V, H * W))) return rc;
-    if(grad_pix_sq && (rc = sil_ids_in(fn, "pix_source", pix_source, n * H * W, H * W))) return rc;
+    if((rc = ids_in(fn, "face id", face, n * H * W, -1, m->F))) return rc;
+    if(grad_vert_sq && (rc = ids_in(fn, "vert_target", vert_target, n * m->V, -1, H * W))) return rc;
+    if(grad_pix_sq && (rc = ids_in(fn, "pix_source", pix_source, n * H * W, -1, H * W))) return rc;
   }
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("silhouette VJP");
+  Frame fr(m->device, &m->arena, space, stream, "silhouette VJP");
   SilhouetteState * s = sil_state(m);
-  In<float> v, c, gs, gp;
-  In<int64_t> f, vt, ps;
-  Out<float> gv;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->verts));
-  HIP_TRY(c.init(camera, (size_t)n * 16, space, st, &s->camera));
-  HIP_TRY(f.init(face, (size_t)(n * H * W), space, st, &s->face));
-  if(grad_vert_sq)
-  {
-    HIP_TRY(vt.init(vert_target, (size_t)(n * m->V), space, st, &s->vt));
-    HIP_TRY(gs.init(grad_vert_sq, (size_t)(n * m->V), space, st, &s->gvs));
-  }
-  if(grad_pix_sq)
-  {
-    HIP_TRY(ps.init(pix_source, (size_t)(n * H * W), space, st, &s->ps));
-    HIP_TRY(gp.init(grad_pix_sq, (size_t)(n * H * W), space, st, &s->gps));
-  }
-  HIP_TRY(gv.init(grad_verts, (size_t)n * m->V * 3, space, &s->gv));
-  if(accumulate) HIP_TRY(gv.load(st));
-  rc = sil_vjp_device(m, s, n, v.d, c.d, H, W, near, f.d, vt.d, ps.d, gs.d, gp.d, gv.d, accumulate, st);
-  if(rc) return rc;
-  HIP_TRY(gv.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * c = fr.in(camera, (size_t)n * 16);
+  const int64_t * f = fr.in(face, (size_t)(n * H * W));
+  // a term without its gradient is left out: its indices are not read
+  const int64_t * vt = grad_vert_sq ? fr.in(vert_target, (size_t)(n * m->V)) : nullptr;
+  const float * gs = fr.in(grad_vert_sq, (size_t)(n * m->V));
+  const int64_t * ps = grad_pix_sq ? fr.in(pix_source, (size_t)(n * H * W)) : nullptr;
+  const float * gp = fr.in(grad_pix_sq, (size_t)(n * H * W));
+  float * gv = fr.out(grad_verts, (size_t)n * m->V * 3, accumulate);
+  return fr.run([&] { return sil_vjp_device(m, s, n, v, c, H, W, near, f, vt, ps, gs, gp, gv, accumulate, fr.st); });
 }

@@ -159,6 +159,7 @@ __global__ void stage_skin_kernel(const float * __restrict__ W, const float * __
 
 using namespace smplpp_hip;
 
+// the checks every stage call makes before its frame selects the device
 static int enter(int device, int space, const char * fn)
 {
   int rc = check_space(space, fn);
@@ -167,7 +168,6 @@ static int enter(int device, int space, const char * fn)
   rc = smplpp_device_count(&ndev);
   if(rc) return rc;
   if(device < 0 || device >= ndev) return fail(SMPLPP_ERR_INVALID, "Failed to fetch device index!");
-  HIP_TRY(hipSetDevice(device));
   return SMPLPP_OK;
 }
 
@@ -179,33 +179,20 @@ extern "C" int smplpp_stage_blend_shape(int device, int64_t V, int64_t n, const 
     return fail(SMPLPP_ERR_INVALID, "Cannot blend shape-dependented shape!"); // src/BlendShape.cpp:679
   int rc = enter(device, space, "smplpp_stage_blend_shape");
   if(rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> b, t, s, p;
-  Out<float> bs, bp, rot;
-  DevPtr<float> rot_tmp;
-  HIP_TRY(b.init(beta, (size_t)n * NB, space, st));
-  HIP_TRY(t.init(theta24, (size_t)n * NJ * 3, space, st));
-  HIP_TRY(s.init(S, (size_t)V * 3 * NB, space, st));
-  HIP_TRY(p.init(P, (size_t)V * 3 * NP, space, st));
-  HIP_TRY(bs.init(shape_blend, (size_t)n * V * 3, space));
-  HIP_TRY(bp.init(pose_blend, (size_t)n * V * 3, space));
-  HIP_TRY(rot.init(pose_rot, (size_t)n * NJ * 9, space));
-  float * rd = rot.d;
-  if(!rd)
-  {
-    HIP_TRY(dev_alloc(rot_tmp, (size_t)n * NJ * 9));
-    rd = rot_tmp.get();
-  }
-  stage_rodrigues_kernel<<<dim3((unsigned)((n * NJ + 255) / 256)), dim3(256), 0, st>>>(t.d, rd, n * NJ);
-  if(bs.d || bp.d)
-    stage_blend_kernel<<<dim3((unsigned)((n * V * 3 + 3) / 4)), dim3(256), 0, st>>>(b.d, rd, s.d, p.d, bs.d, bp.d, V, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = bs.finish(st);
-  if(e == hipSuccess) e = bp.finish(st);
-  if(e == hipSuccess) e = rot.finish(st);
-  if(e == hipSuccess && (space == SMPLPP_HOST || rot_tmp)) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(device, nullptr, space, stream, nullptr);
+  const float * b = fr.in(beta, (size_t)n * NB);
+  const float * t = fr.in(theta24, (size_t)n * NJ * 3);
+  const float * s = fr.in(S, (size_t)V * 3 * NB);
+  const float * p = fr.in(P, (size_t)V * 3 * NP);
+  float * bs = fr.out(shape_blend, (size_t)n * V * 3);
+  float * bp = fr.out(pose_blend, (size_t)n * V * 3);
+  float * rot = pose_rot ? fr.out(pose_rot, (size_t)n * NJ * 9) : fr.scratch<float>((size_t)n * NJ * 9);
+  return fr.run([&]() -> int {
+    stage_rodrigues_kernel<<<dim3((unsigned)((n * NJ + 255) / 256)), dim3(256), 0, fr.st>>>(t, rot, n * NJ);
+    if(bs || bp) stage_blend_kernel<<<dim3((unsigned)((n * V * 3 + 3) / 4)), dim3(256), 0, fr.st>>>(b, rot, s, p, bs, bp, V, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }
 
 extern "C" int smplpp_stage_joint_regression(int device, int64_t V, int64_t n, const float * T, const float * Jreg,
@@ -216,24 +203,19 @@ extern "C" int smplpp_stage_joint_regression(int device, int64_t V, int64_t n, c
     return fail(SMPLPP_ERR_INVALID, "Cannot linearly combine shapes!"); // src/JointRegression.cpp:561
   int rc = enter(device, space, "smplpp_stage_joint_regression");
   if(rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> t, jr, bs, bp;
-  Out<float> rest, jo;
-  HIP_TRY(t.init(T, (size_t)V * 3, space, st));
-  HIP_TRY(jr.init(Jreg, (size_t)NJ * V, space, st));
-  HIP_TRY(bs.init(shape_blend, (size_t)n * V * 3, space, st));
-  HIP_TRY(bp.init(pose_blend, (size_t)n * V * 3, space, st));
-  HIP_TRY(rest.init(rest_shape, (size_t)n * V * 3, space));
-  HIP_TRY(jo.init(joints, (size_t)n * NJ * 3, space));
-  if(rest.d)
-    stage_combine_kernel<<<dim3((unsigned)((n * V * 3 + 255) / 256)), dim3(256), 0, st>>>(t.d, bs.d, bp.d, rest.d, V * 3, n);
-  if(jo.d) stage_regress_kernel<<<dim3((unsigned)(n * NJ * 3)), dim3(256), 0, st>>>(t.d, jr.d, bs.d, jo.d, V);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = rest.finish(st);
-  if(e == hipSuccess) e = jo.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(device, nullptr, space, stream, nullptr);
+  const float * t = fr.in(T, (size_t)V * 3);
+  const float * jr = fr.in(Jreg, (size_t)NJ * V);
+  const float * bs = fr.in(shape_blend, (size_t)n * V * 3);
+  const float * bp = fr.in(pose_blend, (size_t)n * V * 3);
+  float * rest = fr.out(rest_shape, (size_t)n * V * 3);
+  float * jo = fr.out(joints, (size_t)n * NJ * 3);
+  return fr.run([&]() -> int {
+    if(rest) stage_combine_kernel<<<dim3((unsigned)((n * V * 3 + 255) / 256)), dim3(256), 0, fr.st>>>(t, bs, bp, rest, V * 3, n);
+    if(jo) stage_regress_kernel<<<dim3((unsigned)(n * NJ * 3)), dim3(256), 0, fr.st>>>(t, jr, bs, jo, V);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }
 
 extern "C" int smplpp_stage_world_transformation(int device, int64_t n, const int64_t * kintree, const float * joints,
@@ -243,7 +225,6 @@ extern "C" int smplpp_stage_world_transformation(int device, int64_t n, const in
     return fail(SMPLPP_ERR_INVALID, "Cannot transform bones locally!"); // src/WorldTransformation.cpp:512
   int rc = enter(device, space, "smplpp_stage_world_transformation");
   if(rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   // the kinematic tree is always a host array here (it is a model constant, src/SMPL.cpp:603-605)
   int32_t parent[NJ];
   parent[0] = -1;
@@ -252,20 +233,17 @@ extern "C" int smplpp_stage_world_transformation(int device, int64_t n, const in
     if(kintree[i] < 0 || kintree[i] >= i) return fail(SMPLPP_ERR_INVALID, "Cannot set kinematic tree: parent(i) must precede i");
     parent[i] = (int32_t)kintree[i];
   }
-  In<int32_t> par;
-  In<float> j, r;
-  Out<float> o;
-  HIP_TRY(par.init(parent, NJ, SMPLPP_HOST, st));
-  HIP_TRY(hipStreamSynchronize(st)); // parent[] is a stack array
-  HIP_TRY(j.init(joints, (size_t)n * NJ * 3, space, st));
-  HIP_TRY(r.init(pose_rot, (size_t)n * NJ * 9, space, st));
-  HIP_TRY(o.init(xforms, (size_t)n * NJ * 16, space));
-  stage_world_kernel<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(par.d, j.d, r.d, o.d, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = o.finish(st);
-  if(e == hipSuccess) e = hipStreamSynchronize(st); // temporaries (parent) are freed on return
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(device, nullptr, space, stream, nullptr);
+  const int32_t * par = fr.upload(parent, NJ);
+  fr.sync(); // parent[] is a stack array
+  const float * j = fr.in(joints, (size_t)n * NJ * 3);
+  const float * r = fr.in(pose_rot, (size_t)n * NJ * 9);
+  float * o = fr.out(xforms, (size_t)n * NJ * 16);
+  return fr.run([&]() -> int {
+    stage_world_kernel<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, fr.st>>>(par, j, r, o, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }
 
 extern "C" int smplpp_stage_skinning(int device, int64_t V, int64_t n, const float * weights, const float * rest_shape,
@@ -275,18 +253,15 @@ extern "C" int smplpp_stage_skinning(int device, int64_t V, int64_t n, const flo
     return fail(SMPLPP_ERR_INVALID, "Cannot convert Cartesian coordinates to homogeneous one!"); // LinearBlendSkinning.cpp:509
   int rc = enter(device, space, "smplpp_stage_skinning");
   if(rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> w, r, g, rp;
-  Out<float> o;
-  HIP_TRY(w.init(weights, (size_t)V * NJ, space, st));
-  HIP_TRY(r.init(rest_shape, (size_t)n * V * 3, space, st));
-  HIP_TRY(g.init(xforms, (size_t)n * NJ * 16, space, st));
-  HIP_TRY(rp.init(root_pos, (size_t)n * 3, space, st));
-  HIP_TRY(o.init(verts, (size_t)n * V * 3, space));
-  stage_skin_kernel<<<dim3((unsigned)((n * V + 255) / 256)), dim3(256), 0, st>>>(w.d, r.d, g.d, rp.d, o.d, V, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = o.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(device, nullptr, space, stream, nullptr);
+  const float * w = fr.in(weights, (size_t)V * NJ);
+  const float * r = fr.in(rest_shape, (size_t)n * V * 3);
+  const float * g = fr.in(xforms, (size_t)n * NJ * 16);
+  const float * rp = fr.in(root_pos, (size_t)n * 3);
+  float * o = fr.out(verts, (size_t)n * V * 3);
+  return fr.run([&]() -> int {
+    stage_skin_kernel<<<dim3((unsigned)((n * V + 255) / 256)), dim3(256), 0, fr.st>>>(w, r, g, rp, o, V, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }

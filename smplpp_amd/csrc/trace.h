@@ -43,7 +43,7 @@ inline const RoctxApi & roctx_api()
 struct TraceRange
 {
   bool on;
-  explicit TraceRange(const char * name) : on(roctx_api().push != nullptr)
+  explicit TraceRange(const char * name) : on(name && roctx_api().push != nullptr) // (no name: no range)
   {
     if(on) roctx_api().push(name);
   }

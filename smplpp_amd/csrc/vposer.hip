@@ -870,20 +870,11 @@ extern "C" int smplpp_vposer_forward_at(smplpp_vposer * v, int64_t n, int64_t fr
   if(!v || n <= 0 || frame_base < 0 || !z || !out) return fail(SMPLPP_ERR_INVALID, "smplpp_vposer_forward: bad argument");
   int rc = check_space(space, "smplpp_vposer_forward");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(v->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> zi;
-  Out<float> oo, jo;
-  HIP_TRY(zi.init(z, (size_t)n * LAT, space, st));
-  HIP_TRY(oo.init(out, (size_t)n * 63, space));
-  HIP_TRY(jo.init(jac, (size_t)n * 63 * LAT, space));
-  rc = vposer_forward_device(v, n, zi.d, LAT, oo.d, 63, jo.d, st, frame_base, false, nullptr, nullptr, 0u);
-  if(rc) return rc;
-  hipError_t e = oo.finish(st);
-  if(e == hipSuccess) e = jo.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(v->device, &v->arena, space, stream, nullptr);
+  const float * zi = fr.in(z, (size_t)n * LAT);
+  float * oo = fr.out(out, (size_t)n * 63);
+  float * jo = fr.out(jac, (size_t)n * 63 * LAT);
+  return fr.run([&] { return vposer_forward_device(v, n, zi, LAT, oo, 63, jo, fr.st, frame_base, false, nullptr, nullptr, 0u); });
 }
 
 // Development / test hook (not part of include/smplpp_hip.h): the decoded angles by the Jacobian kernel's VALUE-ONLY instantiation —
@@ -892,17 +883,10 @@ extern "C" int smplpp_vposer_forward_at(smplpp_vposer * v, int64_t n, int64_t fr
 extern "C" int smplpp_debug_vposer_value(smplpp_vposer * v, int64_t n, int64_t frame_base, const float * z, float * out)
 {
   if(!v || n <= 0 || frame_base < 0 || !z || !out) return fail(SMPLPP_ERR_INVALID, "smplpp_debug_vposer_value: bad argument");
-  HIP_TRY(hipSetDevice(v->device));
-  In<float> zi;
-  Out<float> oo;
-  HIP_TRY(zi.init(z, (size_t)n * LAT, SMPLPP_HOST, nullptr));
-  HIP_TRY(oo.init(out, (size_t)n * 63, SMPLPP_HOST));
-  int rc = vposer_forward_device(v, n, zi.d, LAT, oo.d, 63, nullptr, nullptr, frame_base, true, nullptr, nullptr, 0u);
-  if(rc) return rc;
-  hipError_t e = oo.finish(nullptr);
-  if(e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(v->device, &v->arena, SMPLPP_HOST, nullptr, nullptr);
+  const float * zi = fr.in(z, (size_t)n * LAT);
+  float * oo = fr.out(out, (size_t)n * 63);
+  return fr.run([&] { return vposer_forward_device(v, n, zi, LAT, oo, 63, nullptr, nullptr, frame_base, true, nullptr, nullptr, 0u); });
 }
 
 extern "C" int smplpp_rotmat_to_axis_angle(int device, int64_t n, const float * rot, float * aa, int space, void * stream)
@@ -914,16 +898,12 @@ extern "C" int smplpp_rotmat_to_axis_angle(int device, int64_t n, const float * 
   rc = smplpp_device_count(&ndev);
   if(rc) return rc;
   if(device < 0 || device >= ndev) return fail(SMPLPP_ERR_INVALID, "Failed to fetch device index!");
-  HIP_TRY(hipSetDevice(device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> ri;
-  Out<float> ao;
-  HIP_TRY(ri.init(rot, (size_t)n * 9, space, st));
-  HIP_TRY(ao.init(aa, (size_t)n * 3, space));
-  rotmat_to_aa_kernel<<<dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st>>>(ri.d, ao.d, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = ao.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(device, nullptr, space, stream, nullptr);
+  const float * ri = fr.in(rot, (size_t)n * 9);
+  float * ao = fr.out(aa, (size_t)n * 3);
+  return fr.run([&]() -> int {
+    rotmat_to_aa_kernel<<<dim3((unsigned)((n + 127) / 128)), dim3(128), 0, fr.st>>>(ri, ao, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }

@@ -250,18 +250,9 @@ extern "C" int smplpp_vposer_jacobian(smplpp_vposer * v, int64_t n, int64_t fram
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_vposer_jacobian: too many frames");
   int rc = check_space(space, "smplpp_vposer_jacobian");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(v->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  In<float> zi;
-  Out<float> oo, jo;
-  HIP_TRY(zi.init(z, (size_t)n * LAT, space, st));
-  HIP_TRY(oo.init(out, (size_t)n * 63, space));
-  HIP_TRY(jo.init(jac, (size_t)n * 63 * LAT, space));
-  rc = vposer_jacobian_device(v, v->jx, n, zi.d, LAT, oo.d, 63, jo.d, st);
-  if(rc) return rc;
-  hipError_t e = jo.finish(st);
-  if(e == hipSuccess) e = oo.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  Frame fr(v->device, &v->arena, space, stream, nullptr);
+  const float * zi = fr.in(z, (size_t)n * LAT);
+  float * jo = fr.out(jac, (size_t)n * 63 * LAT);
+  float * oo = fr.out(out, (size_t)n * 63);
+  return fr.run([&] { return vposer_jacobian_device(v, v->jx, n, zi, LAT, oo, 63, jo, fr.st); });
 }

@@ -18,6 +18,7 @@ struct smplpp_vposer
   smplpp_hip::DevPtr<float> w0r, w1r, w2r;
   smplpp_hip::DevBuf vjp_ws; // smplpp_vposer_vjp's workspace: [n][VW_FRAME] of vposer_kernel<true>
   smplpp_hip::StatePtr<smplpp_hip::VPoserJxWork> jx; // smplpp_vposer_jacobian's workspace: null until its first call on the decoder
+  smplpp_hip::Arena arena;   // staging of the host-space calls on this decoder
   ~smplpp_vposer(); // (vposer.hip)
 };
 

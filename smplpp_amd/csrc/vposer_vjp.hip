@@ -205,25 +205,21 @@ extern "C" int smplpp_vposer_vjp(smplpp_vposer * v, int64_t n, int64_t frame_bas
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_vposer_vjp: too many frames");
   int rc = check_space(space, "smplpp_vposer_vjp");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(v->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  Frame fr(v->device, &v->arena, space, stream, nullptr);
+  if(!fr.ok()) return fr.finish();
   rc = vposer_weight_rows(v, true);
   if(rc) return rc;
   HIP_TRY(v->vjp_ws.reserve(sizeof(float) * (size_t)n * VW_FRAME));
-  In<float> zi, gi;
-  Out<float> gzo, oo;
-  HIP_TRY(zi.init(z, (size_t)n * LAT, space, st));
-  HIP_TRY(gi.init(grad_out, (size_t)n * 63, space, st));
-  HIP_TRY(gzo.init(grad_z, (size_t)n * LAT, space));
-  HIP_TRY(oo.init(out, (size_t)n * 63, space));
-  rc = vposer_value_device(v, n, zi.d, oo.d, v->vjp_ws.as<float>(), st);
-  if(rc) return rc;
-  vposer_vjp_kernel<<<dim3((unsigned)((n + VV_NF - 1) / VV_NF)), dim3(256), 0, st>>>(v->vjp_ws.as<float>(), gi.d, v->w0r.get(), v->w1r.get(),
-                                                                                    v->w2r.get(), gzo.d, n);
-  hipError_t e = hipGetLastError();
-  if(e == hipSuccess) e = gzo.finish(st);
-  if(e == hipSuccess) e = oo.finish(st);
-  if(e == hipSuccess && space == SMPLPP_HOST) e = hipStreamSynchronize(st);
-  HIP_TRY(e);
-  return SMPLPP_OK;
+  const float * zi = fr.in(z, (size_t)n * LAT);
+  const float * gi = fr.in(grad_out, (size_t)n * 63);
+  float * gzo = fr.out(grad_z, (size_t)n * LAT);
+  float * oo = fr.out(out, (size_t)n * 63);
+  return fr.run([&]() -> int {
+    int rc = vposer_value_device(v, n, zi, oo, v->vjp_ws.as<float>(), fr.st);
+    if(rc) return rc;
+    vposer_vjp_kernel<<<dim3((unsigned)((n + VV_NF - 1) / VV_NF)), dim3(256), 0, fr.st>>>(v->vjp_ws.as<float>(), gi, v->w0r.get(), v->w1r.get(),
+                                                                                         v->w2r.get(), gzo, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }

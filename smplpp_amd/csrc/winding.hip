@@ -21,10 +21,9 @@ namespace smplpp_hip
 {
 struct WindingState
 {
-  StatePtr<PointDistState> pd; // the signed distance's point-to-mesh workspace; its io also stages verts and points of every call here
+  StatePtr<PointDistState> pd; // the signed distance's point-to-mesh workspace
   DevBuf part;                 // [n][chunks][K] fp32 chunk partials of a split call
   DevBuf gs;                   // [n][K] sigma g of the backward pass
-  DevBuf winding, inside;      // host-space staging of the winding numbers and inside flags
 };
 void StateDelete::operator()(WindingState * s) const
 {
@@ -177,23 +176,13 @@ extern "C" int smplpp_point_mesh_winding(smplpp_model * m, int64_t n, const floa
   if(!m || n <= 0 || K <= 0 || !verts || !points || !winding) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
   int rc = wn_check(fn, m, n, K, space);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("point-mesh winding");
+  Frame fr(m->device, &m->arena, space, stream, "point-mesh winding");
   WindingState * s = wn_state(m);
-  In<float> v, p;
-  Out<float> wo;
-  Out<uint8_t> io;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &s->pd->io.verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &s->pd->io.points));
-  HIP_TRY(wo.init(winding, (size_t)n * K, space, &s->winding));
-  HIP_TRY(io.init(inside, (size_t)n * K, space, &s->inside));
-  rc = wn_forward_device(m, s, n, v.d, K, p.d, wo.d, io.d, nullptr, st);
-  if(rc) return rc;
-  HIP_TRY(wo.finish(st));
-  HIP_TRY(io.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  float * wo = fr.out(winding, (size_t)n * K);
+  uint8_t * io = fr.out(inside, (size_t)n * K);
+  return fr.run([&] { return wn_forward_device(m, s, n, v, K, p, wo, io, nullptr, fr.st); });
 }
 
 extern "C" int smplpp_point_mesh_signed_distance(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
@@ -205,35 +194,20 @@ extern "C" int smplpp_point_mesh_signed_distance(smplpp_model * m, int64_t n, co
     return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
   int rc = wn_check(fn, m, n, K, space);
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceRange tr("signed point-mesh distance");
+  Frame fr(m->device, &m->arena, space, stream, "signed point-mesh distance");
   WindingState * s = wn_state(m);
-  PointDistState * pd = s->pd.get();
-  In<float> v, p;
-  Out<int64_t> fo;
-  Out<float> wo, co, wno, so;
-  Out<uint8_t> io;
-  HIP_TRY(v.init(verts, (size_t)n * m->V * 3, space, st, &pd->io.verts));
-  HIP_TRY(p.init(points, (size_t)n * K * 3, space, st, &pd->io.points));
-  HIP_TRY(fo.init(face, (size_t)n * K, space, &pd->io.ids));
-  HIP_TRY(wo.init(weights, (size_t)n * K * 3, space, &pd->weights));
-  HIP_TRY(co.init(closest, (size_t)n * K * 3, space, &pd->closest));
-  HIP_TRY(wno.init(winding, (size_t)n * K, space, &s->winding));
-  HIP_TRY(io.init(inside, (size_t)n * K, space, &s->inside));
-  HIP_TRY(so.init(signed_sqdist, (size_t)n * K, space, &pd->sqdist));
-  rc = pd_forward_device(m, pd, n, v.d, K, p.d, fo.d, wo.d, co.d, so.d, st);
-  if(rc) return rc;
-  rc = wn_forward_device(m, s, n, v.d, K, p.d, wno.d, io.d, so.d, st);
-  if(rc) return rc;
-  HIP_TRY(fo.finish(st));
-  HIP_TRY(wo.finish(st));
-  HIP_TRY(co.finish(st));
-  HIP_TRY(wno.finish(st));
-  HIP_TRY(io.finish(st));
-  HIP_TRY(so.finish(st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  int64_t * fo = fr.out(face, (size_t)n * K);
+  float * wo = fr.out(weights, (size_t)n * K * 3);
+  float * co = fr.out(closest, (size_t)n * K * 3);
+  float * wno = fr.out(winding, (size_t)n * K);
+  uint8_t * io = fr.out(inside, (size_t)n * K);
+  float * so = fr.out(signed_sqdist, (size_t)n * K);
+  return fr.run([&]() -> int {
+    int rc = pd_forward_device(m, s->pd.get(), n, v, K, p, fo, wo, co, so, fr.st);
+    return rc ? rc : wn_forward_device(m, s, n, v, K, p, wno, io, so, fr.st);
+  });
 }
 
 extern "C" int smplpp_point_mesh_signed_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
@@ -246,23 +220,17 @@ extern "C" int smplpp_point_mesh_signed_distance_vjp(smplpp_model * m, int64_t n
   if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
   int rc = wn_check(fn, m, n, K, space);
   if(rc) return rc;
-  if(space == SMPLPP_HOST)
-    for(int64_t i = 0; i < n * K; i++)
-      if(face[i] < 0 || face[i] >= m->F) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": face id out of range");
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(space == SMPLPP_HOST && (rc = ids_in(fn, "face id", face, n * K, 0, m->F))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "signed point-mesh distance VJP");
   WindingState * s = wn_state(m);
-  In<uint8_t> ins;
-  HIP_TRY(ins.init(inside, (size_t)n * K, space, st, &s->inside));
-  HIP_TRY(s->gs.reserve(sizeof(float) * (size_t)(n * K)));
-  float * gs = s->gs.as<float>();
-  const uint8_t * ind = ins.d;
-  auto device = [gs, ind](smplpp_model * m, PointDistState * pd, int64_t n, const float * v, int64_t K, const float * p, const int64_t * id,
-                          const float * g, float * gv, float * gp, int acc, hipStream_t st) -> int {
+  const uint8_t * ind = fr.in(inside, (size_t)n * K);
+  auto device = [s, ind](smplpp_model * m, PointDistState * pd, int64_t n, const float * v, int64_t K, const float * p, const int64_t * id,
+                         const float * g, float * gv, float * gp, int acc, hipStream_t st) -> int {
+    HIP_TRY(s->gs.reserve(sizeof(float) * (size_t)(n * K)));
+    float * gs = s->gs.as<float>();
     wn_sign_kernel<<<dim3((unsigned)((n * K + 255) / 256)), dim3(256), 0, st>>>(g, ind, gs, n * K);
     HIP_TRY(hipGetLastError());
     return pd_vjp_device(m, pd, n, v, K, p, id, gs, gv, gp, acc, st);
   };
-  return distance_vjp(device, m, s->pd.get(), "signed point-mesh distance VJP", n, verts, K, points, face, n * K, grad_signed_sqdist,
-                      grad_verts, grad_points, accumulate, space, stream);
+  return distance_vjp(fr, device, m, s->pd.get(), n, verts, K, points, face, n * K, grad_signed_sqdist, grad_verts, grad_points, accumulate);
 }
