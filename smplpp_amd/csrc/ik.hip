@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <type_traits>
 
 using namespace smplpp_hip;
 
@@ -97,14 +98,28 @@ struct smplpp_ik
   }
 };
 
+// What a solver buffer holds when it has just been made.  AS_ALLOCATED: nothing — it is written before it is read.
+enum Fill { AS_ALLOCATED, ZERO_BYTES, VALUE, DEFAULT_NORMAL };
+
+// one device buffer of the solver: allocated, handed to s->owned, and filled (null stream); VALUE and DEFAULT_NORMAL are float fills
 template<class T>
-static hipError_t dalloc(smplpp_ik * s, T ** p, size_t count)
+static hipError_t dalloc(smplpp_ik * s, T *& p, size_t count, Fill fill, float v = 0.0f)
 {
   DevPtr<T> d;
   hipError_t e = dev_alloc(d, count);
-  *p = d.get();
-  if(e == hipSuccess) s->owned.emplace_back(std::move(d));
-  return e;
+  p = d.get();
+  if(e != hipSuccess) return e;
+  s->owned.emplace_back(std::move(d));
+  if(fill == AS_ALLOCATED) return hipSuccess;
+  if(fill == ZERO_BYTES) return hipMemset(p, 0, sizeof(T) * count);
+  if constexpr(std::is_same_v<T, float>)
+  {
+    const dim3 grid((unsigned)((count + 255) / 256));
+    if(fill == VALUE) fill_f32_kernel<<<grid, 256>>>(p, v, (int64_t)count);
+    if(fill == DEFAULT_NORMAL) fill_nrm_kernel<<<grid, 256>>>(p, (int64_t)count);
+    return hipGetLastError();
+  }
+  return hipErrorInvalidValue; // (a float fill of a buffer of another type)
 }
 
 static ModelView view_of(const smplpp_model * m)
@@ -228,66 +243,55 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
   }
   const size_t nk = (size_t)n * K;
   const size_t Dmax = TD75 + 2 * K + NB;
-  HIP_TRY(dalloc(s.get(), &s->ta.face, nk));
-  HIP_TRY(dalloc(s.get(), &s->ta.vw, nk * 3));
-  HIP_TRY(dalloc(s.get(), &s->ta.tang, nk * 6));
-  HIP_TRY(dalloc(s.get(), &s->ta.tpos, nk * 3));
-  HIP_TRY(dalloc(s.get(), &s->ta.tnrm, nk * 3));
-  HIP_TRY(dalloc(s.get(), &s->ta.posw, nk));
-  HIP_TRY(dalloc(s.get(), &s->ta.nrmw, nk));
-  HIP_TRY(dalloc(s.get(), &s->ta.philim, nk));
-  HIP_TRY(dalloc(s.get(), &s->ta.noff, nk));
-  HIP_TRY(dalloc(s.get(), &s->ta.apos, nk * 3));
-  HIP_TRY(dalloc(s.get(), &s->ta.anrm, nk * 3));
-  HIP_TRY(dalloc(s.get(), &s->ta.hint, nk));
-  HIP_TRY(dalloc(s.get(), &s->ta.roww, nk * 2));
-  HIP_TRY(dalloc(s.get(), &s->theta, (size_t)n * s->theta_dim));
-  HIP_TRY(dalloc(s.get(), &s->beta, (size_t)n * NB));
-  HIP_TRY(dalloc(s.get(), &s->theta25, (size_t)n * 75));
-  HIP_TRY(dalloc(s.get(), &s->vbuf[0], (size_t)n * m->V * 3));
-  HIP_TRY(dalloc(s.get(), &s->vbuf[1], (size_t)n * m->V * 3));
-  HIP_TRY(dalloc(s.get(), &s->rest, (size_t)n * m->V * 3));
-  HIP_TRY(dalloc(s.get(), &s->joints, (size_t)n * NJ * 3));
-  HIP_TRY(dalloc(s.get(), &s->poserot, (size_t)n * NJ * 9));
-  HIP_TRY(dalloc(s.get(), &s->pts, nk * 3));
-  HIP_TRY(dalloc(s.get(), &s->e, nk * 4));
-  HIP_TRY(dalloc(s.get(), &s->J, nk * 4 * Dmax));
-  HIP_TRY(dalloc(s.get(), &s->e2, (size_t)n));
-  HIP_TRY(dalloc(s.get(), &s->xout, (size_t)n * Dmax));
-  HIP_TRY(dalloc(s.get(), &s->roles, roles.size()));
-  HIP_TRY(dalloc(s.get(), &s->list_cnt, nk));
-  HIP_TRY(dalloc(s.get(), &s->list_d, nk * PROJ_LIST));
-  HIP_TRY(dalloc(s.get(), &s->list_f, nk * PROJ_LIST));
-  HIP_TRY(dalloc(s.get(), &s->skip, (size_t)n));
-  HIP_TRY(dalloc(s.get(), &s->status, (size_t)n));
-  HIP_TRY(dalloc(s.get(), &s->sticky, (size_t)n));
-  HIP_TRY(dalloc(s.get(), &s->range_word, 1));
-  s->ta.flags = s->sticky;
+  const size_t nV3 = (size_t)n * m->V * 3;
+  smplpp_ik * const p = s.get();
+  // IkTask defaults (include/smplpp/IkTask.h:54-84)
+  HIP_TRY(dalloc(p, p->ta.face, nk, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->ta.vw, nk * 3, VALUE, 1.0f / 3.0f));
+  HIP_TRY(dalloc(p, p->ta.tang, nk * 6, VALUE, 0.0f));
+  HIP_TRY(dalloc(p, p->ta.tpos, nk * 3, VALUE, 0.0f));
+  HIP_TRY(dalloc(p, p->ta.tnrm, nk * 3, DEFAULT_NORMAL));
+  HIP_TRY(dalloc(p, p->ta.posw, nk, VALUE, 1.0f));
+  HIP_TRY(dalloc(p, p->ta.nrmw, nk, VALUE, 1.0f));
+  HIP_TRY(dalloc(p, p->ta.philim, nk, VALUE, 0.04f));
+  HIP_TRY(dalloc(p, p->ta.noff, nk, VALUE, 0.0f));
+  // what the evaluation writes for the solve and the re-projection
+  HIP_TRY(dalloc(p, p->ta.apos, nk * 3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->ta.anrm, nk * 3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->ta.hint, nk, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->ta.roww, nk * 2, AS_ALLOCATED));
+  // the configuration
+  HIP_TRY(dalloc(p, p->theta, (size_t)n * p->theta_dim, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->beta, (size_t)n * NB, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->theta25, (size_t)n * 75, ZERO_BYTES));
+  // the forward pass's outputs
+  HIP_TRY(dalloc(p, p->vbuf[0], nV3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->vbuf[1], nV3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->rest, nV3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->joints, (size_t)n * NJ * 3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->poserot, (size_t)n * NJ * 9, AS_ALLOCATED));
+  // evaluation -> solve -> re-projection
+  HIP_TRY(dalloc(p, p->pts, nk * 3, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->e, nk * 4, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->J, nk * 4 * Dmax, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->e2, (size_t)n, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->xout, (size_t)n * Dmax, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->roles, roles.size(), AS_ALLOCATED)); // (uploaded below)
+  HIP_TRY(dalloc(p, p->list_cnt, nk, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->list_d, nk * PROJ_LIST, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->list_f, nk * PROJ_LIST, AS_ALLOCATED));
+  HIP_TRY(dalloc(p, p->skip, (size_t)n, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->status, (size_t)n, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->sticky, (size_t)n, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->range_word, 1, ZERO_BYTES));
+  HIP_TRY(dalloc(p, p->sig, 128, ZERO_BYTES));
   if(vposer)
   {
-    HIP_TRY(dalloc(s.get(), &s->Jl, nk * 4 * Dmax));
-    HIP_TRY(dalloc(s.get(), &s->vjac, (size_t)n * 63 * 32));
+    HIP_TRY(dalloc(p, p->Jl, nk * 4 * Dmax, AS_ALLOCATED));
+    HIP_TRY(dalloc(p, p->vjac, (size_t)n * 63 * 32, AS_ALLOCATED));
   }
-  // IkTask defaults (include/smplpp/IkTask.h:54-84)
-  auto grid = [](size_t c) { return dim3((unsigned)((c + 255) / 256)); };
-  HIP_TRY(hipMemset(s->ta.face, 0, sizeof(int32_t) * nk));
-  fill_f32_kernel<<<grid(nk * 3), 256>>>(s->ta.vw, 1.0f / 3.0f, nk * 3);
-  fill_f32_kernel<<<grid(nk * 6), 256>>>(s->ta.tang, 0.0f, nk * 6);
-  fill_f32_kernel<<<grid(nk * 3), 256>>>(s->ta.tpos, 0.0f, nk * 3);
-  fill_nrm_kernel<<<grid(nk * 3), 256>>>(s->ta.tnrm, nk * 3);
-  fill_f32_kernel<<<grid(nk), 256>>>(s->ta.posw, 1.0f, nk);
-  fill_f32_kernel<<<grid(nk), 256>>>(s->ta.nrmw, 1.0f, nk);
-  fill_f32_kernel<<<grid(nk), 256>>>(s->ta.philim, 0.04f, nk);
-  fill_f32_kernel<<<grid(nk), 256>>>(s->ta.noff, 0.0f, nk);
-  HIP_TRY(hipMemset(s->theta, 0, sizeof(float) * n * s->theta_dim));
-  HIP_TRY(hipMemset(s->theta25, 0, sizeof(float) * n * 75));
-  HIP_TRY(hipMemset(s->beta, 0, sizeof(float) * n * NB));
-  HIP_TRY(hipMemset(s->skip, 0, sizeof(int) * n));
   HIP_TRY(hipMemcpy(s->roles, roles.data(), sizeof(int32_t) * roles.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(s->list_cnt, 0, sizeof(int) * nk));
-  HIP_TRY(hipMemset(s->status, 0, sizeof(int) * n));
-  HIP_TRY(hipMemset(s->sticky, 0, sizeof(int) * n));
-  HIP_TRY(hipMemset(s->range_word, 0, sizeof(int)));
+  s->ta.flags = s->sticky;
   s->verts = s->vbuf[0];
   // (default priority: a lowest-priority side stream — tried against the scan being dispatched ahead of the solve — halved the
   // latent-IK leg of bench.py, where several solvers' streams exist; what fixes that order is the solve kernel's own "all my
@@ -296,8 +300,6 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
   HIP_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
   {
-    HIP_TRY(dalloc(s.get(), &s->sig, 128));
-    HIP_TRY(hipMemset(s->sig, 0, sizeof(unsigned) * 128));
     // stream memory operations are optional in HIP: probe once (flag 0 >= 0 is satisfied at once); SMPLPP_IK_EVENTS=1 keeps events
     const char * e = getenv("SMPLPP_IK_EVENTS");
     if(!(e && e[0] != '0'))
@@ -322,7 +324,6 @@ static int set_array(Frame & fr, const Src * src, Dst * dst, size_t count, Conv 
   if(!d) return fr.finish(); // (the staging failed)
   conv(d, dst, (int64_t)count);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
   return SMPLPP_OK;
 }
 
@@ -358,6 +359,9 @@ extern "C" int smplpp_ik_set_tasks(smplpp_ik * s, const int64_t * face_idx, cons
   if((rc = set_array(fr, normal_offset, s->ta.noff, nk, cvd))) return rc;
   if(phi_limit)
   {
+    // the one synchronisation of the call: uploads, conversions and copies above run on the null stream in program order, each
+    // staged array in a slot of its own, so nothing in front of this read-back needed one
+    HIP_TRY(hipDeviceSynchronize());
     std::vector<float> h(nk);
     HIP_TRY(hipMemcpy(h.data(), s->ta.philim, sizeof(float) * nk, hipMemcpyDeviceToHost));
     bool locked = true;
@@ -372,22 +376,23 @@ extern "C" int smplpp_ik_set_config(smplpp_ik * s, const float * beta, const flo
   if(!s) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_set_config: null solver");
   int rc = check_space(space, "smplpp_ik_set_config");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  if(beta) HIP_TRY(hipMemcpy(s->beta, beta, sizeof(float) * s->n * NB, kind));
-  if(theta) HIP_TRY(hipMemcpy(s->theta, theta, sizeof(float) * s->n * s->theta_dim, kind));
-  // status bit 1 (smplpp_ik_get_status) reports failures "since the configuration was set": a new configuration starts clean
-  s->jac_ahead = false; // (a Jacobian made ahead belongs to the configuration it was made for)
-  HIP_TRY(hipMemset(s->status, 0, sizeof(int) * s->n));
-  HIP_TRY(hipMemset(s->sticky, 0, sizeof(int) * s->n));
-  if(s->range_word) HIP_TRY(hipMemset(s->range_word, 0, sizeof(int))); // (status bit 3: same lifetime; this solver's own word)
-  if(theta && s->vp) // latent layout: the entries that pass through to theta25 (the decoder fills the rest at every evaluation)
-  {
-    ik_splice_kernel<<<dim3((unsigned)((s->n * 75 + 255) / 256)), 256>>>(s->theta, nullptr, s->theta25, s->n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));
-  }
-  return SMPLPP_OK;
+  Frame fr(s->m->device, &s->arena, space, nullptr, nullptr);
+  fr.store(s->beta, beta, (size_t)s->n * NB);
+  fr.store(s->theta, theta, (size_t)s->n * s->theta_dim);
+  return fr.run([&]() -> int {
+    // status bit 1 (smplpp_ik_get_status) reports failures "since the configuration was set": a new configuration starts clean
+    s->jac_ahead = false; // (a Jacobian made ahead belongs to the configuration it was made for)
+    HIP_TRY(hipMemset(s->status, 0, sizeof(int) * s->n));
+    HIP_TRY(hipMemset(s->sticky, 0, sizeof(int) * s->n));
+    if(s->range_word) HIP_TRY(hipMemset(s->range_word, 0, sizeof(int))); // (status bit 3: same lifetime; this solver's own word)
+    if(theta && s->vp) // latent layout: the entries that pass through to theta25 (the decoder fills the rest at every evaluation)
+    {
+      ik_splice_kernel<<<dim3((unsigned)((s->n * 75 + 255) / 256)), 256>>>(s->theta, nullptr, s->theta25, s->n);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    return SMPLPP_OK;
+  });
 }
 
 extern "C" int smplpp_ik_get_config(smplpp_ik * s, float * beta, float * theta, int space)
@@ -395,12 +400,11 @@ extern "C" int smplpp_ik_get_config(smplpp_ik * s, float * beta, float * theta, 
   if(!s) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_get_config: null solver");
   int rc = check_space(space, "smplpp_ik_get_config");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
+  Frame fr(s->m->device, &s->arena, space, nullptr, nullptr);
   HIP_TRY(hipDeviceSynchronize());
-  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if(beta) HIP_TRY(hipMemcpy(beta, s->beta, sizeof(float) * s->n * NB, kind));
-  if(theta) HIP_TRY(hipMemcpy(theta, s->theta, sizeof(float) * s->n * s->theta_dim, kind));
-  return SMPLPP_OK;
+  fr.fetch(beta, s->beta, (size_t)s->n * NB);
+  fr.fetch(theta, s->theta, (size_t)s->n * s->theta_dim);
+  return fr.finish();
 }
 
 extern "C" int smplpp_ik_get_tasks(smplpp_ik * s, int64_t * face_idx, float * vertex_weights, float * tangents, float * actual_pos,
@@ -412,27 +416,26 @@ extern "C" int smplpp_ik_get_tasks(smplpp_ik * s, int64_t * face_idx, float * ve
   Frame fr(s->m->device, &s->arena, space, nullptr, nullptr);
   HIP_TRY(hipDeviceSynchronize());
   const size_t nk = (size_t)s->n * s->K;
-  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   int64_t * fo = fr.out(face_idx, nk);
-  rc = fr.run([&]() -> int { // (the frame ends here: the face indices are back before the copies below)
+  return fr.run([&]() -> int { // (kernels and copies: the null stream, in program order)
     if(fo) i32_to_i64_kernel<<<dim3((unsigned)((nk + 255) / 256)), 256>>>(s->ta.face, fo, (int64_t)nk);
+    // IkTask::calcActualNormal() evaluated on demand at the current task state (face, weights) and the last posed mesh
+    if(actual_normal)
+      ik_actual_normals_kernel<<<dim3((unsigned)((nk + 63) / 64)), 64>>>(view_of(s->m), s->ta, s->verts, (int)s->K, (int64_t)nk);
     HIP_TRY(hipGetLastError());
+    fr.fetch(vertex_weights, s->ta.vw, nk * 3);
+    fr.fetch(tangents, s->ta.tang, nk * 6);
+    fr.fetch(actual_pos, s->ta.apos, nk * 3);
+    fr.fetch(actual_normal, s->ta.anrm, nk * 3);
     return SMPLPP_OK;
   });
-  if(rc) return rc;
-  if(face_idx) HIP_TRY(hipDeviceSynchronize());
-  if(vertex_weights) HIP_TRY(hipMemcpy(vertex_weights, s->ta.vw, sizeof(float) * nk * 3, kind));
-  if(tangents) HIP_TRY(hipMemcpy(tangents, s->ta.tang, sizeof(float) * nk * 6, kind));
-  if(actual_pos) HIP_TRY(hipMemcpy(actual_pos, s->ta.apos, sizeof(float) * nk * 3, kind));
-  if(actual_normal)
-  {
-    // IkTask::calcActualNormal() evaluated on demand at the current task state (face, weights) and the last posed mesh
-    ik_actual_normals_kernel<<<dim3((unsigned)((nk + 63) / 64)), 64>>>(view_of(s->m), s->ta, s->verts, (int)s->K, (int64_t)nk);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(actual_normal, s->ta.anrm, sizeof(float) * nk * 3, kind));
-  }
-  return SMPLPP_OK;
+}
+
+// workgroups per frame of a kernel that deals a frame's K tasks to several: with few frames, one round of workgroups (one per CU)
+static int frame_split(int64_t n, int K)
+{
+  const int split = n < 256 ? (int)(256 / n) : 1;
+  return std::max(1, std::min(split, K));
 }
 
 // forward + eval for all frames (enqueue only)
@@ -485,9 +488,7 @@ static int ik_forward_eval(smplpp_ik * s, int optimize_beta, int phi_live, int64
   const void * kfn = deep ? (wide ? reinterpret_cast<const void *>(&ik_eval_kernel<DMAX, 64, 3, MAXADJ_WIDE>) : reinterpret_cast<const void *>(&ik_eval_kernel<DMAX, 64, 3>))
                           : (wide ? reinterpret_cast<const void *>(&ik_eval_kernel<9, 76, 4, MAXADJ_WIDE>) : reinterpret_cast<const void *>(&ik_eval_kernel<9, 76, 6>));
   HIP_TRY(lds_opt_in(once_eval[(deep ? 1 : 0) + (wide ? 2 : 0)], m->device, kfn, (int)shmem));
-  int tsplit = (n < 256) ? (int)(256 / n) : 1; // one round of workgroups (one per CU: its LDS is the evaluation's)
-  if(tsplit > K) tsplit = K;
-  if(tsplit < 1) tsplit = 1;
+  const int tsplit = frame_split(n, K); // (a CU's LDS is one evaluation workgroup's)
   if(s->use_flags) eval_done = nullptr; // (flags mode: the fork is the solve kernel's start flag; the evaluation's end is signalled in events mode only)
 #define EVAL_(DM, RC, NG, MA)                                                                                                              \
   hipExtLaunchKernelGGL((ik_eval_kernel<DM, RC, NG, MA>), dim3((unsigned)(n * tsplit)), dim3(EVAL_NT), shmem, st, nullptr, eval_done, 0,     \
@@ -509,27 +510,58 @@ static int ik_forward_eval(smplpp_ik * s, int optimize_beta, int phi_live, int64
   return SMPLPP_OK;
 }
 
-static int ik_check_valence(smplpp_ik * s);
+// The per-frame words of the solve kernel (status: the last solve's outcome; sticky: bit 0 some solve failed, bit 2 raised by the
+// evaluation, see TaskArrays::flags), read once; the caller's stream is idle
+struct StatusWords
+{
+  std::vector<int> status, sticky;
+};
+
+static int ik_read_status(smplpp_ik * s, StatusWords & w)
+{
+  w.status.resize((size_t)s->n);
+  w.sticky.resize((size_t)s->n);
+  HIP_TRY(hipMemcpy(w.status.data(), s->status, sizeof(int) * s->n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w.sticky.data(), s->sticky, sizeof(int) * s->n, hipMemcpyDeviceToHost));
+  return SMPLPP_OK;
+}
+
+// what a host-space call reports: the valence condition first (such a frame's solve reports itself as skipped too), then a failed
+// solve in `llt` (w.status: the last solve; w.sticky: any solve of the sequence; null: the call solved nothing)
+static int ik_first_error(const StatusWords & w, const std::vector<int> * llt)
+{
+  for(int f : w.sticky)
+    if(f & 4)
+      return fail(SMPLPP_ERR_INVALID, "a task with a normal term (normal weight or normal offset) touches a vertex with more than 12 adjacent "
+                                      "faces: the Jacobian of such a term is not supported");
+  if(llt)
+    for(int f : *llt)
+      if(f & 1) return fail(SMPLPP_ERR_NUMERIC, "LLT has numerical issue!"); // node.cpp:934-937
+  return SMPLPP_OK;
+}
+
+static int ik_report(smplpp_ik * s, int space, std::vector<int> StatusWords::*llt)
+{
+  if(space != SMPLPP_HOST) return SMPLPP_OK;
+  StatusWords w;
+  if(int rc = ik_read_status(s, w)) return rc;
+  return ik_first_error(w, llt ? &(w.*llt) : nullptr);
+}
 
 extern "C" int smplpp_ik_eval(smplpp_ik * s, int optimize_beta, double * e, double * J, int space, void * stream)
 {
   if(!s) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_eval: null solver");
   int rc = check_space(space, "smplpp_ik_eval");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  rc = ik_forward_eval(s, optimize_beta, 1, 0, st);
-  if(rc) return rc;
-  const int64_t D = s->theta_dim + 2 * s->K + (optimize_beta ? NB : 0);
-  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if(e) HIP_TRY(hipMemcpyAsync(e, s->e, sizeof(double) * s->n * s->K * 4, kind, st));
-  if(J) HIP_TRY(hipMemcpyAsync(J, s->vp ? s->Jl : s->J, sizeof(double) * s->n * s->K * 4 * D, kind, st));
-  if(space == SMPLPP_HOST)
-  {
-    HIP_TRY(hipStreamSynchronize(st));
-    if((rc = ik_check_valence(s))) return rc;
-  }
-  return SMPLPP_OK;
+  Frame fr(s->m->device, &s->arena, space, stream, nullptr);
+  rc = fr.run([&]() -> int {
+    if(int rc = ik_forward_eval(s, optimize_beta, 1, 0, fr.st)) return rc;
+    const size_t rows = (size_t)s->n * s->K * 4, D = s->theta_dim + 2 * s->K + (optimize_beta ? NB : 0);
+    fr.fetch(e, s->e, rows);
+    fr.fetch(J, s->vp ? s->Jl : s->J, rows * D);
+    return SMPLPP_OK;
+  });
+  return rc ? rc : ik_report(s, space, nullptr);
 }
 
 // `iters` iterations enqueued on st (+ the solver's side stream); leaves the last re-projection pending on the side
@@ -625,11 +657,7 @@ static int ik_iterate_enqueue(smplpp_ik * s, int iters, int enable_qp, int optim
     if(ahead) s->tick_done++;
     unsigned * const done_flag = ahead ? s->sig + 64 : (unsigned *)nullptr;
     unsigned * const done_counter = ahead ? s->sig + 80 : (unsigned *)nullptr;
-#define SOLVE_(DO) ik_solve_kernel<DO><<<dim3((unsigned)s->n), dim3(256), solve_shmem, st>>>(                                              \
-    s->ta, s->e, s->vp ? s->Jl : s->J, s->theta, s->beta, beside ? nullptr : s->pts, K, s->theta_dim, beta_dim, phi_live, qp_k, \
-    s->vp ? 1 : 0, chunk_rows, s->skip, s->e2, s->status, s->sticky, s->xout, dbg_stop, m_dim, s->vp ? s->theta25 : (float *)nullptr, theta_record, \
-    go ? s->sig : (unsigned *)nullptr, go ? s->sig + 16 : (unsigned *)nullptr, s->tick_fork, done_flag, done_counter, s->tick_done)
-#define SOLVE11_(NTR_) ik_solve_kernel<false, NTR_><<<dim3((unsigned)s->n), dim3(256), solve_shmem, st>>>(                                              \
+#define SOLVE_(...) ik_solve_kernel<__VA_ARGS__><<<dim3((unsigned)s->n), dim3(256), solve_shmem, st>>>(                                     \
     s->ta, s->e, s->vp ? s->Jl : s->J, s->theta, s->beta, beside ? nullptr : s->pts, K, s->theta_dim, beta_dim, phi_live, qp_k, \
     s->vp ? 1 : 0, chunk_rows, s->skip, s->e2, s->status, s->sticky, s->xout, dbg_stop, m_dim, s->vp ? s->theta25 : (float *)nullptr, theta_record, \
     go ? s->sig : (unsigned *)nullptr, go ? s->sig + 16 : (unsigned *)nullptr, s->tick_fork, done_flag, done_counter, s->tick_done)
@@ -638,16 +666,15 @@ static int ik_iterate_enqueue(smplpp_ik * s, int iters, int enable_qp, int optim
       if(dual_only)
         SOLVE_(true);
       else if(ntr == 11)
-        SOLVE11_(11);
+        SOLVE_(false, 11);
       else if(ntr == 5)
-        SOLVE11_(5);
+        SOLVE_(false, 5);
       else if(ntr == 3)
-        SOLVE11_(3);
+        SOLVE_(false, 3);
       else
         SOLVE_(false);
     }
 #undef SOLVE_
-#undef SOLVE11_
     HIP_TRY(hipGetLastError());
     DBG_SYNC("solve");
     {
@@ -682,11 +709,9 @@ static int ik_iterate_enqueue(smplpp_ik * s, int iters, int enable_qp, int optim
 #undef SCAN_
       HIP_TRY(hipGetLastError());
       int *& dbg_buf = s->dbg_buf; // (SMPLPP_DEBUG_SYNC only; owned by the solver, on its device)
-      if(dbg && !dbg_buf) HIP_TRY(dalloc(s, &dbg_buf, 8));
+      if(dbg && !dbg_buf) HIP_TRY(dalloc(s, dbg_buf, 8, AS_ALLOCATED)); // (zeroed on the stream below, every iteration)
       if(dbg) HIP_TRY(hipMemsetAsync(dbg_buf, 0, sizeof(int) * 8, st));
-      int fsplit = (s->n < 256) ? (int)(256 / s->n) : 1;
-      if(fsplit > K) fsplit = K;
-      if(fsplit < 1) fsplit = 1;
+      const int fsplit = frame_split(s->n, K);
       const bool join_flag = beside && s->use_flags && !ahead; // (ahead: the Jacobian kernel behind the finish kernel raises the join)
       if(beside && s->use_flags) s->tick_join++;
       hipExtLaunchKernelGGL(proj_finish_kernel, dim3((unsigned)(s->n * fsplit)), dim3(256), 0, pst, nullptr,
@@ -731,56 +756,23 @@ static int ik_join(smplpp_ik * s, hipStream_t st)
   return SMPLPP_OK;
 }
 
-static int ik_check_status(smplpp_ik * s, const int * flags)
-{
-  std::vector<int> h((size_t)s->n);
-  HIP_TRY(hipMemcpy(h.data(), flags, sizeof(int) * s->n, hipMemcpyDeviceToHost));
-  for(int64_t f = 0; f < s->n; f++)
-    if(h[f] & 1) return fail(SMPLPP_ERR_NUMERIC, "LLT has numerical issue!"); // node.cpp:934-937
-  return SMPLPP_OK;
-}
-
-// bit 2 of the sticky word: raised by the evaluation (see TaskArrays::flags)
-static int ik_check_valence(smplpp_ik * s)
-{
-  std::vector<int> h((size_t)s->n);
-  HIP_TRY(hipMemcpy(h.data(), s->sticky, sizeof(int) * s->n, hipMemcpyDeviceToHost));
-  for(int64_t f = 0; f < s->n; f++)
-    if(h[f] & 4)
-      return fail(SMPLPP_ERR_INVALID, "a task with a normal term (normal weight or normal offset) touches a vertex with more than 12 adjacent "
-                                      "faces: the Jacobian of such a term is not supported");
-  return SMPLPP_OK;
-}
-
 extern "C" int smplpp_ik_iterate(smplpp_ik * s, int iters, int enable_qp, int optimize_beta_from, int64_t min_valid,
                                  double * e_sqnorm, int space, void * stream)
 {
   if(!s || iters < 0) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_iterate: bad argument");
   int rc = check_space(space, "smplpp_ik_iterate");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const auto enq_t0 = std::chrono::steady_clock::now();
-  rc = ik_iterate_enqueue(s, iters, enable_qp, optimize_beta_from, min_valid, st);
-  s->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - enq_t0).count();
-  if(rc)
-  {
-    (void)ik_join(s, st);
-    return rc;
-  }
-  if((rc = ik_join(s, st))) return rc;
-  if(e_sqnorm)
-  {
-    hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIP_TRY(hipMemcpyAsync(e_sqnorm, s->e2, sizeof(double) * s->n, kind, st));
-  }
-  if(space == SMPLPP_HOST)
-  {
-    HIP_TRY(hipStreamSynchronize(st));
-    if((rc = ik_check_valence(s))) return rc; // (first: such a frame's solve reports itself as skipped too)
-    if((rc = ik_check_status(s, s->status))) return rc;
-  }
-  return SMPLPP_OK;
+  Frame fr(s->m->device, &s->arena, space, stream, nullptr);
+  rc = fr.run([&]() -> int {
+    const auto enq_t0 = std::chrono::steady_clock::now();
+    const int rc = ik_iterate_enqueue(s, iters, enable_qp, optimize_beta_from, min_valid, fr.st);
+    s->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - enq_t0).count();
+    const int jrc = ik_join(s, fr.st); // (after a failed enqueue too)
+    if(rc || jrc) return rc ? rc : jrc;
+    fr.fetch(e_sqnorm, s->e2, (size_t)s->n);
+    return SMPLPP_OK;
+  });
+  return rc ? rc : ik_report(s, space, &StatusWords::status);
 }
 
 // node/node.cpp:1369-1407 with :681-700 — the frame loop of solveMocapMotion on the device: frame t's marker targets
@@ -860,13 +852,7 @@ static int ik_solve_sequence_impl(smplpp_ik * s, int64_t T, const float * target
     s->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - enq_t0).count();
     return rc ? rc : jrc;
   });
-  if(rc) return rc;
-  if(space == SMPLPP_HOST)
-  {
-    if((rc = ik_check_valence(s))) return rc;
-    if((rc = ik_check_status(s, s->sticky))) return rc;
-  }
-  return SMPLPP_OK;
+  return rc ? rc : ik_report(s, space, &StatusWords::sticky);
 }
 
 extern "C" int smplpp_ik_solve_sequence(smplpp_ik * s, int64_t T, const float * target_pos, const uint8_t * valid, int warmup_iters,
@@ -898,12 +884,11 @@ extern "C" int smplpp_ik_get_status(smplpp_ik * s, int32_t * flags, int space, v
   if(!s || !flags) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_get_status: bad argument");
   int rc = check_space(space, "smplpp_ik_get_status");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<int> a((size_t)s->n), b((size_t)s->n);
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipMemcpy(a.data(), s->status, sizeof(int) * s->n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(b.data(), s->sticky, sizeof(int) * s->n, hipMemcpyDeviceToHost));
+  Frame fr(s->m->device, &s->arena, space, stream, nullptr);
+  if(!fr.sync()) return fr.finish();
+  StatusWords w;
+  if((rc = ik_read_status(s, w))) return rc;
+  const std::vector<int> &a = w.status, &b = w.sticky;
   // bit 3: a forward pass INSIDE this solver's loops met an operand outside the fp16x2 form's range since the last set_config
   // (one word per solver — which frame is not recorded, so every frame of the batch carries it; such a frame's vertices are not
   // finite and its solve then fails on its own)
@@ -916,8 +901,8 @@ extern "C" int smplpp_ik_get_status(smplpp_ik * s, int32_t * flags, int space, v
   if(space == SMPLPP_HOST)
     memcpy(flags, h.data(), sizeof(int32_t) * (size_t)s->n);
   else
-    HIP_TRY(hipMemcpy(flags, h.data(), sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice));
-  return SMPLPP_OK;
+    HIP_TRY(hipMemcpy(flags, h.data(), sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice)); // (composed here, on the host)
+  return fr.finish();
 }
 
 // The step x = (theta, phi, beta) of the last solve of every frame, fp64, as the solve kernel wrote it (xout, [n][last_D])
@@ -928,12 +913,9 @@ extern "C" int smplpp_ik_get_step(smplpp_ik * s, double * x, int64_t * D, int sp
   if(rc) return rc;
   *D = s->last_D;
   if(!x || s->last_D == 0) return SMPLPP_OK;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  HIP_TRY(hipMemcpyAsync(x, s->xout, sizeof(double) * s->n * s->last_D, kind, st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  Frame fr(s->m->device, &s->arena, space, stream, nullptr);
+  fr.fetch(x, s->xout, (size_t)(s->n * s->last_D));
+  return fr.finish();
 }
 
 extern "C" int smplpp_ik_get_vertices(smplpp_ik * s, float * verts, int space, void * stream)
@@ -942,10 +924,7 @@ extern "C" int smplpp_ik_get_vertices(smplpp_ik * s, float * verts, int space, v
   if(!s->have_eval) return fail(SMPLPP_ERR_STATE, "Failed to get vertices of new pose!");
   int rc = check_space(space, "smplpp_ik_get_vertices");
   if(rc) return rc;
-  HIP_TRY(hipSetDevice(s->m->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipMemcpyKind kind = space == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  HIP_TRY(hipMemcpyAsync(verts, s->verts, sizeof(float) * s->n * s->m->V * 3, kind, st));
-  if(space == SMPLPP_HOST) HIP_TRY(hipStreamSynchronize(st));
-  return SMPLPP_OK;
+  Frame fr(s->m->device, &s->arena, space, stream, nullptr);
+  fr.fetch(verts, s->verts, (size_t)s->n * s->m->V * 3);
+  return fr.finish();
 }

@@ -6,6 +6,8 @@
 // pointer — takes no slot.  A frame without an arena (the handle-less entry points) stages through an arena of its own, freed
 // with the frame.  In device space a frame costs the hipSetDevice its entry point always made: no allocation, no other HIP call.
 // The one exception is smplpp_sweep_grid, whose six floats of bounds scratch come from slot 0 of the model's arena in either space.
+// A getter or setter of state the handle keeps on the device (the IK solver's configuration, tasks, step, status, mesh) stages
+// nothing: fetch() / store() copy between the handle's array and the caller's, in the frame's space, on the frame's stream.
 #pragma once
 #include "common.h"
 #include "trace.h"
@@ -27,7 +29,8 @@ inline int ids_in(const char * fn, const char * what, const int64_t * ids, int64
 }
 
 // The call frame of one entry point: selects the device, opens the trace range (name may be null), hands out device pointers for
-// the arguments, and in run() / finish() copies the host-space outputs back in the order they were declared and synchronises.
+// the arguments, copies between the handle's own device arrays and the caller's (fetch / store), and in run() / finish() copies
+// the staged host-space outputs back in the order they were declared and synchronises.
 // The first HIP error sticks: every later request is a no-op giving null, and run() reports it without calling its body, under
 // the name and the place of the entry point that built the frame.
 class Frame
@@ -85,6 +88,23 @@ class Frame
     if(!note(b.reserve(sizeof(T) * count), "hipMalloc (staging slot)")) return nullptr;
     next_++;
     return b.as<T>();
+  }
+  // a device array the handle owns -> the caller's array in the frame's space, enqueued here (no slot; finish() synchronises a
+  // host-space call); a null caller pointer or a zero count: nothing
+  template<class T>
+  void fetch(T * caller_dst, const T * dev_src, size_t count)
+  {
+    if(caller_dst && count && e_ == hipSuccess)
+      note(hipMemcpyAsync(caller_dst, dev_src, sizeof(T) * count, space_ == SMPLPP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st),
+           "hipMemcpyAsync (fetch from the handle)");
+  }
+  // the other way: the caller's array -> a device array the handle owns
+  template<class T>
+  void store(T * dev_dst, const T * caller_src, size_t count)
+  {
+    if(caller_src && count && e_ == hipSuccess)
+      note(hipMemcpyAsync(dev_dst, caller_src, sizeof(T) * count, space_ == SMPLPP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st),
+           "hipMemcpyAsync (store into the handle)");
   }
   // false once a HIP call of the frame has failed (ask before creating state on the device the frame selected)
   bool ok() const { return e_ == hipSuccess; }
