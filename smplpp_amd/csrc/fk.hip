@@ -290,7 +290,7 @@ static char launch_form(const smplpp_model * m, int range_slot, char form_overri
   return form_override ? form_override : range_slot == RANGE_INTERNAL ? m->form_ik : m->form;
 }
 
-// range_slot: which word of the model's range status a launch of the fp16x2 form reports to (common.h RANGE_*): enqueue-only user
+// range_slot: which word of the model's range status a launch of the fp16x2 form reports to (layout.h RANGE_*): enqueue-only user
 // launches, host-space user launches and the IK / VPoser loops' internal launches each have their own, so that an intermediate IK
 // iterate outside the range does not turn a later, in-range smplpp_fk into an error
 // Pose step of a launch of form `form`: joints, relative transforms and the fused kernel's operand images (when `with_ops`) into

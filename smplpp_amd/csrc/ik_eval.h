@@ -232,7 +232,7 @@ __device__ __forceinline__ void ik_eval_body(const ModelView & mv, const TaskArr
     const float vR = (tid < NJ * 9) ? poserot[f * NJ * 9 + tid] : 0.0f;
     const float vJ = (tid < NJ * 3) ? joints[f * NJ * 3 + tid] : 0.0f;
     const float vG = (tid < NJ * 12) ? Gp[f * NJ * 12 + tid] : 0.0f;
-    // tree tables of the model (common.h TREE_*): ancestor masks (with the joint itself; depth(i) = popcount - 1), joints by level
+    // tree tables of the model (layout.h TREE_*): ancestor masks (with the joint itself; depth(i) = popcount - 1), joints by level
     const int vT = (tid < TREE_SIZE) ? mv.anc[tid] : 0;
     const int vP = (tid < NJ) ? mv.parent[tid] : 0;
     float th[3] = {0.f, 0.f, 0.f};

@@ -60,9 +60,9 @@ struct ModelView
   const float * Pvm;
   const float * Svm;
   const float * JS;
-  const uint16_t * faceRing; // [F][3 (madj + 1) + 2] per face: ring size, then the ring (common.h; madj = the model's table width: 12 or 16)
+  const uint16_t * faceRing; // [F][3 (madj + 1) + 2] per face: ring size, then the ring (layout.h; madj = the model's table width: 12 or 16)
   const uint8_t * faceMap;   // [F][3 madj 3] (vertex of the face, adjacent face, corner) -> ring slot
-  const int32_t * anc;       // [TREE_SIZE] tree tables (common.h): ancestor masks, joints by level
+  const int32_t * anc;       // [TREE_SIZE] tree tables (layout.h): ancestor masks, joints by level
   int nlev;
   int64_t V;
   int maxw;

@@ -13,9 +13,8 @@
 //   Pvm [V][3][207], Svm [V][3][10]  the bases once more in the file's vertex-major order, for the IK Jacobian of a
 //                     handful of task vertices (a K-major gather would touch 207 cache lines per vertex).
 #include "common.h"
+#include "model_tables.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <tuple>
 
@@ -68,7 +67,7 @@ __global__ void relayout_basis_kernel(const float * __restrict__ P, const float 
   }
 }
 
-// B3 <- Bm as bf16x3 pieces in MFMA fragment order (layout: common.h).  One thread per (vertex-group pair, k-step,
+// B3 <- Bm as bf16x3 pieces in MFMA fragment order (layout: layout.h).  One thread per (vertex-group pair, k-step,
 // piece, lane): 8 consecutive k of one column.
 __global__ void relayout_basis_bf16x3_kernel(const float * __restrict__ Bm, int64_t ldB, int64_t V, int64_t nvgp,
                                              uint16_t * __restrict__ B3)
@@ -94,7 +93,7 @@ __global__ void relayout_basis_bf16x3_kernel(const float * __restrict__ Bm, int6
   }
 }
 
-// B3e <- Bm as bf16x3 pieces in MFMA fragment order, one 20 KiB image per (vertex group, k-step) (layout: common.h, EB_*).  One
+// B3e <- Bm as bf16x3 pieces in MFMA fragment order, one 20 KiB image per (vertex group, k-step) (layout: layout.h, EB_*).  One
 // thread per (vertex group, k-step, vertex half and coordinate, lane): 8 consecutive k of one column, its three pieces.
 __global__ void relayout_basis_exact_kernel(const float * __restrict__ Bm, int64_t ldB, int64_t V, int64_t nvg, uint8_t * __restrict__ B3e)
 {
@@ -136,9 +135,9 @@ __global__ void skin_tables_exact_kernel(const uint8_t * __restrict__ wIdx, cons
   reinterpret_cast<float *>(g + EB_IMG + EB_TAB_OFF)[c] = v < V ? 1.0f / wSum[v] : 0.0f;
 }
 
-// B2h <- Bm and the skinning weights as fp16x2 pieces in MFMA fragment order (layout: common.h).  One thread per 16-byte
+// B2h <- Bm and the skinning weights as fp16x2 pieces in MFMA fragment order (layout: layout.h).  One thread per 16-byte
 // chunk pair (hi, lo): slots 0..13: ((vg * 15 + ks) * 6 + vh * 3 + x) * 64 + lane; slot 14: weights, cw, padding.
-// hperm [nvg * 64]: the vertex in each slot of each group (-1: none), gflags [nvg]: the group's k-step flags (common.h, HB_PERM_OFF).
+// hperm [nvg * 64]: the vertex in each slot of each group (-1: none), gflags [nvg]: the group's k-step flags (layout.h, HB_PERM_OFF).
 __global__ void relayout_basis_f16x2_kernel(const float * __restrict__ Bm, int64_t ldB, const float * __restrict__ W,
                                             const float * __restrict__ wSum, int64_t V, int64_t nvg, float sB, float sG,
                                             uint8_t * __restrict__ B2h, const int32_t * __restrict__ hperm,
@@ -257,28 +256,6 @@ static hipError_t upload(DevPtr<T> & dst, const T * src, size_t count)
   if(count) e = hipMemcpy(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice);
   return e;
 }
-
-// Forms of the fused kernel, {smplpp_fk's, the IK / VPoser loops' internal launches'}, decided once at model creation.  Default:
-// smplpp_fk runs e (skin_e.hip: fp32-exact operands, the reference's arithmetic) and the loops h (skin_h.hip: fp16x2 operands,
-// 3e-7 m); SMPLPP_SKIN = e | h | b | v puts every launch on that form.  The split-operand kernels address their basis images
-// with 32-bit buffer offsets: a mesh whose image would reach 2 GiB (more than ~745k vertices for h, ~410k for b) takes the
-// first form (64-bit addressing).  e keeps at most 4 skinning weights per vertex in registers and b at most 8: a model with
-// more takes the next form.
-static std::pair<char, char> choose_forms(const char * env, int maxw, int64_t VGPn)
-{
-  const char e = env ? env[0] : 0;
-  char forms[2] = {'e', 'h'};
-  if(e == 'e' || e == 'h' || e == 'b' || e == 'v') forms[0] = forms[1] = e;
-  for(char & f : forms)
-  {
-    if(f == 'h' && VGPn * HB_SLOTS * HB_IMG > 0x7fffff00LL) f = 'v';
-    if(f == 'e' && VGPn * EB_KS * EB_IMG > 0x7fffff00LL) f = 'v';
-    if(f == 'b' && VGPn * BB_KS * BB_B_BYTES > 0x7fffff00LL) f = 'v';
-    if(f == 'e' && maxw > 4) f = 'b';
-    if(f == 'b' && maxw > 8) f = 'v';
-  }
-  return {forms[0], forms[1]};
-}
 } // namespace smplpp_hip
 
 using namespace smplpp_hip;
@@ -315,6 +292,17 @@ extern "C" int smplpp_model_destroy(smplpp_model * m)
   return SMPLPP_OK;
 }
 
+// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM and SMPLPP_DEPTH_RASTER_INLINE are read here, once per model (m.maxw and m.VGPn are set)
+static void read_env(smplpp_model & m)
+{
+  std::tie(m.form, m.form_ik) = choose_forms(getenv("SMPLPP_SKIN"), m.maxw, m.VGPn);
+  const char * pd_env = getenv("SMPLPP_POINT_DISTANCE_FORM"); // query | tiled: one form of smplpp_point_mesh_distance for every K
+  m.pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
+  const char * dr_env = getenv("SMPLPP_DEPTH_RASTER_INLINE"); // 0..4096: the largest box a face's own thread walks in smplpp_depth_raster
+  m.dr_inline = dr_env && dr_env[0] >= '0' && dr_env[0] <= '9' ? atoi(dr_env) : -1;
+}
+
+// Validate, build the host tables (model_tables.h), then upload them and lay the bases out on the device.
 extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const float * S, const float * P,
                                    const float * Jreg, const float * W, const int64_t * kintree, const int32_t * faces1,
                                    int device, smplpp_model ** out)
@@ -327,24 +315,9 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   int rc = smplpp_device_count(&ndev);
   if(rc) return rc;
   if(device < 0 || device >= ndev) return fail(SMPLPP_ERR_INVALID, "Failed to fetch device index!"); // src/SMPL.cpp:295
-  // kinematic tree: row 0 = parent (src/WorldTransformation.cpp:523); must be topologically ordered like SMPL's
-  std::vector<int32_t> parent(NJ);
-  parent[0] = -1;
-  for(int i = 1; i < NJ; i++)
-  {
-    if(kintree[i] < 0 || kintree[i] >= i) return fail(SMPLPP_ERR_INVALID, "Cannot set kinematic tree: parent(i) must precede i");
-    parent[i] = (int32_t)kintree[i];
-  }
-  for(int64_t i = 0; i < F * 3; i++)
-    if(faces1[i] < 1 || faces1[i] > V) return fail(SMPLPP_ERR_INVALID, "face_indices must be 1-based vertex ids");
-  // skinning weights: the non-zeros are kept (real SMPL has <= 4 per vertex), a dense table otherwise
-  int maxnz = 0;
-  for(int64_t v = 0; v < V; v++)
-  {
-    int nz = 0;
-    for(int j = 0; j < NJ; j++) nz += (W[v * NJ + j] != 0.0f);
-    maxnz = std::max(maxnz, nz);
-  }
+  std::vector<int32_t> parent;
+  if(const char * why = check_tree(kintree, parent)) return fail(SMPLPP_ERR_INVALID, why);
+  if(const char * why = check_faces(faces1, F, V)) return fail(SMPLPP_ERR_INVALID, why);
 
   HIP_TRY(hipSetDevice(device));
   std::unique_ptr<smplpp_model> m(new smplpp_model());
@@ -354,19 +327,35 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   m->VGn = (V + VG - 1) / VG;
   m->ldB = m->VGn * 3 * VG;
   m->VGPn = (V + 63) / 64;
-  m->maxw = maxnz <= 4 ? 4 : (maxnz <= 8 ? 8 : NJ);
-  m->h_parent = parent;
-  std::tie(m->form, m->form_ik) = choose_forms(getenv("SMPLPP_SKIN"), m->maxw, m->VGPn);
 
-  // --- blend bases -> Bm, regressor fold (device side; the raw arrays are only needed transiently).  Only the operand layouts
-  // the chosen forms read are built.
-  {
-    const char * pd_env = getenv("SMPLPP_POINT_DISTANCE_FORM"); // query | tiled: one form of smplpp_point_mesh_distance for every K
-    m->pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
-    const char * dr_env = getenv("SMPLPP_DEPTH_RASTER_INLINE"); // 0..4096: the largest box a face's own thread walks in smplpp_depth_raster
-    m->dr_inline = dr_env && dr_env[0] >= '0' && dr_env[0] <= '9' ? atoi(dr_env) : -1;
-  }
+  // --- host tables; only the operand layouts the chosen forms read are built
+  const SkinWeights sw = skin_weights(W, V);
+  m->maxw = sw.maxw;
+  read_env(*m);
   auto uses = [&](char f) { return m->form == f || m->form_ik == f; };
+  VertexGroups hgroups;
+  if(uses('h'))
+  {
+    const HScales hs = h_scales(P, S, vt, V);
+    if(hs.refusal) return fail(SMPLPP_ERR_INVALID, hs.refusal);
+    m->sB = hs.sB;
+    m->sG = hs.sG;
+    hgroups = h_vertex_groups(W, V);
+  }
+  const JointLevels levels = joint_levels(parent);
+  const ChainTables chain = chain_tables(parent, levels);
+  const std::vector<int32_t> anc = ik_tree_tables(parent, levels);
+  Adjacency adj = adjacency(faces1, F, V);
+  const RingTables ring = ik_ring_tables(adj.faces.data(), adj.adjOff.data(), adj.adjFace.data(), F, V);
+  m->nlev = levels.nlev;
+  m->chain_fast = chain.chain_fast;
+  m->madj = ring.madj;
+  m->h_parent = parent;
+  m->h_faces = std::move(adj.faces);
+  m->h_adjOff = std::move(adj.adjOff);
+  m->h_adjFace = std::move(adj.adjFace);
+
+  // --- blend bases -> Bm, regressor fold (device side; the raw arrays are only needed transiently)
   HIP_TRY(upload(m->Pvm, P, (size_t)V * 3 * NP)); // kept: vertex-major copies serve the sparse IK Jacobian (contiguous 2.5 KB per vertex)
   HIP_TRY(upload(m->Svm, S, (size_t)V * 3 * NB));
   DevPtr<float> dT, dJreg;
@@ -391,35 +380,10 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   dT.reset(); // (here, before the launches below: freeing device memory waits for the device)
   dJreg.reset();
 
-  // --- skinning weights (m->maxw per vertex) ---
-  const int64_t Vpad = m->VGn * VG;
-  std::vector<uint8_t> hIdx((size_t)Vpad * m->maxw, 0);
-  std::vector<float> hVal((size_t)Vpad * m->maxw, 0.0f), hSum((size_t)Vpad, 1.0f);
-  for(int64_t v = 0; v < V; v++)
-  {
-    int q = 0;
-    float s = 0.0f;
-    for(int j = 0; j < NJ; j++)
-    {
-      float w = W[v * NJ + j];
-      s += w; // ascending j, fp32: h[3] = sum_j W[v,j] * 1 (src/LinearBlendSkinning.cpp:463-467)
-      if(m->maxw == NJ)
-      {
-        hIdx[v * NJ + j] = (uint8_t)j;
-        hVal[v * NJ + j] = w;
-      }
-      else if(w != 0.0f)
-      {
-        hIdx[v * m->maxw + q] = (uint8_t)j;
-        hVal[v * m->maxw + q] = w;
-        q++;
-      }
-    }
-    hSum[v] = s;
-  }
-  HIP_TRY(upload(m->wIdx, hIdx.data(), hIdx.size()));
-  HIP_TRY(upload(m->wVal, hVal.data(), hVal.size()));
-  HIP_TRY(upload(m->wSum, hSum.data(), hSum.size()));
+  // --- skinning weights, then the operand images of the e and h forms
+  HIP_TRY(upload(m->wIdx, sw.wIdx.data(), sw.wIdx.size()));
+  HIP_TRY(upload(m->wVal, sw.wVal.data(), sw.wVal.size()));
+  HIP_TRY(upload(m->wSum, sw.wSum.data(), sw.wSum.size()));
   HIP_TRY(upload(m->Wdense, W, (size_t)V * NJ));
   if(uses('e'))
   {
@@ -434,80 +398,10 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
   }
   if(uses('h'))
   {
-    // fp16x2 operands: power-of-two scales that put the largest basis entry / a generous bound of the relative
-    // translations (16 x the template's extent) just under fp16's range, so that both pieces of every value that matters
-    // are normal fp16 numbers
-    float bmax = 0.0f, tmax = 0.0f;
-    for(int64_t i = 0; i < V * 3 * NP; i++) bmax = std::max(bmax, std::fabs(P[i]));
-    for(int64_t i = 0; i < V * 3 * NB; i++) bmax = std::max(bmax, std::fabs(S[i]));
-    for(int64_t i = 0; i < V * 3; i++) tmax = std::max(tmax, std::fabs(vt[i]));
-    bmax = std::max(bmax, tmax);
-    if(!(bmax > 0.0f) || !std::isfinite(bmax)) return fail(SMPLPP_ERR_INVALID, "Cannot initialize a SMPL model!");
-    m->sB = std::exp2(std::floor(std::log2(32768.0f / bmax)));
-    m->sG = std::exp2(std::floor(std::log2(32768.0f / (16.0f * tmax > 1.0f ? 16.0f * tmax : 1.0f))));
     HIP_TRY(dev_alloc(m->B2h, (size_t)m->VGPn * HB_SLOTS * HB_IMG));
-    // Vertex groups by skinning class (common.h, HB_PERM_OFF).  (1) A group is 64 CONSECUTIVE vertices and its class what their
-    // weights touch — joints 0..15 only, both halves, joints 16..23 only.  (Sorting the VERTICES by class first, which makes 73 of
-    // the synthetic model's 108 groups single-class instead of 11, was measured: the step went from 46 to 62 us — a group's 64
-    // output rows of 12 bytes were then scattered over ~200 vertex positions, and the 85 MB of write-once output lost its
-    // coalescing.  Models whose vertex order follows the body parts — SMPL's does — have their single-class groups as they are.)
-    // (2) the groups dealt round-robin over the eight XCD slices of skin_kernel_h ([x nvg / 8, (x + 1) nvg / 8)), so that every XCD
-    // gets the same mix; (3) inside a slice the classes interleaved by fractional rank, so that every workgroup's run of
-    // consecutive groups gets it too (a slice of cheap groups beside a slice of full ones would finish with the full ones).
-    const int64_t nvg = m->VGPn;
-    std::vector<int32_t> hperm((size_t)nvg * 64, -1), gflags((size_t)nvg, 1);
-    {
-      std::vector<int> vcls((size_t)V);
-      for(int64_t v = 0; v < V; v++)
-      {
-        bool lo = false, hi = false;
-        for(int j = 0; j < NJ; j++)
-          if(W[v * NJ + j] != 0.0f) (j < 16 ? lo : hi) = true;
-        vcls[(size_t)v] = hi ? (lo ? 1 : 2) : 0;
-      }
-      std::vector<int> tflags((size_t)nvg, 0);
-      for(int64_t t = 0; t < nvg; t++)
-        for(int i = 0; i < 64 && t * 64 + i < V; i++)
-        {
-          const int c = vcls[(size_t)(t * 64 + i)];
-          tflags[(size_t)t] |= (c == 0 ? 1 : (c == 1 ? 3 : 2));
-        }
-      // (2) + (3): per XCD slice the sorted groups it is dealt, then their order inside the slice
-      std::vector<std::vector<int64_t>> bin(8);
-      {
-        int x = 0;
-        for(int64_t t = 0; t < nvg; t++)
-        {
-          for(int tries = 0; tries < 8 && (int64_t)bin[x].size() >= (((x + 1) * nvg) >> 3) - ((x * nvg) >> 3); tries++) x = (x + 1) & 7;
-          bin[x].push_back(t);
-          x = (x + 1) & 7;
-        }
-      }
-      int64_t g = 0;
-      for(int x = 0; x < 8; x++)
-      {
-        int cnt[4] = {0, 0, 0, 0}, seen[4] = {0, 0, 0, 0};
-        for(int64_t t : bin[x]) cnt[tflags[(size_t)t]]++;
-        std::vector<std::pair<double, int64_t>> keyed;
-        for(int64_t t : bin[x])
-        {
-          const int f = tflags[(size_t)t];
-          keyed.push_back({(seen[f] + 0.5) / cnt[f], t});
-          seen[f]++;
-        }
-        std::stable_sort(keyed.begin(), keyed.end(), [](const std::pair<double, int64_t> & a, const std::pair<double, int64_t> & b) { return a.first < b.first; });
-        for(auto & kt : keyed)
-        {
-          const int64_t t = kt.second;
-          for(int i = 0; i < 64 && t * 64 + i < V; i++) hperm[(size_t)(g * 64 + i)] = (int32_t)(t * 64 + i);
-          gflags[(size_t)g] = tflags[(size_t)t] ? tflags[(size_t)t] : 1;
-          g++;
-        }
-      }
-    }
     DevPtr<int32_t> dPerm, dFlags;
-    HIP_TRY(upload(dPerm, hperm.data(), hperm.size()));
-    HIP_TRY(upload(dFlags, gflags.data(), gflags.size()));
+    HIP_TRY(upload(dPerm, hgroups.perm.data(), hgroups.perm.size()));
+    HIP_TRY(upload(dFlags, hgroups.flags.data(), hgroups.flags.size()));
     const int64_t cnt = m->VGPn * (HB_KS * 6 * 64 + 4 * 64 + 64);
     relayout_basis_f16x2_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256)>>>(m->Bm.get(), m->ldB, m->Wdense.get(), m->wSum.get(), V,
                                                                                  m->VGPn, m->sB, m->sG, m->B2h.get(), dPerm.get(), dFlags.get());
@@ -515,141 +409,22 @@ extern "C" int smplpp_model_create(int64_t V, int64_t F, const float * vt, const
     HIP_TRY(hipDeviceSynchronize());
   }
   if(!uses('v')) m->Bm.reset(); // only the fp32-MFMA form reads the K-major fp32 basis
+
+  // --- the small tables: kinematic tree, faces and adjacency, IK tree and ring tables
   HIP_TRY(upload(m->parent, parent.data(), parent.size()));
   {
     const int zero[RANGE_SLOTS] = {};
     HIP_TRY(upload(m->range_flag, zero, RANGE_SLOTS));
   }
-  {
-    // joints by depth: the FK chain advances one tree level per step (SMPL: 9 levels)
-    std::vector<int32_t> depth(NJ, 0), lv(NJ + 1 + NJ, 0);
-    int nlev = 1;
-    for(int i = 1; i < NJ; i++)
-    {
-      depth[i] = depth[parent[i]] + 1;
-      nlev = std::max(nlev, depth[i] + 1);
-    }
-    int pos = 0;
-    for(int L = 0; L < nlev; L++)
-    {
-      lv[L] = pos;
-      for(int i = 0; i < NJ; i++)
-        if(depth[i] == L) lv[NJ + 1 + pos++] = i;
-    }
-    lv[nlev] = pos;
-    m->nlev = nlev;
-    // per (level, slot) the joint and its parent for the pose kernel's chain wavefront (5 joints of a level at a time, 12
-    // lanes each): read once into registers instead of three dependent LDS look-ups per level.  chain_fast: the tree has at
-    // most CT_LEV levels of at most 5 joints (SMPL: 9 levels, widest 5); other trees take the generic loop.
-    m->chain_fast = nlev <= CT_LEV;
-    lv.resize(CT_OFF + 60 * CT_LEV * 2, 0);
-    for(int q = 0; q < 60 * CT_LEV; q++)
-    {
-      lv[CT_OFF + 2 * q] = 0x00ffff;
-      lv[CT_OFF + 2 * q + 1] = CT_P_ZERO | (CT_P_ZERO << 10) | (1 << 20);
-    }
-    std::vector<int> slot_of(NJ, 0); // slot of a joint inside its level
-    for(int L = 0; L < nlev && m->chain_fast; L++)
-    {
-      const int cnt = lv[L + 1] - lv[L];
-      if(cnt > 5) m->chain_fast = false;
-      for(int q = 0; q < cnt && q < 5; q++)
-      {
-        const int i = lv[NJ + 1 + lv[L] + q];
-        slot_of[i] = q;
-        const int p = parent[i];
-        const int word = i | ((p >= 0 ? p : 0xff) << 8) | ((p >= 0 ? slot_of[p] : 0) << 16); // (the parent sits one level up: already placed)
-        for(int e = 0; e < 12; e++)
-        {
-          const int c = e % 4;
-          // the lane's operand: column c of R_i (stride 3), or j_i minus j_p (root: minus zero)
-          const int aidx = c < 3 ? CT_P_R + i * 9 + c : CT_P_J + i * 3;
-          const int bidx = (c == 3 && p >= 0) ? CT_P_J + p * 3 : CT_P_ZERO;
-          lv[CT_OFF + ((q * 12 + e) * CT_LEV + L) * 2] = word;
-          lv[CT_OFF + ((q * 12 + e) * CT_LEV + L) * 2 + 1] = aidx | (bidx << 10) | ((c < 3 ? 3 : 1) << 20);
-        }
-      }
-    }
-    HIP_TRY(upload(m->lvl, lv.data(), lv.size()));
-  }
-
-  // --- faces + adjacency (src/SMPL.cpp:620-640; emplace keeps one entry per (vertex, face)) ---
-  m->h_faces.resize((size_t)F * 3);
-  for(int64_t i = 0; i < F * 3; i++) m->h_faces[i] = faces1[i] - 1;
-  std::vector<std::vector<int32_t>> adj((size_t)V);
-  for(int64_t f = 0; f < F; f++)
-    for(int i = 0; i < 3; i++)
-    {
-      auto & a = adj[m->h_faces[f * 3 + i]];
-      if(a.empty() || a.back() != (int32_t)f) a.push_back((int32_t)f);
-    }
-  m->h_adjOff.assign((size_t)V + 1, 0);
-  for(int64_t v = 0; v < V; v++) m->h_adjOff[v + 1] = m->h_adjOff[v] + (int32_t)adj[v].size();
-  m->h_adjFace.reserve((size_t)m->h_adjOff[V]);
-  for(int64_t v = 0; v < V; v++) m->h_adjFace.insert(m->h_adjFace.end(), adj[v].begin(), adj[v].end());
+  HIP_TRY(upload(m->lvl, chain.lvl.data(), chain.lvl.size()));
   HIP_TRY(upload(m->faces, m->h_faces.data(), m->h_faces.size()));
   HIP_TRY(upload(m->adjOff, m->h_adjOff.data(), m->h_adjOff.size()));
   HIP_TRY(upload(m->adjFace, m->h_adjFace.data(), m->h_adjFace.size()));
+  HIP_TRY(upload(m->anc, anc.data(), anc.size()));
+  if(!ring.faceRing.empty())
   {
-    // tree tables of the IK evaluation (common.h TREE_*); trees deeper than TREE_DMAX keep the masks only (smplpp_ik_create
-    // refuses them)
-    std::vector<int32_t> tr(TREE_SIZE, -1), depth(NJ, 0);
-    for(int i = 0; i < NJ; i++)
-    {
-      tr[TREE_ANC + i] = (1 << i) | (i ? tr[TREE_ANC + parent[i]] : 0);
-      depth[i] = i ? depth[parent[i]] + 1 : 0;
-    }
-    int pos = 0;
-    for(int L = 0; L <= TREE_DMAX; L++)
-    {
-      tr[TREE_LVL + L] = pos;
-      for(int i = 0; i < NJ && L < TREE_DMAX; i++)
-        if(depth[i] == L) tr[TREE_LVLJ + pos++] = i;
-    }
-    HIP_TRY(upload(m->anc, tr.data(), tr.size()));
-  }
-  if(V <= 65535 && F > 0)
-  {
-    // IK ring tables (topology only): what a task on face f touches when it differentiates a normal — the face's vertices
-    // (slots 0..2), then the distinct vertices of the faces around them, first occurrence first; the map gives every
-    // (vertex of the face, adjacent face, corner) its slot.  The tables hold `madj` faces per vertex: 12, or 16 when some vertex of
-    // this topology has more (the evaluation then runs its 16-face instantiation; beyond 16 a task with a normal term on such a
-    // vertex is reported, smplpp_ik_get_status bit 2) — and 3 (madj + 1) + 1 ring vertices.
-    int maxval = 0;
-    for(int64_t v = 0; v < V; v++) maxval = std::max<int>(maxval, m->h_adjOff[v + 1] - m->h_adjOff[v]);
-    m->madj = maxval > MAXADJ ? MAXADJ_WIDE : MAXADJ;
-    const int MADJ_ = m->madj, MRING_ = 3 * (MADJ_ + 1) + 1;
-    std::vector<uint16_t> ring((size_t)F * (MRING_ + 1), 0);
-    std::vector<uint8_t> map((size_t)F * 3 * MADJ_ * 3, 0);
-    for(int64_t f = 0; f < F; f++)
-    {
-      uint16_t * rg = ring.data() + f * (MRING_ + 1);
-      uint8_t * mp = map.data() + f * (3 * MADJ_ * 3);
-      int nr = 0;
-      for(int i = 0; i < 3; i++) rg[1 + nr++] = (uint16_t)m->h_faces[f * 3 + i];
-      for(int i = 0; i < 3; i++)
-      {
-        const int32_t u = m->h_faces[f * 3 + i], b0 = m->h_adjOff[u];
-        const int cnt = std::min<int>(m->h_adjOff[u + 1] - b0, MADJ_);
-        for(int a = 0; a < cnt; a++)
-          for(int cc = 0; cc < 3; cc++)
-          {
-            const int32_t v = m->h_faces[(int64_t)m->h_adjFace[b0 + a] * 3 + cc];
-            int slot = -1;
-            for(int q = 0; q < nr; q++)
-              if(rg[1 + q] == (uint16_t)v) slot = q;
-            if(slot < 0 && nr < MRING_)
-            {
-              slot = nr;
-              rg[1 + nr++] = (uint16_t)v;
-            }
-            mp[(i * MADJ_ + a) * 3 + cc] = (uint8_t)(slot < 0 ? 0 : slot);
-          }
-      }
-      rg[0] = (uint16_t)nr;
-    }
-    HIP_TRY(upload(m->faceRing, ring.data(), ring.size()));
-    HIP_TRY(upload(m->faceMap, map.data(), map.size()));
+    HIP_TRY(upload(m->faceRing, ring.faceRing.data(), ring.faceRing.size()));
+    HIP_TRY(upload(m->faceMap, ring.faceMap.data(), ring.faceMap.size()));
   }
   *out = m.release();
   return SMPLPP_OK;

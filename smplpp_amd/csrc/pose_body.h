@@ -233,7 +233,7 @@ __device__ __forceinline__ void pose_body(const PoseArgs & pa, const int64_t f, 
   // ---- phase 2
   if(pa.A3 && tid < 84)
   {
-    // bf16x3 pieces in MFMA fragment order (layout: common.h): chunk c = k / 8 is element block j of MFMA lane 32 h + r in
+    // bf16x3 pieces in MFMA fragment order (layout: layout.h): chunk c = k / 8 is element block j of MFMA lane 32 h + r in
     // k-step ks = c / 2, h = c % 2; thread (c, s) writes the 16 bytes of piece s
     const int c = tid % 28, sp = tid / 28, ks = c >> 1, h = c & 1;
     const int64_t ftp = f >> 6;
@@ -256,7 +256,7 @@ __device__ __forceinline__ void pose_body(const PoseArgs & pa, const int64_t f, 
   }
   if(pa.A2h && tid >= 96 && tid < 96 + 28)
   {
-    // fp16x2 pieces in MFMA fragment order (layout: common.h): chunk c = k / 8 is element block j of MFMA lane 32 h + r in
+    // fp16x2 pieces in MFMA fragment order (layout: layout.h): chunk c = k / 8 is element block j of MFMA lane 32 h + r in
     // k-step ks = c / 2, h = c % 2; both pieces of the chunk by one thread
     const int c = tid - 96, ks = c >> 1, h = c & 1;
     const int64_t ft = f >> 6;
@@ -320,7 +320,7 @@ __device__ __forceinline__ void pose_body(const PoseArgs & pa, const int64_t f, 
   if(pa.G2h && tid >= 64 && tid < 64 + 36)
   {
     // the relative transforms once more as the A operand of the blend MFMAs of skin_h.hip (rows = frames, k = joint):
-    // thread (entry e, chunk c) writes both fp16x2 pieces of joints 8 c .. 8 c + 7 of entry e (layout: common.h)
+    // thread (entry e, chunk c) writes both fp16x2 pieces of joints 8 c .. 8 c + 7 of entry e (layout: layout.h)
     const int e = (tid - 64) / 3, c = (tid - 64) % 3, r4 = e / 4, cc = e % 4;
     const int64_t ft = f >> 6;
     const int fh = (int)((f >> 5) & 1), r = (int)(f & 31);

@@ -2,7 +2,7 @@
 // Reference path: rest = T + S.beta + P.c (/root/reference/src/BlendShape.cpp:670-683, 762-765,
 // src/JointRegression.cpp:551-565) and the skinning of src/LinearBlendSkinning.cpp:445-553 (+ src/SMPL.cpp:726-727).
 //
-// Operands: every fp32 value is carried as TWO fp16 pieces of a power-of-two multiple of it (common.h, "fp16x2"): 22
+// Operands: every fp32 value is carried as TWO fp16 pieces of a power-of-two multiple of it (layout.h, "fp16x2"): 22
 // significant bits, and a product costs THREE v_mfma_f32_32x32x16_f16 (lo.hi + hi.lo + hi.hi) instead of the six of the
 // bf16x3 form (skin_b.hip).  Error of the representation alone, measured at real-SMPL magnitudes (|posedirs| <= 5e-2,
 // |beta| <= 3, 1.5 rad rotations): 3e-7 m, below the accumulation error of a plain fp32 GEMM of the same data
@@ -22,7 +22,7 @@
 // (buffer_load_dwordx4 ... lds) seven slots ahead; slot 14 of an item carries the group's skinning weights.
 // One raw s_barrier per slot publishes the next image (counted vmcnt: DMAs stay in flight across it).
 // XCD x owns an eighth of the vertex groups (its slice of B2h, 2.4 MB, lives in that XCD's L2 and is read from HBM once).
-// Round 5: a vertex group is 64 CONSECUTIVE vertices with a skinning class (common.h, HB_PERM_OFF: which k-steps of the skinning
+// Round 5: a vertex group is 64 CONSECUTIVE vertices with a skinning class (layout.h, HB_PERM_OFF: which k-steps of the skinning
 // product its vertices' weights touch; the groups are dealt over and inside the XCD slices with the classes interleaved; slot 14
 // carries the group's vertex ids and its flags).  A group whose weights live in one k-step runs the skinning phase in the instantiation that issues only that k-step's
 // MFMAs and G' fragment reads — 3 (joints 0..15 only) or 2 (joints 16..23 only) MFMAs per entry instead of 5; exact zeros skipped.

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void vposer_kernel(const float * __restrict__ 
 // ---- forward + Jacobian on the f16 matrix pipe.
 // d(out)/dz is carried through the MLP as 32 tangent columns per row.  Layer 1: [512 x 512] . [512 x 32], layer 2:
 // [126 x 512] . [512 x 32] per frame: v_mfma_f32_32x32x16_f16 with every fp32 operand as two fp16 pieces of a power-of-two
-// multiple (common.h, "fp16x2": 22 significant bits, three products hi.hi + hi.lo + lo.hi) — 96 MFMAs of 32 cycles per
+// multiple (layout.h, "fp16x2": 22 significant bits, three products hi.hi + hi.lo + lo.hi) — 96 MFMAs of 32 cycles per
 // 32-row tile where the exact-fp32 form (v_mfma_f32_32x32x2_f32, 1/16 of the rate) took 256 of 64.
 //   A operand: the weights, split once at creation, in fragment order: w1h [16 row tiles][32 k-steps][piece 2][64 lanes][8 fp16]
 //              (lane 32 h + r holds W[32 tile + r][16 ks + 8 h + j], j = 0..7), straight from L2 to registers;

@@ -250,7 +250,7 @@ def relabel_vertices(model: dict, order) -> dict:
 
 def skinning_classes(weights):
     """Per vertex: 0 = weights on joints 0..15 only, 1 = on both halves, 2 = on joints 16..23 only (the two k-steps of the fused
-    kernel's skinning product: smplpp_amd/csrc/common.h, HB_PERM_OFF)."""
+    kernel's skinning product: smplpp_amd/csrc/layout.h, HB_PERM_OFF)."""
     import numpy as np
 
     w = np.asarray(weights)

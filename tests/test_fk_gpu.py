@@ -466,7 +466,7 @@ def test_fk_out_of_range_operands_are_reported(smpl, synth_model, oracle_synth, 
 
 def test_fk_skinning_class_groups_on_a_part_ordered_numbering(synth_model, oracle_synth, monkeypatch):
     """skin_kernel_h runs a vertex group (64 consecutive vertices) whose skinning weights live in ONE k-step of the blend product —
-    joints 0..15 only, or joints 16..23 only (SMPL's arms) — in an instantiation that issues only that k-step's MFMAs (common.h,
+    joints 0..15 only, or joints 16..23 only (SMPL's arms) — in an instantiation that issues only that k-step's MFMAs (layout.h,
     HB_PERM_OFF), and deals the groups over the XCD slices by class.  The stand-in's spiral numbering has 11 such groups of 108 and
     none of the second kind; the SAME body renumbered so that its vertex order follows the parts (as SMPL's does) has 54 + 19.  The
     renumbered model must match the oracle on ITS numbering, and — the skipped products being exact zeros — give the original

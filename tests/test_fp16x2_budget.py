@@ -38,7 +38,7 @@ def test_fp16x2_three_product_error(name, pmag, bmag, th, ftz):
     B[207:217] = rng.normal(0, 0.03, (10, C)) * (1 / np.arange(1, 11))[:, None]
     B[217] = rng.uniform(-0.9, 0.9, C)
     ref = A.astype(np.float64) @ B.astype(np.float64)
-    sA = 64.0  # HB_SA in smplpp_amd/csrc/common.h
+    sA = 64.0  # HB_SA in smplpp_amd/csrc/layout.h
     sB = 2.0 ** np.floor(np.log2(32768 / np.abs(B).max()))  # smplpp_model_create
     ah, al = _split(A, sA, ftz)
     bh, bl = _split(B, sB, ftz)
