@@ -523,6 +523,60 @@ public:
           "SMPL");
     return out;
   }
+  // A per-vertex quantity attr [N,V,C] (C <= 32) carried into the image of depthRaster (smplpp_raster_interpolate): image [N,H,W,C]
+  // from `face` [N,H,W] and `bary` [N,H,W,3] as depthRaster gave them; 0 at background.
+  Tensor rasterInterpolate(const Tensor & attr, const Tensor & face, const Tensor & bary) const
+  {
+    const char * what = "Cannot interpolate over the image!";
+    if(attr.dim() != 3 || attr.dtype != kFloat32 || attr.size(1) != V_ || face.dim() != 3 || face.size(0) != attr.size(0) ||
+       (face.dtype != kInt64 && face.dtype != kInt32) || bary.dtype != kFloat32 || bary.numel() != face.numel() * 3)
+      throw Exception("SMPL", what);
+    const int64_t n = attr.size(0), C = attr.size(2), H = face.size(1), W = face.size(2);
+    Tensor image({n, H, W, C});
+    check(smplpp_raster_interpolate(m_.get(), n, attr.ptr(), C, H, W, face.idata.data(), bary.ptr(), image.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return image;
+  }
+  // Its backward pass (smplpp_raster_interpolate_vjp) on the last launch's vertices, with the camera and near of the depthRaster call
+  // that gave `face` and `bary`: dL/dattr [N,V,C] and, through the barycentrics, dL/dverts [N,V,3] for dL/dimage = gradImage
+  // [N,H,W,C].  wantAttr / wantVerts false: that output stays undefined.  accumulate: an output that is defined on entry is added
+  // into.
+  struct RasterInterpolateGrad
+  {
+    Tensor attr, verts;
+  };
+  RasterInterpolateGrad rasterInterpolateBackward(const Tensor & attr, const Tensor & camera, const Tensor & face, const Tensor & bary,
+                                                  const Tensor & gradImage, float near = 0.05f, bool wantAttr = true,
+                                                  bool wantVerts = true, RasterInterpolateGrad * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    const char * what = "Cannot back-propagate through the interpolated image!";
+    const std::vector<float> cam = cameraRows(camera, n, what);
+    if(attr.dim() != 3 || attr.dtype != kFloat32 || attr.size(0) != n || attr.size(1) != V_ || face.dim() != 3 || face.size(0) != n ||
+       (face.dtype != kInt64 && face.dtype != kInt32) || bary.dtype != kFloat32 || bary.numel() != face.numel() * 3 ||
+       gradImage.dtype != kFloat32 || gradImage.numel() != face.numel() * attr.size(2) || (!wantAttr && !wantVerts))
+      throw Exception("SMPL", what);
+    RasterInterpolateGrad local;
+    RasterInterpolateGrad & out = accumulate ? *accumulate : local;
+    if(accumulate)
+    {
+      if(wantAttr != out.attr.defined() || wantVerts != out.verts.defined() ||
+         (wantAttr && (out.attr.dtype != kFloat32 || out.attr.numel() != attr.numel())) ||
+         (wantVerts && (out.verts.dtype != kFloat32 || out.verts.numel() != n * V_ * 3)))
+        throw Exception("SMPL", what);
+    }
+    else
+    {
+      if(wantAttr) out.attr = Tensor(attr.shape);
+      if(wantVerts) out.verts = Tensor({n, V_, 3});
+    }
+    check(smplpp_raster_interpolate_vjp(m_.get(), n, attr.ptr(), attr.size(2), verts_.ptr(), cam.data(), face.size(1), face.size(2), near,
+                                        face.idata.data(), bary.ptr(), gradImage.ptr(), wantAttr ? out.attr.ptr() : nullptr,
+                                        wantVerts ? out.verts.ptr() : nullptr, accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return out;
+  }
   // Exact Euclidean feature transform of binary images mask [N,H,W] (integer tensor, nonzero = set; smplpp_mask_distance_transform):
   // nearest [N,H,W] kInt64 (the linear index of the nearest set pixel of the frame, the lowest among equal distances; -1 without a
   // set pixel) and sqdist [N,H,W] kInt64 (px^2).

@@ -336,6 +336,44 @@ int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * verts /*[n,V,
 int smplpp_depth_raster_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H,
                             int64_t W, const int64_t * face /*[n,H,W]*/, const float * grad_depth /*[n,H,W]*/,
                             float * grad_verts /*[n,V,3]*/, int accumulate, int space, void * stream);
+/* Raster attribute interpolation: a per-vertex quantity attr [n,V,C], C in [1, 32], carried into the image of smplpp_depth_raster.
+ * face [n,H,W] and bary [n,H,W,3] are that call's outputs.  In fp32 with every operation rounded on its own (no FMA): for a pixel
+ * with f = face in [0, F), (a, b, c) the model's corners of f and (beta_a, beta_b, beta_c) = bary at the pixel, for each channel k
+ *    image[k] = (beta_a attr[a][k] + beta_b attr[b][k]) + beta_c attr[c][k];
+ * a background pixel (face = -1) gives +0 in every channel, whatever its bary and the attributes hold; so does a device-space id
+ * outside [-1, F).  image [n,H,W,C].  The bits of a frame do not depend on n, on its position in the batch or on the memory space.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, H or W outside [1, 8192], C outside [1, 32], n H W C, n V C, n V or
+ *    n F beyond int32 indexing, a host-space face id outside [-1, F) (the output is untouched).  Device data is never refused. */
+int smplpp_raster_interpolate(smplpp_model * m, int64_t n, const float * attr /*[n,V,C]*/, int64_t C, int64_t H, int64_t W,
+                              const int64_t * face /*[n,H,W]*/, const float * bary /*[n,H,W,3]*/, float * image /*[n,H,W,C]*/,
+                              int space, void * stream);
+/* Vector-Jacobian product of image above to the attributes and to the world-space vertices.  verts, camera, H, W, near are the
+ * arguments of the smplpp_depth_raster call that gave face and bary.  With g = grad_image [n,H,W,C] at a pixel:
+ *  - grad_attr [n,V,C] (face and bary held fixed as data): corner i of the pixel's face receives beta_i g[k] in channel k.
+ *  - grad_verts [n,V,3] is the gradient through the barycentrics (face and the pixel's ray held fixed, coverage not differentiated):
+ *    the function differentiated is sum_i beta_i(verts) (sum_k g[k] attr[i][k]), beta as the rasteriser defines them (the hit
+ *    point of the pixel centre's ray on the plane of the face's camera-space corners).  With e1, e2, n, nn, d, nd, dot and cross of
+ *    the rasteriser's rule, in fp32: gamma_i = sum over k, ascending from +0, of g[k] attr[i][k]; c1 = cross(e2, n),
+ *    c2 = cross(n, e1); q.x = ((gamma_b - gamma_a) c1.x + (gamma_c - gamma_a) c2.x) / nn (y, z alike); s = dot(q, d) / nd;
+ *    h.x = n.x s - q.x (y, z alike); camera-space corner i receives beta_i h (beta from bary), and R^T is applied once per vertex.
+ *  - the order of every sum: per face, its snapped bounding box (the rasteriser's vertex rule with `near`, clipped to the image,
+ *    row-major) is walked, entry r by lane r mod 8 in ascending r, over the pixels that name the face; the eight partial sums are
+ *    combined as ((l0+l4)+(l2+l6)) + ((l1+l5)+(l3+l7)); a vertex sums its faces' values in ascending face id, each from +0; for
+ *    grad_verts R^T follows as in smplpp_depth_raster_vjp.  accumulate = 0 stores the sum (untouched vertices get 0), 1 adds it to
+ *    the output.  No floating-point atomics; the bits do not depend on n, on the frame's position in the batch, on the memory space,
+ *    on which of the two outputs is asked for, or on SMPLPP_DEPTH_RASTER_INLINE (which is not read).
+ *  - a cotangent element g[k] of exactly 0 contributes nothing to either output, even on NaN data: a pixel whose C values are all 0
+ *    is as good as absent.  So is a pixel with face = -1 (or, in device space, an id out of range), a pixel outside its face's
+ *    snapped box, and a face with a refused corner.
+ *  - grad_attr or grad_verts may be NULL, not both.  No gradient to camera.
+ *  - SMPLPP_ERR_INVALID: as the forward, near not finite or <= 0, accumulate not 0 or 1, both outputs NULL (the outputs are
+ *    untouched).
+ *  - the handle keeps 24 bytes per (frame, vertex) and 48 bytes per (frame, face) of workspace, grown to the largest call. */
+int smplpp_raster_interpolate_vjp(smplpp_model * m, int64_t n, const float * attr /*[n,V,C]*/, int64_t C,
+                                  const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H, int64_t W, float near,
+                                  const int64_t * face /*[n,H,W]*/, const float * bary /*[n,H,W,3]*/,
+                                  const float * grad_image /*[n,H,W,C]*/, float * grad_attr /*[n,V,C] nullable*/,
+                                  float * grad_verts /*[n,V,3] nullable*/, int accumulate, int space, void * stream);
 /* Exact Euclidean feature transform of n binary images mask [n,H,W] (a nonzero byte = set), all in integers.  For pixel p = (row j,
  * column i) and the set pixels q = (j', i') of the same frame, d2(p, q) = (i-i')^2 + (j-j')^2: sqdist[p] is the minimum and
  * nearest[p] the linear index j' W + i' of the set pixel that attains it; among equal distances the lowest linear index wins (the

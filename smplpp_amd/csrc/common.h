@@ -167,6 +167,7 @@ struct WindingState;    // batched winding numbers and the signed point-to-mesh 
 struct SelfPenState;    // self-intersections, the self-penetration energy and its backward pass (self_penetration.hip)
 struct DepthRasterState; // the depth rasteriser and its backward pass (depth_raster.hip)
 struct SilhouetteState;  // the mask distance transform, the silhouette residuals and their backward pass (silhouette.hip)
+struct RasterInterpState; // the backward pass of the raster attribute interpolation (raster_interpolate.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -179,6 +180,7 @@ struct StateDelete
   void operator()(SelfPenState * s) const;
   void operator()(DepthRasterState * s) const;
   void operator()(SilhouetteState * s) const;
+  void operator()(RasterInterpState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -242,5 +244,6 @@ struct smplpp_model
   int dr_inline = -1;           // depth rasteriser: box pixels a face's own thread walks (SMPLPP_DEPTH_RASTER_INLINE, read at model creation): -1 = default
   smplpp_hip::StatePtr<smplpp_hip::DepthRasterState> dr; // depth-rasteriser workspace (depth_raster.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::SilhouetteState> sil; // silhouette workspace (silhouette.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::RasterInterpState> ri; // raster-interpolation backward workspace (raster_interpolate.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

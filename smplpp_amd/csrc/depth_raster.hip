@@ -39,9 +39,6 @@ constexpr int DR_INLINE_MAX = 4096;
 constexpr unsigned DR_LARGE_BLOCKS = 2048;  // grid of dr_large_kernel: 8192 wavefronts
 constexpr unsigned long long DR_EMPTY = ~0ull;
 
-__host__ __device__ inline int64_t dr_min(int64_t a, int64_t b) { return a < b ? a : b; }
-__host__ __device__ inline int64_t dr_max(int64_t a, int64_t b) { return a > b ? a : b; }
-
 struct DepthRasterState
 {
   DevBuf cam, snap;   // [n][V] float4 camera-space vertex, int2 snapped projection
@@ -66,44 +63,6 @@ __global__ __launch_bounds__(DR_T) void dr_vertex_kernel(const float * __restric
   const bool ok = dr_project(c, verts[idx * 3], verts[idx * 3 + 1], verts[idx * 3 + 2], near, xc, u, v, su, sv);
   cam[idx] = make_float4(xc[0], xc[1], xc[2], 0.0f);
   snap[idx] = ok ? make_int2((int)su, (int)sv) : make_int2(DR_BAD, DR_BAD);
-}
-
-enum
-{
-  DR_FACE_OK = 0,
-  DR_FACE_SKIPPED = 1, // a refused corner
-  DR_FACE_EMPTY = 2    // zero snapped area, or a box that holds no pixel centre of the image
-};
-__device__ inline int dr_face_setup(DrFace & t, const float4 * __restrict__ cam, const int2 * __restrict__ snap,
-                                    const int32_t * __restrict__ faces, int64_t frame, int64_t f, int64_t V, int64_t H, int64_t W)
-{
-  int32_t c[3];
-  int2 s[3];
-  for(int k = 0; k < 3; k++)
-  {
-    c[k] = faces[f * 3 + k];
-    s[k] = snap[frame * V + c[k]];
-  }
-  if(s[0].x == DR_BAD || s[1].x == DR_BAD || s[2].x == DR_BAD) return DR_FACE_SKIPPED;
-  for(int k = 0; k < 3; k++) t.x[k] = s[k].x, t.y[k] = s[k].y;
-  const int64_t A2 = (t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (t.y[1] - t.y[0]) * (t.x[2] - t.x[0]);
-  if(A2 == 0) return DR_FACE_EMPTY;
-  t.sgn = A2 > 0 ? 1 : -1;
-  const int64_t xmin = dr_min(t.x[0], dr_min(t.x[1], t.x[2])), xmax = dr_max(t.x[0], dr_max(t.x[1], t.x[2]));
-  const int64_t ymin = dr_min(t.y[0], dr_min(t.y[1], t.y[2])), ymax = dr_max(t.y[0], dr_max(t.y[1], t.y[2]));
-  // pixel centres 256 i + 128 inside [min, max]
-  t.i0 = (int)dr_max(0, (xmin + 127) >> 8), t.i1 = (int)dr_min(W - 1, (xmax - 128) >> 8);
-  t.j0 = (int)dr_max(0, (ymin + 127) >> 8), t.j1 = (int)dr_min(H - 1, (ymax - 128) >> 8);
-  if(t.i0 > t.i1 || t.j0 > t.j1) return DR_FACE_EMPTY;
-  const float4 a = cam[frame * V + c[0]], b = cam[frame * V + c[1]], cc = cam[frame * V + c[2]];
-  t.ax = a.x, t.ay = a.y, t.az = a.z;
-  t.e1[0] = b.x - a.x, t.e1[1] = b.y - a.y, t.e1[2] = b.z - a.z;
-  t.e2[0] = cc.x - a.x, t.e2[1] = cc.y - a.y, t.e2[2] = cc.z - a.z;
-  t.nx = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1];
-  t.ny = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2];
-  t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
-  t.na = (t.nx * t.ax + t.ny * t.ay) + t.nz * t.az;
-  return DR_FACE_OK;
 }
 
 // coverage of pixel (row j, column i) by the face, its depth, the depth test

@@ -724,6 +724,83 @@ class SMPL:
             raise SmplppError(1, "depth_raster_differentiable needs torch")
         return _DepthRasterFunction.apply(verts, self, camera, int(H), int(W), float(near))
 
+    # ---- raster attribute interpolation (smplpp_raster_interpolate / smplpp_raster_interpolate_vjp)
+    def _ri_inputs(self, c, attr, face, bary):
+        if len(attr.shape) != 3 or attr.shape[1] != self.vertex_num or not 1 <= attr.shape[2] <= 32:
+            c.refuse("expected attr of shape (N, %d, C) with C in [1, 32]" % self.vertex_num)
+        if len(bary.shape) != 4 or bary.shape[0] != attr.shape[0] or bary.shape[3] != 3 or min(bary.shape) < 1:
+            c.refuse("expected bary of shape (N, H, W, 3)")
+        n, Cn = int(attr.shape[0]), int(attr.shape[2])
+        H, W = int(bary.shape[1]), int(bary.shape[2])
+        attr, bary, f = c.input(attr, (n, self.vertex_num, Cn)), c.input(bary, (n, H, W, 3)), c.ids(face)
+        if f.shape[0] != n * H * W:
+            c.refuse("expected face of shape (%d, %d, %d)" % (n, H, W))
+        return n, Cn, H, W, attr, f, bary
+
+    def _raster_interpolate(self, name, attr, face, bary, device_only=False):
+        c = _Call(name, attr, bary, device_only=device_only)
+        n, Cn, H, W, attr, f, bary = self._ri_inputs(c, attr, face, bary)
+        image = c.empty((n, H, W, Cn))
+        check(_lib.load().smplpp_raster_interpolate(self.handle, n, _ptr(attr), Cn, H, W, _ptr(f), _ptr(bary), _ptr(image), c.space,
+                                                    c.stream))
+        return image
+
+    def rasterInterpolate(self, attr, face, bary):
+        """A per-vertex quantity attr [N,V,C] (C <= 32) carried into the image of depthRaster (smplpp_raster_interpolate): image
+        [N,H,W,C] with image = (beta_a attr[a] + beta_b attr[b]) + beta_c attr[c] at a pixel whose face [N,H,W] has the corners
+        (a, b, c) and whose barycentrics are bary [N,H,W,3]; 0 at background.  face and bary are depthRaster's outputs.  The rule is
+        exact and stated in the C header.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        return self._raster_interpolate("rasterInterpolate", attr, face, bary)
+
+    def rasterInterpolateBackward(self, attr, verts, camera, H, W, face, bary, grad_image, near=0.05, want=("attr", "verts"), out=None):
+        """Vector-Jacobian product of rasterInterpolate's image (smplpp_raster_interpolate_vjp): a dict of `attr`, grad_attr [N,V,C]
+        (face and bary held fixed), and `verts`, grad_verts [N,V,3], the gradient through the barycentrics (face and the pixels'
+        rays held fixed; coverage is not differentiated), for dL/dimage = grad_image [N,H,W,C].  verts, camera, H, W, near are the
+        arguments of the depthRaster call that gave face and bary.  A cotangent of exactly 0 or a pixel with face -1 contributes
+        nothing.  `want` drops an output; with `out`, a dict of arrays under the same keys, a gradient is added into its array."""
+        c = _Call("rasterInterpolateBackward", attr, verts, bary, grad_image, *(out or {}).values())
+        want = tuple(want)
+        if not want or any(k not in ("attr", "verts") for k in want) or any(k not in want for k in (out or {})):
+            c.refuse("want must name attr and / or verts, and out only what want names")
+        n, Cn, Hb, Wb, attr, f, bary = self._ri_inputs(c, attr, face, bary)
+        n, verts, camera, H, W = self._dr_inputs(c, verts, camera, H, W)
+        if (H, W) != (Hb, Wb) or n != attr.shape[0]:
+            c.refuse("expected face and bary of %d frames of %d x %d" % (n, H, W))
+        g = c.input(grad_image, (n, H, W, Cn))
+        acc = bool(out)
+        if acc and set(out) != set(want):
+            c.refuse("out must hold every output that want names")
+        shapes = {"attr": (n, self.vertex_num, Cn), "verts": (n, self.vertex_num, 3)}
+        r = {k: c.inout(out[k], shapes[k]) if acc else c.empty(shapes[k]) for k in want}
+        check(_lib.load().smplpp_raster_interpolate_vjp(self.handle, n, _ptr(attr), Cn, _ptr(verts), _ptr(camera), H, W, float(near),
+                                                        _ptr(f), _ptr(bary), _ptr(g), _ptr(r.get("attr")), _ptr(r.get("verts")), int(acc),
+                                                        c.space, c.stream))
+        return r
+
+    def raster_interpolate_differentiable(self, attr, verts, camera, H, W, near=0.05):
+        """(image [N,H,W,C], face [N,H,W], depth [N,H,W]) of device attributes attr [N,V,C] on device vertices verts [N,V,3]: one
+        depthRaster and one rasterInterpolate, with image differentiable through torch.autograd in attr and, through the
+        barycentrics, in verts (smplpp_raster_interpolate_vjp at the same face and bary), on torch's current stream.  depth carries
+        no gradient here (depth_raster_differentiable does that)."""
+        if torch is None:
+            raise SmplppError(1, "raster_interpolate_differentiable needs torch")
+        return _RasterInterpolateFunction.apply(attr, verts, self, camera, int(H), int(W), float(near))
+
+    def normal_map_differentiable(self, verts, camera, H, W, near=0.05):
+        """(normals [N,H,W,3], face [N,H,W]) of device vertices verts [N,V,3]: the whole-mesh vertex normals
+        (vertex_normals_differentiable) rotated into camera space, interpolated by raster_interpolate_differentiable and normalised
+        per pixel in torch; 0 at background.  The gradient reaches verts through the vertex normals and through the barycentrics."""
+        if torch is None:
+            raise SmplppError(1, "normal_map_differentiable needs torch")
+        n = verts.shape[0]
+        cam = camera if _is_torch(camera) else torch.from_numpy(pinhole_camera_rows(camera, n)).to(verts.device)
+        R = (cam.expand(n, 16) if cam.dim() == 1 else cam)[:, :9].reshape(n, 3, 3)
+        nc = torch.matmul(self.vertex_normals_differentiable(verts), R.transpose(1, 2))
+        image, face, _ = self.raster_interpolate_differentiable(nc, verts, cam, H, W, near)
+        length = image.norm(dim=-1, keepdim=True)
+        covered = (face >= 0).unsqueeze(-1) & (length > 0)
+        return torch.where(covered, image / torch.where(covered, length, torch.ones_like(length)), torch.zeros_like(image)), face
+
     # ---- silhouette term (smplpp_mask_distance_transform / smplpp_silhouette / smplpp_silhouette_vjp)
     def maskDistanceTransform(self, mask, want=("nearest", "sqdist")):
         """Exact Euclidean feature transform of binary images mask [N,H,W] (nonzero = set; smplpp_mask_distance_transform): returns
@@ -969,6 +1046,32 @@ if torch is not None:
                 return None, None, None, None, None, None
             gv = ctx.smpl.depthRasterBackward(verts, camera, ctx.size[0], ctx.size[1], face, grad_depth.contiguous())
             return gv, None, None, None, None, None
+
+
+    class _RasterInterpolateFunction(torch.autograd.Function):
+        """smplpp_depth_raster + smplpp_raster_interpolate forward / smplpp_raster_interpolate_vjp backward
+        (SMPL.raster_interpolate_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, attr, verts, smpl, camera, H, W, near):
+            attr, verts = attr.detach().contiguous(), verts.detach().contiguous()
+            camera = torch.from_numpy(pinhole_camera_rows(camera, verts.shape[0])).to(verts.device) if not _is_torch(camera) else camera
+            r = smpl._depth_raster("raster_interpolate_differentiable", verts, camera, H, W, near, want=("bary",), device_only=True)
+            image = smpl._raster_interpolate("raster_interpolate_differentiable", attr, r["face"], r["bary"], device_only=True)
+            ctx.mark_non_differentiable(r["face"], r["depth"])
+            ctx.smpl, ctx.size, ctx.near = smpl, (H, W), near
+            ctx.save_for_backward(attr, verts, camera, r["face"], r["bary"])
+            return image, r["face"], r["depth"]
+
+        @staticmethod
+        def backward(ctx, grad_image, _gf, _gd):
+            attr, verts, camera, face, bary = ctx.saved_tensors
+            want = tuple(k for k, need in zip(("attr", "verts"), ctx.needs_input_grad[:2]) if need)
+            if grad_image is None or not want:
+                return None, None, None, None, None, None, None
+            g = ctx.smpl.rasterInterpolateBackward(attr, verts, camera, ctx.size[0], ctx.size[1], face, bary, grad_image.contiguous(),
+                                                   near=ctx.near, want=want)
+            return g.get("attr"), g.get("verts"), None, None, None, None, None
 
 
     class _SilhouetteFunction(torch.autograd.Function):
