@@ -577,6 +577,62 @@ public:
           "SMPL");
     return out;
   }
+  // SMPL+D on the last launch (smplpp_vertex_offsets): the posed vertices and the rest shape of the body whose rest shape carries the
+  // per-vertex offsets `offsets`, [V,3] or [1,V,3] (one field for every frame) or [N,V,3].  The stored launch is left as it is.
+  struct VertexOffsets
+  {
+    Tensor verts, rest;
+  };
+  VertexOffsets vertexOffsets(const Tensor & offsets) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    if(offsets.dtype != kFloat32 || (offsets.numel() != V_ * 3 && offsets.numel() != n * V_ * 3))
+      throw Exception("SMPL", "Cannot displace the vertices!");
+    VertexOffsets r{Tensor({n, V_, 3}), Tensor({n, V_, 3})};
+    check(smplpp_vertex_offsets(m_.get(), n, verts_.ptr(), xforms_.ptr(), offsets.ptr(), offsets.numel() / (V_ * 3), rest_.ptr(), r.rest.ptr(),
+                                r.verts.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
+  // Its backward pass to the offsets (smplpp_vertex_offsets_vjp) at the last launch's transforms: dL/doffsets [N,V,3], or [1,V,3] with
+  // `shared` (one field for every frame), for dL/dverts = gradVerts [N,V,3].  `accumulate` non-null: the product is added into it (and
+  // it is returned).  (dL/dbeta and dL/dtheta of the displaced body: launchBackward's entry point with VertexOffsets::rest.)
+  Tensor vertexOffsetsBackward(const Tensor & gradVerts, bool shared = false, Tensor * accumulate = nullptr) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0), frames = shared ? 1 : n;
+    const char * what = "Cannot back-propagate through the vertex offsets!";
+    if(gradVerts.dtype != kFloat32 || gradVerts.numel() != n * V_ * 3) throw Exception("SMPL", what);
+    Tensor local;
+    Tensor & out = accumulate ? *accumulate : local;
+    if(accumulate)
+    {
+      if(accumulate->dtype != kFloat32 || accumulate->numel() != frames * V_ * 3) throw Exception("SMPL", what);
+    }
+    else
+      out = Tensor({frames, V_, 3});
+    check(smplpp_vertex_offsets_vjp(m_.get(), n, xforms_.ptr(), gradVerts.ptr(), frames, out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return out;
+  }
+  // The mesh Laplacian of a per-vertex field x [N,V,C], C <= 32 (smplpp_mesh_laplacian): twice the graph Laplacian on a closed manifold
+  // mesh, and its own backward pass.  `accumulate` non-null: the result is added into it (and it is returned).
+  Tensor meshLaplacian(const Tensor & x, Tensor * accumulate = nullptr) const
+  {
+    const char * what = "Cannot apply the mesh Laplacian!";
+    if(x.dim() != 3 || x.dtype != kFloat32 || x.size(1) != V_) throw Exception("SMPL", what);
+    Tensor local;
+    Tensor & out = accumulate ? *accumulate : local;
+    if(accumulate)
+    {
+      if(accumulate->dtype != kFloat32 || accumulate->numel() != x.numel()) throw Exception("SMPL", what);
+    }
+    else
+      out = Tensor(x.shape);
+    check(smplpp_mesh_laplacian(m_.get(), x.size(0), x.ptr(), x.size(2), out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST, nullptr), "SMPL");
+    return out;
+  }
   // Exact Euclidean feature transform of binary images mask [N,H,W] (integer tensor, nonzero = set; smplpp_mask_distance_transform):
   // nearest [N,H,W] kInt64 (the linear index of the nearest set pixel of the frame, the lowest among equal distances; -1 without a
   // set pixel) and sqdist [N,H,W] kInt64 (px^2).

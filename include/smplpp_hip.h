@@ -374,6 +374,54 @@ int smplpp_raster_interpolate_vjp(smplpp_model * m, int64_t n, const float * att
                                   const int64_t * face /*[n,H,W]*/, const float * bary /*[n,H,W,3]*/,
                                   const float * grad_image /*[n,H,W,C]*/, float * grad_attr /*[n,V,C] nullable*/,
                                   float * grad_verts /*[n,V,3] nullable*/, int accumulate, int space, void * stream);
+#define SMPLPP_VERTEX_OFFSETS_TILE 32 /* frames per tile of the shared sum of smplpp_vertex_offsets_vjp */
+/* SMPL+D: per-vertex offsets D in the rest pose, carried through linear blend skinning, verts_D = LBS(rest + D, G') with the joints
+ * regressed from the undisplaced shape.  Skinning is linear in the rest position, so verts_D = verts + (sum_j w_vj R'_fj) D_v / wSum_v,
+ * with verts, xforms (G', of which R'_fj is the upper-left 3x3 of joint j in frame f) as smplpp_fk returned them, whatever form
+ * (SMPLPP_SKIN) computed them.  In fp32 with every operation rounded on its own (no FMA), per (frame f, vertex v), with w the model's
+ * skinning weights and wSum_v the model's sum of them in ascending j (the homogeneous divide of smplpp_fk):
+ *    M[a][b]  = the sum over the joints j with w_vj != 0, in ascending j, starting from +0, of w_vj * R'_fj[a][b];
+ *    delta[a] = ((M[a][0] d[0] + M[a][1] d[1]) + M[a][2] d[2]) / wSum_v,   d = offsets[f][v] (offset_frames = n) or offsets[0][v] (= 1);
+ *    verts_out[f][v][a] = verts[f][v][a] + delta[a];      rest_displaced[f][v][a] = rest[f][v][a] + d[a].
+ * A joint with a zero weight is not read, so models that keep 4, 8 or 24 weights per vertex follow the one rule.  A zero offsets row
+ * returns the vertex (== ; the sign of a zero may differ).  verts_out may be verts, and rest_displaced may be rest (in place: the same
+ * bits).  rest and rest_displaced may both be NULL; rest alone is ignored.  rest_displaced is the `rest` smplpp_fk_vjp takes to give the
+ * exact dL/dbeta and dL/dtheta of the displaced body.  The bits do not depend on n, on the frame's position in the batch or on the
+ * memory space, nor on the frames a workgroup takes (by n; SMPLPP_VERTEX_OFFSETS_FRAMES = 1..32 in the environment of
+ * smplpp_model_create fixes it, for tests).
+ *  - SMPLPP_ERR_INVALID: n <= 0, a NULL verts, xforms, offsets or verts_out, offset_frames neither 1 nor n, rest_displaced without
+ *    rest, n * V * 3 beyond int32 indexing (the outputs are untouched, nothing is launched). */
+int smplpp_vertex_offsets(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, const float * xforms /*[n,24,4,4]*/,
+                          const float * offsets /*[offset_frames,V,3]*/, int64_t offset_frames /*1 or n*/,
+                          const float * rest /*[n,V,3] nullable*/, float * rest_displaced /*[n,V,3] nullable*/,
+                          float * verts_out /*[n,V,3], may be == verts*/, int space, void * stream);
+/* Vector-Jacobian product of verts_out above to the offsets (to verts it is the identity; to beta and theta it is smplpp_fk_vjp with
+ * rest = rest_displaced).  Per (f, v), with M as above and g = grad_verts[f][v], in fp32, every operation rounded on its own:
+ *    gt[a] = g[a] / wSum_v;      t[b] = (M[0][b] gt[0] + M[1][b] gt[1]) + M[2][b] gt[2].
+ *  - offset_frames = n: grad_offsets[f][v] = t.
+ *  - offset_frames = 1 (one field shared by all frames): grad_offsets[0][v] is the sum of t over the frames in a fixed two-level
+ *    order: the frames are cut into consecutive tiles of SMPLPP_VERTEX_OFFSETS_TILE; a tile's sum starts from its first frame's t and
+ *    adds the others in ascending frame; the result starts from the first tile's sum and adds the others in ascending tile.  It
+ *    depends on n through that tree only, never on the launch geometry.
+ *  - accumulate = 0 stores the finished value, 1 adds it to what grad_offsets holds (one addition at the end).
+ *  - a vertex whose cotangent rows are all zero receives 0.  No floating-point atomics; the same inputs give the same bits, in
+ *    either memory space.
+ *  - SMPLPP_ERR_INVALID: n <= 0, a NULL xforms, grad_verts or grad_offsets, grad_offsets == grad_verts, offset_frames neither 1 nor
+ *    n, accumulate not 0 or 1, n * V * 3 beyond int32 indexing (the output is untouched, nothing is launched).
+ *  - the shared sum keeps 12 bytes per (tile, vertex) of workspace on the handle, grown to the largest call. */
+int smplpp_vertex_offsets_vjp(smplpp_model * m, int64_t n, const float * xforms /*[n,24,4,4]*/, const float * grad_verts /*[n,V,3]*/,
+                              int64_t offset_frames /*1 or n*/, float * grad_offsets /*[offset_frames,V,3]*/, int accumulate,
+                              int space, void * stream);
+/* Mesh Laplacian of a per-vertex field x [n,V,C], C in [1, 32], the smoothness operator for the offsets.  In fp32, per (frame,
+ * vertex v, channel): over the faces t that contain v, in ascending t (the adjacency of the normals' backward pass), starting from +0,
+ *    (L x)_v = sum_t ((x_v - x_a) + (x_v - x_b)),   a, b = the other two corners of t in its cyclic order after v.
+ * Every edge of a closed manifold mesh lies in two faces, so there L is twice the graph Laplacian (deg(v) x_v - sum of the
+ * neighbours).  L is symmetric, so it is its own vector-Jacobian product: lambda |L D|^2 has the gradient 2 lambda L (L D), two
+ * calls.  A field that is constant over the mesh gives exactly 0.  accumulate = 0 stores, 1 adds the finished value to out.
+ *  - SMPLPP_ERR_INVALID: n <= 0, C outside [1, 32], a NULL x or out, out == x, a model without faces, accumulate not 0 or 1,
+ *    n * V * C beyond int32 indexing (the output is untouched, nothing is launched). */
+int smplpp_mesh_laplacian(smplpp_model * m, int64_t n, const float * x /*[n,V,C], 1 <= C <= 32*/, int64_t C, float * out /*[n,V,C]*/,
+                          int accumulate, int space, void * stream);
 /* Exact Euclidean feature transform of n binary images mask [n,H,W] (a nonzero byte = set), all in integers.  For pixel p = (row j,
  * column i) and the set pixels q = (j', i') of the same frame, d2(p, q) = (i-i')^2 + (j-j')^2: sqdist[p] is the minimum and
  * nearest[p] the linear index j' W + i' of the set pixel that attains it; among equal distances the lowest linear index wins (the

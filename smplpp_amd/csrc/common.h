@@ -168,6 +168,7 @@ struct SelfPenState;    // self-intersections, the self-penetration energy and i
 struct DepthRasterState; // the depth rasteriser and its backward pass (depth_raster.hip)
 struct SilhouetteState;  // the mask distance transform, the silhouette residuals and their backward pass (silhouette.hip)
 struct RasterInterpState; // the backward pass of the raster attribute interpolation (raster_interpolate.hip)
+struct VertexOffsetsState; // the tile sums of the shared SMPL+D backward (vertex_offsets.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -181,6 +182,7 @@ struct StateDelete
   void operator()(DepthRasterState * s) const;
   void operator()(SilhouetteState * s) const;
   void operator()(RasterInterpState * s) const;
+  void operator()(VertexOffsetsState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -245,5 +247,7 @@ struct smplpp_model
   smplpp_hip::StatePtr<smplpp_hip::DepthRasterState> dr; // depth-rasteriser workspace (depth_raster.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::SilhouetteState> sil; // silhouette workspace (silhouette.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::RasterInterpState> ri; // raster-interpolation backward workspace (raster_interpolate.hip): null until its first call
+  int vo_frames = 0;            // SMPL+D: frames per tile of the forward and the per-frame backward (SMPLPP_VERTEX_OFFSETS_FRAMES, read at model creation): 0 = by n
+  smplpp_hip::StatePtr<smplpp_hip::VertexOffsetsState> vo; // SMPL+D shared-backward workspace (vertex_offsets.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

@@ -292,7 +292,7 @@ extern "C" int smplpp_model_destroy(smplpp_model * m)
   return SMPLPP_OK;
 }
 
-// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM and SMPLPP_DEPTH_RASTER_INLINE are read here, once per model (m.maxw and m.VGPn are set)
+// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM, SMPLPP_DEPTH_RASTER_INLINE and SMPLPP_VERTEX_OFFSETS_FRAMES are read here, once per model (m.maxw and m.VGPn are set)
 static void read_env(smplpp_model & m)
 {
   std::tie(m.form, m.form_ik) = choose_forms(getenv("SMPLPP_SKIN"), m.maxw, m.VGPn);
@@ -300,6 +300,9 @@ static void read_env(smplpp_model & m)
   m.pd_form = pd_env && (pd_env[0] == 'q' || pd_env[0] == 't') ? pd_env[0] : 0;
   const char * dr_env = getenv("SMPLPP_DEPTH_RASTER_INLINE"); // 0..4096: the largest box a face's own thread walks in smplpp_depth_raster
   m.dr_inline = dr_env && dr_env[0] >= '0' && dr_env[0] <= '9' ? atoi(dr_env) : -1;
+  const char * vo_env = getenv("SMPLPP_VERTEX_OFFSETS_FRAMES"); // 1..32: frames per tile of smplpp_vertex_offsets and its per-frame backward (no bit depends on it)
+  const int vo_ft = vo_env ? atoi(vo_env) : 0;
+  m.vo_frames = vo_ft >= 1 && vo_ft <= SMPLPP_VERTEX_OFFSETS_TILE ? vo_ft : 0;
 }
 
 // Validate, build the host tables (model_tables.h), then upload them and lay the bases out on the device.

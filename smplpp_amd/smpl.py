@@ -801,6 +801,80 @@ class SMPL:
         covered = (face >= 0).unsqueeze(-1) & (length > 0)
         return torch.where(covered, image / torch.where(covered, length, torch.ones_like(length)), torch.zeros_like(image)), face
 
+    # ---- SMPL+D: vertex offsets through skinning and the mesh Laplacian (smplpp_vertex_offsets / _vjp / smplpp_mesh_laplacian)
+    def _offset_rows(self, c, offsets, n):
+        """offsets [V,3], [1,V,3] or [n,V,3] as the call's input: (array [frames,V,3], frames)."""
+        V = self.vertex_num
+        shape = tuple(offsets.shape)
+        if shape == (V, 3):
+            offsets, shape = offsets.reshape(1, V, 3), (1, V, 3)
+        if shape not in ((1, V, 3), (n, V, 3)):
+            c.refuse("expected offsets of shape (%d, 3), (1, %d, 3) or (%d, %d, 3)" % (V, V, n, V))
+        return c.input(offsets, shape), shape[0]
+
+    def _vertex_offsets(self, c, verts, xforms, offsets, rest, out=None):
+        n, V = int(verts.shape[0]), self.vertex_num
+        verts, xforms, rest = c.input(verts, (n, V, 3)), c.input(xforms, (n, 24, 4, 4)), c.input(rest, (n, V, 3))
+        d, frames = self._offset_rows(c, offsets, n)
+        vo = c.inout(out, (n, V, 3)) if out is not None else c.empty((n, V, 3))
+        rd = c.empty((n, V, 3)) if rest is not None else None
+        check(_lib.load().smplpp_vertex_offsets(self.handle, n, _ptr(verts), _ptr(xforms), _ptr(d), frames, _ptr(rest), _ptr(rd), _ptr(vo),
+                                                c.space, c.stream))
+        return vo, rd
+
+    def vertexOffsets(self, verts, xforms, offsets, rest=None, out=None):
+        """SMPL+D (smplpp_vertex_offsets): the posed vertices of the body whose rest shape carries the per-vertex offsets `offsets`
+        ([V,3] or [1,V,3]: one field for every frame; [N,V,3]: one per frame), LBS(rest + D, G'), from `verts` [N,V,3] and `xforms`
+        [N,24,4,4] as launch returned them.  With `rest` [N,V,3] it returns (verts_displaced, rest_displaced), and rest_displaced is
+        the `rest` launchBackward takes for the displaced body.  `out` [N,V,3] receives the vertices (it may be `verts`: in place).
+        The rule is exact and stated in the C header.  numpy (the call synchronises) or float32 device tensors (torch's current
+        stream)."""
+        c = _Call("vertexOffsets", verts, xforms, offsets, rest, out)
+        vo, rd = self._vertex_offsets(c, verts, xforms, offsets, rest, out)
+        return vo if rest is None else (vo, rd)
+
+    def vertexOffsetsBackward(self, xforms, grad_verts, shared=False, out=None):
+        """Vector-Jacobian product of vertexOffsets to the offsets (smplpp_vertex_offsets_vjp): grad_offsets [N,V,3] for dL/dverts =
+        grad_verts [N,V,3], or [1,V,3] with `shared` (one field for every frame: the frames' sum in the fixed order of the C
+        header).  With `out` the gradient is added into it and it is returned."""
+        c = _Call("vertexOffsetsBackward", xforms, grad_verts, out)
+        n, V = int(grad_verts.shape[0]), self.vertex_num
+        xforms, g = c.input(xforms, (n, 24, 4, 4)), c.input(grad_verts, (n, V, 3))
+        frames = 1 if shared else n
+        acc = out is not None
+        go = c.inout(out, (frames, V, 3)) if acc else c.empty((frames, V, 3))
+        check(_lib.load().smplpp_vertex_offsets_vjp(self.handle, n, _ptr(xforms), _ptr(g), frames, _ptr(go), int(acc), c.space, c.stream))
+        return go
+
+    def meshLaplacian(self, x, out=None):
+        """The mesh Laplacian of a per-vertex field x [N,V,C], C <= 32 (smplpp_mesh_laplacian): (L x)_v = the sum over the faces at v
+        of (x_v - x_a) + (x_v - x_b), twice the graph Laplacian on a closed manifold mesh.  L is symmetric: the gradient of
+        |L D|^2 is 2 L (L D).  With `out` the result is added into it and it is returned."""
+        c = _Call("meshLaplacian", x, out)
+        if len(x.shape) != 3 or x.shape[1] != self.vertex_num or not 1 <= x.shape[2] <= 32:
+            c.refuse("expected x of shape (N, %d, C) with C in [1, 32]" % self.vertex_num)
+        shape = tuple(int(k) for k in x.shape)
+        x = c.input(x, shape)
+        acc = out is not None
+        o = c.inout(out, shape) if acc else c.empty(shape)
+        check(_lib.load().smplpp_mesh_laplacian(self.handle, shape[0], _ptr(x), shape[2], _ptr(o), int(acc), c.space, c.stream))
+        return o
+
+    def mesh_laplacian_differentiable(self, x):
+        """meshLaplacian of a device tensor x [N,V,C], differentiable with torch.autograd (the operator is its own backward)."""
+        if torch is None:
+            raise SmplppError(1, "mesh_laplacian_differentiable needs torch")
+        return _LaplacianFunction.apply(x, self)
+
+    def forward_displaced_differentiable(self, beta, theta, offsets):
+        """(verts [N,V,3], joints [N,24,3]) of the SMPL+D body for device tensors beta [N,10], theta [N,25,3] and offsets [V,3],
+        [1,V,3] (one field for every frame) or [N,V,3], differentiable with torch.autograd in all three: the forward is one
+        smplpp_fk and one smplpp_vertex_offsets, the backward smplpp_vertex_offsets_vjp and smplpp_fk_vjp on the displaced rest
+        shape, on torch's current stream.  The joints are those of the undisplaced shape."""
+        if torch is None:
+            raise SmplppError(1, "forward_displaced_differentiable needs torch")
+        return _FKDisplacedFunction.apply(beta, theta, offsets, self)
+
     # ---- silhouette term (smplpp_mask_distance_transform / smplpp_silhouette / smplpp_silhouette_vjp)
     def maskDistanceTransform(self, mask, want=("nearest", "sqdist")):
         """Exact Euclidean feature transform of binary images mask [N,H,W] (nonzero = set; smplpp_mask_distance_transform): returns
@@ -920,6 +994,44 @@ if torch is not None:
                 return None, None, None
             g = ctx.smpl.launchBackward(beta, theta, grad_verts=grad_verts, grad_joints=grad_joints, rest=rest)
             return (g["beta"] if ctx.needs_input_grad[0] else None, g["theta"] if ctx.needs_input_grad[1] else None, None)
+
+    class _FKDisplacedFunction(torch.autograd.Function):
+        """smplpp_fk + smplpp_vertex_offsets forward / smplpp_vertex_offsets_vjp + smplpp_fk_vjp(rest = rest_displaced) backward
+        (SMPL.forward_displaced_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, beta, theta, offsets, smpl):
+            c = _Call("forward_displaced_differentiable", beta, theta, offsets, fail="Cannot launch a SMPL model!", device_only=True)
+            beta, theta, out = smpl._fk(c, beta, theta, ("verts", "joints", "xforms", "rest"))
+            _, rd = smpl._vertex_offsets(c, out["verts"], out["xforms"], offsets, out["rest"], out=out["verts"])
+            ctx.smpl, ctx.offsets_shape = smpl, tuple(offsets.shape)
+            ctx.save_for_backward(beta, theta, out["xforms"], rd)
+            return out["verts"], out["joints"]
+
+        @staticmethod
+        def backward(ctx, grad_verts, grad_joints):
+            beta, theta, xforms, rd = ctx.saved_tensors
+            gb = gt = gd = None
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+                g = ctx.smpl.launchBackward(beta, theta, grad_verts=grad_verts, grad_joints=grad_joints, rest=rd)
+                gb, gt = (g["beta"] if ctx.needs_input_grad[0] else None), (g["theta"] if ctx.needs_input_grad[1] else None)
+            if ctx.needs_input_grad[2]:
+                n, V = beta.shape[0], ctx.smpl.vertex_num
+                shared = ctx.offsets_shape != (n, V, 3)
+                gd = ctx.smpl.vertexOffsetsBackward(xforms, grad_verts.contiguous(), shared=shared).reshape(ctx.offsets_shape)
+            return gb, gt, gd, None
+
+    class _LaplacianFunction(torch.autograd.Function):
+        """smplpp_mesh_laplacian forward and, the operator being symmetric, backward (SMPL.mesh_laplacian_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, x, smpl):
+            ctx.smpl = smpl
+            return smpl.meshLaplacian(x.detach().contiguous())
+
+        @staticmethod
+        def backward(ctx, grad):
+            return (ctx.smpl.meshLaplacian(grad.contiguous()) if ctx.needs_input_grad[0] else None), None
 
     class _NormalsFunction(torch.autograd.Function):
         """The normal queries forward / their vector-Jacobian products backward (SMPL.face_normals_differentiable,
