@@ -368,7 +368,9 @@ int smplpp_raster_interpolate(smplpp_model * m, int64_t n, const float * attr /*
  *  - grad_attr or grad_verts may be NULL, not both.  No gradient to camera.
  *  - SMPLPP_ERR_INVALID: as the forward, near not finite or <= 0, accumulate not 0 or 1, both outputs NULL (the outputs are
  *    untouched).
- *  - the handle keeps 24 bytes per (frame, vertex) and 48 bytes per (frame, face) of workspace, grown to the largest call. */
+ *  - the handle keeps 24 bytes per (frame, vertex) and 48 bytes per (frame, face) of workspace, grown to the largest call and shared
+ *    with smplpp_depth_raster and smplpp_depth_raster_vjp: concurrent calls on one handle from different streams need the caller's
+ *    own ordering (see "Streams and sharing" below). */
 int smplpp_raster_interpolate_vjp(smplpp_model * m, int64_t n, const float * attr /*[n,V,C]*/, int64_t C,
                                   const float * verts /*[n,V,3]*/, const float * camera /*[n,16]*/, int64_t H, int64_t W, float near,
                                   const int64_t * face /*[n,H,W]*/, const float * bary /*[n,H,W,3]*/,

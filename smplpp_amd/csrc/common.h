@@ -165,9 +165,8 @@ struct PointDistState;  // point-to-mesh distance and its backward pass (point_d
 struct MeshPointDistState; // mesh-to-point distance and its backward pass (mesh_point_distance.hip)
 struct WindingState;    // batched winding numbers and the signed point-to-mesh distance (winding.hip)
 struct SelfPenState;    // self-intersections, the self-penetration energy and its backward pass (self_penetration.hip)
-struct DepthRasterState; // the depth rasteriser and its backward pass (depth_raster.hip)
+struct DepthRasterState; // the depth rasteriser, its backward pass and that of the raster interpolation (raster_walk.h)
 struct SilhouetteState;  // the mask distance transform, the silhouette residuals and their backward pass (silhouette.hip)
-struct RasterInterpState; // the backward pass of the raster attribute interpolation (raster_interpolate.hip)
 struct VertexOffsetsState; // the tile sums of the shared SMPL+D backward (vertex_offsets.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
@@ -181,7 +180,6 @@ struct StateDelete
   void operator()(SelfPenState * s) const;
   void operator()(DepthRasterState * s) const;
   void operator()(SilhouetteState * s) const;
-  void operator()(RasterInterpState * s) const;
   void operator()(VertexOffsetsState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
@@ -244,9 +242,8 @@ struct smplpp_model
   smplpp_hip::StatePtr<smplpp_hip::WindingState> wn; // winding-number and signed-distance workspace (winding.hip): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::SelfPenState> sp; // self-intersection and self-penetration workspace (self_penetration.hip): null until its first call
   int dr_inline = -1;           // depth rasteriser: box pixels a face's own thread walks (SMPLPP_DEPTH_RASTER_INLINE, read at model creation): -1 = default
-  smplpp_hip::StatePtr<smplpp_hip::DepthRasterState> dr; // depth-rasteriser workspace (depth_raster.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::DepthRasterState> dr; // workspace of the depth rasteriser and of the raster interpolation's backward pass (raster_walk.h): null until its first call
   smplpp_hip::StatePtr<smplpp_hip::SilhouetteState> sil; // silhouette workspace (silhouette.hip): null until its first call
-  smplpp_hip::StatePtr<smplpp_hip::RasterInterpState> ri; // raster-interpolation backward workspace (raster_interpolate.hip): null until its first call
   int vo_frames = 0;            // SMPL+D: frames per tile of the forward and the per-frame backward (SMPLPP_VERTEX_OFFSETS_FRAMES, read at model creation): 0 = by n
   smplpp_hip::StatePtr<smplpp_hip::VertexOffsetsState> vo; // SMPL+D shared-backward workspace (vertex_offsets.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves

@@ -18,12 +18,13 @@
 //  dr_resolve_kernel  per pixel: key -> face, depth, the 3-D barycentrics of the hit point, and a plain byte store of 1 into
 //                     `visible` for the three corners (every writer stores the same value).
 // Backward (the face image is an input and held fixed):
-//  dr_vjp_face_kernel   per (frame, face), DR_SPLIT lanes: the face's clipped box in row-major order, lane l taking entries l,
-//                       l + DR_SPLIT, ...; a pixel that names the face and has a nonzero cotangent adds beta_i * (g / (n.d)) to
-//                       corner i's sum; the lanes' sums meet in a fixed xor tree (4, 2, 1) and lane 0 stores n times each.
-//  dr_vjp_vertex_kernel per (frame, vertex): its faces' vectors in ascending face id (the adjacency of the normals' backward pass),
-//                       then R^T once.  One fixed-order sum per vertex, no floating-point atomics.
-#include "depth_raster_device.h"
+//  dr_vjp_face_kernel   the walk of raster_walk.h (DR_SPLIT lanes per (frame, face), a fixed xor tree): a pixel that names the face
+//                       and has a nonzero cotangent adds beta_i * (g / (n.d)) to corner i's sum; lane 0 stores n times each.
+//  dr_gather_kernel     per (frame, vertex): its faces' values in ascending face id (the adjacency of the normals' backward pass),
+//                       then R^T once (ROT) or the plain store.  One fixed-order sum per element, no floating-point atomics.
+// dr_vertex_kernel and dr_gather_kernel also serve raster_interpolate.hip, through dr_vertex_pass and dr_gather of raster_walk.h,
+// with the handle's one DepthRasterState.
+#include "raster_walk.h"
 #include "trace.h"
 
 #include <algorithm>
@@ -32,21 +33,11 @@
 
 namespace smplpp_hip
 {
-constexpr int DR_T = 256;                   // threads of every kernel here
-constexpr int DR_SPLIT = 8;                 // lanes per face in the backward walk
 constexpr int DR_INLINE_DEFAULT = 16;       // box pixels a face's own thread walks (SMPLPP_DEPTH_RASTER_INLINE)
 constexpr int DR_INLINE_MAX = 4096;
 constexpr unsigned DR_LARGE_BLOCKS = 2048;  // grid of dr_large_kernel: 8192 wavefronts
 constexpr unsigned long long DR_EMPTY = ~0ull;
 
-struct DepthRasterState
-{
-  DevBuf cam, snap;   // [n][V] float4 camera-space vertex, int2 snapped projection
-  DevBuf keys;        // [n][H][W] uint64
-  DevBuf queue, qn;   // [n][F] int32 queued (frame, face) items and their count
-  DevBuf fgrad;       // [n][F][9] per-face corner vectors of the backward pass
-  int inline_px = DR_INLINE_DEFAULT;
-};
 void StateDelete::operator()(DepthRasterState * s) const
 {
   delete s;
@@ -162,97 +153,96 @@ __global__ __launch_bounds__(DR_T) void dr_resolve_kernel(const float4 * __restr
   const DrCamera c = dr_camera(camera, frame);
   const float4 a = cam[frame * V + c0], b = cam[frame * V + c1], cc = cam[frame * V + c2];
   DrFace t;
-  t.ax = a.x, t.ay = a.y, t.az = a.z;
-  t.e1[0] = b.x - a.x, t.e1[1] = b.y - a.y, t.e1[2] = b.z - a.z;
-  t.e2[0] = cc.x - a.x, t.e2[1] = cc.y - a.y, t.e2[2] = cc.z - a.z;
-  t.nx = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1];
-  t.ny = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2];
-  t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
+  dr_plane(t, &a.x, &b.x, &cc.x);
   float dx, dy, ba, bb, bc;
   dr_ray(c, (int)(pix % W), (int)(pix / W), dx, dy);
   dr_bary(t, z, dx, dy, ba, bb, bc);
   bary[idx * 3] = ba, bary[idx * 3 + 1] = bb, bary[idx * 3 + 2] = bc;
 }
 
+// the depth term's share of a pixel: beta_i * (g / (n.d)) to corner i
+struct DrDepthBody
+{
+  const float * camera, * gd;
+  int64_t HW;
+  DrCamera c;
+  const float * gf;
+  __device__ void face(const DrFace &, int64_t frame, int64_t)
+  {
+    c = dr_camera(camera, frame);
+    gf = gd + frame * HW;
+  }
+  __device__ void pixel(const DrFace & t, int i, int j, int64_t pix, float * s) const
+  {
+    const float g = gf[pix];
+    if(g == 0.0f) return;
+    float dx, dy, b[3];
+    dr_ray(c, i, j, dx, dy);
+    const float nd = (t.nx * dx + t.ny * dy) + t.nz;
+    const float depth = t.na / nd;
+    dr_bary(t, depth, dx, dy, b[0], b[1], b[2]);
+    const float coef = g / nd;
+    for(int k = 0; k < 3; k++) s[k] = s[k] + b[k] * coef;
+  }
+};
+
 __global__ __launch_bounds__(DR_T) void dr_vjp_face_kernel(const float4 * __restrict__ cam, const int2 * __restrict__ snap,
                                                            const int32_t * __restrict__ faces, const float * __restrict__ camera,
                                                            const int64_t * __restrict__ face, const float * __restrict__ gd,
-                                                           float * __restrict__ fgrad, int64_t H, int64_t W, int64_t V, int64_t F,
+                                                           float * __restrict__ fsum, int64_t H, int64_t W, int64_t V, int64_t F,
                                                            int64_t nf)
 {
-  const int64_t tid = (int64_t)blockIdx.x * DR_T + threadIdx.x;
-  const int64_t idx = tid / DR_SPLIT;
-  const int part = (int)(tid % DR_SPLIT);
-  const bool in = idx < nf;
-  const int64_t frame = in ? idx / F : 0, f = in ? idx % F : 0;
-  DrFace t;
-  const bool live = in && dr_face_setup(t, cam, snap, faces, frame, f, V, H, W) == DR_FACE_OK;
-  float s[3] = {0.0f, 0.0f, 0.0f};
-  if(live)
-  {
-    const DrCamera c = dr_camera(camera, frame);
-    const int64_t * ff = face + frame * H * W;
-    const float * gf = gd + frame * H * W;
-    const int w = t.i1 - t.i0 + 1;
-    const int64_t area = (int64_t)w * (t.j1 - t.j0 + 1);
-    for(int64_t r = part; r < area; r += DR_SPLIT)
-    {
-      const int i = t.i0 + (int)(r % w), j = t.j0 + (int)(r / w);
-      const int64_t pix = (int64_t)j * W + i;
-      if(ff[pix] != f) continue;
-      const float g = gf[pix];
-      if(g == 0.0f) continue;
-      float dx, dy, b[3];
-      dr_ray(c, i, j, dx, dy);
-      const float nd = (t.nx * dx + t.ny * dy) + t.nz;
-      const float depth = t.na / nd;
-      dr_bary(t, depth, dx, dy, b[0], b[1], b[2]);
-      const float coef = g / nd;
-      for(int k = 0; k < 3; k++) s[k] = s[k] + b[k] * coef;
-    }
-  }
-  for(int m = DR_SPLIT / 2; m >= 1; m >>= 1)
-    for(int k = 0; k < 3; k++) s[k] = s[k] + __shfl_xor(s[k], m);
-  if(!in || part != 0) return;
-  float * o = fgrad + idx * 9;
+  float s[3];
+  DrDepthBody body{camera, gd, H * W};
+  const DrWalk w = dr_walk(cam, snap, faces, face, H, W, V, F, nf, s, body);
+  if(!w.in || w.part != 0) return;
+  float * o = fsum + w.idx * 9;
   for(int k = 0; k < 3; k++)
   {
-    o[3 * k] = live ? s[k] * t.nx : 0.0f;
-    o[3 * k + 1] = live ? s[k] * t.ny : 0.0f;
-    o[3 * k + 2] = live ? s[k] * t.nz : 0.0f;
+    o[3 * k] = w.live ? s[k] * w.t.nx : 0.0f;
+    o[3 * k + 1] = w.live ? s[k] * w.t.ny : 0.0f;
+    o[3 * k + 2] = w.live ? s[k] * w.t.nz : 0.0f;
   }
 }
 
-__global__ __launch_bounds__(DR_T) void dr_vjp_vertex_kernel(const float * __restrict__ fgrad, const int32_t * __restrict__ faces,
-                                                             const int32_t * __restrict__ adjOff, const int32_t * __restrict__ adjFace,
-                                                             const float * __restrict__ camera, float * __restrict__ gv, int accumulate,
-                                                             int64_t V, int64_t F, int64_t nv)
+// see dr_gather (raster_walk.h); instantiated on the width, so that a corner's values come in one load
+template<int WIDTH, bool ROT>
+__global__ __launch_bounds__(DR_T) void dr_gather_kernel(const float * __restrict__ fsum, const int32_t * __restrict__ faces,
+                                                         const int32_t * __restrict__ adjOff, const int32_t * __restrict__ adjFace,
+                                                         const float * __restrict__ camera, float * __restrict__ out, int row,
+                                                         int stride, int off, int accumulate, int64_t V, int64_t F, int64_t nv)
 {
   const int64_t idx = (int64_t)blockIdx.x * DR_T + threadIdx.x;
   if(idx >= nv) return;
   const int64_t frame = idx / V;
   const int32_t v = (int32_t)(idx % V);
-  float g[3] = {0.0f, 0.0f, 0.0f};
+  float g[WIDTH];
+  for(int x = 0; x < WIDTH; x++) g[x] = 0.0f;
   for(int32_t q = adjOff[v]; q < adjOff[v + 1]; q++)
   {
     const int64_t f = adjFace[q];
     for(int k = 0; k < 3; k++)
       if(faces[f * 3 + k] == v)
       {
-        const float * p = fgrad + ((frame * F + f) * 3 + k) * 3;
-        for(int x = 0; x < 3; x++) g[x] = g[x] + p[x];
+        const float * p = fsum + (frame * F + f) * row + k * WIDTH;
+        for(int x = 0; x < WIDTH; x++) g[x] = g[x] + p[x];
       }
   }
-  const float * R = camera + frame * 16;
-  float * o = gv + idx * 3;
-  for(int x = 0; x < 3; x++)
+  float * o = out + idx * stride + off;
+  if(ROT)
   {
-    const float w = (R[x] * g[0] + R[3 + x] * g[1]) + R[6 + x] * g[2];
-    o[x] = accumulate ? o[x] + w : w;
+    const float * R = camera + frame * 16;
+    for(int x = 0; x < 3; x++)
+    {
+      const float w = (R[x] * g[0] + R[3 + x] * g[1]) + R[6 + x] * g[2];
+      o[x] = accumulate ? o[x] + w : w;
+    }
+    return;
   }
+  for(int x = 0; x < WIDTH; x++) o[x] = accumulate ? o[x] + g[x] : g[x];
 }
 
-static DepthRasterState * dr_state(smplpp_model * m)
+DepthRasterState * dr_state(smplpp_model * m)
 {
   if(!m->dr)
   {
@@ -262,18 +252,29 @@ static DepthRasterState * dr_state(smplpp_model * m)
   return m->dr.get();
 }
 
-static unsigned dr_grid(int64_t items)
-{
-  return (unsigned)((items + DR_T - 1) / DR_T);
-}
-
-static int dr_vertex_pass(smplpp_model * m, DepthRasterState * s, int64_t n, const float * verts, const float * camera, float near,
-                          hipStream_t st)
+int dr_vertex_pass(smplpp_model * m, DepthRasterState * s, int64_t n, const float * verts, const float * camera, float near, hipStream_t st)
 {
   const int64_t nv = n * m->V;
   HIP_TRY(s->cam.reserve(sizeof(float4) * (size_t)nv));
   HIP_TRY(s->snap.reserve(sizeof(int2) * (size_t)nv));
   dr_vertex_kernel<<<dim3(dr_grid(nv)), dim3(DR_T), 0, st>>>(verts, camera, s->cam.as<float4>(), s->snap.as<int2>(), near, m->V, nv);
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+
+int dr_gather(smplpp_model * m, int64_t n, const float * fsum, int row, int width, bool rot, const float * camera, float * out,
+              int stride, int off, int accumulate, hipStream_t st)
+{
+  const int64_t nv = n * m->V;
+#define DR_GATHER(WIDTH, ROT)                                                                                                         \
+  dr_gather_kernel<WIDTH, ROT><<<dim3(dr_grid(nv)), dim3(DR_T), 0, st>>>(fsum, m->faces.get(), m->adjOff.get(), m->adjFace.get(), camera, \
+                                                                         out, row, stride, off, accumulate, m->V, m->F, nv)
+  if(rot) DR_GATHER(3, true);
+  else if(width == 1) DR_GATHER(1, false);
+  else if(width == 2) DR_GATHER(2, false);
+  else if(width == 3) DR_GATHER(3, false);
+  else DR_GATHER(4, false);
+#undef DR_GATHER
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
@@ -316,14 +317,11 @@ static int dr_vjp_device(smplpp_model * m, DepthRasterState * s, int64_t n, cons
   // no near plane here: the face image names the faces; a vertex is refused for a non-finite or out-of-band projection only
   int rc = dr_vertex_pass(m, s, n, verts, camera, -INFINITY, st);
   if(rc) return rc;
-  HIP_TRY(s->fgrad.reserve(sizeof(float) * 9 * (size_t)nf));
+  HIP_TRY(s->fsum.reserve(sizeof(float) * 9 * (size_t)nf));
   dr_vjp_face_kernel<<<dim3(dr_grid(nf * DR_SPLIT)), dim3(DR_T), 0, st>>>(s->cam.as<float4>(), s->snap.as<int2>(), m->faces.get(), camera,
-                                                                          face, gd, s->fgrad.as<float>(), H, W, V, F, nf);
+                                                                          face, gd, s->fsum.as<float>(), H, W, V, F, nf);
   HIP_TRY(hipGetLastError());
-  dr_vjp_vertex_kernel<<<dim3(dr_grid(n * V)), dim3(DR_T), 0, st>>>(s->fgrad.as<float>(), m->faces.get(), m->adjOff.get(),
-                                                                    m->adjFace.get(), camera, gv, accumulate, V, F, n * V);
-  HIP_TRY(hipGetLastError());
-  return SMPLPP_OK;
+  return dr_gather(m, n, s->fsum.as<float>(), 9, 3, true, camera, gv, 3, 0, accumulate, st);
 }
 } // namespace smplpp_hip
 
@@ -335,7 +333,7 @@ extern "C" int smplpp_depth_raster(smplpp_model * m, int64_t n, const float * ve
 {
   const char * fn = "smplpp_depth_raster";
   if(!m || n <= 0 || !verts || !camera || !face || !depth) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
-  if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
+  if(int rc = dr_check_near(fn, near)) return rc;
   int rc = dr_check(fn, m, n, H, W, space);
   if(rc) return rc;
   Frame fr(m->device, &m->arena, space, stream, "depth raster");

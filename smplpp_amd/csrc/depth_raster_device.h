@@ -1,5 +1,6 @@
 // The pieces of the depth rasteriser's rule that other image-space terms restate: the camera row, the vertex
 // projection with its refusal, the pixel-centre ray, the plane of a face in camera space and the 3-D barycentrics of a hit point.
+// raster_walk.h builds the backward passes' shared walk on them.
 // Every fp32 operation is rounded on its own (no contraction to FMA), as include/smplpp_hip.h states the rule.
 #pragma once
 #include "staging.h"
@@ -100,13 +101,7 @@ __device__ inline int dr_face_setup(DrFace & t, const float4 * __restrict__ cam,
   t.j0 = (int)dr_max(0, (ymin + 127) >> 8), t.j1 = (int)dr_min(H - 1, (ymax - 128) >> 8);
   if(t.i0 > t.i1 || t.j0 > t.j1) return DR_FACE_EMPTY;
   const float4 a = cam[frame * V + c[0]], b = cam[frame * V + c[1]], cc = cam[frame * V + c[2]];
-  t.ax = a.x, t.ay = a.y, t.az = a.z;
-  t.e1[0] = b.x - a.x, t.e1[1] = b.y - a.y, t.e1[2] = b.z - a.z;
-  t.e2[0] = cc.x - a.x, t.e2[1] = cc.y - a.y, t.e2[2] = cc.z - a.z;
-  t.nx = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1];
-  t.ny = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2];
-  t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
-  t.na = (t.nx * t.ax + t.ny * t.ay) + t.nz * t.az;
+  dr_plane(t, &a.x, &b.x, &cc.x);
   return DR_FACE_OK;
 }
 
@@ -129,7 +124,12 @@ __device__ inline void dr_bary(const DrFace & t, float depth, float dx, float dy
   ba = (1.0f - bb) - bc;
 }
 
-// the call rules every image-space entry shares
+// the call rules every image-space entry shares; dr_check_near for the entries that take a near plane
+inline int dr_check_near(const char * fn, float near)
+{
+  if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
+  return SMPLPP_OK;
+}
 inline int dr_check(const char * fn, smplpp_model * m, int64_t n, int64_t H, int64_t W, int space)
 {
   if(m->F <= 0) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": the model has no faces");

@@ -512,7 +512,7 @@ extern "C" int smplpp_silhouette(smplpp_model * m, int64_t n, const float * vert
   const char * fn = "smplpp_silhouette";
   if(!m || n <= 0 || !verts || !camera || !face || !mask || (!vert_target && !vert_sq && !pix_source && !pix_sq))
     return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
-  if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
+  if(int rc = dr_check_near(fn, near)) return rc;
   int rc = dr_check(fn, m, n, H, W, space);
   if(rc) return rc;
   if(space == SMPLPP_HOST && (rc = ids_in(fn, "face id", face, n * H * W, -1, m->F))) return rc;
@@ -538,7 +538,7 @@ extern "C" int smplpp_silhouette_vjp(smplpp_model * m, int64_t n, const float * 
   if(!m || n <= 0 || !verts || !camera || !face || !grad_verts || (!grad_vert_sq && !grad_pix_sq) || (grad_vert_sq && !vert_target) ||
      (grad_pix_sq && !pix_source))
     return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
-  if(!(std::isfinite(near) && near > 0.0f)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": near must be finite and > 0");
+  if(int rc = dr_check_near(fn, near)) return rc;
   if(accumulate != 0 && accumulate != 1) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": accumulate must be 0 or 1");
   int rc = dr_check(fn, m, n, H, W, space);
   if(rc) return rc;
