@@ -182,34 +182,10 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
   if(m->nlev > DMAX) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_create: kinematic trees deeper than 12 levels are not supported");
   if(m->V > 65535) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_create: at most 65535 vertices are supported (ring tables hold 16-bit ids)");
   if(!m->faceRing || !m->faceMap || !m->anc) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_create: the model carries no ring tables");
-  // the evaluation advances the chain derivatives one tree level per step with one thread per (joint of the level, ancestor
-  // depth, axis, row): the per-thread entries of every level (ik_eval_kernel: role), and every level must fit the workgroup
+  // the per-thread entries of the evaluation's chain-derivative steps (ik_plan.h: eval_roles); every level must fit the workgroup
   // (SMPL: at most 5 x 9 x 9 = 405 of 1024)
-  std::vector<int32_t> roles((size_t)DMAX * EVAL_NT, -1);
-  {
-    std::vector<int> depth(NJ, 0);
-    std::vector<std::vector<int>> at(NJ + 1);
-    for(int i = 0; i < NJ; i++)
-    {
-      depth[i] = i ? depth[m->h_parent[i]] + 1 : 0;
-      at[depth[i]].push_back(i);
-    }
-    // every (joint i, ancestor depth da <= depth(i), axis, row) once, dealt to the threads ROUND-ROBIN: entry e goes to thread
-    // e % EVAL_NT as its e / EVAL_NT-th (SMPL: 1.2 k entries, two per thread at most).  (Rounds 1-3 filled row L with the entries
-    // of the joints at tree level L, the order their level-by-level recurrence needed; the closed form has no order, and with
-    // that filling the first wavefronts held nine entries each while the last held none.)
-    size_t e = 0;
-    for(int L = 0; L < DMAX; L++)
-    {
-      const int per = 9 * (L + 1);
-      for(int t = 0; t < (int)at[L].size() * per; t++, e++)
-      {
-        if(e >= roles.size()) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_create: kinematic tree too wide for the evaluation kernel");
-        const int ji = t / per, rem = t % per, da = rem / 9, a9 = rem % 9, i = at[L][ji];
-        roles[e] = i | ((m->h_parent[i] & 31) << 5) | ((3 * da + a9 / 3) << 10) | ((a9 % 3) << 16) | ((da == L ? 1 : 0) << 18);
-      }
-    }
-  }
+  std::vector<int32_t> roles;
+  if(const char * why = eval_roles(m->h_parent, EVAL_NT, roles)) return fail(SMPLPP_ERR_INVALID, why);
   if(K > PROJ_MAXK) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_create: at most 48 tasks per frame are supported");
   if(TD75 + 2 * K + NB > MAXD)
     return fail(SMPLPP_ERR_INVALID, "smplpp_ik_create: too many tasks for the in-LDS solver (75 + 2K + 10 must be <= 181)");
@@ -228,13 +204,7 @@ extern "C" int smplpp_ik_create(smplpp_model * m, int64_t n, int64_t K, smplpp_v
     if((e = getenv("SMPLPP_IK_DBG_STOP"))) s->dbg_stop = atoi(e);
     if((e = getenv("SMPLPP_IK_OVERLAP"))) s->overlap_ok = e[0] != '0';
     if(s->dbg_sync) s->overlap_ok = false;
-    // workgroups of the face scan.  Few frames: 1536 in all (a capture fit's 64 chains: 24 chunks of 574 faces per frame, measured
-    // against 9 / 18 / 36 chunks).  256 frames: TWO chunks per frame — the scan then runs beside kernels that fill the chip
-    // themselves (solve, pose, FK: one workgroup per frame or per CU), and fewer, longer scan workgroups take less from them than
-    // many short ones: configs[2] 89.2 -> 85.0 us per iteration in three alternating pairs on one box (6 chunks before); 512 frames
-    // keep their three (2 and 3 measured level).  SMPLPP_SCAN_BLOCKS overrides.
-    s->scan_blocks = (n >= 256 && n < 512) ? 2 * n : 1536;
-    if(n >= 512 && K <= 8 && (m->F + 767) / 768 <= 32) s->scan_blocks = n * ((m->F + 767) / 768); // (chunks of at most 768 faces: the 80-register instantiation, below)
+    s->scan_blocks = default_scan_blocks(n, K, m->F); // (workgroups of the face scan: ik_plan.h; SMPLPP_SCAN_BLOCKS overrides)
     if((e = getenv("SMPLPP_SCAN_BLOCKS"))) s->scan_blocks = atoll(e);
     if((e = getenv("SMPLPP_SCAN_FORM"))) s->scan_form = atoi(e);
     s->latent_split = vposer != nullptr && n <= 128 && s->dbg_stop == 0;
@@ -431,11 +401,50 @@ extern "C" int smplpp_ik_get_tasks(smplpp_ik * s, int64_t * face_idx, float * ve
   });
 }
 
-// workgroups per frame of a kernel that deals a frame's K tasks to several: with few frames, one round of workgroups (one per CU)
-static int frame_split(int64_t n, int K)
+static int ik_join(smplpp_ik * s, hipStream_t st)
 {
-  const int split = n < 256 ? (int)(256 / n) : 1;
-  return std::max(1, std::min(split, K));
+  if(s->side_pending) // everything the caller does next on its stream is ordered behind the last re-projection
+  {
+    if(s->use_flags)
+      HIP_TRY(hipStreamWaitValue32(st, s->sig + 32, s->tick_join, hipStreamWaitValueGte, 0xffffffffu));
+    else
+      HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));
+    s->side_pending = false;
+  }
+  return SMPLPP_OK;
+}
+
+// The instantiations of ik_eval_kernel, by tree depth (deep: more than 9 levels; see EvalPlan) and by the width of the adjacency
+// tables (wide: a topology with a vertex of 13..16 faces: 16-face tables, fewer normal tasks per group): kernel, dynamic LDS, launch
+struct EvalCall
+{
+  const float * th25;
+  int optimize_beta, phi_live, min_valid, tsplit;
+  size_t shmem;
+  hipStream_t st;
+  hipEvent_t done;
+};
+template<int DM, int RC, int NG, int MA>
+static void eval_launch(smplpp_ik * s, const EvalCall & c)
+{
+  smplpp_model * m = s->m;
+  hipExtLaunchKernelGGL((ik_eval_kernel<DM, RC, NG, MA>), dim3((unsigned)(s->n * c.tsplit)), dim3(EVAL_NT), c.shmem, c.st, nullptr, c.done, 0,
+                        view_of(m), s->ta, c.th25, (const float *)s->verts, (const float *)s->rest, (const float *)m->ws.Gp.as<float>(),
+                        (const float *)s->joints, (const float *)s->poserot, (int)s->K, c.optimize_beta, c.phi_live, c.min_valid, s->pts, s->e,
+                        s->J, s->skip, s->dbg_stop, c.tsplit, s->roles, s->vp ? (const float *)s->vjac : (const float *)nullptr,
+                        s->vp ? s->Jl : (double *)nullptr);
+}
+struct EvalForm
+{
+  const void * kfn;
+  size_t lds;
+  void (*launch)(smplpp_ik *, const EvalCall &);
+};
+template<int DM, int RC, int NG, int MA>
+static EvalForm eval_form()
+{
+  return {reinterpret_cast<const void *>(&ik_eval_kernel<DM, RC, NG, MA>), sizeof(float) * EvalPlan<DM, RC, NG>::L_END + L_ANC_BYTES,
+          &eval_launch<DM, RC, NG, MA>};
 }
 
 // forward + eval for all frames (enqueue only)
@@ -471,40 +480,18 @@ static int ik_forward_eval(smplpp_ik * s, int optimize_beta, int phi_live, int64
     if(rc) return rc;
   }
   TraceRange tr_eval("calculate IK matrices"); // node.cpp:796-881
-  if(s->side_pending) // the previous iteration's re-projection (side stream) wrote the faces / weights read from here on
-  {
-    if(s->use_flags)
-      HIP_TRY(hipStreamWaitValue32(st, s->sig + 32, s->tick_join, hipStreamWaitValueGte, 0xffffffffu));
-    else
-      HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));
-    s->side_pending = false;
-  }
+  // the previous iteration's re-projection (side stream) wrote the faces / weights read from here on
+  if(int rc = ik_join(s, st)) return rc;
   s->jac_ahead = false; // (consumed by the evaluation below: the join above covers the Jacobian kernel, which raised it)
-  const bool deep = m->nlev > 9; // (ik_eval_kernel's instantiations: see EvalPlan)
-  const bool wide = m->madj > MAXADJ; // a topology with a vertex of 13..16 faces: 16-face tables, fewer normal tasks per group
-  const size_t shmem = sizeof(float) * (deep ? (wide ? EvalPlan<DMAX, 64, 3>::L_END : EvalPlan<DMAX, 64, 3>::L_END)
-                                             : (wide ? EvalPlan<9, 76, 4>::L_END : EvalPlan<9, 76, 6>::L_END)) + L_ANC_BYTES;
+  const bool deep = m->nlev > 9, wide = m->madj > MAXADJ;
+  static const EvalForm forms[4] = {eval_form<DMAX, 64, 3, MAXADJ_WIDE>(), eval_form<DMAX, 64, 3, MAXADJ>(), eval_form<9, 76, 4, MAXADJ_WIDE>(),
+                                    eval_form<9, 76, 6, MAXADJ>()};
   static PerDeviceOnce once_eval[4];
-  const void * kfn = deep ? (wide ? reinterpret_cast<const void *>(&ik_eval_kernel<DMAX, 64, 3, MAXADJ_WIDE>) : reinterpret_cast<const void *>(&ik_eval_kernel<DMAX, 64, 3>))
-                          : (wide ? reinterpret_cast<const void *>(&ik_eval_kernel<9, 76, 4, MAXADJ_WIDE>) : reinterpret_cast<const void *>(&ik_eval_kernel<9, 76, 6>));
-  HIP_TRY(lds_opt_in(once_eval[(deep ? 1 : 0) + (wide ? 2 : 0)], m->device, kfn, (int)shmem));
+  const int fi = (deep ? 0 : 2) + (wide ? 0 : 1);
+  HIP_TRY(lds_opt_in(once_eval[fi], m->device, forms[fi].kfn, (int)forms[fi].lds));
   const int tsplit = frame_split(n, K); // (a CU's LDS is one evaluation workgroup's)
   if(s->use_flags) eval_done = nullptr; // (flags mode: the fork is the solve kernel's start flag; the evaluation's end is signalled in events mode only)
-#define EVAL_(DM, RC, NG, MA)                                                                                                              \
-  hipExtLaunchKernelGGL((ik_eval_kernel<DM, RC, NG, MA>), dim3((unsigned)(n * tsplit)), dim3(EVAL_NT), shmem, st, nullptr, eval_done, 0,     \
-                        view_of(m), s->ta, th25, (const float *)s->verts, (const float *)s->rest, (const float *)m->ws.Gp.as<float>(),     \
-                        (const float *)s->joints, (const float *)s->poserot, K, optimize_beta, phi_live, (int)min_valid, s->pts, s->e,     \
-                        s->J, s->skip, s->dbg_stop, tsplit, s->roles, s->vp ? (const float *)s->vjac : (const float *)nullptr,             \
-                        s->vp ? s->Jl : (double *)nullptr)
-  if(deep && wide)
-    EVAL_(DMAX, 64, 3, MAXADJ_WIDE);
-  else if(deep)
-    EVAL_(DMAX, 64, 3, MAXADJ);
-  else if(wide)
-    EVAL_(9, 76, 4, MAXADJ_WIDE);
-  else
-    EVAL_(9, 76, 6, MAXADJ);
-#undef EVAL_
+  forms[fi].launch(s, {th25, optimize_beta, phi_live, (int)min_valid, tsplit, forms[fi].lds, st, eval_done});
   HIP_TRY(hipGetLastError());
   s->have_eval = true;
   return SMPLPP_OK;
@@ -564,8 +551,6 @@ extern "C" int smplpp_ik_eval(smplpp_ik * s, int optimize_beta, double * e, doub
   return rc ? rc : ik_report(s, space, nullptr);
 }
 
-// `iters` iterations enqueued on st (+ the solver's side stream); leaves the last re-projection pending on the side
-// stream (s->side_pending) — the caller joins (ik_join) before anything else may touch the task arrays or the mesh.
 // What the sequence driver wants done around the LAST of the iterations: the configuration after it recorded (by the solve
 // kernel itself) and the NEXT frame's targets put in place (by the re-projection's finish kernel, wherever it runs: the
 // evaluation that read the old targets is over by then, nothing else reads them, and the next evaluation waits for it).
@@ -577,19 +562,130 @@ struct SeqHook
   int shared = 0;                        // next_tpos / next_valid are [K] / [K][3]: one capture for every chain
 };
 
+// ---- one iteration's launches behind the evaluation.  Each kernel's instantiations are named once, in a table or a chain of tests;
+// which one runs, with how much LDS, is the plan's (ik_plan.h)
+struct SolveCall
+{
+  SolvePlan p;
+  SidePlan sp;
+  int beta_dim, phi_live;
+  float * theta_record; // the sequence driver's record of the configuration after this solve, or null
+  hipStream_t st;
+};
+template<bool DUAL_ONLY, int NTR>
+static void solve_launch(smplpp_ik * s, const SolveCall & c)
+{
+  const SolvePlan & p = c.p;
+  const bool go = c.sp.go, ahead = c.sp.ahead;
+  ik_solve_kernel<DUAL_ONLY, NTR><<<dim3((unsigned)s->n), dim3(256), p.shmem, c.st>>>(
+      s->ta, s->e, s->vp ? s->Jl : s->J, s->theta, s->beta, c.sp.beside ? nullptr : s->pts, (int)s->K, s->theta_dim, c.beta_dim, c.phi_live, p.qp_k,
+      s->vp ? 1 : 0, p.chunk_rows, s->skip, s->e2, s->status, s->sticky, s->xout, s->dbg_stop, p.m_dim, s->vp ? s->theta25 : (float *)nullptr,
+      c.theta_record, go ? s->sig : (unsigned *)nullptr, go ? s->sig + 16 : (unsigned *)nullptr, s->tick_fork,
+      ahead ? s->sig + 64 : (unsigned *)nullptr, ahead ? s->sig + 80 : (unsigned *)nullptr, s->tick_done);
+}
+struct SolveForm
+{
+  bool dual_only;
+  int ntr;
+  const void * kfn;
+  void (*launch)(smplpp_ik *, const SolveCall &);
+};
+template<bool DUAL_ONLY, int NTR>
+static SolveForm solve_form()
+{
+  return {DUAL_ONLY, NTR, reinterpret_cast<const void *>(&ik_solve_kernel<DUAL_ONLY, NTR>), &solve_launch<DUAL_ONLY, NTR>};
+}
+constexpr int SOLVE_FORMS = 5;
+static const SolveForm * solve_forms()
+{
+  static const SolveForm forms[SOLVE_FORMS] = {solve_form<false, 6>(), solve_form<true, 6>(), solve_form<false, 11>(), solve_form<false, 5>(),
+                                               solve_form<false, 3>()};
+  return forms;
+}
+
+static int ik_enqueue_solve(smplpp_ik * s, const SolveCall & c)
+{
+  {
+    TraceRange tr_solve("solve IK"); // node.cpp:907-943
+    const SolveForm * f = solve_forms();
+    while(f->dual_only != c.p.dual_only || f->ntr != c.p.ntr) f++; // (solve_plan's ntr is 3, 5, 6 or 11; 6 with dual_only)
+    f->launch(s, c);
+  }
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+
+template<int KPR, int NBT>
+static void scan_launch(smplpp_ik * s, int chunks, const float * qpts, const float * hint, hipStream_t pst)
+{
+  proj_scan_kernel<KPR, NBT><<<dim3((unsigned)(s->n * chunks)), dim3(256), 0, pst>>>(view_of(s->m), s->ta, s->verts, qpts, hint, s->m->F, (int)s->K, chunks,
+                                                                                    s->skip, s->list_cnt, s->list_d, s->list_f, s->dbg_stop);
+}
+
+// scan + finish of iteration `it`, on the side stream when sp.beside; last: the sequence driver's hook on the last of its iterations
+static int ik_enqueue_reproject(smplpp_ik * s, const SidePlan & sp, int it, const SeqHook * last, hipStream_t st)
+{
+  smplpp_model * m = s->m;
+  const int K = (int)s->K;
+  const bool dbg = s->dbg_sync, beside = sp.beside;
+  TraceRange tr_proj("project point"); // node.cpp:974-988
+  const float * qpts = beside ? s->ta.apos : s->pts;
+  hipStream_t pst = st;
+  if(beside)
+  {
+    if(s->use_flags)
+      HIP_TRY(hipStreamWaitValue32(s->side, s->sig, s->tick_fork, hipStreamWaitValueGte, 0xffffffffu));
+    else
+      HIP_TRY(hipStreamWaitEvent(s->side, s->ev_fork, 0));
+    pst = s->side;
+  }
+  const ScanPlan sc = scan_plan(s->n, K, m->F, s->scan_blocks, s->scan_form);
+  const float * hint = beside ? s->ta.hint : nullptr; // the evaluation's distance is to the ACTUAL position
+  if(sc.nbt3) scan_launch<0, 3>(s, sc.chunks, qpts, hint, pst);
+  else if(sc.kpr == 0) scan_launch<0, CP_BATCH>(s, sc.chunks, qpts, hint, pst);
+  else if(sc.kpr == 2) scan_launch<2, CP_BATCH>(s, sc.chunks, qpts, hint, pst);
+  else scan_launch<4, CP_BATCH>(s, sc.chunks, qpts, hint, pst);
+  HIP_TRY(hipGetLastError());
+  int *& dbg_buf = s->dbg_buf; // (SMPLPP_DEBUG_SYNC only; owned by the solver, on its device)
+  if(dbg && !dbg_buf) HIP_TRY(dalloc(s, dbg_buf, 8, AS_ALLOCATED)); // (zeroed on the stream below, every iteration)
+  if(dbg) HIP_TRY(hipMemsetAsync(dbg_buf, 0, sizeof(int) * 8, st));
+  const int fsplit = frame_split(s->n, K);
+  if(sp.go) s->tick_join++;
+  hipExtLaunchKernelGGL(proj_finish_kernel, dim3((unsigned)(s->n * fsplit)), dim3(256), 0, pst, nullptr,
+                        (beside && !s->use_flags) ? s->ev_join : nullptr, 0,
+                        view_of(m), s->ta, (const float *)s->verts, qpts, m->F, K, (const int *)s->skip, s->list_cnt, s->list_d,
+                        s->list_f, dbg ? dbg_buf : (int *)nullptr, fsplit, sp.join_flag ? s->sig + 32 : (unsigned *)nullptr,
+                        sp.join_flag ? s->sig + 48 : (unsigned *)nullptr, s->tick_join, last ? last->next_tpos : (const float *)nullptr,
+                        last ? last->next_valid : (const uint8_t *)nullptr, last ? last->shared : 0);
+  HIP_TRY(hipGetLastError());
+  if(sp.ahead)
+  {
+    HIP_TRY(hipStreamWaitValue32(s->side, s->sig + 64, s->tick_done, hipStreamWaitValueGte, 0xffffffffu));
+    int rc = vposer_forward_device(s->vp, s->n, s->theta + 6, TD44, nullptr, 75, s->vjac, s->side, s->frame_base, false, s->sig + 32,
+                                   s->sig + 48, s->tick_join);
+    if(rc) return rc;
+    s->jac_ahead = true;
+  }
+  if(beside) s->side_pending = true;
+  if(dbg)
+  {
+    int h[8];
+    HIP_TRY(hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[smplpp dbg] it %d: project lists: tasks %d, empty %d, overflow %d, nan %d, max cnt %d\n", it, h[0], h[1], h[2], h[3], h[4]);
+  }
+  return SMPLPP_OK;
+}
+
+// `iters` iterations enqueued on st (+ the solver's side stream); leaves the last re-projection pending on the side
+// stream (s->side_pending) — the caller joins (ik_join) before anything else may touch the task arrays or the mesh.
 // more_follows: the caller enqueues another iteration right behind this call's last one (the sequence driver, frame after frame)
 static int ik_iterate_enqueue(smplpp_ik * s, int iters, int enable_qp, int optimize_beta_from, int64_t min_valid, hipStream_t st,
                               const SeqHook * hook = nullptr, bool more_follows = false)
 {
   int rc = SMPLPP_OK;
-  smplpp_model * m = s->m;
   const int K = (int)s->K;
-  static PerDeviceOnce once_solve[5];
-  HIP_TRY(lds_opt_in(once_solve[0], m->device, reinterpret_cast<const void *>(&ik_solve_kernel<false>), (int)SOLVE_LDS_MAX));
-  HIP_TRY(lds_opt_in(once_solve[1], m->device, reinterpret_cast<const void *>(&ik_solve_kernel<true>), (int)SOLVE_LDS_MAX));
-  HIP_TRY(lds_opt_in(once_solve[2], m->device, reinterpret_cast<const void *>(&ik_solve_kernel<false, 11>), (int)SOLVE_LDS_MAX));
-  HIP_TRY(lds_opt_in(once_solve[3], m->device, reinterpret_cast<const void *>(&ik_solve_kernel<false, 5>), (int)SOLVE_LDS_MAX));
-  HIP_TRY(lds_opt_in(once_solve[4], m->device, reinterpret_cast<const void *>(&ik_solve_kernel<false, 3>), (int)SOLVE_LDS_MAX));
+  static PerDeviceOnce once_solve[SOLVE_FORMS];
+  for(int i = 0; i < SOLVE_FORMS; i++) HIP_TRY(lds_opt_in(once_solve[i], s->m->device, solve_forms()[i].kfn, (int)SOLVE_LDS_MAX));
   if(s->use_flags && (s->tick_fork > 0x7fff0000u || s->tick_join > 0x7fff0000u || s->tick_done > 0x7fff0000u))
   {
     // the hand-over flags carry iteration numbers compared with >=: start over long before they could wrap
@@ -598,160 +694,35 @@ static int ik_iterate_enqueue(smplpp_ik * s, int iters, int enable_qp, int optim
     HIP_TRY(hipMemset(s->sig, 0, sizeof(unsigned) * 128));
     s->tick_fork = s->tick_join = s->tick_done = 0;
   }
-  const bool dbg = s->dbg_sync;
-  const int dbg_stop = s->dbg_stop;
-  const bool overlap_ok = s->overlap_ok;
-  const int64_t scan_blocks = s->scan_blocks;
-#define DBG_SYNC(tag)                                                            \
-  if(dbg)                                                                        \
-  {                                                                              \
-    fprintf(stderr, "[smplpp dbg] it %d: %s ...\n", it, tag);                    \
-    HIP_TRY(hipStreamSynchronize(st));                                           \
-    fprintf(stderr, "[smplpp dbg] it %d: %s done\n", it, tag);                   \
-  }
+  auto dbg_sync = [&](int it, const char * tag) -> int {
+    if(!s->dbg_sync) return SMPLPP_OK;
+    fprintf(stderr, "[smplpp dbg] it %d: %s ...\n", it, tag);
+    HIP_TRY(hipStreamSynchronize(st));
+    fprintf(stderr, "[smplpp dbg] it %d: %s done\n", it, tag);
+    return SMPLPP_OK;
+  };
   for(int it = 0; it < iters; it++)
   {
-    const int opt_beta = (optimize_beta_from >= 0 && it >= optimize_beta_from) ? 1 : 0; // node.cpp:655
-    const int phi_live = (optimize_beta_from >= 0) ? (it >= optimize_beta_from ? 1 : 0) : 1; // :693-700
-    // x_phi = 0 for every task (no task's surface coordinates can move): the query points are the actual positions the
-    // evaluation wrote, so scan + finish run on the side stream beside the solve and the next iteration's pose / FK
-    const bool beside = overlap_ok && (!phi_live || s->phi_locked);
-    rc = ik_forward_eval(s, opt_beta, phi_live, min_valid, st, beside ? s->ev_fork : nullptr);
-    if(rc) return rc;
-    DBG_SYNC("forward+eval");
-    const int beta_dim = opt_beta ? NB : 0;
-    // LDS plan: packed system + vectors, the rest (up to a 150 KB total) for the J row chunk
-    const int D = s->theta_dim + 2 * K + beta_dim, rows = 4 * K;
-    s->last_D = D;
-    // the packed system is sized for the unknowns that CAN be free: a pinned phi (zero limit, node.cpp:567,699) never is,
-    // which leaves 75 of the 157 unknowns of a 41-marker motion solve and room for its 164 Jacobian rows in two chunks
-    const int m_dim = D - ((!phi_live || s->phi_locked) ? 2 * K : 0);
-    // the box of node.cpp:911-929 bounds phi and d beta only: with every phi pinned and beta fixed (each motion-stage solve) no
-    // variable has a finite bound, the QP's optimum IS the LLT solution (x = 0 + 1.0 (x_llt - 0): the same bits), and the kernel
-    // takes its LLT exit instead of a ratio test and a bound check that cannot find anything (six barriers)
-    const int qp_k = (enable_qp && !((!phi_live || s->phi_locked) && beta_dim == 0)) ? 1 : 0;
-    // tiles of 16 the register-tiled factorisation covers (176 < m_dim + 1: all-LDS path).  5 (round 4): the motion solve of a capture
-    // fit has 75 unknowns that can be free (+ the rhs row = 76 <= 80): 15 register tiles per thread instead of 21 in every rank-4
-    // update of its 19 column steps, its own instantiation like 11 (one tile count per instantiation: DESIGN.md §3.3)
-    // (and the same fit in the 44-d latent layout has 44 + 1 <= 48: 6 register tiles per thread in its 11 steps)
-    const int ntr_primal = (m_dim + 1 <= 48) ? 3 : (m_dim + 1 <= 80) ? 5 : ((m_dim + 1 <= 96 || m_dim + 1 > 176) ? 6 : 11);
-    // theta is never bound, so the free set keeps at least theta_dim unknowns: with fewer residual rows than that every pass
-    // (also every active-set pass of the QP) takes the dual form.  (Decided up here because the kernel's LDS plan depends on the
-    // instantiation's tile count: ik_solve_kernel<true> carries the default, 6.)
-    const bool dual_shape = rows < s->theta_dim && rows <= 63 && D <= 192 && dbg_stop != 9;
-    const int ntr = dual_shape ? 6 : ntr_primal;
-    const size_t fixed = sizeof(double) * ((size_t)(m_dim + 1) * (m_dim + 2) / 2 + 7 * (size_t)D + 2 * (size_t)rows + 128 * (size_t)ntr + 4) + sizeof(int) * 2 * (size_t)D;
-    const size_t budget = SOLVE_LDS_MAX;
-    int chunk_rows = (int)((budget - fixed) / (sizeof(double) * (size_t)D));
-    if(chunk_rows > rows) chunk_rows = rows;
-    if(chunk_rows < 4) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_iterate: system too large for the in-LDS solver");
-    const size_t solve_shmem = fixed + sizeof(double) * (size_t)chunk_rows * D;
-    const bool dual_only = dual_shape && chunk_rows >= rows;
-    if(dual_shape && !dual_only) return fail(SMPLPP_ERR_INVALID, "smplpp_ik_iterate: system too large for the in-LDS solver");
-    const bool last = hook && it == iters - 1;
-    float * theta_record = last ? hook->theta_record : nullptr;
-    const bool go = beside && s->use_flags; // the side stream's fork: raised by the solve kernel once all its workgroups run
-    if(go) s->tick_fork++;
-    // latent_split: the NEXT iteration's decoder Jacobian on the side stream, behind this solve's "configuration final" flag
-    const bool ahead = s->latent_split && go && !opt_beta && (it + 1 < iters || more_follows);
-    if(ahead) s->tick_done++;
-    unsigned * const done_flag = ahead ? s->sig + 64 : (unsigned *)nullptr;
-    unsigned * const done_counter = ahead ? s->sig + 80 : (unsigned *)nullptr;
-#define SOLVE_(...) ik_solve_kernel<__VA_ARGS__><<<dim3((unsigned)s->n), dim3(256), solve_shmem, st>>>(                                     \
-    s->ta, s->e, s->vp ? s->Jl : s->J, s->theta, s->beta, beside ? nullptr : s->pts, K, s->theta_dim, beta_dim, phi_live, qp_k, \
-    s->vp ? 1 : 0, chunk_rows, s->skip, s->e2, s->status, s->sticky, s->xout, dbg_stop, m_dim, s->vp ? s->theta25 : (float *)nullptr, theta_record, \
-    go ? s->sig : (unsigned *)nullptr, go ? s->sig + 16 : (unsigned *)nullptr, s->tick_fork, done_flag, done_counter, s->tick_done)
-    {
-      TraceRange tr_solve("solve IK"); // node.cpp:907-943
-      if(dual_only)
-        SOLVE_(true);
-      else if(ntr == 11)
-        SOLVE_(false, 11);
-      else if(ntr == 5)
-        SOLVE_(false, 5);
-      else if(ntr == 3)
-        SOLVE_(false, 3);
-      else
-        SOLVE_(false);
-    }
-#undef SOLVE_
-    HIP_TRY(hipGetLastError());
-    DBG_SYNC("solve");
-    {
-      TraceRange tr_proj("project point"); // node.cpp:974-988
-      const float * qpts = beside ? s->ta.apos : s->pts;
-      hipStream_t pst = st;
-      if(beside)
-      {
-        if(s->use_flags)
-          HIP_TRY(hipStreamWaitValue32(s->side, s->sig, s->tick_fork, hipStreamWaitValueGte, 0xffffffffu));
-        else
-          HIP_TRY(hipStreamWaitEvent(s->side, s->ev_fork, 0));
-        pst = s->side;
-      }
-      int chunks = (int)(scan_blocks / s->n);
-      chunks = chunks < 1 ? 1 : (chunks > 32 ? 32 : chunks);
-      const float * hint = beside ? s->ta.hint : nullptr; // the evaluation's distance is to the ACTUAL position
-      const dim3 sg((unsigned)(s->n * chunks));
-#define SCAN_(KPR, NBT_) proj_scan_kernel<KPR, NBT_><<<sg, dim3(256), 0, pst>>>(view_of(m), s->ta, s->verts, qpts, hint, m->F, K, chunks, s->skip, \
-                                                                   s->list_cnt, s->list_d, s->list_f, dbg_stop)
-      const bool small_chunk = (m->F + chunks - 1) / chunks <= 3 * 256; // (a thread then meets at most three faces)
-      // K <= 8 with 512 frames and more (configs[4]): the K > 8 instantiation on chunks of at most 768 faces — 80 registers, six
-      // wavefronts per SIMD instead of three — is the faster one beside the decoder, whose workgroups wait for the scan's to drain
-      // (44.8 against 51.6 us, the latent loop -4 %); at 256 frames the queries-in-registers form stays ahead (81.5 against 84.2 us)
-      const bool many = s->scan_form < 0 ? (s->n >= 512 && small_chunk) : s->scan_form == 0;
-      if(K <= 8 && many && small_chunk) SCAN_(0, 3);
-      else if(K <= 8 && many) SCAN_(0, CP_BATCH);
-      else if(K <= 4) SCAN_(2, CP_BATCH);
-      else if(K <= 8) SCAN_(4, CP_BATCH);
-      else if(small_chunk) SCAN_(0, 3);
-      else SCAN_(0, CP_BATCH);
-#undef SCAN_
-      HIP_TRY(hipGetLastError());
-      int *& dbg_buf = s->dbg_buf; // (SMPLPP_DEBUG_SYNC only; owned by the solver, on its device)
-      if(dbg && !dbg_buf) HIP_TRY(dalloc(s, dbg_buf, 8, AS_ALLOCATED)); // (zeroed on the stream below, every iteration)
-      if(dbg) HIP_TRY(hipMemsetAsync(dbg_buf, 0, sizeof(int) * 8, st));
-      const int fsplit = frame_split(s->n, K);
-      const bool join_flag = beside && s->use_flags && !ahead; // (ahead: the Jacobian kernel behind the finish kernel raises the join)
-      if(beside && s->use_flags) s->tick_join++;
-      hipExtLaunchKernelGGL(proj_finish_kernel, dim3((unsigned)(s->n * fsplit)), dim3(256), 0, pst, nullptr,
-                            (beside && !s->use_flags) ? s->ev_join : nullptr, 0,
-                            view_of(m), s->ta, (const float *)s->verts, qpts, m->F, K, (const int *)s->skip, s->list_cnt, s->list_d,
-                            s->list_f, dbg ? dbg_buf : (int *)nullptr, fsplit, join_flag ? s->sig + 32 : (unsigned *)nullptr,
-                            join_flag ? s->sig + 48 : (unsigned *)nullptr, s->tick_join, last ? hook->next_tpos : (const float *)nullptr,
-                            last ? hook->next_valid : (const uint8_t *)nullptr, last ? hook->shared : 0);
-      HIP_TRY(hipGetLastError());
-      if(ahead)
-      {
-        HIP_TRY(hipStreamWaitValue32(s->side, s->sig + 64, s->tick_done, hipStreamWaitValueGte, 0xffffffffu));
-        rc = vposer_forward_device(s->vp, s->n, s->theta + 6, TD44, nullptr, 75, s->vjac, s->side, s->frame_base, false, s->sig + 32,
-                                   s->sig + 48, s->tick_join);
-        if(rc) return rc;
-        s->jac_ahead = true;
-      }
-      if(beside) s->side_pending = true;
-      if(dbg)
-      {
-        int h[8];
-        HIP_TRY(hipMemcpy(h, dbg_buf, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[smplpp dbg] it %d: project lists: tasks %d, empty %d, overflow %d, nan %d, max cnt %d\n", it, h[0], h[1], h[2], h[3], h[4]);
-      }
-    }
-    DBG_SYNC("project");
-  }
-#undef DBG_SYNC
-  return SMPLPP_OK;
-}
-
-static int ik_join(smplpp_ik * s, hipStream_t st)
-{
-  if(s->side_pending) // everything the caller does next on its stream is ordered behind the last re-projection
-  {
-    if(s->use_flags)
-      HIP_TRY(hipStreamWaitValue32(st, s->sig + 32, s->tick_join, hipStreamWaitValueGte, 0xffffffffu));
-    else
-      HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));
-    s->side_pending = false;
+    // the plan (ik_plan.h) ...
+    const IterFlags f = iter_flags(optimize_beta_from, it);
+    const bool phi_free = f.phi_live && !s->phi_locked;
+    const int beta_dim = f.opt_beta ? NB : 0;
+    const SolvePlan p = solve_plan(K, s->theta_dim, beta_dim, phi_free, enable_qp != 0, s->dbg_stop == 9);
+    const SidePlan sp = side_plan(s->overlap_ok, phi_free, s->use_flags, s->latent_split, f.opt_beta != 0, it + 1 < iters || more_follows);
+    // ... the evaluation ...
+    if((rc = ik_forward_eval(s, f.opt_beta, f.phi_live, min_valid, st, sp.beside ? s->ev_fork : nullptr))) return rc;
+    if((rc = dbg_sync(it, "forward+eval"))) return rc;
+    s->last_D = p.D;
+    if(p.refusal) return fail(SMPLPP_ERR_INVALID, SOLVE_TOO_LARGE);
+    // ... the solve: it raises the side stream's fork once all its workgroups run, and "configuration final" for a Jacobian made ahead ...
+    const SeqHook * last = (hook && it == iters - 1) ? hook : nullptr;
+    if(sp.go) s->tick_fork++;
+    if(sp.ahead) s->tick_done++;
+    if((rc = ik_enqueue_solve(s, {p, sp, beta_dim, f.phi_live, last ? last->theta_record : nullptr, st}))) return rc;
+    if((rc = dbg_sync(it, "solve"))) return rc;
+    // ... and the re-projection, beside the solve when no task's surface coordinates can move
+    if((rc = ik_enqueue_reproject(s, sp, it, last, st))) return rc;
+    if((rc = dbg_sync(it, "project"))) return rc;
   }
   return SMPLPP_OK;
 }

@@ -1,6 +1,7 @@
 // Shared by the IK kernels (ik_eval.h, ik_solve.h, ik_proj.h) and their host side (ik.hip): sizes, the task arrays and the model view
-// the kernels take by value, the development stamps.
+// the kernels take by value, the development stamps.  The sizes the host's plans share with the kernels come from ik_plan.h.
 #pragma once
+#include "ik_plan.h"
 #include "mesh_device.h"
 #include "staging.h"
 #include "trace.h"
@@ -19,12 +20,7 @@ int vposer_forward_device(smplpp_vposer * v, int64_t n, const float * z, int64_t
                           float * jac, hipStream_t st, int64_t frame_base, bool value_like_jac = false, unsigned * sig_flag = nullptr,
                           unsigned * sig_counter = nullptr, unsigned sig_tick = 0u);
 
-constexpr int TD75 = SMPLPP_THETA_DIM;        // 75
-constexpr int TD44 = SMPLPP_LATENT_POSE_DIM;  // 44
-constexpr int NQ = TD75 + NB;                 // differentiation columns handled per frame: theta(75) | beta(10)
-constexpr int IK_MAXK = 48;                   // tasks per frame supported (the reference uses at most 41: MocapBody markers)
-constexpr size_t SOLVE_LDS_MAX = 160 * 1024 - 1536; // dynamic LDS the solve kernels may ask for (160 KiB per CU, minus their static LDS: 1.2 KB)
-constexpr int MAXD = TD75 + 2 * IK_MAXK + NB;  // 181: unknowns per frame supported by the in-LDS solver (every task count up to IK_MAXK, beta included)
+constexpr int NQ = TD75 + NB;                 // differentiation columns handled per frame: theta(75) | beta(10)  (TD75, IK_MAXK, MAXD ...: ik_plan.h)
 
 struct TaskArrays
 {

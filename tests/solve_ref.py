@@ -5,7 +5,7 @@ test infrastructure for tests/test_ik_solve_gpu.py.
 on the diagonal, the latent prior) and the box of node.cpp:911-929, and solves them with the oracle's box QP or LLT.
 `kkt_residual` judges any candidate step on its own (plain numpy, no active-set solver), `step_bound` is the agreement a
 backward-stable fp64 solve of that system owes, and `solve_plan` restates the host side of smplpp_ik_iterate
-(smplpp_amd/csrc/ik.hip) so that a case list can show which instantiation, dual-form factorisation and row chunking it reaches."""
+(smplpp_amd/csrc/ik_plan.h) so that a case list can show which instantiation, dual-form factorisation and row chunking it reaches."""
 import numpy as np
 
 from oracle import cpu
@@ -13,7 +13,7 @@ from oracle import cpu
 EPS = 2.220446049250313e-16
 NB = 10
 TD75, TD44 = 75, 44
-SOLVE_LDS_MAX = 160 * 1024 - 1536  # ik_types.h: dynamic LDS of the solve kernels
+SOLVE_LDS_MAX = 160 * 1024 - 1536  # ik_plan.h: dynamic LDS of the solve kernels
 
 
 def box(theta_dim, K, beta_dim, phi_limit, enable_qp, phi_live=True):
@@ -102,15 +102,18 @@ def _dual_chol(r):
 
 
 def solve_plan(K, theta_dim, beta_dim, phi_locked, rows_live=None, enable_qp=True, phi_live=True, primal_only=False):
-    """The host's choice for one iteration of smplpp_ik_iterate (ik.hip, ik_iterate_enqueue), line for line:
+    """The host's choice for one iteration of smplpp_ik_iterate, restated independently of smplpp_amd/csrc/ik_plan.h
+    (solve_plan there, whose SolvePlan fields are named on the left; tests/test_ik_plan_cpu.py holds the two together row by row):
 
-      D, rows        ik.hip:593   D = theta_dim + 2K + beta_dim, rows = 4K
-      m_dim          ik.hip:597   D - 2K when phi cannot move (not live this iteration, or every limit <= 0)
-      qp_k           ik.hip:601   enable_qp unless phi is pinned and beta fixed (the kernel's LLT exit)
-      ntr_primal     ik.hip:606   3 / 5 / 6 / 11 tiles by m_dim + 1 <= 48 / 80 / 96 (or > 176) / 176
-      dual_shape     ik.hip:610   rows < theta_dim, rows <= 63, D <= 192, not SMPLPP_IK_DBG_STOP=9 (`primal_only`)
-      fixed, chunk   ik.hip:612-615
-      dual_only      ik.hip:618
+      D, rows        D = theta_dim + 2K + beta_dim, rows = 4K
+      m_dim          D - 2K when phi cannot move (not live this iteration, or every limit <= 0: ik_plan.h's phi_free is false)
+      qp_k           enable_qp unless phi is pinned and beta fixed (the kernel's LLT exit)
+      ntr            3 / 5 / 6 / 11 tiles by m_dim + 1 <= 48 / 80 / 96 (or > 176) / 176; 6 for a dual shape: rows < theta_dim,
+                     rows <= 63, D <= 192, not SMPLPP_IK_DBG_STOP=9 (`primal_only`)
+      chunk_rows     what is left of SOLVE_LDS_MAX beside the fixed part, in rows of J; fewer than 4 is refusal 1 (the first
+                     assertion below)
+      shmem          fixed + 8 chunk_rows D
+      dual_only      a dual shape whose rows all fit; one whose rows do not is refusal 2 (the second assertion)
 
     plus what the kernel decides from it: `kernel` the instantiation (dual / ntr3 / ntr5 / ntr6 / ntr11), `first_factor` the
     factorisation of the first pass with every non-pinned unknown free (dual, reg (register tiles) or lds (the all-LDS primal):
