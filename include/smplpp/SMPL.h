@@ -21,6 +21,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <unordered_map>
 #include <vector>
@@ -225,6 +226,7 @@ public:
           "SMPL");
     beta_ = beta;
     theta_ = theta;
+    rot_ = Tensor(); // (the outputs are no longer launchRotmat's)
   }
 
   // What backward() through the last launch's graph gave the reference (e.g. node/node.cpp:823-869): for the beta / theta of the
@@ -243,6 +245,63 @@ public:
                         gb.ptr(), gt.ptr(), SMPLPP_HOST, nullptr),
           "SMPL");
     return {gb, gt};
+  }
+
+  // Axis-angles [..., 3] as rotation matrices [..., 3, 3], row-major, with the bits launch computes internally
+  // (smplpp_axis_angle_to_rotmat): launchRotmat(beta, theta[:, 0], axisAngleToRotmat(theta[:, 1:])) gives the bits of launch.
+  Tensor axisAngleToRotmat(const Tensor & aa) const
+  {
+    if(aa.shape.empty() || aa.shape.back() != 3 || aa.numel() == 0 || aa.dtype != kFloat32)
+      throw Exception("SMPL", "axisAngleToRotmat: expected float32 axis-angles of shape [..., 3]");
+    std::vector<int64_t> shape(aa.shape.begin(), aa.shape.end() - 1);
+    shape.push_back(3);
+    shape.push_back(3);
+    Tensor rot(shape);
+    check(smplpp_axis_angle_to_rotmat(device_.index, aa.numel() / 3, aa.ptr(), rot.ptr(), SMPLPP_HOST, nullptr), "SMPL");
+    return rot;
+  }
+
+  // launch from rotation matrices (smplpp_fk_rotmat): beta [N,10], trans [N,3] (root translation), rot [N,24,3,3] row-major, joint 0
+  // the root orientation, used as given.  An empty beta or trans = zero.  The getters return its outputs as they do launch's.
+  void launchRotmat(const Tensor & beta, const Tensor & trans, const Tensor & rot)
+  {
+    const bool hb = !beta.data.empty(), ht = !trans.data.empty();
+    if(!m_ || rot.shape.size() != 4 || rot.size(1) != JOINT_NUM || rot.size(2) != 3 || rot.size(3) != 3 || rot.dtype != kFloat32
+       || (hb && (beta.numel() != rot.size(0) * SHAPE_BASIS_DIM || beta.dtype != kFloat32))
+       || (ht && (trans.numel() != rot.size(0) * 3 || trans.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot launch a SMPL model!");
+    const int64_t n = rot.size(0);
+    verts_ = Tensor({n, V_, 3});
+    rest_ = Tensor({n, V_, 3});
+    joints_ = Tensor({n, JOINT_NUM, 3});
+    xforms_ = Tensor({n, JOINT_NUM, 4, 4});
+    check(smplpp_fk_rotmat(m_.get(), n, hb ? beta.ptr() : nullptr, ht ? trans.ptr() : nullptr, rot.ptr(), verts_.ptr(), joints_.ptr(),
+                           xforms_.ptr(), rest_.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    betaR_ = beta;
+    transR_ = trans;
+    rot_ = rot;
+    beta_ = theta_ = Tensor(); // (the outputs are no longer launch's: launchBackward refuses)
+  }
+
+  // The backward of the last launchRotmat (smplpp_fk_rotmat_vjp, reusing its rest shape): {dL/dbeta [N,10], dL/dtrans [N,3],
+  // dL/drot [N,24,3,3]} for dL/dverts = gradVert and dL/djoints = gradJoint (an empty Tensor = zero).  dL/drot is the gradient to nine
+  // independent entries per joint.
+  std::tuple<Tensor, Tensor, Tensor> launchRotmatBackward(const Tensor & gradVert, const Tensor & gradJoint) const
+  {
+    const Tensor & rest = need(rest_);
+    if(rot_.data.empty()) throw Exception("SMPL", "Cannot back-propagate through a SMPL model!");
+    const int64_t n = rot_.size(0);
+    const bool hv = !gradVert.data.empty(), hj = !gradJoint.data.empty();
+    if((hv && (gradVert.numel() != n * V_ * 3 || gradVert.dtype != kFloat32)) ||
+       (hj && (gradJoint.numel() != n * JOINT_NUM * 3 || gradJoint.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot back-propagate through a SMPL model!");
+    Tensor gb({n, SHAPE_BASIS_DIM}), gt({n, 3}), gr({n, JOINT_NUM, 3, 3});
+    check(smplpp_fk_rotmat_vjp(m_.get(), n, betaR_.data.empty() ? nullptr : betaR_.ptr(), transR_.data.empty() ? nullptr : transR_.ptr(),
+                               rot_.ptr(), rest.ptr(), hv ? gradVert.ptr() : nullptr, hj ? gradJoint.ptr() : nullptr, gb.ptr(), gt.ptr(),
+                               gr.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return {gb, gt, gr};
   }
 
   Tensor getVertex() const { return need(verts_); }       // [N,6890,3] copy (src/SMPL.cpp:492-506)
@@ -824,6 +883,7 @@ private:
   Tensor faces1_;
   Tensor verts_, rest_, joints_, xforms_;
   Tensor beta_, theta_; // inputs of the last launch (launchBackward)
+  Tensor betaR_, transR_, rot_; // inputs of the last launchRotmat (launchRotmatBackward)
 };
 } // namespace smplpp
 #endif

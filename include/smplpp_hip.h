@@ -95,6 +95,24 @@ int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const float * the
  * The first call on a model builds the basis operand image of the backward (~19 MB for SMPL; freed by smplpp_model_destroy). */
 int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * grad_verts,
                   const float * grad_joints, float * grad_beta, float * grad_theta, int space, void * stream);
+/* smplpp_fk from rotation matrices (what smplx calls pose2rot=False): rot [n,24,3,3] row-major, joint 0 the root orientation (the
+ * layout of a rotation-matrix or 6-D regressor's output); trans [n,3] the root translation (NULL = zero); beta [n,10] (NULL = zero).
+ * With rot = smplpp_axis_angle_to_rotmat(theta[:,1:]) and trans = theta[:,0] every output has the bits of smplpp_fk(beta, theta).
+ * The matrices are used AS GIVEN: no re-orthonormalisation and no determinant check, so the call is the polynomial map
+ * rest = T + S beta + P vec(R_j - I, j >= 1), A_0 = R_0, A_j = A_parent(j) R_j.  Outputs, NULL handling, forms (SMPLPP_SKIN), the
+ * range word of the fp16x2 form (there also: entries of R_j - I below 1023) and smplpp_fk_status: as smplpp_fk. */
+int smplpp_fk_rotmat(smplpp_model * m, int64_t n, const float * beta /*[n,10], NULL = 0*/, const float * trans /*[n,3], NULL = 0*/,
+                     const float * rot /*[n,24,3,3]*/, float * verts, float * joints, float * xforms, float * rest, int space, void * stream);
+/* Vector-Jacobian product of smplpp_fk_rotmat: given dL/dverts [n,V,3] and/or dL/djoints [n,24,3] (either may be NULL = zero), writes
+ * dL/dbeta [n,10], dL/dtrans [n,3] and dL/drot [n,24,3,3] (any may be NULL).  grad_rot is the gradient to NINE INDEPENDENT ENTRIES per
+ * joint (the map above is polynomial in them): it is not projected onto the tangent space of the rotations and has no singularity at
+ * rotation 0 or pi; a caller that parametrises R (6-D, quaternion, axis-angle) contracts it with that parametrisation's derivative.
+ * trans is accepted for symmetry and not read (nothing here depends on it).  rest: as smplpp_fk_vjp (NULL = recomputed in the
+ * backward's own workspace; pass rest + D for an SMPL+D body).  Overwrites its outputs; deterministic.  grad_beta and grad_trans have the
+ * bits smplpp_fk_vjp gives for the same body: the two calls share everything but the last contraction. */
+int smplpp_fk_rotmat_vjp(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, const float * rest /*nullable*/,
+                         const float * grad_verts, const float * grad_joints, float * grad_beta /*[n,10]*/, float * grad_trans /*[n,3]*/,
+                         float * grad_rot /*[n,24,3,3]*/, int space, void * stream);
 /* Input range of the fp16x2 form (SMPLPP_SKIN=h): |beta| < 1023 and relative transforms whose
  * translations stay within 16 x the template's extent (65504 / sG).  Outside it the operand pieces overflow fp16 and the
  * vertices of the frame are not finite, where the reference and the default form (and SMPLPP_SKIN=b|v) stay finite.  A launch that
@@ -642,6 +660,10 @@ int smplpp_vposer_jacobian(smplpp_vposer * v, int64_t n, int64_t frame_base, con
                            void * stream);
 /* convertRotMatToAxisAngle (src/VPoser.cpp:25-120): rot [n,3,3] -> aa [n,3]. */
 int smplpp_rotmat_to_axis_angle(int device, int64_t n, const float * rot, float * aa, int space, void * stream);
+/* The inverse companion: aa [n,3] -> rot [n,3,3] row-major by the reference's Rodrigues formula (src/BlendShape.cpp:803-844:
+ * angle = ||aa + 1e-8||, so aa = 0 gives the identity without a branch), with the operation order of smplpp_fk's pose step: the bits
+ * smplpp_fk computes internally for the same axis-angle. */
+int smplpp_axis_angle_to_rotmat(int device, int64_t n, const float * aa /*[n,3]*/, float * rot /*[n,3,3]*/, int space, void * stream);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,8 @@ def load():
         "smplpp_fk": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_fk_status": [vp, C.POINTER(C.c_int), vp],
         "smplpp_fk_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_fk_rotmat": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_fk_rotmat_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_blend_shape": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_joint_regression": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_world_transformation": [C.c_int, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
@@ -121,6 +123,7 @@ def load():
         "smplpp_vposer_vjp": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_vposer_jacobian": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_rotmat_to_axis_angle": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
+        "smplpp_axis_angle_to_rotmat": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name, None)

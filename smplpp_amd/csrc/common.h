@@ -156,6 +156,7 @@ struct Workspace
   DevBuf A2h;     // the same coefficients as fp16x2 pieces in fragment order (skin_h.hip)
   DevBuf G2h;     // relative transforms as fp16x2 pieces, the A operand of the blend MFMAs (skin_h.hip)
   DevBuf Gp;      // [n][24][12] relative transforms, 3x4 row-major
+  DevBuf root;    // [n][25][3], row 0 written: smplpp_fk_rotmat's root translation where the fused kernels read theta[f][0][:]
   int64_t ldA = 0;
 };
 // Per-feature state of a handle, created by the feature's first call on it and owned by the handle

@@ -48,6 +48,18 @@ __global__ __launch_bounds__(256) void pose_kernel(PoseArgs a)
   pose_body(a, f, (int)threadIdx.x, a.theta + f * ((NJ + 1) * 3));
 }
 
+// smplpp_fk_rotmat's pose step: the rotation-input instantiation of the body (a.theta = rot [n][24][9]).  The fused kernels read the
+// root translation as theta[f][0][:], stride 75: this kernel writes the frame's translation (NULL = zero) as row 0 of a [n][25][3]
+// image in the workspace, which the fused kernel of any form is then handed as its `theta`.
+__global__ __launch_bounds__(256) void pose_kernel_rot(PoseArgs a, const float * __restrict__ trans, float * __restrict__ root)
+{
+  const int64_t f = blockIdx.x;
+  if(f >= a.n) return;
+  const int tid = (int)threadIdx.x;
+  if(tid >= 252 && tid < 255) root[f * ((NJ + 1) * 3) + (tid - 252)] = trans ? trans[f * 3 + (tid - 252)] : 0.0f;
+  pose_body<true>(a, f, tid, a.theta + f * (NJ * 9));
+}
+
 // rows [n, ldA) of AT are padding for the last 32-frame tile: keep them zero (re-zeroed whenever n changes)
 __global__ void zero_pad_kernel(float * __restrict__ AT, int64_t ldA, int64_t n)
 {
@@ -295,11 +307,19 @@ static char launch_form(const smplpp_model * m, int range_slot, char form_overri
 // iterate outside the range does not turn a later, in-range smplpp_fk into an error
 // Pose step of a launch of form `form`: joints, relative transforms and the fused kernel's operand images (when `with_ops`) into
 // the model's workspace.
+// rot_in: `theta` is rot [n][24][9] (smplpp_fk_rotmat) and `trans` [n][3] (nullable) the root translation, which goes to ws.root.
 static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * beta, const float * theta, float * joints, float * xforms44,
-                          float * poserot, hipStream_t st, int * range_word, bool with_ops)
+                          float * poserot, hipStream_t st, int * range_word, bool with_ops, bool rot_in = false, const float * trans = nullptr)
 {
   Workspace & ws = m->ws;
   const int64_t n64 = ((n + 63) / 64) * 64;
+  if(rot_in) HIP_TRY(ws.root.reserve(sizeof(float) * (size_t)n * (NJ + 1) * 3));
+  auto launch_pose = [&](const PoseArgs & pa) {
+    if(rot_in)
+      pose_kernel_rot<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa, trans, ws.root.as<float>());
+    else
+      pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
+  };
   HIP_TRY(ws.Gp.reserve(sizeof(float) * (size_t)n64 * NJ * 12)); // e / b stage whole frame tiles of G' (padding never stored)
   if(form == 'h')
   {
@@ -307,7 +327,7 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
     HIP_TRY(ws.G2h.reserve((size_t)(n64 / 64) * HB_G_BYTES));
     PoseArgs pa = fk_pose_args(m, n, beta, theta, joints, poserot, xforms44, with_ops);
     pa.range_flag = range_word;
-    pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
+    launch_pose(pa);
   }
   else if(form == 'e' || form == 'b')
   {
@@ -316,7 +336,7 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
     pa.A3 = with_ops ? ws.A3.as<uint16_t>() : nullptr;
     pa.gscale = 1.0f;
     pa.range_flag = nullptr;
-    pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
+    launch_pose(pa);
   }
   else
   {
@@ -334,7 +354,7 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
     pa.ldA = ldA;
     pa.gscale = 1.0f;
     pa.range_flag = nullptr;
-    pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
+    launch_pose(pa);
   }
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
@@ -386,6 +406,29 @@ int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * the
                           verts || rest);
   if(rc) return rc;
   return fk_skin_device(m, form, n, theta, verts, rest, st);
+}
+
+// smplpp_fk_rotmat on device pointers (enqueue only): the rotation-input pose step, then the fused kernel of the model's form with the
+// workspace's root image as its `theta`.
+int fk_rotmat_device(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, float * verts, float * joints,
+                     float * xforms44, float * rest, hipStream_t st, int range_slot, int * range_word)
+{
+  const char form = launch_form(m, range_slot, 0);
+  int rc = fk_pose_device(m, form, n, beta, rot, joints, xforms44, nullptr, st, range_word ? range_word : m->range_flag.get() + range_slot,
+                          verts || rest, true, trans);
+  if(rc) return rc;
+  return fk_skin_device(m, form, n, m->ws.root.as<float>(), verts, rest, st);
+}
+
+// R = rodrigues9(theta) per row: the inverse companion of rotmat_to_aa_kernel (vposer.hip)
+__global__ void aa_to_rotmat_kernel(const float * __restrict__ aa, float * __restrict__ rot, int64_t n)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n) return;
+  float R[9];
+  rodrigues9(aa[i * 3 + 0], aa[i * 3 + 1], aa[i * 3 + 2], R);
+#pragma unroll
+  for(int q = 0; q < 9; q++) rot[i * 9 + q] = R[q];
 }
 } // namespace smplpp_hip
 
@@ -473,4 +516,58 @@ extern "C" int smplpp_fk(smplpp_model * m, int64_t n, const float * beta, const 
     return fail(SMPLPP_ERR_NUMERIC, "smplpp_fk: an operand left the range of the fp16x2 form (|beta| < 1023, relative transforms within 16 x the "
                                     "template's extent): the vertices of such frames are not finite; create the model under SMPLPP_SKIN=e or b");
   return SMPLPP_OK;
+}
+
+extern "C" int smplpp_fk_rotmat(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, float * verts,
+                                float * joints, float * xforms, float * rest, int space, void * stream)
+{
+  if(!m) return fail(SMPLPP_ERR_INVALID, "Cannot launch a SMPL model!");
+  if(n <= 0 || !rot) return fail(SMPLPP_ERR_INVALID, "Cannot launch a SMPL model!");
+  if(int rc = check_space(space, "smplpp_fk_rotmat")) return rc;
+  if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_rotmat: too many frames");
+  Frame fr(m->device, &m->arena, space, stream, "forward SMPL");
+  if(space == SMPLPP_DEVICE)
+    return fr.run([&] { return fk_rotmat_device(m, n, beta, trans, rot, verts, joints, xforms, rest, fr.st, RANGE_DEVICE, nullptr); });
+
+  const size_t nv = (size_t)n * m->V * 3;
+  const float * b = fr.in(beta, (size_t)n * NB);
+  const float * t = fr.in(trans, (size_t)n * 3);
+  const float * ro = fr.in(rot, (size_t)n * NJ * 9);
+  float * v = fr.out(verts, nv);
+  float * r = fr.out(rest, nv);
+  float * j = fr.out(joints, (size_t)n * NJ * 3);
+  float * x = fr.out(xforms, (size_t)n * NJ * 16);
+  // (the range word of a host-space launch: as smplpp_fk)
+  const bool ranged = m->range_flag && m->form == 'h';
+  int rc = fr.run([&]() -> int {
+    if(ranged) HIP_TRY(hipMemsetAsync(m->range_flag.get() + RANGE_HOST, 0, sizeof(int), fr.st));
+    return fk_rotmat_device(m, n, b, t, ro, v, j, x, r, fr.st, RANGE_HOST, nullptr);
+  });
+  if(rc) return rc;
+  int bits = 0;
+  if(ranged) HIP_TRY(hipMemcpy(&bits, m->range_flag.get() + RANGE_HOST, sizeof(int), hipMemcpyDeviceToHost));
+  if(bits & 1)
+    return fail(SMPLPP_ERR_NUMERIC, "smplpp_fk_rotmat: an operand left the range of the fp16x2 form (|beta| < 1023, entries of R - I below 1023, "
+                                    "relative transforms within 16 x the template's extent): the vertices of such frames are not finite; create "
+                                    "the model under SMPLPP_SKIN=e or b");
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_axis_angle_to_rotmat(int device, int64_t n, const float * aa, float * rot, int space, void * stream)
+{
+  if(n <= 0 || !aa || !rot) return fail(SMPLPP_ERR_INVALID, "smplpp_axis_angle_to_rotmat: bad argument");
+  int rc = check_space(space, "smplpp_axis_angle_to_rotmat");
+  if(rc) return rc;
+  int ndev = 0;
+  rc = smplpp_device_count(&ndev);
+  if(rc) return rc;
+  if(device < 0 || device >= ndev) return fail(SMPLPP_ERR_INVALID, "Failed to fetch device index!");
+  Frame fr(device, nullptr, space, stream, nullptr);
+  const float * ai = fr.in(aa, (size_t)n * 3);
+  float * ro = fr.out(rot, (size_t)n * 9);
+  return fr.run([&]() -> int {
+    aa_to_rotmat_kernel<<<dim3((unsigned)((n + 127) / 128)), dim3(128), 0, fr.st>>>(ai, ro, n);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  });
 }

@@ -40,6 +40,8 @@ int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * the
               float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word, char form_override = 0);
 PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * joints, float * poserot, float * xforms44,
                       bool with_ops);
+int fk_rotmat_device(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, float * verts, float * joints,
+                     float * xforms44, float * rest, hipStream_t st, int range_slot, int * range_word);
 
 constexpr int VJ_FT = 32;              // frames per workgroup of the hot kernel (the MFMA rows)
 constexpr int VJ_KN = 224;             // columns of the operand image (k < 217 live)
@@ -87,6 +89,14 @@ __global__ __launch_bounds__(256) void vjp_pose_kernel(PoseArgs a)
   const int64_t f = blockIdx.x;
   if(f >= a.n) return;
   pose_body(a, f, (int)threadIdx.x, a.theta + f * ((NJ + 1) * 3));
+}
+
+// smplpp_fk_rotmat_vjp's pose step: the rotation-input instantiation (a.theta = rot [n][24][9])
+__global__ __launch_bounds__(256) void vjp_pose_kernel_rot(PoseArgs a)
+{
+  const int64_t f = blockIdx.x;
+  if(f >= a.n) return;
+  pose_body<true>(a, f, (int)threadIdx.x, a.theta + f * (NJ * 9));
 }
 
 // grid: nft frame tiles x nch chunks of `gpc` vertex groups (gpc a multiple of 4: the four wavefronts take one group each per round).
@@ -274,11 +284,16 @@ __global__ __launch_bounds__(256, 2) void vjp_skin_kernel(const float * __restri
 }
 
 // one workgroup per frame.  nch = 0: no vertex gradient (the slabs are not read).
+// ROT_OUT (smplpp_fk_rotmat_vjp): `rot` is the caller's rot [n][24][9], `theta` unused; instead of contracting dL/dR with the Rodrigues
+// derivative the kernel writes it, nine independent entries per joint, to gtheta = grad_rot [n][24][9], and the root sum to gtrans [n][3]
+// (either may be null).  Everything up to there is the same code in the same order: the same bits.
+template<bool ROT_OUT>
 __global__ __launch_bounds__(256) void vjp_chain_kernel(const float * __restrict__ slab, int nch, const float * __restrict__ Gp,
                                                      const float * __restrict__ joints, const float * __restrict__ rot,
                                                      const float * __restrict__ theta, const float * __restrict__ gj,
                                                      const float * __restrict__ JS, const int32_t * __restrict__ parent,
-                                                     float * __restrict__ gbeta, float * __restrict__ gtheta, int64_t n)
+                                                     float * __restrict__ gbeta, float * __restrict__ gtheta,
+                                                     float * __restrict__ gtrans, int64_t n)
 {
   const int64_t f = blockIdx.x;
   const int tid = threadIdx.x;
@@ -389,6 +404,12 @@ __global__ __launch_bounds__(256) void vjp_chain_kernel(const float * __restrict
     for(int i = 0; i < NJ * 3; i++) s += JS[i * NB + tid] * dJ[i / 3][i % 3];
     gbeta[f * NB + tid] = s;
   }
+  if constexpr(ROT_OUT)
+  {
+    if(gtheta && tid < NJ * 9) gtheta[f * (NJ * 9) + tid] = dR[tid / 9][tid % 9];
+    if(gtrans && tid >= 224 && tid < 227) gtrans[f * 3 + (tid - 224)] = sS[VJ_ROOT + tid - 224];
+    return;
+  }
   if(gtheta && tid >= 64 && tid < 64 + NJ * 3)
   {
     const int t = tid - 64, jj = t / 3, m = t % 3;
@@ -421,8 +442,11 @@ static void vjp_chunks(const smplpp_model * m, int64_t n, int & nft, int & nch, 
   nch = (int)((m->VGn + gpc - 1) / gpc);
 }
 
+// rot_in (smplpp_fk_rotmat_vjp): `theta` is rot [n][24][9], `trans` [n][3] (nullable) the root translation, gtheta = grad_rot
+// [n][24][9] and gtrans = grad_trans [n][3]
 static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * gv,
-                      const float * gj, float * gbeta, float * gtheta, hipStream_t st)
+                      const float * gj, float * gbeta, float * gtheta, hipStream_t st, bool rot_in = false, const float * trans = nullptr,
+                      float * gtrans = nullptr)
 {
   VjpState * s = m->vjp.get();
   if(!s->BT)
@@ -439,7 +463,9 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
     std::swap(m->ws, s->fws);
     const bool prof = m->profiling;
     m->profiling = false;
-    int rc = fk_device(m, n, beta, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), nullptr, st, RANGE_DEVICE, s->range_word.get());
+    int rc = rot_in ? fk_rotmat_device(m, n, beta, trans, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), st, RANGE_DEVICE,
+                                       s->range_word.get())
+                    : fk_device(m, n, beta, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), nullptr, st, RANGE_DEVICE, s->range_word.get());
     m->profiling = prof;
     std::swap(m->ws, s->fws);
     if(rc) return rc;
@@ -447,14 +473,18 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
   }
   HIP_TRY(s->Gp.reserve(sizeof(float) * (size_t)n * NJ * 12));
   HIP_TRY(s->joints.reserve(sizeof(float) * (size_t)n * NJ * 3));
-  HIP_TRY(s->rot.reserve(sizeof(float) * (size_t)n * NJ * 9));
-  PoseArgs pa = fk_pose_args(m, n, beta, theta, s->joints.as<float>(), s->rot.as<float>(), nullptr, false);
+  if(!rot_in) HIP_TRY(s->rot.reserve(sizeof(float) * (size_t)n * NJ * 9));
+  // (rotation input: the chain kernel reads the caller's matrices, no copy)
+  PoseArgs pa = fk_pose_args(m, n, beta, theta, s->joints.as<float>(), rot_in ? nullptr : s->rot.as<float>(), nullptr, false);
   pa.Gp = s->Gp.as<float>();
   pa.A3 = nullptr;
   pa.AT = nullptr;
   pa.gscale = 1.0f;
   pa.range_flag = nullptr;
-  vjp_pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
+  if(rot_in)
+    vjp_pose_kernel_rot<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
+  else
+    vjp_pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
   HIP_TRY(hipGetLastError());
   int nft = 0, nch = 0, gpc = 0;
   if(gv)
@@ -469,15 +499,33 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
       default: HIP_TRY(launch_vjp_skin<NJ>(m, s, n, rest, gv, slab, nft, nch, gpc, st)); break;
     }
   }
-  vjp_chain_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(gv ? s->slab.as<float>() : nullptr, gv ? nch : 0, s->Gp.as<float>(),
-                                                           s->joints.as<float>(), s->rot.as<float>(), theta, gj, m->JS.get(), m->parent.get(),
-                                                           gbeta, gtheta, n);
+  if(rot_in)
+    vjp_chain_kernel<true><<<dim3((unsigned)n), dim3(256), 0, st>>>(gv ? s->slab.as<float>() : nullptr, gv ? nch : 0, s->Gp.as<float>(),
+                                                                   s->joints.as<float>(), theta, nullptr, gj, m->JS.get(), m->parent.get(),
+                                                                   gbeta, gtheta, gtrans, n);
+  else
+    vjp_chain_kernel<false><<<dim3((unsigned)n), dim3(256), 0, st>>>(gv ? s->slab.as<float>() : nullptr, gv ? nch : 0, s->Gp.as<float>(),
+                                                                    s->joints.as<float>(), s->rot.as<float>(), theta, gj, m->JS.get(),
+                                                                    m->parent.get(), gbeta, gtheta, nullptr, n);
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
 } // namespace smplpp_hip
 
 using namespace smplpp_hip;
+
+// the backward state of a model, created by the first backward call on it
+static int vjp_state(smplpp_model * m)
+{
+  if(!m->vjp)
+  {
+    StatePtr<VjpState> s(new VjpState());
+    HIP_TRY(dev_alloc(s->range_word, 1));
+    HIP_TRY(hipMemset(s->range_word.get(), 0, sizeof(int)));
+    m->vjp = std::move(s);
+  }
+  return SMPLPP_OK;
+}
 
 extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * grad_verts,
                              const float * grad_joints, float * grad_beta, float * grad_theta, int space, void * stream)
@@ -488,13 +536,7 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: too many frames");
   Frame fr(m->device, &m->arena, space, stream, "backward SMPL");
   if(!fr.ok()) return fr.finish();
-  if(!m->vjp)
-  {
-    StatePtr<VjpState> s(new VjpState());
-    HIP_TRY(dev_alloc(s->range_word, 1));
-    HIP_TRY(hipMemset(s->range_word.get(), 0, sizeof(int)));
-    m->vjp = std::move(s);
-  }
+  if(int rc = vjp_state(m)) return rc;
   if(!grad_beta && !grad_theta) return SMPLPP_OK;
   if(space == SMPLPP_DEVICE)
     return fr.run([&] { return vjp_device(m, n, beta, theta, rest, grad_verts, grad_joints, grad_beta, grad_theta, fr.st); });
@@ -508,4 +550,34 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
   float * gb = fr.out(grad_beta, nb);
   float * gt = fr.out(grad_theta, nt);
   return fr.run([&] { return vjp_device(m, n, b, t, r, gv, gj, gb, gt, fr.st); });
+}
+
+extern "C" int smplpp_fk_rotmat_vjp(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, const float * rest,
+                                    const float * grad_verts, const float * grad_joints, float * grad_beta, float * grad_trans,
+                                    float * grad_rot, int space, void * stream)
+{
+  if(!m) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_rotmat_vjp: null model");
+  if(n <= 0 || !rot) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_rotmat_vjp: needs n > 0 and rot");
+  if(int rc = check_space(space, "smplpp_fk_rotmat_vjp")) return rc;
+  if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_rotmat_vjp: too many frames");
+  Frame fr(m->device, &m->arena, space, stream, "backward SMPL");
+  if(!fr.ok()) return fr.finish();
+  if(int rc = vjp_state(m)) return rc;
+  if(!grad_beta && !grad_trans && !grad_rot) return SMPLPP_OK;
+  // `trans` is not read: neither the rest shape nor any of the three gradients depends on it (and the call stages eight arguments)
+  (void)trans;
+  if(space == SMPLPP_DEVICE)
+    return fr.run(
+        [&] { return vjp_device(m, n, beta, rot, rest, grad_verts, grad_joints, grad_beta, grad_rot, fr.st, true, nullptr, grad_trans); });
+
+  const size_t nb = (size_t)n * NB, nr = (size_t)n * NJ * 9, nv = (size_t)n * m->V * 3;
+  const float * b = fr.in(beta, nb);
+  const float * ro = fr.in(rot, nr);
+  const float * r = grad_verts ? fr.in(rest, nv) : nullptr;
+  const float * gv = fr.in(grad_verts, nv);
+  const float * gj = fr.in(grad_joints, (size_t)n * NJ * 3);
+  float * gb = fr.out(grad_beta, nb);
+  float * gt = fr.out(grad_trans, (size_t)n * 3);
+  float * gr = fr.out(grad_rot, nr);
+  return fr.run([&] { return vjp_device(m, n, b, ro, r, gv, gj, gb, gr, fr.st, true, nullptr, gt); });
 }

@@ -13,7 +13,7 @@ typedef _Float16 pose_f16x8 __attribute__((ext_vector_type(8)));
 struct PoseArgs
 {
   const float * beta;       // [n][10] (nullable: zeros)
-  const float * theta;      // [n][25][3]
+  const float * theta;      // [n][25][3]; the rotation-input instantiation: rot [n][24][9]
   const float *J0, *JS, *JSp;
   const int32_t *parent, *lvl_off, *lvl_joint;
   int nlev;
@@ -60,6 +60,10 @@ __device__ __forceinline__ void block_sync_lds()
 #define PSTC(i)
 #endif
 // theta_frame: the frame's [25][3] configuration (global memory in pose_kernel; the solve kernel hands over its LDS copy)
+// ROT_IN (pose_kernel_rot, vjp_pose_kernel_rot: smplpp_fk_rotmat and its backward): theta_frame is the frame's 24 rotation matrices
+// [24][9] instead, row-major, used as given; threads 0..23 load their nine floats where the other instantiation runs Rodrigues, and
+// everything after reads them from LDS as before.
+template<bool ROT_IN = false>
 __device__ __forceinline__ void pose_body(const PoseArgs & pa, const int64_t f, const int tid, const float * __restrict__ theta_frame)
 {
   // rotations [24][9] | joints [24][3] | zero[4] in ONE array: the chain's operand addresses are indices into it (CT_* below)
@@ -139,8 +143,16 @@ __device__ __forceinline__ void pose_body(const PoseArgs & pa, const int64_t f, 
   if(tid < NJ)
   {
     float R[9];
-    const float * th = theta_frame + (1 + tid) * 3; // theta[:,1:,:] (src/SMPL.cpp:685-686)
-    rodrigues9(th[0], th[1], th[2], R);
+    if constexpr(ROT_IN)
+    {
+#pragma unroll
+      for(int q = 0; q < 9; q++) R[q] = theta_frame[tid * 9 + q];
+    }
+    else
+    {
+      const float * th = theta_frame + (1 + tid) * 3; // theta[:,1:,:] (src/SMPL.cpp:685-686)
+      rodrigues9(th[0], th[1], th[2], R);
+    }
 #pragma unroll
     for(int q = 0; q < 9; q++) sR[tid][q] = R[q];
     if(pa.rot_out)

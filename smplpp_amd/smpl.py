@@ -133,6 +133,24 @@ class _Call:
         return np.empty(shape, dtype)
 
 
+def rot6d_to_rotmat(x):
+    """The 6-D rotation representation as rotation matrices, [..., 6] -> [..., 3, 3], in plain differentiable torch: x[..., 0::2] and
+    x[..., 1::2] are read as the first two columns (the [..., 3, 2] view of the reference's decoder, src/VPoser.cpp:129-141); b1 =
+    normalize(a1), b2 = normalize(a2 - (b1 . a2) b1), b3 = b1 x b2, stacked as columns.  On the first two columns of a rotation
+    it is the identity.  With SMPL.forward_rotmat_differentiable the 6-D output of a regressor drives the body end to end, with
+    no axis-angle in between."""
+    if torch is None:
+        raise SmplppError(1, "rot6d_to_rotmat needs torch")
+    if x.shape[-1] != 6:
+        raise SmplppError(1, "rot6d_to_rotmat: expected [..., 6], got %s" % (tuple(x.shape),))
+    m = x.reshape(*x.shape[:-1], 3, 2)
+    a1, a2 = m[..., 0], m[..., 1]
+    b1 = torch.nn.functional.normalize(a1, dim=-1)
+    b2 = torch.nn.functional.normalize(a2 - (b1 * a2).sum(-1, keepdim=True) * b1, dim=-1)
+    b3 = torch.cross(b1, b2, dim=-1)
+    return torch.stack([b1, b2, b3], dim=-1)
+
+
 def parse_device(device) -> int:
     """Reference: `torch::Device` with an explicit index (src/SMPL.cpp:289-297); "CUDA" selects the GPU engine
     (node/node.cpp:360-371).  There is no CPU engine here."""
@@ -258,6 +276,67 @@ class SMPL:
         if torch is None:
             raise SmplppError(1, "forward_differentiable needs torch")
         return _FKFunction.apply(beta, theta, self)
+
+    # ---- launch from rotation matrices (smplpp_axis_angle_to_rotmat / smplpp_fk_rotmat / smplpp_fk_rotmat_vjp)
+    def axisAngleToRotmat(self, aa):
+        """Axis-angles [..., 3] as rotation matrices [..., 3, 3], row-major (smplpp_axis_angle_to_rotmat): the reference's Rodrigues
+        formula with the bits `launch` computes internally, so launchRotmat(beta, theta[:, 0], axisAngleToRotmat(theta[:, 1:]))
+        returns the bits of launch(beta, theta).  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("axisAngleToRotmat", aa)
+        shape = tuple(aa.shape) if c.dev else np.shape(aa)
+        if not shape or shape[-1] != 3 or int(np.prod(shape)) == 0:
+            c.refuse("expected axis-angles of shape (..., 3)")
+        rows = int(np.prod(shape[:-1]))
+        aa = c.input(aa.reshape(rows, 3) if c.dev else _np32(aa).reshape(rows, 3), (rows, 3))
+        rot = c.empty((rows, 3, 3))
+        check(_lib.load().smplpp_axis_angle_to_rotmat(self._device, rows, _ptr(aa), _ptr(rot), c.space, c.stream))
+        return rot.reshape(tuple(shape[:-1]) + (3, 3))
+
+    def _fk_rotmat(self, c, beta, trans, rot, want, out=None):
+        """smplpp_fk_rotmat in the space of `c`: (beta, trans, rot as passed to it, {"verts", "joints", "xforms", "rest"})."""
+        n, V = int(rot.shape[0]) if c.dev else len(rot), self.vertex_num
+        beta, trans, rot = c.input(beta, (n, 10)), c.input(trans, (n, 3)), c.input(rot, (n, 24, 3, 3))
+        pre = out or {}
+        out = {k: pre[k] if k in pre else (c.empty(s) if k in want else None)
+               for k, s in (("verts", (n, V, 3)), ("joints", (n, 24, 3)), ("xforms", (n, 24, 4, 4)), ("rest", (n, V, 3)))}
+        check(_lib.load().smplpp_fk_rotmat(self.handle, n, _ptr(beta), _ptr(trans), _ptr(rot), _ptr(out["verts"]), _ptr(out["joints"]),
+                                           _ptr(out["xforms"]), _ptr(out["rest"]), c.space, c.stream))
+        return beta, trans, rot, out
+
+    def launchRotmat(self, beta, trans, rot, want=("verts", "joints", "xforms", "rest"), out=None):
+        """`launch` from rotation matrices (smplpp_fk_rotmat): beta [N,10] (None = zero), trans [N,3] the root translation (None =
+        zero), rot [N,24,3,3] row-major with joint 0 the root orientation.  The matrices are used as given, without
+        re-orthonormalisation.  Outputs are kept for the getters, as launch keeps them; `out` as in launch.  The result feeds
+        vertexOffsets directly (it returns xforms), and launchRotmatBackward(rest=rest + D) then gives the SMPL+D chain rule exactly
+        as launchBackward does."""
+        c = _Call("launchRotmat", rot, beta, trans, fail="Cannot launch a SMPL model!")
+        _, _, rot, out = self._fk_rotmat(c, beta, trans, rot, want, out)
+        self._out, self._n = out, rot.shape[0]
+        return out
+
+    def launchRotmatBackward(self, beta, trans, rot, grad_verts=None, grad_joints=None, rest=None):
+        """Vector-Jacobian product of `launchRotmat` (smplpp_fk_rotmat_vjp): {"beta": dL/dbeta [N,10], "trans": dL/dtrans [N,3],
+        "rot": dL/drot [N,24,3,3]} for dL/dverts = grad_verts [N,V,3] and dL/djoints = grad_joints [N,24,3] (None = zero).  "rot" is
+        the gradient to nine independent entries per joint (no projection onto the rotations, no singularity).  `rest` as in
+        launchBackward: the rest shape launchRotmat returned, rest + D for an SMPL+D body, or None to recompute it."""
+        c = _Call("launchRotmatBackward", rot, beta, trans, grad_verts, grad_joints, rest)
+        n, V = int(rot.shape[0]) if c.dev else len(rot), self.vertex_num
+        beta, trans, rot = c.input(beta, (n, 10)), c.input(trans, (n, 3)), c.input(rot, (n, 24, 3, 3))
+        gv, gj, rest = c.input(grad_verts, (n, V, 3)), c.input(grad_joints, (n, 24, 3)), c.input(rest, (n, V, 3))
+        out = {"beta": c.empty((n, 10)), "trans": c.empty((n, 3)), "rot": c.empty((n, 24, 3, 3))}
+        check(_lib.load().smplpp_fk_rotmat_vjp(self.handle, n, _ptr(beta), _ptr(trans), _ptr(rot), _ptr(rest), _ptr(gv), _ptr(gj),
+                                               _ptr(out["beta"]), _ptr(out["trans"]), _ptr(out["rot"]), c.space, c.stream))
+        return out
+
+    def forward_rotmat_differentiable(self, beta, trans, rot):
+        """(verts [N,V,3], joints [N,24,3], xforms [N,24,4,4]) for device tensors beta [N,10], trans [N,3], rot [N,24,3,3],
+        differentiable with torch.autograd in all three inputs: the forward is one smplpp_fk_rotmat (rest shape kept for the
+        backward), the backward one smplpp_fk_rotmat_vjp, on torch's current stream.  First derivatives only.  xforms carries no
+        gradient (it is marked non-differentiable), as forward_differentiable returns none for them: it is there to feed
+        vertexOffsets.  rot6d_to_rotmat in front gives the 6-D parametrisation."""
+        if torch is None:
+            raise SmplppError(1, "forward_rotmat_differentiable needs torch")
+        return _FKRotmatFunction.apply(beta, trans, rot, self)
 
     def launchStatus(self):
         """Status word of the launches since the last read (synchronises the current stream): bit 0 = an operand left the
@@ -994,6 +1073,26 @@ if torch is not None:
                 return None, None, None
             g = ctx.smpl.launchBackward(beta, theta, grad_verts=grad_verts, grad_joints=grad_joints, rest=rest)
             return (g["beta"] if ctx.needs_input_grad[0] else None, g["theta"] if ctx.needs_input_grad[1] else None, None)
+
+    class _FKRotmatFunction(torch.autograd.Function):
+        """smplpp_fk_rotmat forward / smplpp_fk_rotmat_vjp backward (SMPL.forward_rotmat_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, beta, trans, rot, smpl):
+            c = _Call("forward_rotmat_differentiable", rot, beta, trans, fail="Cannot launch a SMPL model!", device_only=True)
+            beta, trans, rot, out = smpl._fk_rotmat(c, beta, trans, rot, ("verts", "joints", "xforms", "rest"))
+            ctx.smpl = smpl
+            ctx.save_for_backward(beta, trans, rot, out["rest"])
+            ctx.mark_non_differentiable(out["xforms"])
+            return out["verts"], out["joints"], out["xforms"]
+
+        @staticmethod
+        def backward(ctx, grad_verts, grad_joints, _grad_xforms):
+            beta, trans, rot, rest = ctx.saved_tensors
+            if not any(ctx.needs_input_grad[:3]):
+                return None, None, None, None
+            g = ctx.smpl.launchRotmatBackward(beta, trans, rot, grad_verts=grad_verts, grad_joints=grad_joints, rest=rest)
+            return tuple(g[k] if need else None for k, need in zip(("beta", "trans", "rot"), ctx.needs_input_grad)) + (None,)
 
     class _FKDisplacedFunction(torch.autograd.Function):
         """smplpp_fk + smplpp_vertex_offsets forward / smplpp_vertex_offsets_vjp + smplpp_fk_vjp(rest = rest_displaced) backward
