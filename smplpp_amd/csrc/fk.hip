@@ -17,6 +17,7 @@
 // XCD-aware mapping: blocks b and b+8 share an XCD (round-robin dispatch); all frame tiles of one vertex quad are
 // given to one XCD, consecutively, so each 338 KB slice of Bm is pulled into that XCD's L2 once per launch.
 #include "common.h"
+#include "fk_plan.h"
 #include "pose_math.h"
 #ifdef POSE_STAMP
 namespace smplpp_hip
@@ -220,36 +221,32 @@ __global__ __launch_bounds__(256, 2) void skin_kernel(const float * __restrict__
 }
 
 template<int FT, int MAXW>
-static hipError_t launch_skin(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest,
+static hipError_t launch_skin(const smplpp_model * m, const SkinVPlan & p, int64_t n, const float * theta, float * verts, float * rest,
                               hipStream_t st)
 {
-  const int nft = (int)((n + 32 * FT - 1) / (32 * FT));
-  const int nq = (int)((m->VGn + 3) / 4);
-  const int grid = 8 * ((nq + 7) / 8) * nft;
-  const size_t shmem = sizeof(float) * (size_t)(32 * FT) * (NJ * 12 + 3);
   static PerDeviceOnce once;
   {
-    hipError_t e = lds_opt_in(once, m->device, reinterpret_cast<const void *>(&skin_kernel<FT, MAXW>), (int)shmem);
+    hipError_t e = lds_opt_in(once, m->device, reinterpret_cast<const void *>(&skin_kernel<FT, MAXW>), (int)p.shmem);
     if(e != hipSuccess) return e;
   }
-  skin_kernel<FT, MAXW><<<dim3(grid), dim3(256), shmem, st>>>(m->ws.AT.as<float>(), m->ws.ldA, m->Bm.get(), m->ldB,
-                                                              m->ws.Gp.as<float>(), theta, m->wIdx.get(), m->wVal.get(), m->wSum.get(), verts,
-                                                              rest, n, m->V, (int)m->VGn, nft);
+  skin_kernel<FT, MAXW><<<dim3(p.grid), dim3(256), p.shmem, st>>>(m->ws.AT.as<float>(), m->ws.ldA, m->Bm.get(), m->ldB,
+                                                                  m->ws.Gp.as<float>(), theta, m->wIdx.get(), m->wVal.get(), m->wSum.get(),
+                                                                  verts, rest, n, m->V, (int)m->VGn, p.nft);
   return hipGetLastError();
 }
 
 template<int FT>
-static hipError_t launch_skin_w(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest,
+static hipError_t launch_skin_w(const smplpp_model * m, const SkinVPlan & p, int64_t n, const float * theta, float * verts, float * rest,
                                 hipStream_t st)
 {
   switch(m->maxw)
   {
     case 4:
-      return launch_skin<FT, 4>(m, n, theta, verts, rest, st);
+      return launch_skin<FT, 4>(m, p, n, theta, verts, rest, st);
     case 8:
-      return launch_skin<FT, 8>(m, n, theta, verts, rest, st);
+      return launch_skin<FT, 8>(m, p, n, theta, verts, rest, st);
     default:
-      return launch_skin<FT, NJ>(m, n, theta, verts, rest, st);
+      return launch_skin<FT, NJ>(m, p, n, theta, verts, rest, st);
   }
 }
 
@@ -290,18 +287,6 @@ PoseArgs fk_pose_args(smplpp_model * m, int64_t n, const float * beta, const flo
   return pa;
 }
 
-// Form of the fused kernel a launch runs (decided once per launch, here, for both halves of the forward pass).  m->form (from
-// SMPLPP_SKIN at model creation; default e) is what smplpp_fk runs: e (skin_e.hip) carries every fp32 operand exactly (bf16x3
-// pieces, six MFMA products per fp32 product, fp32 VALU skinning) — the reference's arithmetic; h (skin_h.hip): fp16x2 pieces,
-// 22-bit operands, skinning on the matrix pipe too; b (skin_b.hip): round 1's bf16x3 kernel; v: the first form (fp32 MFMA).
-// The IK / VPoser loops' internal launches (range_slot RANGE_INTERNAL: intermediate iterates whose mesh feeds the residual's few
-// vertices and the re-projection's face scan) run m->form_ik: h unless SMPLPP_SKIN chose a form for everything.
-// form_override (0: none): the form the caller chose for this launch (an IK solver in exact-arithmetic mode runs m->form).
-static char launch_form(const smplpp_model * m, int range_slot, char form_override)
-{
-  return form_override ? form_override : range_slot == RANGE_INTERNAL ? m->form_ik : m->form;
-}
-
 // range_slot: which word of the model's range status a launch of the fp16x2 form reports to (layout.h RANGE_*): enqueue-only user
 // launches, host-space user launches and the IK / VPoser loops' internal launches each have their own, so that an intermediate IK
 // iterate outside the range does not turn a later, in-range smplpp_fk into an error
@@ -312,26 +297,23 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
                           float * poserot, hipStream_t st, int * range_word, bool with_ops, bool rot_in = false, const float * trans = nullptr)
 {
   Workspace & ws = m->ws;
-  const int64_t n64 = ((n + 63) / 64) * 64;
-  if(rot_in) HIP_TRY(ws.root.reserve(sizeof(float) * (size_t)n * (NJ + 1) * 3));
+  const FkWorkspacePlan wp = fk_workspace_plan(form, n, rot_in);
+  const std::pair<DevBuf *, size_t> reserve[] = {{&ws.root, wp.root}, {&ws.Gp, wp.Gp}, {&ws.A2h, wp.A2h}, {&ws.G2h, wp.G2h}, {&ws.A3, wp.A3}, {&ws.AT, wp.AT}};
+  for(auto [buf, bytes] : reserve) HIP_TRY(buf->reserve(bytes)); // (0 bytes: a buffer the form does not use)
   auto launch_pose = [&](const PoseArgs & pa) {
     if(rot_in)
       pose_kernel_rot<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa, trans, ws.root.as<float>());
     else
       pose_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(pa);
   };
-  HIP_TRY(ws.Gp.reserve(sizeof(float) * (size_t)n64 * NJ * 12)); // e / b stage whole frame tiles of G' (padding never stored)
   if(form == 'h')
   {
-    HIP_TRY(ws.A2h.reserve((size_t)(n64 / 64) * HB_KS * HB_A_BYTES));
-    HIP_TRY(ws.G2h.reserve((size_t)(n64 / 64) * HB_G_BYTES));
     PoseArgs pa = fk_pose_args(m, n, beta, theta, joints, poserot, xforms44, with_ops);
     pa.range_flag = range_word;
     launch_pose(pa);
   }
   else if(form == 'e' || form == 'b')
   {
-    HIP_TRY(ws.A3.reserve((size_t)(n64 / 64) * BB_KS * BB_A_BYTES));
     PoseArgs pa = fk_pose_args(m, n, beta, theta, joints, poserot, xforms44, false);
     pa.A3 = with_ops ? ws.A3.as<uint16_t>() : nullptr;
     pa.gscale = 1.0f;
@@ -340,18 +322,12 @@ static int fk_pose_device(smplpp_model * m, char form, int64_t n, const float * 
   }
   else
   {
-    const int64_t ldA = n64;
-    HIP_TRY(ws.AT.reserve(sizeof(float) * (size_t)KP * ldA));
-    if(n64 > n) HIP_TRY(hipMemsetAsync(ws.Gp.as<float>() + n * NJ * 12, 0, sizeof(float) * (size_t)(n64 - n) * NJ * 12, st));
-    ws.ldA = ldA;
-    if(ldA > n)
-    {
-      int64_t cnt = (int64_t)KP * (ldA - n);
-      zero_pad_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st>>>(ws.AT.as<float>(), ldA, n);
-    }
+    if(wp.gp_pad_bytes) HIP_TRY(hipMemsetAsync(ws.Gp.as<float>() + wp.gp_pad_off, 0, wp.gp_pad_bytes, st));
+    ws.ldA = wp.ldA;
+    if(wp.at_pad) zero_pad_kernel<<<dim3((unsigned)((wp.at_pad + 255) / 256)), dim3(256), 0, st>>>(ws.AT.as<float>(), wp.ldA, n);
     PoseArgs pa = fk_pose_args(m, n, beta, theta, joints, poserot, xforms44, false);
     pa.AT = ws.AT.as<float>();
-    pa.ldA = ldA;
+    pa.ldA = wp.ldA;
     pa.gscale = 1.0f;
     pa.range_flag = nullptr;
     launch_pose(pa);
@@ -387,10 +363,10 @@ static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * 
       HIP_TRY(launch_skin_f16x2(m, n, theta, verts, rest, st));
     else if(form == 'b')
       HIP_TRY(launch_skin_bf16x3(m, n, theta, verts, rest, st));
-    else if(n <= 32)
-      HIP_TRY(launch_skin_w<1>(m, n, theta, verts, rest, st));
+    else if(const SkinVPlan p = skin_v_plan(n, m->VGn); p.FT == 1)
+      HIP_TRY(launch_skin_w<1>(m, p, n, theta, verts, rest, st));
     else
-      HIP_TRY(launch_skin_w<2>(m, n, theta, verts, rest, st));
+      HIP_TRY(launch_skin_w<2>(m, p, n, theta, verts, rest, st));
     if(m->profiling) HIP_TRY(hipEventRecord(e1, st));
   }
   return SMPLPP_OK;
@@ -401,7 +377,7 @@ static int fk_skin_device(smplpp_model * m, char form, int64_t n, const float * 
 int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, float * verts, float * joints,
               float * xforms44, float * rest, float * poserot, hipStream_t st, int range_slot, int * range_word, char form_override = 0)
 {
-  const char form = launch_form(m, range_slot, form_override);
+  const char form = launch_form(m->form, m->form_ik, range_slot, form_override);
   int rc = fk_pose_device(m, form, n, beta, theta, joints, xforms44, poserot, st, range_word ? range_word : m->range_flag.get() + range_slot,
                           verts || rest);
   if(rc) return rc;
@@ -413,7 +389,7 @@ int fk_device(smplpp_model * m, int64_t n, const float * beta, const float * the
 int fk_rotmat_device(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, float * verts, float * joints,
                      float * xforms44, float * rest, hipStream_t st, int range_slot, int * range_word)
 {
-  const char form = launch_form(m, range_slot, 0);
+  const char form = launch_form(m->form, m->form_ik, range_slot, 0);
   int rc = fk_pose_device(m, form, n, beta, rot, joints, xforms44, nullptr, st, range_word ? range_word : m->range_flag.get() + range_slot,
                           verts || rest, true, trans);
   if(rc) return rc;

@@ -22,7 +22,9 @@
 // skinning epilogue of the PREVIOUS item (16 accumulator rows at a pitch of 13 slots), the DMA of the operands three
 // k-steps ahead, the fragment reads of the next coordinates and the G' tile of the current item all issue in the MFMA
 // shadows.  One raw s_barrier per k-step (slot 6) orders the LDS images; DMAs stay in flight across it.
+// Which workgroup runs which items: fk_plan.h (xcd_items).
 #include "common.h"
+#include "fk_launch.h"
 #include "slot_pipe.h"
 
 #include <cstdlib>
@@ -156,24 +158,18 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
                                                         const float * __restrict__ Gp, const float * __restrict__ theta,
                                                         const uint8_t * __restrict__ wIdx, const float * __restrict__ wVal,
                                                         const float * __restrict__ wSum, float * __restrict__ verts,
-                                                        float * __restrict__ rest, int64_t n, int64_t V, int nvgp, int nftp,
-                                                        int items_per_block)
+                                                        float * __restrict__ rest, int64_t n, int64_t V, int nvgp, int nftp)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wf = wave & 1, wv = wave >> 1;
-  // Work assignment, XCD- and L2-aware.  Workgroup b runs on XCD b & 7 (round-robin dispatch).  XCD x owns a contiguous
-  // range of vertex-group pairs, i.e. a private 1/8 of B3 (each B3 byte is fetched from HBM by one XCD only), and its
-  // workgroups take the range's items (vertex-group pair major, frame-tile pair minor) INTERLEAVED: workgroup j does
-  // items j, j + nbx, j + 2 nbx, ...  So at any moment the ~32 workgroups of an XCD stream the same one or two 258 KB
-  // slices of B3 (L2 hits for all but the first) against different frame tiles; a contiguous run per workgroup instead
-  // puts 32 different slices (8 MB) through a 4 MB L2 and every staging load misses it (measured: 453 MB of L2 misses per
+  // Work assignment, XCD- and L2-aware: this workgroup's interleaved list of its XCD's items (fk_plan.h, xcd_items).  XCD x owns
+  // a private 1/8 of B3 (each B3 byte is fetched from HBM by one XCD only), and at any moment its ~32 workgroups stream the same
+  // one or two 258 KB slices of B3 (L2 hits for all but the first) against different frame tiles; a contiguous run per workgroup
+  // instead puts 32 different slices (8 MB) through a 4 MB L2 and every staging load misses it (measured: 453 MB of L2 misses per
   // launch for 27 MB of B3).  A wrong placement guess costs speed, never correctness: the item lists tile the work either way.
-  const int nbx = (int)(gridDim.x >> 3), xcd = (int)(blockIdx.x & 7), jb = (int)(blockIdx.x >> 3);
-  const int vg0 = (xcd * nvgp) >> 3, vg1 = ((xcd + 1) * nvgp) >> 3;
-  const int cnt = (vg1 - vg0) * nftp; // items of this XCD
-  (void)items_per_block;
-  if(jb >= cnt) return; // whole workgroup leaves: no barrier is ever skipped by a subset of its wavefronts
+  const XcdItems items = xcd_items(gridDim.x, blockIdx.x, nvgp, nftp);
+  if(items.first >= items.cnt) return; // whole workgroup leaves: no barrier is ever skipped by a subset of its wavefronts
 
   // ---- descriptors (SGPR) and per-thread constant offsets (VGPR)
   const __amdgpu_buffer_rsrc_t rsA =
@@ -227,11 +223,10 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
   } cur, prev;
 
   auto item_bases = [&](int i, int & Ab, int & Bb, int & Gb) { // i: index into this XCD's item list
-    const int iu = __builtin_amdgcn_readfirstlane(i);
-    const int vgp = vg0 + iu / nftp, ftp = iu % nftp;
-    Ab = ftp * (BB_KS * BB_A_BYTES);
-    Bb = vgp * (BB_KS * BB_B_BYTES);
-    Gb = ftp * B_LDS_G;
+    const ItemTile it = xcd_item_tile(items, __builtin_amdgcn_readfirstlane(i), nftp);
+    Ab = it.ft * (BB_KS * BB_A_BYTES);
+    Bb = it.vg * (BB_KS * BB_B_BYTES);
+    Gb = it.ft * B_LDS_G;
   };
   // chunk i (0..5) of one k-step image, HBM/L2 -> LDS by DMA (Ak / Bk: byte bases of that k-step in A3 / B3; dst: LDS byte
   // offset of this wavefront's share of the image)
@@ -252,7 +247,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
   // ---- prologue: k-steps 0, 1, 2 of the first item into images 0, 1, 2
   {
     int Abase, Bbase, Gbase;
-    item_bases(jb, Abase, Bbase, Gbase);
+    item_bases(items.first, Abase, Bbase, Gbase);
     (void)Gbase;
 #pragma unroll
     for(int d = 0; d < 3; d++)
@@ -272,8 +267,8 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
   auto do_item = [&](int t, auto hp_tag) {
     constexpr bool HP = decltype(hp_tag)::value;
     constexpr bool EPI = HP && !(SKINB_ABL & 1);
-    const int tu = __builtin_amdgcn_readfirstlane(t);
-    const int vgp = vg0 + tu / nftp, ftp = tu % nftp;
+    const ItemTile it = xcd_item_tile(items, __builtin_amdgcn_readfirstlane(t), nftp);
+    const int vgp = it.vg, ftp = it.ft;
     const int64_t v = (int64_t)vgp * 64 + wv * 32 + l31;
     const bool has_v = v < V;
     const int f0_cur = ftp * 64 + wf * 32; // first frame of this wavefront's 32 (wave-uniform: stays in an SGPR)
@@ -291,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
       }
       cur.winv = 1.0f / wSum[vv];
     }
-    const int tn = (t + nbx < cnt) ? t + nbx : t; // next item (or this one again: harmless extra prefetch)
+    const int tn = xcd_items_next(items, t);
     int Abn, Bbn, Gbn;
     item_bases(tn, Abn, Bbn, Gbn);
     (void)Gbn;
@@ -488,8 +483,8 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
     }
   };
 
-  do_item(jb, std::false_type{});
-  for(int t = jb + nbx; t < cnt; t += nbx)
+  do_item(items.first, std::false_type{});
+  for(int t = items.first + items.stride; t < items.cnt; t += items.stride)
   {
 #if SKINB_ABL & 256
     dbg_item++;
@@ -541,30 +536,19 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_b(const uint8_t * __restri
 }
 
 template<int MAXW, bool WANT_REST>
-static hipError_t launch_b(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st, int64_t f_off)
+static hipError_t launch_b(const smplpp_model * m, const SkinBatch & b, hipStream_t st)
 {
-  const int nftp = (int)((n + 63) / 64);
+  const int nftp = (int)((b.n + 63) / 64);
   const int nvgp = (int)m->VGPn;
-  const int total = nvgp * nftp;
-  const int cus = device_cus(m->device);
-  // per XCD: ceil(nvgp / 8) * nftp items at most; no more workgroups per XCD than that, and no more than the CUs it has
-  const int per_xcd_items = ((nvgp + 7) / 8) * nftp;
-  int nbx = cus / 8;
-  if(nbx > per_xcd_items) nbx = per_xcd_items;
-  if(nbx < 1) nbx = 1;
-  const int blocks = nbx * 8;
-  const int ipb = 0;
-  (void)total;
+  const int nbx = skin_grid(device_cus(m->device), nvgp, nftp, false);
   static PerDeviceOnce once;
   {
     hipError_t e = lds_opt_in(once, m->device, reinterpret_cast<const void *>(&skin_kernel_b<MAXW, WANT_REST>), B_LDS_TOTAL);
     if(e != hipSuccess) return e;
   }
-  // f_off (a multiple of 64): first frame of this launch inside the workspace / caller arrays of a longer batch
-  skin_kernel_b<MAXW, WANT_REST><<<dim3(blocks), dim3(256), B_LDS_TOTAL, st>>>(
-      m->ws.A3.as<uint8_t>() + (f_off / 64) * (int64_t)(BB_KS * BB_A_BYTES), m->B3.get(), m->ws.Gp.as<float>() + f_off * (NJ * 12),
-      theta + f_off * ((NJ + 1) * 3), m->wIdx.get(), m->wVal.get(), m->wSum.get(), verts ? verts + f_off * m->V * 3 : nullptr,
-      rest ? rest + f_off * m->V * 3 : nullptr, n, m->V, nvgp, nftp, ipb);
+  skin_kernel_b<MAXW, WANT_REST><<<dim3(nbx * 8), dim3(256), B_LDS_TOTAL, st>>>(
+      b.tiles<uint8_t>(m->ws.A3, BB_KS * BB_A_BYTES), m->B3.get(), b.tiles<float>(m->ws.Gp, B_LDS_G), b.theta, m->wIdx.get(), m->wVal.get(),
+      m->wSum.get(), b.verts, b.rest, b.n, m->V, nvgp, nftp);
   return hipGetLastError();
 }
 
@@ -577,21 +561,10 @@ extern "C" int smplpp_debug_slot_times(unsigned long long * out)
 // Gp must hold whole 64-frame tiles (padding content is irrelevant: the rows it feeds are never stored)
 hipError_t launch_skin_bf16x3(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st)
 {
-  // the kernel addresses its outputs with 32-bit buffer offsets: longer batches go in launches of <= 2 GiB of vertices
-  int64_t per = (0x7fffff00LL / (m->V * 12)) & ~63LL;
-  if(per < 64) return hipErrorInvalidValue;
-  for(int64_t off = 0; off < n; off += per)
-  {
-    const int64_t nn = (n - off < per) ? n - off : per;
-    hipError_t e;
-    if(m->maxw == 4)
-      e = rest ? launch_b<4, true>(m, nn, theta, verts, rest, st, off) : launch_b<4, false>(m, nn, theta, verts, rest, st, off);
-    else if(m->maxw == 8)
-      e = rest ? launch_b<8, true>(m, nn, theta, verts, rest, st, off) : launch_b<8, false>(m, nn, theta, verts, rest, st, off);
-    else
-      return hipErrorInvalidValue; // dense weights keep the first form
-    if(e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  if(m->maxw != 4 && m->maxw != 8) return hipErrorInvalidValue; // dense weights keep the first form
+  return for_each_skin_batch(m->V, n, B_LDS_G, theta, verts, rest, [&](const SkinBatch & b) {
+    if(m->maxw == 4) return rest ? launch_b<4, true>(m, b, st) : launch_b<4, false>(m, b, st);
+    return rest ? launch_b<8, true>(m, b, st) : launch_b<8, false>(m, b, st);
+  });
 }
 } // namespace smplpp_hip

@@ -16,10 +16,12 @@
 //    translations stay resident in LDS for the run, and only the basis streams: one 20 KiB image per k-step (18 KiB of
 //    fragments + the group's skinning tables, five 1 KiB LDS-DMA pieces per wavefront) through a ring of FOUR images filled
 //    three k-steps ahead (buffer_load_dwordx4 ... lds); per item a wavefront issues 70 DMAs (skin_b: 102);
-//  * XCD x owns an eighth of the vertex groups: its 3.8 MB slice of B3e is read from HBM once and served from that XCD's L2;
+//  * which workgroup runs which items: fk_plan.h (xcd_run) — XCD x owns an eighth of the vertex groups, so its 3.8 MB slice of B3e
+//    is read from HBM once and served from that XCD's L2;
 //  * one raw s_barrier per k-step; every barrier that publishes DMA data carries a counted s_waitcnt vmcnt(N), N derived at
 //    compile time from a table of what each slot issues (hipcc does not order LDS reads behind LDS-DMA writes).
 #include "common.h"
+#include "fk_launch.h"
 #include "slot_pipe.h"
 
 namespace smplpp_hip
@@ -171,12 +173,9 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
   typedef __attribute__((address_space(3))) void * lds_ptr_t;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wf = wave & 1, wv = wave >> 1;
-  // ---- work assignment (as skin_kernel_h).  Workgroup b runs on XCD b & 7 (round-robin dispatch; a wrong guess costs speed
-  // only).  XCD x owns vertex groups [vg0, vg1); its items, frame tile major, are cut into contiguous runs, one per workgroup.
-  const int nbx = (int)(gridDim.x >> 3), xcd = (int)(blockIdx.x & 7), jb = (int)(blockIdx.x >> 3);
-  const int vg0 = (xcd * nvg) >> 3, vg1 = ((xcd + 1) * nvg) >> 3, nvx = vg1 - vg0;
-  const int cnt = nvx * nft;
-  const int i0 = (int)(((unsigned)jb * (unsigned)cnt) / (unsigned)nbx), i1 = (int)(((unsigned)(jb + 1) * (unsigned)cnt) / (unsigned)nbx);
+  // ---- work assignment: this workgroup's run of its XCD's items (fk_plan.h)
+  const XcdRun run = xcd_run(gridDim.x, blockIdx.x, nvg, nft);
+  const int vg0 = run.vg0, nvx = run.nvx, i0 = run.i0, i1 = run.i1;
   if(i0 >= i1) return; // whole workgroup leaves
 #if SKINE_ABL & 512
   const unsigned long long t_start = __builtin_amdgcn_s_memtime(), r_start = __builtin_amdgcn_s_memrealtime();
@@ -296,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
     const int Bcur = vg * (EB_KS * EB_IMG), Bnext = vgn * (EB_KS * EB_IMG), Gbase = ft * E_G_BYTES;
     {
       const int v = vg * 64 + wv * 32 + l31;
-      cur.voff = v < (int)V ? v * 12 + (4 * half) * frameB : 0x7fffff00; // (V * 12 * 64 frames < 2^31: launch_skin_exact cuts the batch)
+      cur.voff = v < (int)V ? v * 12 + (4 * half) * frameB : 0x7fffff00; // (V * 12 * 64 frames < 2^31: skin_batch_frames cuts the batch)
       cur.sb = __builtin_amdgcn_readfirstlane((ft * 64 + wf * 32) * frameB);
 #pragma unroll
       for(int i = 0; i < MAXW; i++)
@@ -589,18 +588,16 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
     }
     else
       load_frame_tile(ft, std::true_type{});
-    // item k of the run: vertex group vgk; the item after it: the next group, the XCD's first one when the frame tile ends there,
-    // the same one when the workgroup's items end there (its prefetches land in images nobody reads)
+    // item k of the run: vertex group vgk; the item after it: xcd_next_vg
 #if SKINE_ABL & 512
     if(i == i0) t_first = __builtin_amdgcn_s_memtime(); else t_run2 = __builtin_amdgcn_s_memtime();
 #endif
     int vgk = vg0 + (i - ft * nvx);
-    auto next_vg = [&](int k, int vgc) { return k + 1 < i1 ? (vgc + 1 < vg1 ? vgc + 1 : vg0) : vgc; };
-    do_item(ft, vgk, next_vg(i, vgk), std::false_type{});
+    do_item(ft, vgk, xcd_next_vg(run, i, vgk), std::false_type{});
     for(int k = i + 1; k < iend; k++)
     {
       vgk++;
-      do_item(ft, vgk, next_vg(k, vgk), std::true_type{});
+      do_item(ft, vgk, xcd_next_vg(run, k, vgk), std::true_type{});
     }
     i = iend;
   }
@@ -625,29 +622,18 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_e(const uint8_t * __restri
 }
 
 template<int MAXW, bool WANT_REST>
-static hipError_t launch_e(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st, int64_t f_off)
+static hipError_t launch_e(const smplpp_model * m, const SkinBatch & b, hipStream_t st)
 {
-  const int nft = (int)((n + 63) / 64);
+  const int nft = (int)((b.n + 63) / 64);
   const int nvg = (int)m->VGPn;
-  // per XCD: ceil(nvg / 8) * nft items at most; no more workgroups per XCD than that, and no more than the CUs it has; and no
-  // more than the longest workgroup's item count needs (as launch_h)
-  const int per_xcd_items = ((nvg + 7) / 8) * nft;
-  int nbx = device_cus(m->device) / 8;
-  if(nbx > per_xcd_items) nbx = per_xcd_items;
-  if(nbx < 1) nbx = 1;
-  {
-    const int rounds = (per_xcd_items + nbx - 1) / nbx;
-    nbx = (per_xcd_items + rounds - 1) / rounds;
-  }
+  const int nbx = skin_grid(device_cus(m->device), nvg, nft, true);
   static PerDeviceOnce once;
   {
     hipError_t e = lds_opt_in(once, m->device, reinterpret_cast<const void *>(&skin_kernel_e<MAXW, WANT_REST>), E_LDS_TOTAL);
     if(e != hipSuccess) return e;
   }
-  // f_off (a multiple of 64): first frame of this launch inside the workspace / caller arrays of a longer batch
   skin_kernel_e<MAXW, WANT_REST><<<dim3(nbx * 8), dim3(256), E_LDS_TOTAL, st>>>(
-      m->ws.A3.as<uint8_t>() + (f_off / 64) * (int64_t)(BB_KS * BB_A_BYTES), m->B3e.get(), m->ws.Gp.as<float>() + f_off * (NJ * 12),
-      theta + f_off * ((NJ + 1) * 3), verts ? verts + f_off * m->V * 3 : nullptr, rest ? rest + f_off * m->V * 3 : nullptr, n, m->V, nvg, nft);
+      b.tiles<uint8_t>(m->ws.A3, BB_KS * BB_A_BYTES), m->B3e.get(), b.tiles<float>(m->ws.Gp, E_G_BYTES), b.theta, b.verts, b.rest, b.n, m->V, nvg, nft);
   return hipGetLastError();
 }
 
@@ -666,18 +652,8 @@ extern "C" int smplpp_debug_ewg_times(unsigned long long * out)
 // A3 / Gp must hold whole 64-frame tiles (padding content is irrelevant: the rows it feeds are never stored)
 hipError_t launch_skin_exact(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st)
 {
-  // the kernel addresses its outputs with 32-bit buffer offsets: longer batches go in launches of <= 2 GiB of vertices
-  // ... and of few enough frames that the Gp offsets (nft * 72 KiB) stay below 2^31 too (small meshes)
-  int64_t per = (0x7fffff00LL / (m->V * 12)) & ~63LL;
-  const int64_t per_g = (0x7fffff00LL / E_G_BYTES) * 64;
-  if(per > per_g) per = per_g;
-  if(per < 64) return hipErrorInvalidValue;
-  for(int64_t off = 0; off < n; off += per)
-  {
-    const int64_t nn = (n - off < per) ? n - off : per;
-    hipError_t e = rest ? launch_e<4, true>(m, nn, theta, verts, rest, st, off) : launch_e<4, false>(m, nn, theta, verts, rest, st, off);
-    if(e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_each_skin_batch(m->V, n, E_G_BYTES, theta, verts, rest, [&](const SkinBatch & b) {
+    return rest ? launch_e<4, true>(m, b, st) : launch_e<4, false>(m, b, st);
+  });
 }
 } // namespace smplpp_hip

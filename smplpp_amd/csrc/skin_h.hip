@@ -21,12 +21,14 @@
 // LDS, and only the basis streams: one 12 KiB image per k-step through a ring of 7 LDS images filled by LDS-DMA
 // (buffer_load_dwordx4 ... lds) seven slots ahead; slot 14 of an item carries the group's skinning weights.
 // One raw s_barrier per slot publishes the next image (counted vmcnt: DMAs stay in flight across it).
-// XCD x owns an eighth of the vertex groups (its slice of B2h, 2.4 MB, lives in that XCD's L2 and is read from HBM once).
+// Which workgroup runs which items: fk_plan.h (xcd_run).  XCD x owns an eighth of the vertex groups (its slice of B2h, 2.4 MB,
+// lives in that XCD's L2 and is read from HBM once).
 // Round 5: a vertex group is 64 CONSECUTIVE vertices with a skinning class (layout.h, HB_PERM_OFF: which k-steps of the skinning
 // product its vertices' weights touch; the groups are dealt over and inside the XCD slices with the classes interleaved; slot 14
 // carries the group's vertex ids and its flags).  A group whose weights live in one k-step runs the skinning phase in the instantiation that issues only that k-step's
 // MFMAs and G' fragment reads — 3 (joints 0..15 only) or 2 (joints 16..23 only) MFMAs per entry instead of 5; exact zeros skipped.
 #include "common.h"
+#include "fk_launch.h"
 #include "slot_pipe.h"
 
 namespace smplpp_hip
@@ -119,13 +121,10 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
   typedef __attribute__((address_space(3))) void * lds_ptr_t;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wf = wave & 1, wv = wave >> 1;
-  // ---- work assignment.  Workgroup b runs on XCD b & 7 (round-robin dispatch; a wrong guess costs speed only).  XCD x owns
-  // vertex groups [vg0, vg1); its items, frame tile major, are cut into contiguous runs, one per workgroup: a run stays
-  // inside one frame tile as long as possible (the A registers and the G' image are reloaded when the frame tile changes).
-  const int nbx = (int)(gridDim.x >> 3), xcd = (int)(blockIdx.x & 7), jb = (int)(blockIdx.x >> 3);
-  const int vg0 = (xcd * nvg) >> 3, vg1 = ((xcd + 1) * nvg) >> 3, nvx = vg1 - vg0;
-  const int cnt = nvx * nft;
-  const int i0 = (int)(((unsigned)jb * (unsigned)cnt) / (unsigned)nbx), i1 = (int)(((unsigned)(jb + 1) * (unsigned)cnt) / (unsigned)nbx); // cnt < 2^26
+  // ---- work assignment: this workgroup's run of its XCD's items (fk_plan.h; the A registers and the G' image are reloaded when
+  // the run changes its frame tile)
+  const XcdRun run = xcd_run(gridDim.x, blockIdx.x, nvg, nft);
+  const int vg0 = run.vg0, vg1 = run.vg1, nvx = run.nvx, i0 = run.i0, i1 = run.i1;
   if(i0 >= i1) return; // whole workgroup leaves
 
 #if SKINH_ABL & 512
@@ -500,8 +499,8 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
     else
       load_frame_tile(ft, std::true_type{});
     // (later items find the fragments of their first k-step read by the blend phase of the item before)
-    // item k of the run: vertex group vgk; the item after it: the next group, the XCD's first one when the frame tile ends
-    // there, the same one when the workgroup's items end there
+    // item k of the run: vertex group vgk; the item after it: xcd_next_vg (fk_plan.h), restated here on the kernel's own scalars —
+    // the call through the struct exchanges two register quads of this kernel (a[32:35] / a[36:39]), this line leaves its text alone
     int vgk = vg0 + (i - ft * nvx);
     auto next_vg = [&](int k, int vgc) { return k + 1 < i1 ? (vgc + 1 < vg1 ? vgc + 1 : vg0) : vgc; };
     do_item(ft, vgk, next_vg(i, vgk), std::false_type{});
@@ -533,39 +532,23 @@ __global__ __launch_bounds__(256, 1) void skin_kernel_h(const uint8_t * __restri
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the last prefetches land before the wavefront ends
 }
 
-static hipError_t launch_h(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st,
-                           int64_t f_off)
+static hipError_t launch_h(const smplpp_model * m, const SkinBatch & b, hipStream_t st)
 {
-  const int nft = (int)((n + 63) / 64);
+  const int nft = (int)((b.n + 63) / 64);
   const int nvg = (int)m->VGPn;
-  // per XCD: ceil(nvg / 8) * nft items at most; no more workgroups per XCD than that, and no more than the CUs it has
-  const int per_xcd_items = ((nvg + 7) / 8) * nft;
-  int nbx = device_cus(m->device) / 8;
-  if(nbx > per_xcd_items) nbx = per_xcd_items;
-  if(nbx < 1) nbx = 1;
-  // ... and no more than the longest workgroup's item count needs: 56 items per XCD (256 frames) are two rounds on 32 workgroups and
-  // on 28 — the four CUs per XCD left alone are where the IK loops' side stream (face scan, finish kernel) runs beside this kernel,
-  // whose workgroups share a CU with nothing (1024 frames: 224 items, seven rounds on 32: unchanged)
-  {
-    const int rounds = (per_xcd_items + nbx - 1) / nbx;
-    nbx = (per_xcd_items + rounds - 1) / rounds;
-  }
-  const bool wr = rest != nullptr;
+  const int nbx = skin_grid(device_cus(m->device), nvg, nft, true);
+  const bool wr = b.rest != nullptr;
   static PerDeviceOnce once[2];
   {
     hipError_t e = lds_opt_in(once[wr], m->device, wr ? reinterpret_cast<const void *>(&skin_kernel_h<true>) : reinterpret_cast<const void *>(&skin_kernel_h<false>), H_LDS_TOTAL);
     if(e != hipSuccess) return e;
   }
   const float cAB = 1.0f / (HB_SA * m->sB);
-  const uint8_t * A2 = m->ws.A2h.as<uint8_t>() + (f_off / 64) * (int64_t)(HB_KS * HB_A_BYTES);
-  const uint8_t * G2 = m->ws.G2h.as<uint8_t>() + (f_off / 64) * (int64_t)HB_G_BYTES;
-  const float * th = theta + f_off * ((NJ + 1) * 3);
-  float * vo = verts ? verts + f_off * m->V * 3 : nullptr;
-  float * ro = rest ? rest + f_off * m->V * 3 : nullptr;
+  const uint8_t * A2 = b.tiles<uint8_t>(m->ws.A2h, HB_KS * HB_A_BYTES), * G2 = b.tiles<uint8_t>(m->ws.G2h, HB_G_BYTES);
   if(wr)
-    skin_kernel_h<true><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h.get(), G2, th, vo, ro, n, m->V, nvg, nft, cAB);
+    skin_kernel_h<true><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h.get(), G2, b.theta, b.verts, b.rest, b.n, m->V, nvg, nft, cAB);
   else
-    skin_kernel_h<false><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h.get(), G2, th, vo, ro, n, m->V, nvg, nft, cAB);
+    skin_kernel_h<false><<<dim3(nbx * 8), dim3(256), H_LDS_TOTAL, st>>>(A2, m->B2h.get(), G2, b.theta, b.verts, b.rest, b.n, m->V, nvg, nft, cAB);
   return hipGetLastError();
 }
 
@@ -582,18 +565,6 @@ extern "C" int smplpp_debug_hslot_times(unsigned long long * out)
 // A2h / G2h must hold whole 64-frame tiles (padding content is irrelevant: the rows it feeds are never stored)
 hipError_t launch_skin_f16x2(const smplpp_model * m, int64_t n, const float * theta, float * verts, float * rest, hipStream_t st)
 {
-  // the kernel addresses its outputs with 32-bit buffer offsets: longer batches go in launches of <= 2 GiB of vertices
-  // ... and of few enough frames that the G2h offsets (nft * 72 KiB) stay below 2^31 too (small meshes)
-  int64_t per = (0x7fffff00LL / (m->V * 12)) & ~63LL;
-  const int64_t per_g = (0x7fffff00LL / HB_G_BYTES) * 64;
-  if(per > per_g) per = per_g;
-  if(per < 64) return hipErrorInvalidValue;
-  for(int64_t off = 0; off < n; off += per)
-  {
-    const int64_t nn = (n - off < per) ? n - off : per;
-    hipError_t e = launch_h(m, nn, theta, verts, rest, st, off);
-    if(e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_each_skin_batch(m->V, n, HB_G_BYTES, theta, verts, rest, [&](const SkinBatch & b) { return launch_h(m, b, st); });
 }
 } // namespace smplpp_hip
