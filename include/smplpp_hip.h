@@ -53,6 +53,8 @@ enum
 typedef struct smplpp_model smplpp_model;   /* stands in for smplpp::SMPL            (SMPL.h:140-270) */
 typedef struct smplpp_ik smplpp_ik;         /* the IK loop state of node/node.cpp:645-1002, batched over frames */
 typedef struct smplpp_vposer smplpp_vposer; /* stands in for smplpp::VPoserDecoder   (VPoser.h:53-90) */
+struct smplpp_landmarks;                    /* a sparse landmark regressor over a model's vertices and joints (no reference counterpart);
+                                               written `struct smplpp_landmarks` throughout: the name alone is the regression call below */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -501,6 +503,68 @@ int smplpp_silhouette_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,
                           const int64_t * pix_source /*[n,H,W] nullable*/, const float * grad_vert_sq /*[n,V] nullable*/,
                           const float * grad_pix_sq /*[n,H,W] nullable*/, float * grad_verts /*[n,V,3]*/, int accumulate, int space,
                           void * stream);
+/* ------------------------------------------------------------------ keypoints: landmark regression, projection, 2-D energy
+ * A landmark regressor is a CSR matrix of L rows over V + 24 source columns: column c < V is vertex c, column V + j is joint j of
+ * smplpp_fk's `joints`.  One regressor so expresses the 24 joints, vertex picks (nose, ears, toes) and sparse rows over the vertices
+ * (H36M- or COCO-style joints); its two gradients are the grad_verts and grad_joints smplpp_fk_vjp and smplpp_fk_rotmat_vjp take.
+ * row_ptr [L+1], col [nnz = row_ptr[L]], val [nnz] are host pointers, like the arrays of smplpp_model_create; a column may repeat
+ * within a row (it is summed like any other entry), a row may be empty.  The handle copies what it needs of the model (V, the device):
+ * it may outlive it.  Creation builds, on the host, the CSR with int32 columns and the transposed lists (per source, its entries in
+ * ascending e), and uploads them once.
+ *  - SMPLPP_ERR_INVALID: L outside [1, 65535], row_ptr[0] != 0, row_ptr not non-decreasing, a column outside [0, V + 24), a val that
+ *    is not finite, nnz beyond int32 indexing (*out = NULL). */
+int smplpp_landmarks_create(smplpp_model * m, int64_t L, const int64_t * row_ptr /*[L+1]*/, const int64_t * col /*[nnz]*/,
+                            const float * val /*[nnz]*/, struct smplpp_landmarks ** out);
+int smplpp_landmarks_destroy(struct smplpp_landmarks * lm);
+int smplpp_landmarks_info(const struct smplpp_landmarks * lm, int64_t * L, int64_t * nnz);
+/* points [n,L,3] = A [verts; joints].  In fp32 with every operation rounded on its own (no FMA), per (frame, row l, component): entry
+ * e of the row has rank r = e - row_ptr[l]; partial p = r mod 8 runs s_p = s_p + val[e] * x[col[e]] over its entries in ascending r,
+ * starting from +0; the result is ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7)).  An empty row gives +0.  The bits of a frame do
+ * not depend on n, on its position in the batch, on the memory space or on the work split.
+ *  - SMPLPP_ERR_INVALID: n <= 0, a NULL array, n (V + 24) or n L 3 beyond int32 indexing (the output is untouched). */
+int smplpp_landmarks(struct smplpp_landmarks * lm, int64_t n, const float * verts /*[n,V,3]*/, const float * joints /*[n,24,3]*/,
+                     float * points /*[n,L,3]*/, int space, void * stream);
+/* Vector-Jacobian product of smplpp_landmarks.  Each element of grad_verts [n,V,3] and grad_joints [n,24,3] is one sequential sum,
+ * starting from +0, of val[e] * grad_points[l(e)] over the entries e that name that source, in ascending e; then accumulate = 0 stores
+ * it (untouched sources get 0) and 1 adds it to the output.  No floating-point atomics; the same independence as the forward.  Either
+ * output may be NULL, not both.
+ *  - SMPLPP_ERR_INVALID: as the forward, accumulate not 0 or 1, both outputs NULL (the outputs are untouched). */
+int smplpp_landmarks_vjp(struct smplpp_landmarks * lm, int64_t n, const float * grad_points /*[n,L,3]*/, float * grad_verts /*[n,V,3] nullable*/,
+                         float * grad_joints /*[n,24,3] nullable*/, int accumulate, int space, void * stream);
+/* Projection of any points [n,K,3] (K = L for landmarks, K = V for raw vertices) and a 2-D keypoint energy against target [n,K,3] =
+ * (u, v, confidence).  camera [n,16] and the projection are smplpp_depth_raster's vertex rule, unchanged: the same operations and the
+ * same refusal (xc finite, xc.z > near, the guard band).  A refused point gives valid = 0, uv = (0, 0), energy = 0; else valid = 1 and
+ * uv is the unsnapped (u, v).  Energy, in fp32 with every operation rounded on its own, with c = the target's confidence:
+ *    c == 0: 0, and nothing else of the target row is read into the result, even on NaN data;
+ *    else r = (u - tu, v - tv), q = r.x r.x + r.y r.y;  rho == 0: energy = (c c) q;
+ *    rho > 0: p2 = rho rho, energy = (c c) ((p2 q) / (p2 + q))  (Geman-McClure on the squared pixel distance, as SMPLify has it).
+ * uv [n,K,2], energy [n,K] (needs target), valid [n,K] bytes: each may be NULL, not all three.  Takes no handle: `device` as the stage
+ * calls.  The bits do not depend on n, on the frame's position in the batch or on the memory space.
+ *  - SMPLPP_ERR_INVALID: n or K <= 0, n K 3 beyond int32 indexing, near not finite or <= 0, rho < 0 or not finite, a NULL points or
+ *    camera, energy without target (the outputs are untouched). */
+int smplpp_project_points(int device, int64_t n, int64_t K, const float * points /*[n,K,3]*/, const float * camera /*[n,16]*/, float near,
+                          const float * target /*[n,K,3]: u, v, confidence; nullable*/, float rho,
+                          float * uv /*[n,K,2] nullable*/, float * energy /*[n,K] nullable, needs target*/, uint8_t * valid /*[n,K] nullable*/,
+                          int space, void * stream);
+/* Vector-Jacobian product of uv and energy above to the points and to the camera row: the library's gradient to the camera.  Per
+ * live (not refused) point, in fp32, every operation rounded on its own:
+ *    k = grad_uv (NULL reads as +0);  if grad_energy is given, g = grad_energy != 0 and c != 0: w = c c (rho == 0), else d = p2 /
+ *    (p2 + q), w = (c c) (d d);  k.x = k.x + ((2 g) w) r.x, k.y likewise.  A NULL input, a g of exactly 0 or a confidence of 0
+ *    contributes nothing, even on NaN data;
+ *    jx = (fx k.x) / xc.z, jy = (fy k.y) / xc.z, jz = -((jx xc.x + jy xc.y) / xc.z)  (the pull of smplpp_silhouette_vjp);
+ *    grad_points, world component a = (R[a] jx + R[3+a] jy) + R[6+a] jz; a refused point gets +0.
+ *  - grad_camera [n,16] in the layout of camera, R as NINE INDEPENDENT ENTRIES (the convention of smplpp_fk_rotmat_vjp): R[3a+b] sums
+ *    j_a * x_b with x the world point, t[a] sums j_a, fx sums k.x * (xc.x / xc.z), fy sums k.y * (xc.y / xc.z), cx sums k.x, cy sums
+ *    k.y, over the live points of the frame.  Each of the 16 is one fixed-order sum: point k goes to partial k mod 64, summed in
+ *    ascending k starting from +0; the 64 partials p_i meet as p_i = p_i + p_(i xor m) for m = 32, 16, 8, 4, 2, 1.
+ *  - accumulate = 0 stores, 1 adds the finished value to the output, for both outputs.  grad_uv or grad_energy (needs target) may be
+ *    NULL, not both; grad_points or grad_camera may be NULL, not both.  No floating-point atomics; the bits do not depend on n, on the
+ *    frame's position in the batch, on the memory space or on which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID: as the forward, accumulate not 0 or 1 (the outputs are untouched). */
+int smplpp_project_points_vjp(int device, int64_t n, int64_t K, const float * points, const float * camera, float near,
+                              const float * target /*nullable*/, float rho, const float * grad_uv /*[n,K,2] nullable*/,
+                              const float * grad_energy /*[n,K] nullable, needs target*/, float * grad_points /*[n,K,3] nullable*/,
+                              float * grad_camera /*[n,16] nullable*/, int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

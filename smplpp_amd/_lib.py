@@ -95,6 +95,13 @@ def load():
         "smplpp_mask_distance_transform": [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int, vp],
         "smplpp_silhouette": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_silhouette_vjp": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_landmarks_create": [vp, C.c_int64, vp, vp, vp, C.POINTER(vp)],
+        "smplpp_landmarks_destroy": [vp],
+        "smplpp_landmarks_info": [vp, i64p, i64p],
+        "smplpp_landmarks": [vp, C.c_int64, vp, vp, vp, C.c_int, vp],
+        "smplpp_landmarks_vjp": [vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_project_points": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, C.c_float, vp, vp, vp, C.c_int, vp],
+        "smplpp_project_points_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],

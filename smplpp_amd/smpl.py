@@ -133,6 +133,60 @@ class _Call:
         return np.empty(shape, dtype)
 
 
+def _pp_inputs(c, points, camera, target, device):
+    """(n, K, points, camera, target, device index) of a projection call in the space of `c`."""
+    if len(points.shape) != 3 or points.shape[2] != 3 or min(points.shape) < 1:
+        c.refuse("expected points of shape (N, K, 3)")
+    n, K = int(points.shape[0]), int(points.shape[1])
+    if not c.dev:
+        camera = pinhole_camera_rows(camera, n)
+    dev = c.device.index if c.dev and c.device.index is not None else device
+    return n, K, c.input(points, (n, K, 3)), c.input(camera, (n, 16)), c.input(target, (n, K, 3)), int(dev)
+
+
+def project_points(points, camera, target=None, rho=0.0, near=0.05, want=("uv", "energy", "valid"), device=0):
+    """Any points [N,K,3] (landmarks, or raw vertices) through the cameras [N,16] ([16] with numpy: one camera for every frame) by the
+    depth rasteriser's vertex rule, and their 2-D keypoint energy against target [N,K,3] = (u, v, confidence) (smplpp_project_points):
+    a dict of uv [N,K,2], energy [N,K] (with a target; c^2 q for rho = 0, else the Geman-McClure form c^2 rho^2 q / (rho^2 + q) on the
+    squared pixel distance q) and valid [N,K] uint8.  A refused point (behind `near`, not finite, outside the guard band) gives
+    valid 0, uv 0 and energy 0.  numpy (the call synchronises, on `device`) or float32 device tensors (torch's current stream)."""
+    c = _Call("project_points", points, target)
+    n, K, points, camera, target, dev = _pp_inputs(c, points, camera, target, device)
+    shapes = {"uv": ((n, K, 2), "float32"), "energy": ((n, K), "float32"), "valid": ((n, K), "uint8")}
+    out = {k: c.empty(*shapes[k]) for k in shapes if k in want and (k != "energy" or target is not None)}
+    check(_lib.load().smplpp_project_points(dev, n, K, _ptr(points), _ptr(camera), float(near), _ptr(target), float(rho), _ptr(out.get("uv")),
+                                            _ptr(out.get("energy")), _ptr(out.get("valid")), c.space, c.stream))
+    return out
+
+
+def project_points_backward(points, camera, target=None, rho=0.0, grad_uv=None, grad_energy=None, near=0.05, want=("points", "camera"),
+                            out=None, device=0):
+    """Vector-Jacobian product of project_points (smplpp_project_points_vjp): {"points": [N,K,3], "camera": [N,16]} for dL/duv =
+    grad_uv [N,K,2] and dL/denergy = grad_energy [N,K] (either may be None).  "camera" is in the layout of the camera rows, with R as
+    nine independent entries.  `want` drops one; with `out` (a dict keyed the same way) the gradients are added into its arrays."""
+    acc = out is not None
+    c = _Call("project_points_backward", points, target, grad_uv, grad_energy, *(out.values() if acc else ()))
+    n, K, points, camera, target, dev = _pp_inputs(c, points, camera, target, device)
+    guv, ge = c.input(grad_uv, (n, K, 2)), c.input(grad_energy, (n, K))
+    shapes = {"points": (n, K, 3), "camera": (n, 16)}
+    keys = [k for k in shapes if k in (out if acc else want)]
+    if not keys:
+        c.refuse("points or camera must be asked for")
+    res = {k: c.inout(out[k], shapes[k]) if acc else c.empty(shapes[k]) for k in keys}
+    check(_lib.load().smplpp_project_points_vjp(dev, n, K, _ptr(points), _ptr(camera), float(near), _ptr(target), float(rho), _ptr(guv),
+                                                _ptr(ge), _ptr(res.get("points")), _ptr(res.get("camera")), int(acc), c.space, c.stream))
+    return res
+
+
+def project_points_differentiable(points, camera, target, rho, near=0.05):
+    """(uv [N,K,2], energy [N,K], valid [N,K] bool) of device tensors points [N,K,3], camera [N,16], target [N,K,3] (the bits of
+    project_points), differentiable in points AND camera through torch.autograd: smplpp_project_points forward,
+    smplpp_project_points_vjp backward, on torch's current stream.  A keypoint term is energy.sum()."""
+    if torch is None:
+        raise SmplppError(1, "project_points_differentiable needs torch")
+    return _ProjectPointsFunction.apply(points, camera, target, float(rho), float(near))
+
+
 def rot6d_to_rotmat(x):
     """The 6-D rotation representation as rotation matrices, [..., 6] -> [..., 3, 3], in plain differentiable torch: x[..., 0::2] and
     x[..., 1::2] are read as the first two columns (the [..., 3, 2] view of the reference's decoder, src/VPoser.cpp:129-141); b1 =
@@ -1309,6 +1363,31 @@ if torch is not None:
                                              None if grad_vert_sq is None else grad_vert_sq.contiguous(),
                                              None if grad_pix_sq is None else grad_pix_sq.contiguous(), near=ctx.near)
             return gv, None, None, None, None, None, None
+
+
+    class _ProjectPointsFunction(torch.autograd.Function):
+        """smplpp_project_points forward / smplpp_project_points_vjp backward (project_points_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, points, camera, target, rho, near):
+            points, camera = points.detach().contiguous(), camera.detach().contiguous()
+            r = project_points(points, camera, target, rho, near)
+            valid = r["valid"].bool()
+            ctx.mark_non_differentiable(valid)
+            ctx.rho, ctx.near = rho, near
+            ctx.set_materialize_grads(False)  # an output the loss does not use: None, and the backward does not read it
+            ctx.save_for_backward(points, camera, target.detach())
+            return r["uv"], r["energy"], valid
+
+        @staticmethod
+        def backward(ctx, grad_uv, grad_energy, _gv):
+            points, camera, target = ctx.saved_tensors
+            want = tuple(k for k, need in zip(("points", "camera"), ctx.needs_input_grad[:2]) if need)
+            if (grad_uv is None and grad_energy is None) or not want:
+                return None, None, None, None, None
+            g = project_points_backward(points, camera, target, ctx.rho, None if grad_uv is None else grad_uv.contiguous(),
+                                        None if grad_energy is None else grad_energy.contiguous(), near=ctx.near, want=want)
+            return g.get("points"), g.get("camera"), None, None, None
 
 
 # ---- stage classes' functional forms (BlendShape / JointRegression / WorldTransformation / LinearBlendSkinning)
