@@ -55,6 +55,8 @@ typedef struct smplpp_ik smplpp_ik;         /* the IK loop state of node/node.cp
 typedef struct smplpp_vposer smplpp_vposer; /* stands in for smplpp::VPoserDecoder   (VPoser.h:53-90) */
 struct smplpp_landmarks;                    /* a sparse landmark regressor over a model's vertices and joints (no reference counterpart);
                                                written `struct smplpp_landmarks` throughout: the name alone is the regression call below */
+struct smplpp_pose_prior;                   /* a max-mixture Gaussian pose prior with joint limits (no reference counterpart); written
+                                               `struct smplpp_pose_prior` throughout, as above: the name alone is the evaluation call */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -565,6 +567,58 @@ int smplpp_project_points_vjp(int device, int64_t n, int64_t K, const float * po
                               const float * target /*nullable*/, float rho, const float * grad_uv /*[n,K,2] nullable*/,
                               const float * grad_energy /*[n,K] nullable, needs target*/, float * grad_points /*[n,K,3] nullable*/,
                               float * grad_camera /*[n,16] nullable*/, int accumulate, int space, void * stream);
+/* ------------------------------------------------------------------ pose priors: max-mixture Gaussian and joint limits
+ * One handle carries a mixture of M components over D pose coordinates and, optionally, per-coordinate limits: the two pose terms a
+ * single-view fit pairs with the keypoint energy.  mean [M,D], mat [M,D,D] (row j gives output j), offset [M], lo, hi, limit_weight [D]
+ * are host pointers, like the arrays of smplpp_landmarks_create.  With mat = sqrt(1/2) L^T, where the precision of component m is
+ * L L^T, and offset[m] = -log w_m + 1/2 log det Sigma_m - (the least of these over m), the energy below is the negative log of the best
+ * component up to a constant common to all of them.  lo, hi and limit_weight are all given or all NULL; +-inf in lo or hi means no limit
+ * on that side.  M = 0 needs limits.  Creation validates the arrays on the host, makes the two device images of mat (as given, and
+ * transposed) and uploads everything once.
+ *  - SMPLPP_ERR_INVALID: M outside [0, 32], D outside [1, 128], M = 0 without limits, M > 0 with a NULL mean, mat or offset, only some
+ *    of lo, hi, limit_weight, a mean, mat or offset that is not finite, a NaN in lo or hi, lo[k] > hi[k], a limit_weight that is
+ *    negative or not finite (*out = NULL). */
+int smplpp_pose_prior_create(int device, int64_t M, int64_t D, const float * mean /*[M,D]*/, const float * mat /*[M,D,D], row j = output j*/,
+                             const float * offset /*[M]*/, const float * lo /*[D] nullable*/, const float * hi /*[D] nullable*/,
+                             const float * limit_weight /*[D] nullable*/, struct smplpp_pose_prior ** out);
+int smplpp_pose_prior_destroy(struct smplpp_pose_prior * prior);
+int smplpp_pose_prior_info(const struct smplpp_pose_prior * prior, int64_t * M, int64_t * D, int * has_limits);
+/* Both terms of n frames.  `pose` points at coordinate 0 of frame 0; frame i starts i ld floats later, ld >= D: the body pose of a
+ * theta [n,25,3] buffer is (theta + 6, ld = 75, D = 69) with no copy.  A host-space call stages (n-1) ld + D floats.  In fp32 with every
+ * operation rounded on its own (no FMA), per frame:
+ *  mixture, per component m:  d_k = pose_k - mean[m][k];  y_j = sum_k mat[m][j][k] d_k, where partial p = k mod 8 runs s_p = s_p +
+ *    mat[m][j][k] d_k in ascending k from +0 and y_j = ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7));  q_m = sum_j y_j y_j by the
+ *    camera-sum rule of smplpp_project_points_vjp (j goes to partial j mod 64 in ascending j from +0; the 64 partials meet as p_i = p_i +
+ *    p_(i xor s) for s = 32, 16, 8, 4, 2, 1);  e_m = q_m + offset[m].
+ *    The component starts at 0 and, for m = 1 .. M-1 in order, is replaced when e_m < e_best: a tie goes to the lowest m, a NaN e_m
+ *    never replaces and a NaN e_0 is never replaced.  energy [n] = e of the chosen component, component [n] = its index, residual
+ *    [n,D] = its y (energy = |residual|^2 + offset[component]).
+ *  limits:  per coordinate a = pose_k - hi_k, b = lo_k - pose_k, v = a if a > 0, else b if b > 0, else +0 (so a NaN pose_k gives 0, and
+ *    a coordinate exactly at a limit contributes nothing);  limit_energy [n] = sum_k limit_weight_k (v v) by the same 64-partial rule.
+ * Each output may be NULL, not all four.  The bits of a frame do not depend on n, on its position in the batch, on the memory space, on
+ * the work split or on which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID: n <= 0, ld < D, a NULL pose, every output NULL, energy, component or residual on a prior with M = 0,
+ *    limit_energy on a prior without limits, a bad space, n ld beyond int32 indexing (the outputs are untouched). */
+int smplpp_pose_prior(struct smplpp_pose_prior * prior, int64_t n, const float * pose, int64_t ld, float * energy /*[n] nullable*/,
+                      int64_t * component /*[n] nullable*/, float * residual /*[n,D] nullable*/, float * limit_energy /*[n] nullable*/,
+                      int space, void * stream);
+/* Vector-Jacobian product of energy, residual and limit_energy above to the pose; grad_pose has the rows of `pose` (the same ld), and
+ * only its D coordinates per row are written: with accumulate = 1 it lands directly in a grad_theta buffer.  Per frame i, in fp32 with
+ * every operation rounded on its own:
+ *  mixture (when grad_energy or grad_residual is given):  the component is component[i] when that array is given, else it is chosen
+ *    as in the forward (the selection has no gradient);  v_j = (2 g) y_j with g = grad_energy[i], y recomputed by the forward's rule,
+ *    or +0 when grad_energy is NULL or g is exactly 0, even on NaN data;  then v_j = v_j + grad_residual[i][j] when that is given;
+ *    t_k = sum_j mat[m][j][k] v_j by the 8-partial rule over j.  A device-space component outside [0, M) gives t = +0.
+ *  limits (when grad_limit_energy is given):  u_k = ((2 g_l) limit_weight_k) a on the upper side, -(((2 g_l) limit_weight_k) b) on the
+ *    lower side, +0 when g_l = grad_limit_energy[i] is exactly 0 or neither side is active.
+ *  The element is t_k + u_k, or the one alone when the other part's cotangents are NULL; accumulate = 0 stores it, 1 adds it to the
+ *  output.  No floating-point atomics; the same independence as the forward.
+ *  - SMPLPP_ERR_INVALID: as the forward (cotangents for outputs), a NULL grad_pose, accumulate not 0 or 1, a host-space component
+ *    outside [0, M) (the output is untouched).  Without a mixture cotangent `component` is not read, in either space. */
+int smplpp_pose_prior_vjp(struct smplpp_pose_prior * prior, int64_t n, const float * pose, int64_t ld, const int64_t * component /*[n] nullable*/,
+                          const float * grad_energy /*[n] nullable*/, const float * grad_residual /*[n,D] nullable*/,
+                          const float * grad_limit_energy /*[n] nullable*/, float * grad_pose /*rows of ld*/, int accumulate, int space,
+                          void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

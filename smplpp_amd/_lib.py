@@ -102,6 +102,11 @@ def load():
         "smplpp_landmarks_vjp": [vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_project_points": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, C.c_float, vp, vp, vp, C.c_int, vp],
         "smplpp_project_points_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_pose_prior_create": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
+        "smplpp_pose_prior_destroy": [vp],
+        "smplpp_pose_prior_info": [vp, i64p, i64p, C.POINTER(C.c_int)],
+        "smplpp_pose_prior": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_pose_prior_vjp": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],
