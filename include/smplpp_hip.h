@@ -57,6 +57,8 @@ struct smplpp_landmarks;                    /* a sparse landmark regressor over 
                                                written `struct smplpp_landmarks` throughout: the name alone is the regression call below */
 struct smplpp_pose_prior;                   /* a max-mixture Gaussian pose prior with joint limits (no reference counterpart); written
                                                `struct smplpp_pose_prior` throughout, as above: the name alone is the evaluation call */
+struct smplpp_lbfgs;                        /* a batched L-BFGS over n independent frames (no reference counterpart); written
+                                               `struct smplpp_lbfgs` throughout, as the two above */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -619,6 +621,56 @@ int smplpp_pose_prior_vjp(struct smplpp_pose_prior * prior, int64_t n, const flo
                           const float * grad_energy /*[n] nullable*/, const float * grad_residual /*[n,D] nullable*/,
                           const float * grad_limit_energy /*[n] nullable*/, float * grad_pose /*rows of ld*/, int accumulate, int space,
                           void * stream);
+/* ------------------------------------------------------------------ a batched L-BFGS with a device-side line search
+ * One handle optimises n independent frames of D unknowns each.  Every frame has its own history of at most m pairs, its own step
+ * length, line-search state and status; all of it stays on the device between calls.  The caller evaluates energies f [n] and gradients
+ * g (rows of ld_g floats) at the points x it holds (rows of ld_x floats, D coordinates per row touched, the convention of
+ * smplpp_pose_prior: (theta + 3, ld = 75, D = 72) optimises rotation and pose inside a theta buffer), and smplpp_lbfgs_step consumes
+ * them and overwrites x with the next points to evaluate: one kernel launch per evaluation, nothing read back.  Options: c1 in (0, 1)
+ * (1e-4 is usual), tol_grad >= 0 (1e-5), tol_f >= 0 (0 = off), max_ls in [1, 64] (20), curv_eps in [0, 1) (1e-10).
+ *  - SMPLPP_ERR_INVALID: n or D <= 0, m outside [1, 32], n m D beyond int32 indexing, an option out of range or not finite
+ *    (*out = NULL). */
+int smplpp_lbfgs_create(int device, int64_t n, int64_t D, int64_t m, float c1, float tol_grad, float tol_f, int max_ls, float curv_eps,
+                        struct smplpp_lbfgs ** out);
+int smplpp_lbfgs_destroy(struct smplpp_lbfgs * opt);
+int smplpp_lbfgs_info(const struct smplpp_lbfgs * opt, int64_t * n, int64_t * D, int64_t * m);
+/* Every frame back to "not evaluated yet" (status 0, counters 0, an empty history), enqueued on `stream`. */
+int smplpp_lbfgs_reset(struct smplpp_lbfgs * opt, void * stream);
+/* One evaluation of every running frame.  In fp32 with every operation rounded on its own (no FMA).  sum(v) below is ONE fixed-order
+ * sum by the camera-sum rule of smplpp_project_points_vjp: element k goes to partial k mod 64 in ascending k from +0, and the 64
+ * partials meet as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1.  `finite` means: f and every g_k are neither NaN nor +-inf.
+ * gmax = max_k |g_k|.  A frame keeps x0, f0, g0 (its last accepted point), d, t, gtd, ls, a ring of at most m pairs (s_i, y_i, sy_i)
+ * and gamma.  Per frame whose status is 0:
+ *  first evaluation:  evaluations = 1; x0 = x, f0 = f.  Not finite: status 4.  Else gmax <= tol_grad: status 1.  Else g0 = g, d_k = -g_k,
+ *    t = min(1, 1 / sum(|g_k|)), gtd = sum(g_k d_k), x_k = x0_k + t d_k, ls = 0.
+ *  later:  evaluations + 1.  The trial is accepted iff finite and f <= f0 + (c1 t) gtd.
+ *  accepted:  s_k = x_k - x0_k, y_k = g_k - g0_k, sy = sum(s_k y_k), yy = sum(y_k y_k).  When yy > 0 and sy > curv_eps yy the pair enters
+ *    the ring with its sy (a full ring loses its oldest pair) and gamma = sy / yy.  Let fo = f0; then x0 = x, f0 = f, g0 = g;
+ *    iterations + 1.  gmax <= tol_grad: status 1.  Else tol_f > 0 and fo - f <= tol_f max(max(|fo|, |f|), 1): status 2.  Else the
+ *    two-loop recursion: q = g; for the pairs from the newest to the oldest, alpha_i = sum(s_ik q_k) / sy_i, then q_k = q_k - alpha_i
+ *    y_ik;  r_k = gamma q_k (r = q with no pair);  from the oldest to the newest, c = alpha_i - sum(y_ik r_k) / sy_i, then r_k = r_k +
+ *    c s_ik;  d_k = -r_k, gtd = sum(g_k d_k).  Unless gtd < 0: the ring is emptied, d_k = -g_k, gtd = -sum(g_k g_k).  Then t = 1,
+ *    ls = 0, x_k = x0_k + d_k.
+ *  rejected:  ls + 1.  ls > max_ls: status 3 and x = x0.  Else tn = 0.5 t; when f is finite and den = 2 ((f - f0) - gtd t) > 0:
+ *    tn = -((gtd t) t) / den, raised to 0.1 t unless tn >= 0.1 t (so a NaN becomes 0.1 t), then lowered to 0.5 t if above.  t = tn,
+ *    x_k = x0_k + t d_k.
+ * Status: 0 running, 1 gradient tolerance met, 2 energy tolerance met, 3 line search exhausted, 4 not finite at the first evaluation.
+ * A frame whose status is not 0 has its accepted point in x from the call in which it stopped; after that call its row of x, f and g
+ * is neither read nor written by the kernel, whatever it holds.  The bits of a frame do not depend on n, on its slot in the batch, on
+ * the memory space, on ld_x or ld_g, on what the other frames do or on the work split.  In device space the call enqueues one kernel
+ * on `stream`: no allocation, no synchronisation.  A host-space call stages (n-1) ld + D floats of x and g and copies x back.
+ *  - SMPLPP_ERR_INVALID: ld_x or ld_g < D, n ld beyond int32 indexing, a NULL x, f or g, a bad space (x and the state are untouched). */
+int smplpp_lbfgs_step(struct smplpp_lbfgs * opt, float * x, int64_t ld_x, const float * f /*[n]*/, const float * g, int64_t ld_g, int space,
+                      void * stream);
+/* The state of every frame: status [n], iterations [n] (accepted steps), evaluations [n], all int32; f_best [n] = f0 and step [n] = t
+ * (floats; before the first evaluation both are 0); running [1] int64 = the number of frames with status 0.  Each may be NULL, not all.
+ *  - SMPLPP_ERR_INVALID: every output NULL, a bad space. */
+int smplpp_lbfgs_state(struct smplpp_lbfgs * opt, int32_t * status, int32_t * iterations, int32_t * evaluations, float * f_best, float * step,
+                       int64_t * running, int space, void * stream);
+/* x0 of every frame into x (rows of ld_x floats, D per row written) and f0 into f [n] (nullable): what a caller needs when its
+ * evaluation budget ends while some frames are in the middle of a line search.  A frame not evaluated yet is left as it is.
+ *  - SMPLPP_ERR_INVALID: ld_x < D, n ld_x beyond int32 indexing, a NULL x, a bad space (the outputs are untouched). */
+int smplpp_lbfgs_best(struct smplpp_lbfgs * opt, float * x, int64_t ld_x, float * f /*[n] nullable*/, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -107,6 +107,13 @@ def load():
         "smplpp_pose_prior_info": [vp, i64p, i64p, C.POINTER(C.c_int)],
         "smplpp_pose_prior": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_pose_prior_vjp": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_lbfgs_create": [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.POINTER(vp)],
+        "smplpp_lbfgs_destroy": [vp],
+        "smplpp_lbfgs_info": [vp, i64p, i64p, i64p],
+        "smplpp_lbfgs_reset": [vp, vp],
+        "smplpp_lbfgs_step": [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp],
+        "smplpp_lbfgs_state": [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_lbfgs_best": [vp, vp, C.c_int64, vp, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],

@@ -1,0 +1,429 @@
+// A batched L-BFGS with a device-side backtracking line search: n independent frames of D unknowns, each with its own
+// history of m pairs, its own step length and its own status, all kept on the device between calls.  The rule is in
+// include/smplpp_hip.h; every fp32 operation below is rounded on its own (no contraction to FMA), every dot product is one fixed-order
+// sum by the 64-partial rule of smplpp_project_points_vjp, and there are no atomics.
+//
+//  lbfgs_step_kernel   one wavefront per frame, LBFGS_FT frames a workgroup, no barrier.  Lane l owns the coordinates k = l, l + 64, ...
+//                      of every vector of its frame: the partial l of each sum and the element-wise updates need those alone, so that
+//                      a frame's passes are ordered by its own wavefront's program order.  The working vector of the two-loop recursion
+//                      (q, then r) lives in LDS when D <= LBFGS_LDS_D, else in the frame's direction row in global memory; alpha_i stays
+//                      in a register of lane i.  Each update of the working vector is folded into the pass that takes the next dot
+//                      product, so the recursion over c pairs is 2 c + 1 passes over the working vector and 4 c rows of history.
+//  lbfgs_best_kernel   the accepted points into the caller's rows.
+//  lbfgs_running_kernel  one workgroup counts the frames with status 0.
+#include "lbfgs_plan.h"
+#include "staging.h"
+
+#pragma clang fp contract(off)
+
+struct smplpp_lbfgs
+{
+  int device = 0;
+  int64_t n = 0, D = 0, m = 0;
+  smplpp_hip::LbfgsOptions opt{};
+  smplpp_hip::DevBuf ints, floats, sy, vec, hist; // lbfgs_plan.h: LbfgsSizes
+  smplpp_hip::DevBuf running;                    // one int64: the count smplpp_lbfgs_state reports
+  smplpp_hip::Arena arena;                       // staging of the host-space calls on this handle
+};
+
+namespace smplpp_hip
+{
+using Lbfgs = struct ::smplpp_lbfgs;
+
+// the device view of a handle
+struct LbfgsState
+{
+  int * ints;
+  float *floats, *sy, *vec, *hist;
+  LbfgsOptions o;
+  int64_t n;
+  int D, m;
+};
+
+// the 64 partials of a wavefront meet: p_i = p_i + p_(i xor s), s = 32, 16, 8, 4, 2, 1 (every lane ends with p_0's bits)
+__device__ inline float lb_tree(float p)
+{
+  for(int s = 32; s >= 1; s >>= 1) p = p + __shfl_xor(p, s);
+  return p;
+}
+__device__ inline float lb_tree_max(float p)
+{
+  for(int s = 32; s >= 1; s >>= 1) p = fmaxf(p, __shfl_xor(p, s));
+  return p;
+}
+
+// grid: ceil(n / LBFGS_FT); dynamic LDS: LBFGS_FT * D floats when LDS_VECTOR.  A frame whose status is not 0 returns before it reads
+// or writes anything of the caller's.
+template<bool LDS_VECTOR>
+__global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float * x, int64_t ld_x, const float * __restrict__ f,
+                                                             const float * __restrict__ g, int64_t ld_g)
+{
+  extern __shared__ __attribute__((aligned(16))) float lb_smem[];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, D = s.D, m = s.m;
+  const int64_t n = s.n, frame = (int64_t)blockIdx.x * LBFGS_FT + w;
+  if(frame >= n) return;
+  int * I = s.ints + frame;     // scalar j of the frame: I[j n]
+  float * F = s.floats + frame; // likewise
+  if(I[LBFGS_STATUS * n] != 0) return;
+  float * xr = x + frame * ld_x;
+  const float * gr = g + frame * ld_g;
+  float * x0 = s.vec + (LBFGS_X0 * n + frame) * D;
+  float * g0 = s.vec + (LBFGS_G0 * n + frame) * D;
+  float * dir = s.vec + (LBFGS_DIR * n + frame) * D;
+  float * S = s.hist + frame * m * D;
+  float * Y = S + n * m * D;
+  float * sy = s.sy + frame * m;
+  const float fv = f[frame];
+  const int evals = I[LBFGS_EVAL * n];
+
+  // one pass over g: is it finite, max |g_k|, the partials of sum |g_k|
+  int fin = fabsf(fv) < INFINITY;
+  float gmax = 0.0f, pa = 0.0f;
+#pragma unroll 4
+  for(int k = lane; k < D; k += 64)
+  {
+    const float a = fabsf(gr[k]);
+    fin &= a < INFINITY;
+    gmax = fmaxf(gmax, a);
+    pa = pa + a;
+  }
+  fin = __all(fin);
+  gmax = lb_tree_max(gmax);
+
+  if(evals == 0) // the first evaluation of the frame
+  {
+    if(lane == 0) I[LBFGS_EVAL * n] = 1, F[LBFGS_F0 * n] = fv;
+#pragma unroll 4
+    for(int k = lane; k < D; k += 64) x0[k] = xr[k];
+    if(!fin || gmax <= s.o.tol_grad)
+    {
+      if(lane == 0) I[LBFGS_STATUS * n] = fin ? 1 : 4;
+      return;
+    }
+    const float t = fminf(1.0f, 1.0f / lb_tree(pa));
+    float p = 0.0f;
+#pragma unroll 4
+    for(int k = lane; k < D; k += 64)
+    {
+      const float gk = gr[k], dk = -gk;
+      g0[k] = gk, dir[k] = dk;
+      p = p + gk * dk;
+      xr[k] = x0[k] + t * dk;
+    }
+    const float gtd = lb_tree(p);
+    if(lane == 0) F[LBFGS_STEP * n] = t, F[LBFGS_GTD * n] = gtd, I[LBFGS_LS * n] = 0;
+    return;
+  }
+
+  const float f0 = F[LBFGS_F0 * n], t = F[LBFGS_STEP * n];
+  float gtd = F[LBFGS_GTD * n];
+  if(lane == 0) I[LBFGS_EVAL * n] = evals + 1;
+  if(!(fin && fv <= f0 + (s.o.c1 * t) * gtd)) // rejected
+  {
+    const int ls = I[LBFGS_LS * n] + 1;
+    if(lane == 0) I[LBFGS_LS * n] = ls;
+    if(ls > s.o.max_ls)
+    {
+      if(lane == 0) I[LBFGS_STATUS * n] = 3;
+#pragma unroll 4
+      for(int k = lane; k < D; k += 64) xr[k] = x0[k];
+      return;
+    }
+    float tn = 0.5f * t;
+    if(fabsf(fv) < INFINITY)
+    {
+      const float den = 2.0f * ((fv - f0) - gtd * t);
+      if(den > 0.0f)
+      {
+        const float lo = 0.1f * t, hi = 0.5f * t;
+        tn = -((gtd * t) * t) / den;
+        if(!(tn >= lo)) tn = lo;
+        if(tn > hi) tn = hi;
+      }
+    }
+    if(lane == 0) F[LBFGS_STEP * n] = tn;
+#pragma unroll 4
+    for(int k = lane; k < D; k += 64) xr[k] = x0[k] + tn * dir[k];
+    return;
+  }
+
+  // accepted: the pair, then the accepted point moves
+  int head = I[LBFGS_HEAD * n], count = I[LBFGS_COUNT * n];
+  float psy = 0.0f, pyy = 0.0f;
+#pragma unroll 4
+  for(int k = lane; k < D; k += 64)
+  {
+    const float sk = xr[k] - x0[k], yk = gr[k] - g0[k];
+    psy = psy + sk * yk;
+    pyy = pyy + yk * yk;
+  }
+  const float sy_new = lb_tree(psy), yy = lb_tree(pyy);
+  const bool push = yy > 0.0f && sy_new > s.o.curv_eps * yy;
+  float gamma = F[LBFGS_GAMMA * n];
+  int slot = 0;
+  if(push)
+  {
+    slot = lbfgs_ring_push(head, count, m);
+    gamma = sy_new / yy;
+    if(lane == 0) sy[slot] = sy_new, F[LBFGS_GAMMA * n] = gamma;
+  }
+#pragma unroll 4
+  for(int k = lane; k < D; k += 64)
+  {
+    const float xk = xr[k], gk = gr[k];
+    if(push) S[slot * D + k] = xk - x0[k], Y[slot * D + k] = gk - g0[k];
+    x0[k] = xk, g0[k] = gk;
+  }
+  int status = 0;
+  if(gmax <= s.o.tol_grad) status = 1;
+  else if(s.o.tol_f > 0.0f && f0 - fv <= s.o.tol_f * fmaxf(fmaxf(fabsf(f0), fabsf(fv)), 1.0f))
+    status = 2;
+  if(lane == 0)
+  {
+    I[LBFGS_ITER * n] = I[LBFGS_ITER * n] + 1;
+    F[LBFGS_F0 * n] = fv;
+    I[LBFGS_STATUS * n] = status;
+  }
+  if(status == 0)
+  {
+    // the two-loop recursion.  v: q, then r; every pass first applies the update the pass before it found (v = v + c u), then sums
+    float * v = LDS_VECTOR ? lb_smem + w * D : dir;
+    float akeep = 0.0f, c = 0.0f;
+    const float * u = nullptr;
+    for(int i = 0; i < count; i++) // newest to oldest
+    {
+      const int sl = lbfgs_ring_slot(head, count, m, i);
+      const float * si = S + sl * D;
+      float p = 0.0f;
+#pragma unroll 4
+      for(int k = lane; k < D; k += 64)
+      {
+        const float qk = u ? v[k] - c * u[k] : gr[k];
+        v[k] = qk;
+        p = p + si[k] * qk;
+      }
+      c = lb_tree(p) / sy[sl];
+      if(lane == i) akeep = c;
+      u = Y + sl * D;
+    }
+    if(count > 0)
+    {
+#pragma unroll 4
+      for(int k = lane; k < D; k += 64) v[k] = gamma * (v[k] - c * u[k]);
+    }
+    else
+#pragma unroll 4
+      for(int k = lane; k < D; k += 64) v[k] = gr[k];
+    u = nullptr;
+    for(int i = count - 1; i >= 0; i--) // oldest to newest
+    {
+      const int sl = lbfgs_ring_slot(head, count, m, i);
+      const float * yi = Y + sl * D;
+      float p = 0.0f;
+#pragma unroll 4
+      for(int k = lane; k < D; k += 64)
+      {
+        float rk = v[k];
+        if(u) rk = rk + c * u[k], v[k] = rk;
+        p = p + yi[k] * rk;
+      }
+      c = __shfl(akeep, i) - lb_tree(p) / sy[sl];
+      u = S + sl * D;
+    }
+    float p = 0.0f;
+#pragma unroll 4
+    for(int k = lane; k < D; k += 64)
+    {
+      float rk = v[k];
+      if(u) rk = rk + c * u[k];
+      const float dk = -rk;
+      dir[k] = dk;
+      p = p + gr[k] * dk;
+    }
+    gtd = lb_tree(p);
+    if(!(gtd < 0.0f)) // not a descent direction: the history is dropped
+    {
+      lbfgs_ring_drop(head, count);
+      p = 0.0f;
+#pragma unroll 4
+      for(int k = lane; k < D; k += 64)
+      {
+        const float gk = gr[k];
+        dir[k] = -gk;
+        p = p + gk * gk;
+      }
+      gtd = -lb_tree(p);
+    }
+#pragma unroll 4
+    for(int k = lane; k < D; k += 64) xr[k] = x0[k] + dir[k];
+    if(lane == 0) F[LBFGS_STEP * n] = 1.0f, F[LBFGS_GTD * n] = gtd, I[LBFGS_LS * n] = 0;
+  }
+  if(lane == 0) I[LBFGS_HEAD * n] = head, I[LBFGS_COUNT * n] = count;
+}
+
+// grid: ceil(n D / 256).  x, f: the caller's; f may be null.  A frame that has not been evaluated yet has no accepted point: left alone
+__global__ __launch_bounds__(256) void lbfgs_best_kernel(LbfgsState s, float * __restrict__ x, int64_t ld_x, float * __restrict__ f)
+{
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if(i >= s.n * s.D) return;
+  const int64_t frame = i / s.D, k = i % s.D;
+  if(s.ints[LBFGS_EVAL * s.n + frame] == 0) return;
+  x[frame * ld_x + k] = s.vec[LBFGS_X0 * s.n * s.D + i];
+  if(f && k == 0) f[frame] = s.floats[LBFGS_F0 * s.n + frame];
+}
+
+// one workgroup of 256: *running = the number of frames with status 0
+__global__ __launch_bounds__(256) void lbfgs_running_kernel(LbfgsState s, int64_t * running)
+{
+  __shared__ int part[4];
+  int c = 0;
+  for(int64_t i = threadIdx.x; i < s.n; i += 256) c += s.ints[LBFGS_STATUS * s.n + i] == 0;
+  for(int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+  if((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if(threadIdx.x == 0) *running = (int64_t)part[0] + part[1] + part[2] + part[3];
+}
+
+static LbfgsState lb_state(const Lbfgs * o)
+{
+  return LbfgsState{o->ints.as<int>(), o->floats.as<float>(), o->sy.as<float>(), o->vec.as<float>(), o->hist.as<float>(), o->opt, o->n, (int)o->D,
+                    (int)o->m};
+}
+
+// every scalar of every frame to zero: status 0 (running), no evaluation yet, an empty ring
+static hipError_t lb_clear(Lbfgs * o, hipStream_t st)
+{
+  const LbfgsSizes z = lbfgs_sizes(o->n, o->D, o->m);
+  hipError_t e = hipMemsetAsync(o->ints.p.get(), 0, sizeof(int) * z.ints, st);
+  if(e == hipSuccess) e = hipMemsetAsync(o->floats.p.get(), 0, sizeof(float) * z.floats, st);
+  if(e == hipSuccess) e = hipMemsetAsync(o->sy.p.get(), 0, sizeof(float) * z.sy, st);
+  return e;
+}
+
+// what the calls on rows of the caller's refuse alike
+static int lb_check_rows(const char * fn, Lbfgs * o, const void * x, int64_t ld_x, int space)
+{
+  if(!o) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": no optimiser");
+  if(const char * why = lbfgs_rows_refusal(o->n, o->D, ld_x)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + why);
+  if(!x) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": x is NULL");
+  return check_space(space, fn);
+}
+} // namespace smplpp_hip
+
+using namespace smplpp_hip;
+
+extern "C" int smplpp_lbfgs_create(int device, int64_t n, int64_t D, int64_t m, float c1, float tol_grad, float tol_f, int max_ls,
+                                   float curv_eps, struct smplpp_lbfgs ** out)
+{
+  const char * fn = "smplpp_lbfgs_create";
+  if(!out) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": no out");
+  *out = nullptr;
+  const LbfgsOptions opt{c1, tol_grad, tol_f, max_ls, curv_eps};
+  if(const char * why = lbfgs_shape_refusal(n, D, m)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + why);
+  if(const char * why = lbfgs_options_refusal(opt)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + why);
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<Lbfgs> o(new Lbfgs());
+  o->device = device, o->n = n, o->D = D, o->m = m, o->opt = opt;
+  const LbfgsSizes z = lbfgs_sizes(n, D, m);
+  HIP_TRY(o->ints.reserve(sizeof(int) * z.ints));
+  HIP_TRY(o->floats.reserve(sizeof(float) * z.floats));
+  HIP_TRY(o->sy.reserve(sizeof(float) * z.sy));
+  HIP_TRY(o->vec.reserve(sizeof(float) * z.vec));
+  HIP_TRY(o->hist.reserve(sizeof(float) * z.hist));
+  HIP_TRY(o->running.reserve(sizeof(int64_t)));
+  HIP_TRY(lb_clear(o.get(), nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  *out = o.release();
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_lbfgs_destroy(struct smplpp_lbfgs * opt)
+{
+  if(!opt) return SMPLPP_OK;
+  (void)hipSetDevice(opt->device);
+  delete opt;
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_lbfgs_info(const struct smplpp_lbfgs * opt, int64_t * n, int64_t * D, int64_t * m)
+{
+  if(!opt) return fail(SMPLPP_ERR_INVALID, "smplpp_lbfgs_info: no optimiser");
+  if(n) *n = opt->n;
+  if(D) *D = opt->D;
+  if(m) *m = opt->m;
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_lbfgs_reset(struct smplpp_lbfgs * opt, void * stream)
+{
+  if(!opt) return fail(SMPLPP_ERR_INVALID, "smplpp_lbfgs_reset: no optimiser");
+  HIP_TRY(hipSetDevice(opt->device));
+  HIP_TRY(lb_clear(opt, static_cast<hipStream_t>(stream)));
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_lbfgs_step(struct smplpp_lbfgs * opt, float * x, int64_t ld_x, const float * f, const float * g, int64_t ld_g, int space,
+                                 void * stream)
+{
+  const char * fn = "smplpp_lbfgs_step";
+  if(int rc = lb_check_rows(fn, opt, x, ld_x, space)) return rc;
+  if(const char * why = lbfgs_rows_refusal(opt->n, opt->D, ld_g)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": (g) " + why);
+  if(!f || !g) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": f or g is NULL");
+  const int64_t n = opt->n, D = opt->D;
+  const LbfgsLaunch L = lbfgs_launch(n, D);
+  Frame fr(opt->device, &opt->arena, space, stream, "lbfgs step");
+  // (a host-space row travels whole, and comes back as it went where the kernel leaves it alone)
+  float * xd = fr.out(x, (size_t)((n - 1) * ld_x + D), true);
+  const float * fd = fr.in(f, (size_t)n);
+  const float * gd = fr.in(g, (size_t)((n - 1) * ld_g + D));
+  return fr.run([&] {
+    if(L.lds_vector)
+      lbfgs_step_kernel<true><<<dim3(L.grid), dim3(L.threads), L.lds_bytes, fr.st>>>(lb_state(opt), xd, ld_x, fd, gd, ld_g);
+    else
+      lbfgs_step_kernel<false><<<dim3(L.grid), dim3(L.threads), 0, fr.st>>>(lb_state(opt), xd, ld_x, fd, gd, ld_g);
+    HIP_TRY(hipGetLastError());
+    return (int)SMPLPP_OK;
+  });
+}
+
+extern "C" int smplpp_lbfgs_state(struct smplpp_lbfgs * opt, int32_t * status, int32_t * iterations, int32_t * evaluations, float * f_best,
+                                  float * step, int64_t * running, int space, void * stream)
+{
+  const char * fn = "smplpp_lbfgs_state";
+  if(!opt) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": no optimiser");
+  if(!status && !iterations && !evaluations && !f_best && !step && !running) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": every output is NULL");
+  if(int rc = check_space(space, fn)) return rc;
+  const size_t n = (size_t)opt->n;
+  Frame fr(opt->device, &opt->arena, space, stream, "lbfgs state");
+  return fr.run([&] {
+    const int * I = opt->ints.as<int>();
+    const float * F = opt->floats.as<float>();
+    fr.fetch(status, I + LBFGS_STATUS * n, n);
+    fr.fetch(iterations, I + LBFGS_ITER * n, n);
+    fr.fetch(evaluations, I + LBFGS_EVAL * n, n);
+    fr.fetch(f_best, F + LBFGS_F0 * n, n);
+    fr.fetch(step, F + LBFGS_STEP * n, n);
+    if(running)
+    {
+      lbfgs_running_kernel<<<dim3(1), dim3(256), 0, fr.st>>>(lb_state(opt), opt->running.as<int64_t>());
+      HIP_TRY(hipGetLastError());
+      fr.fetch(running, opt->running.as<int64_t>(), 1);
+    }
+    return (int)SMPLPP_OK;
+  });
+}
+
+extern "C" int smplpp_lbfgs_best(struct smplpp_lbfgs * opt, float * x, int64_t ld_x, float * f, int space, void * stream)
+{
+  const char * fn = "smplpp_lbfgs_best";
+  if(int rc = lb_check_rows(fn, opt, x, ld_x, space)) return rc;
+  const int64_t n = opt->n, D = opt->D;
+  Frame fr(opt->device, &opt->arena, space, stream, "lbfgs best");
+  float * xd = fr.out(x, (size_t)((n - 1) * ld_x + D), ld_x > D);
+  float * fd = fr.out(f, (size_t)n);
+  return fr.run([&] {
+    lbfgs_best_kernel<<<dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, fr.st>>>(lb_state(opt), xd, ld_x, fd);
+    HIP_TRY(hipGetLastError());
+    return (int)SMPLPP_OK;
+  });
+}
