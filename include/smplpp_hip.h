@@ -671,6 +671,31 @@ int smplpp_lbfgs_state(struct smplpp_lbfgs * opt, int32_t * status, int32_t * it
  * evaluation budget ends while some frames are in the middle of a line search.  A frame not evaluated yet is left as it is.
  *  - SMPLPP_ERR_INVALID: ld_x < D, n ld_x beyond int32 indexing, a NULL x, a bad space (the outputs are untouched). */
 int smplpp_lbfgs_best(struct smplpp_lbfgs * opt, float * x, int64_t ld_x, float * f /*[n] nullable*/, int space, void * stream);
+/* ------------------------------------------------------------------ L-BFGS problems that span groups of rows
+ * A grouped handle holds P problems where smplpp_lbfgs_create holds n frames.  Problem p owns the rows row_start[p] .. row_start[p+1]-1 of
+ * the caller's x and g (rows ld floats apart, D coordinates per row touched, as above); its unknown vector has N_p = (rows of p) D
+ * elements, element j = r D + k being coordinate k of the problem's r-th row.  It has ONE history of at most m pairs of N_p elements, one
+ * step length, one line search and one status: what a β shared by the frames of a sequence, a velocity term between consecutive frames or
+ * one SMPL+D offset field need.  Problems of different lengths share a handle.  A vector shared by T frames of a θ buffer takes a row of
+ * its own: a buffer [T+1, 75] whose last row carries β in its first 10 coordinates; the unused coordinates have gradient 0 and never move.
+ * smplpp_lbfgs_step, _state, _best, _reset, _info and _destroy take such a handle unchanged: f and every array of _state (and f of _best)
+ * have P entries, `running` counts problems, _info still reports n, D and m.
+ * The rule of a grouped handle is the per-frame rule of smplpp_lbfgs_step word for word, applied to the problem's N elements (read
+ * "problem" for "frame" and j < N for k), with one change: sum(v) is the 1024-PARTIAL RULE.  Element j goes to partial j mod 1024 in
+ * ascending j, starting from +0, and the 1024 partials meet as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64.
+ * `finite` and gmax run over all N elements.  fp32 throughout, every operation rounded on its own, no FMA contraction, no atomics.  A
+ * grouped handle always uses this rule, also for a problem of one row, whose bits therefore differ from those of the same row on a handle
+ * from smplpp_lbfgs_create: per-frame fits belong on the ungrouped handle (one wavefront a frame; a problem here costs a workgroup of 1024).
+ * The bits of a problem depend on nothing but the problem: not on P, on its slot, on the lengths of the other problems, on the memory
+ * space, on ld_x or ld_g, or on what the other problems do.  After the call in which a problem stops, none of its rows in x and g and not
+ * its entry of f is read or written.  One kernel launch per smplpp_lbfgs_step, one workgroup per problem.
+ *  - SMPLPP_ERR_INVALID (*out = NULL): P <= 0, a NULL row_start, row_start[0] != 0, a row_start that does not strictly increase,
+ *    row_start[P] != n, and what smplpp_lbfgs_create refuses. */
+int smplpp_lbfgs_create_grouped(int device, int64_t n, int64_t D, int64_t m, int64_t P, const int64_t * row_start /*[P+1], host*/, float c1,
+                                float tol_grad, float tol_f, int max_ls, float curv_eps, struct smplpp_lbfgs ** out);
+/* The groups of a handle: *P (nullable) and row_start [P+1] (host, nullable).  A handle from smplpp_lbfgs_create reports P = n and
+ * row_start = 0 .. n. */
+int smplpp_lbfgs_groups(const struct smplpp_lbfgs * opt, int64_t * P, int64_t * row_start /*[P+1] host, nullable*/);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -114,6 +114,9 @@ def load():
         "smplpp_lbfgs_step": [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp],
         "smplpp_lbfgs_state": [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_lbfgs_best": [vp, vp, C.c_int64, vp, C.c_int, vp],
+        "smplpp_lbfgs_create_grouped": [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
+                                        C.POINTER(vp)],
+        "smplpp_lbfgs_groups": [vp, i64p, i64p],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],

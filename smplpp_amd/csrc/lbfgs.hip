@@ -11,7 +11,11 @@
 //                      product, so the recursion over c pairs is 2 c + 1 passes over the working vector and 4 c rows of history.
 //  lbfgs_best_kernel   the accepted points into the caller's rows.
 //  lbfgs_running_kernel  one workgroup counts the frames with status 0.
-#include "lbfgs_plan.h"
+// A handle from smplpp_lbfgs_create_grouped has P problems of consecutive rows where this one has n frames: the same entry
+// points, the scalars [.][P], and the step and best kernels of lbfgs_wide.hip.
+#include <vector>
+
+#include "lbfgs_wide.h"
 #include "staging.h"
 
 #pragma clang fp contract(off)
@@ -23,6 +27,12 @@ struct smplpp_lbfgs
   smplpp_hip::LbfgsOptions opt{};
   smplpp_hip::DevBuf ints, floats, sy, vec, hist; // lbfgs_plan.h: LbfgsSizes
   smplpp_hip::DevBuf running;                    // one int64: the count smplpp_lbfgs_state reports
+  // a grouped handle: P problems, problem p the rows row_start[p] .. row_start[p+1]-1 (lbfgs_wide_plan.h); else P = n
+  bool grouped = false;
+  int64_t P = 0;
+  std::vector<int64_t> row_start;
+  smplpp_hip::DevBuf rows;            // row_start as int32, for the kernels
+  smplpp_hip::LbfgsWideLaunch wide{}; // the step kernel's launch, decided once
   smplpp_hip::Arena arena;                       // staging of the host-space calls on this handle
 };
 
@@ -290,10 +300,17 @@ static LbfgsState lb_state(const Lbfgs * o)
                     (int)o->m};
 }
 
-// every scalar of every frame to zero: status 0 (running), no evaluation yet, an empty ring
+static LbfgsWideState lb_wide_state(const Lbfgs * o)
+{
+  return LbfgsWideState{o->ints.as<int>(), o->floats.as<float>(), o->sy.as<float>(), o->vec.as<float>(), o->hist.as<float>(), o->rows.as<int>(),
+                        o->opt,            o->n,                  (int)o->P,         (int)o->D,          (int)o->m};
+}
+
+// every scalar of every frame (of every problem: P of them, P = n without groups) to zero: status 0 (running), no evaluation yet, an
+// empty ring
 static hipError_t lb_clear(Lbfgs * o, hipStream_t st)
 {
-  const LbfgsSizes z = lbfgs_sizes(o->n, o->D, o->m);
+  const LbfgsSizes z = lbfgs_sizes(o->P, o->D, o->m);
   hipError_t e = hipMemsetAsync(o->ints.p.get(), 0, sizeof(int) * z.ints, st);
   if(e == hipSuccess) e = hipMemsetAsync(o->floats.p.get(), 0, sizeof(float) * z.floats, st);
   if(e == hipSuccess) e = hipMemsetAsync(o->sy.p.get(), 0, sizeof(float) * z.sy, st);
@@ -312,28 +329,59 @@ static int lb_check_rows(const char * fn, Lbfgs * o, const void * x, int64_t ld_
 
 using namespace smplpp_hip;
 
-extern "C" int smplpp_lbfgs_create(int device, int64_t n, int64_t D, int64_t m, float c1, float tol_grad, float tol_f, int max_ls,
-                                   float curv_eps, struct smplpp_lbfgs ** out)
+// row_start: null for a handle without groups (every row its own frame), else P + 1 row numbers
+static int lb_create(const char * fn, int device, int64_t n, int64_t D, int64_t m, int64_t P, const int64_t * row_start, bool grouped,
+                     const LbfgsOptions & opt, struct smplpp_lbfgs ** out)
 {
-  const char * fn = "smplpp_lbfgs_create";
   if(!out) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": no out");
   *out = nullptr;
-  const LbfgsOptions opt{c1, tol_grad, tol_f, max_ls, curv_eps};
   if(const char * why = lbfgs_shape_refusal(n, D, m)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + why);
   if(const char * why = lbfgs_options_refusal(opt)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + why);
+  if(grouped)
+    if(const char * why = lbfgs_groups_refusal(n, P, row_start)) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": " + why);
   HIP_TRY(hipSetDevice(device));
   std::unique_ptr<Lbfgs> o(new Lbfgs());
-  o->device = device, o->n = n, o->D = D, o->m = m, o->opt = opt;
-  const LbfgsSizes z = lbfgs_sizes(n, D, m);
-  HIP_TRY(o->ints.reserve(sizeof(int) * z.ints));
-  HIP_TRY(o->floats.reserve(sizeof(float) * z.floats));
-  HIP_TRY(o->sy.reserve(sizeof(float) * z.sy));
+  o->device = device, o->n = n, o->D = D, o->m = m, o->opt = opt, o->grouped = grouped, o->P = grouped ? P : n;
+  const LbfgsSizes z = lbfgs_sizes(n, D, m); // (vec and hist are as large with groups: lbfgs_wide_sizes)
+  const LbfgsSizes zs = lbfgs_sizes(o->P, D, m);
+  HIP_TRY(o->ints.reserve(sizeof(int) * zs.ints));
+  HIP_TRY(o->floats.reserve(sizeof(float) * zs.floats));
+  HIP_TRY(o->sy.reserve(sizeof(float) * zs.sy));
   HIP_TRY(o->vec.reserve(sizeof(float) * z.vec));
   HIP_TRY(o->hist.reserve(sizeof(float) * z.hist));
   HIP_TRY(o->running.reserve(sizeof(int64_t)));
+  if(grouped)
+  {
+    o->row_start.assign(row_start, row_start + P + 1);
+    o->wide = lbfgs_wide_launch(D, P, row_start);
+    const std::vector<int> rows(o->row_start.begin(), o->row_start.end()); // n <= int32 by lbfgs_shape_refusal
+    HIP_TRY(o->rows.reserve(sizeof(int) * rows.size()));
+    HIP_TRY(hipMemcpy(o->rows.p.get(), rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice));
+  }
   HIP_TRY(lb_clear(o.get(), nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
   *out = o.release();
+  return SMPLPP_OK;
+}
+
+extern "C" int smplpp_lbfgs_create(int device, int64_t n, int64_t D, int64_t m, float c1, float tol_grad, float tol_f, int max_ls,
+                                   float curv_eps, struct smplpp_lbfgs ** out)
+{
+  return lb_create("smplpp_lbfgs_create", device, n, D, m, n, nullptr, false, LbfgsOptions{c1, tol_grad, tol_f, max_ls, curv_eps}, out);
+}
+
+extern "C" int smplpp_lbfgs_create_grouped(int device, int64_t n, int64_t D, int64_t m, int64_t P, const int64_t * row_start, float c1,
+                                           float tol_grad, float tol_f, int max_ls, float curv_eps, struct smplpp_lbfgs ** out)
+{
+  return lb_create("smplpp_lbfgs_create_grouped", device, n, D, m, P, row_start, true, LbfgsOptions{c1, tol_grad, tol_f, max_ls, curv_eps}, out);
+}
+
+extern "C" int smplpp_lbfgs_groups(const struct smplpp_lbfgs * opt, int64_t * P, int64_t * row_start)
+{
+  if(!opt) return fail(SMPLPP_ERR_INVALID, "smplpp_lbfgs_groups: no optimiser");
+  if(P) *P = opt->P;
+  if(row_start)
+    for(int64_t p = 0; p <= opt->P; p++) row_start[p] = opt->grouped ? opt->row_start[(size_t)p] : p;
   return SMPLPP_OK;
 }
 
@@ -374,8 +422,13 @@ extern "C" int smplpp_lbfgs_step(struct smplpp_lbfgs * opt, float * x, int64_t l
   Frame fr(opt->device, &opt->arena, space, stream, "lbfgs step");
   // (a host-space row travels whole, and comes back as it went where the kernel leaves it alone)
   float * xd = fr.out(x, (size_t)((n - 1) * ld_x + D), true);
-  const float * fd = fr.in(f, (size_t)n);
+  const float * fd = fr.in(f, (size_t)opt->P);
   const float * gd = fr.in(g, (size_t)((n - 1) * ld_g + D));
+  if(opt->grouped)
+    return fr.run([&] {
+      HIP_TRY(lbfgs_wide_step(opt->device, lb_wide_state(opt), opt->wide, xd, ld_x, fd, gd, ld_g, fr.st));
+      return (int)SMPLPP_OK;
+    });
   return fr.run([&] {
     if(L.lds_vector)
       lbfgs_step_kernel<true><<<dim3(L.grid), dim3(L.threads), L.lds_bytes, fr.st>>>(lb_state(opt), xd, ld_x, fd, gd, ld_g);
@@ -393,7 +446,7 @@ extern "C" int smplpp_lbfgs_state(struct smplpp_lbfgs * opt, int32_t * status, i
   if(!opt) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": no optimiser");
   if(!status && !iterations && !evaluations && !f_best && !step && !running) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": every output is NULL");
   if(int rc = check_space(space, fn)) return rc;
-  const size_t n = (size_t)opt->n;
+  const size_t n = (size_t)opt->P; // the scalars are [.][P]; P = n without groups
   Frame fr(opt->device, &opt->arena, space, stream, "lbfgs state");
   return fr.run([&] {
     const int * I = opt->ints.as<int>();
@@ -405,7 +458,9 @@ extern "C" int smplpp_lbfgs_state(struct smplpp_lbfgs * opt, int32_t * status, i
     fr.fetch(step, F + LBFGS_STEP * n, n);
     if(running)
     {
-      lbfgs_running_kernel<<<dim3(1), dim3(256), 0, fr.st>>>(lb_state(opt), opt->running.as<int64_t>());
+      LbfgsState s = lb_state(opt);
+      s.n = opt->P;
+      lbfgs_running_kernel<<<dim3(1), dim3(256), 0, fr.st>>>(s, opt->running.as<int64_t>());
       HIP_TRY(hipGetLastError());
       fr.fetch(running, opt->running.as<int64_t>(), 1);
     }
@@ -420,7 +475,12 @@ extern "C" int smplpp_lbfgs_best(struct smplpp_lbfgs * opt, float * x, int64_t l
   const int64_t n = opt->n, D = opt->D;
   Frame fr(opt->device, &opt->arena, space, stream, "lbfgs best");
   float * xd = fr.out(x, (size_t)((n - 1) * ld_x + D), ld_x > D);
-  float * fd = fr.out(f, (size_t)n);
+  float * fd = fr.out(f, (size_t)opt->P);
+  if(opt->grouped)
+    return fr.run([&] {
+      HIP_TRY(lbfgs_wide_best(lb_wide_state(opt), xd, ld_x, fd, fr.st));
+      return (int)SMPLPP_OK;
+    });
   return fr.run([&] {
     lbfgs_best_kernel<<<dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, fr.st>>>(lb_state(opt), xd, ld_x, fd);
     HIP_TRY(hipGetLastError());

@@ -34,9 +34,17 @@ def _rows(name, a):
 class BatchedLBFGS:
     """L-BFGS over the rows of x [n,D]: a float32 CUDA tensor with requires_grad, or a row-strided view of one (theta.view(n, 75)[:, 3:]
     optimises rotation and pose inside a theta buffer), or for the host-space path a float32 numpy array.  history: pairs kept per
-    frame (1..32).  Options: c1, tol_grad, tol_f, max_ls, curv_eps (smplpp_lbfgs_create)."""
+    frame (1..32).  Options: c1, tol_grad, tol_f, max_ls, curv_eps (smplpp_lbfgs_create).
 
-    def __init__(self, x, history=10, device=None, **options):
+    groups=[len_0, len_1, ...] (row counts summing to n) makes problem p the len_p consecutive rows after those of problem p - 1, with
+    one history, step length, line search and status for all its len_p * D unknowns (smplpp_lbfgs_create_grouped): a sequence whose
+    frames are coupled by a velocity term or share a vector.  Then step(closure) expects energies of shape (P,), state() arrays have P
+    entries, and everything else works as without groups.  Sums follow the 1024-partial rule, so the numbers of a one-row problem are
+    not those of the same row without groups: per-frame fits belong on a handle without groups.  The recipe for a vector shared by T
+    frames: optimise a buffer [T + 1, 75] whose rows 0 .. T - 1 are theta and whose last row carries beta in its first 10 coordinates
+    (groups=[T + 1]); the closure reads beta from buf[T, :10], and the unused coordinates have zero gradient and never move."""
+
+    def __init__(self, x, history=10, device=None, groups=None, **options):
         self._h = None
         bad = set(options) - set(DEFAULTS)
         if bad:
@@ -51,9 +59,41 @@ class BatchedLBFGS:
         self._device = parse_device(x.device if self.dev else ("cuda:0" if device is None else device))
         o = self.options
         h = C.c_void_p()
-        check(_lib.load().smplpp_lbfgs_create(self._device, self.n, self.dim, self.history, float(o["c1"]), float(o["tol_grad"]), float(o["tol_f"]),
-                                              int(o["max_ls"]), float(o["curv_eps"]), C.byref(h)))
+        scalars = (float(o["c1"]), float(o["tol_grad"]), float(o["tol_f"]), int(o["max_ls"]), float(o["curv_eps"]))
+        self.groups, self.problems = None, self.n
+        if groups is None:
+            check(_lib.load().smplpp_lbfgs_create(self._device, self.n, self.dim, self.history, *scalars, C.byref(h)))
+        else:
+            self.groups = self._groups(groups)
+            self.problems = len(self.groups)
+            start = (C.c_int64 * (self.problems + 1))(0, *np.cumsum(self.groups).tolist())
+            check(_lib.load().smplpp_lbfgs_create_grouped(self._device, self.n, self.dim, self.history, self.problems, start, *scalars, C.byref(h)))
         self._h = h
+
+    def _groups(self, groups):
+        """The row counts as a list of ints; what smplpp_lbfgs_create_grouped refuses is refused here, with or without a device."""
+        try:
+            lens = [int(r) for r in groups]
+            exact = all(r == v for r, v in zip(lens, groups))
+        except (TypeError, ValueError):
+            lens, exact = [], False
+        if not exact:
+            raise SmplppError(1, "BatchedLBFGS: groups must be a sequence of whole row counts")
+        if not lens:
+            raise SmplppError(1, "BatchedLBFGS: P must be positive")
+        if any(r <= 0 for r in lens):
+            raise SmplppError(1, "BatchedLBFGS: row_start must strictly increase (every group needs a row)")
+        if sum(lens) != self.n:
+            raise SmplppError(1, "BatchedLBFGS: row_start[P] must be n (the groups sum to %d, x has %d rows)" % (sum(lens), self.n))
+        return lens
+
+    def row_start(self):
+        """(P, row_start [P+1]) as the handle reports them (smplpp_lbfgs_groups)."""
+        P = C.c_int64()
+        check(_lib.load().smplpp_lbfgs_groups(self.handle, C.byref(P), None))
+        start = (C.c_int64 * (P.value + 1))()
+        check(_lib.load().smplpp_lbfgs_groups(self.handle, None, start))
+        return P.value, list(start)
 
     def __del__(self):
         try:
@@ -78,19 +118,19 @@ class BatchedLBFGS:
         return dict(n=n.value, dim=D.value, history=m.value)
 
     def step_with(self, f, g):
-        """One call of smplpp_lbfgs_step with energies f [n] and gradients g [n,D] (or a row-strided view) at the current x, which is
-        overwritten in place with the next points to evaluate."""
+        """One call of smplpp_lbfgs_step with energies f [n] ([P] with groups) and gradients g [n,D] (or a row-strided view) at the current
+        x, which is overwritten in place with the next points to evaluate."""
         x = self.x.detach() if self.dev else self.x
         if _is_torch(f) != self.dev or _is_torch(g) != self.dev:
             raise SmplppError(1, "BatchedLBFGS: mix of torch tensors and numpy arrays")
         if self.dev:
-            if not (f.is_cuda and g.is_cuda and f.dtype == torch.float32 and tuple(f.shape) == (self.n,)):
-                raise SmplppError(1, "BatchedLBFGS: expected float32 device energies of shape (%d,)" % self.n)
+            if not (f.is_cuda and g.is_cuda and f.dtype == torch.float32 and tuple(f.shape) == (self.problems,)):
+                raise SmplppError(1, "BatchedLBFGS: expected float32 device energies of shape (%d,)" % self.problems)
             f = f.detach().contiguous()
         else:
             f = np.ascontiguousarray(f, np.float32)
-            if f.shape != (self.n,):
-                raise SmplppError(1, "BatchedLBFGS: expected energies of shape (%d,)" % self.n)
+            if f.shape != (self.problems,):
+                raise SmplppError(1, "BatchedLBFGS: expected energies of shape (%d,)" % self.problems)
         gn, gD, ld_g = _rows("BatchedLBFGS: g", g)
         if (gn, gD) != (self.n, self.dim):
             raise SmplppError(1, "BatchedLBFGS: expected gradients of shape (%d, %d)" % (self.n, self.dim))
@@ -98,8 +138,9 @@ class BatchedLBFGS:
         check(_lib.load().smplpp_lbfgs_step(self.handle, _ptr(x), self._ld, _ptr(f), _ptr(g), ld_g, space, stream))
 
     def step(self, closure):
-        """One evaluation: closure() returns the per-frame energies [n] of the current x; their sum is back-propagated, the step is
-        taken on x.data, x.grad and the energies, and the gradient is cleared.  Returns the energies (detached)."""
+        """One evaluation: closure() returns the per-frame energies [n] (per-problem [P] with groups) of the current x; their sum is
+        back-propagated, the step is taken on x.data, x.grad and the energies, and the gradient is cleared.  Returns the energies
+        (detached)."""
         if not self.dev:
             raise SmplppError(1, "BatchedLBFGS.step needs a torch tensor; use step_with(f, g) with numpy arrays")
         root = self.x if self.x.is_leaf else self.x._base
@@ -108,8 +149,8 @@ class BatchedLBFGS:
         root.grad = None
         with torch.enable_grad():
             f = closure()
-            if tuple(f.shape) != (self.n,):
-                raise SmplppError(1, "BatchedLBFGS.step: the closure must return per-frame energies of shape (%d,)" % self.n)
+            if tuple(f.shape) != (self.problems,):
+                raise SmplppError(1, "BatchedLBFGS.step: the closure must return per-frame energies of shape (%d,)" % self.problems)
             f.sum().backward()
         if root.grad is None:
             raise SmplppError(1, "BatchedLBFGS.step: the energies do not depend on x")
@@ -136,7 +177,7 @@ class BatchedLBFGS:
             raise SmplppError(1, "BatchedLBFGS.state: want must name some of %s" % ", ".join(kinds))
         res = {}
         for k in want:
-            shape = (1,) if k == "running" else (self.n,)
+            shape = (1,) if k == "running" else (self.problems,)
             res[k] = torch.empty(shape, dtype=getattr(torch, kinds[k]), device=self.x.device) if self.dev else np.empty(shape, kinds[k])
         space, stream = self._space()
         check(_lib.load().smplpp_lbfgs_state(self.handle, *(_ptr(res.get(k)) for k in kinds), space, stream))
@@ -147,7 +188,7 @@ class BatchedLBFGS:
         x = self.x.detach() if self.dev else self.x
         f = None
         if want_f:
-            f = torch.empty(self.n, dtype=torch.float32, device=x.device) if self.dev else np.empty(self.n, np.float32)
+            f = torch.empty(self.problems, dtype=torch.float32, device=x.device) if self.dev else np.empty(self.problems, np.float32)
         space, stream = self._space()
         check(_lib.load().smplpp_lbfgs_best(self.handle, _ptr(x), self._ld, _ptr(f), space, stream))
         return f
