@@ -16,7 +16,7 @@ __global__ void face_normals_kernel(const float * __restrict__ verts, const int3
   if(i >= n * count) return;
   const int64_t f = i / count;
   float nn[3];
-  face_normal_dev(verts + f * V * 3, faces, (int)ids[i % count], nn);
+  face_normal_dev<true>(verts + f * V * 3, faces, (int)ids[i % count], nn);
   out[i * 3] = nn[0];
   out[i * 3 + 1] = nn[1];
   out[i * 3 + 2] = nn[2];
@@ -31,7 +31,7 @@ __global__ void vertex_normals_kernel(const float * __restrict__ verts, const in
   if(i >= n * count) return;
   const int64_t f = i / count;
   float nn[3];
-  vertex_normal_dev(verts + f * V * 3, faces, adjOff, adjFace, (int)ids[i % count], nn);
+  vertex_normal_dev<true>(verts + f * V * 3, faces, adjOff, adjFace, (int)ids[i % count], nn);
   out[i * 3] = nn[0];
   out[i * 3 + 1] = nn[1];
   out[i * 3 + 2] = nn[2];
@@ -58,7 +58,7 @@ __global__ void mesh_vertex_normals_kernel(const float * __restrict__ verts, con
   if(i >= n * V) return;
   const int64_t f = i / V;
   float nn[3];
-  vertex_normal_dev(verts + f * V * 3, faces, adjOff, adjFace, (int)(i % V), nn);
+  vertex_normal_dev<true>(verts + f * V * 3, faces, adjOff, adjFace, (int)(i % V), nn);
   out[i * 3] = nn[0];
   out[i * 3 + 1] = nn[1];
   out[i * 3 + 2] = nn[2];

@@ -21,20 +21,39 @@ __device__ inline void normalize3(float * x)
   x[2] /= nrm;
 }
 
-// SMPL::calcNormal (src/SMPL.cpp:518-525)
+// cross3 with every product rounded on its own (no contraction into an fma): with a == b both products of a component are the
+// same number and the component is EXACTLY 0.  Contracted, x * y - fl(y * x) is the rounding error of the product, some 1e-8 of it,
+// and normalize3 would scale that residue up to a unit vector.
+__device__ inline void cross3_rounded(const float * a, const float * b, float * c)
+{
+#pragma clang fp contract(off)
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// SMPL::calcNormal (src/SMPL.cpp:518-525).  ROUNDED (the mesh queries, mesh.hip / mesh_grad.h): a face with two corners on one
+// point has the normal (0,0,0) exactly, whichever two.  The IK evaluation keeps the contracted cross product its recorded bits
+// (tests/golden/ik_bits.json) were computed with.
+template<bool ROUNDED = false>
 __device__ inline void face_normal_pts(const float * v0, const float * v1, const float * v2, float * nn)
 {
   float a[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]};
   float b[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
-  cross3(a, b, nn);
+  if(ROUNDED)
+    cross3_rounded(a, b, nn);
+  else
+    cross3(a, b, nn);
   normalize3(nn);
 }
+template<bool ROUNDED = false>
 __device__ inline void face_normal_dev(const float * verts, const int32_t * faces, int face, float * nn)
 {
-  face_normal_pts(verts + 3 * faces[face * 3 + 0], verts + 3 * faces[face * 3 + 1], verts + 3 * faces[face * 3 + 2], nn);
+  face_normal_pts<ROUNDED>(verts + 3 * faces[face * 3 + 0], verts + 3 * faces[face * 3 + 1], verts + 3 * faces[face * 3 + 2], nn);
 }
 
 // SMPL::calcVertexNormal (src/SMPL.cpp:527-535), uniform weights 1/deg (:630-639), ascending face id
+template<bool ROUNDED = false>
 __device__ inline void vertex_normal_dev(const float * verts, const int32_t * faces, const int32_t * adjOff,
                                          const int32_t * adjFace, int vertex, float * nn)
 {
@@ -46,7 +65,7 @@ __device__ inline void vertex_normal_dev(const float * verts, const int32_t * fa
   for(int q = b; q < e; q++)
   {
     float fn[3];
-    face_normal_dev(verts, faces, adjFace[q], fn);
+    face_normal_dev<ROUNDED>(verts, faces, adjFace[q], fn);
     acc[0] += w * fn[0];
     acc[1] += w * fn[1];
     acc[2] += w * fn[2];

@@ -41,7 +41,7 @@ __device__ inline void vertex_normal_sum_dev(const float * verts, const int32_t 
   for(int q = b; q < e; q++)
   {
     float fn[3];
-    face_normal_dev(verts, faces, adjFace[q], fn);
+    face_normal_dev<true>(verts, faces, adjFace[q], fn);
     acc[0] += w * fn[0];
     acc[1] += w * fn[1];
     acc[2] += w * fn[2];

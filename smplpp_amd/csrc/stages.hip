@@ -93,20 +93,23 @@ __global__ __launch_bounds__(256) void stage_regress_kernel(const float * __rest
   if(threadIdx.x == 0) joints[(f * NJ + j) * 3 + x] = (float)((part[0] + part[1]) + (part[2] + part[3]));
 }
 
-// WorldTransformation::transform on arbitrary 3x3 "rotations" (src/WorldTransformation.cpp:421-677): one thread per frame
+// WorldTransformation::transform on arbitrary 3x3 "rotations" (src/WorldTransformation.cpp:421-677): one thread per frame.
+// The chain and the relative transform's t - A.j are carried in double and rounded once on the way out (as stage_regress_kernel
+// does): in fp32 the cancellation in t - A.j makes a frame's worst element depend on the order of the sums by several 2^-24 of
+// the largest one, which tests/test_stages_gpu.py does not admit.  Not the hot path.
 __global__ void stage_world_kernel(const int32_t * __restrict__ parent, const float * __restrict__ joints,
                                    const float * __restrict__ rot, float * __restrict__ out, int64_t n)
 {
   int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if(f >= n) return;
-  float G[NJ][12];
+  double G[NJ][12];
   const float * J = joints + f * NJ * 3;
   const float * R = rot + f * NJ * 9;
   for(int i = 0; i < NJ; i++)
   {
     int p = parent[i];
-    float t[3];
-    for(int x = 0; x < 3; x++) t[x] = (i == 0) ? J[x] : J[i * 3 + x] - J[p * 3 + x];
+    double t[3];
+    for(int x = 0; x < 3; x++) t[x] = (i == 0) ? (double)J[x] : (double)J[i * 3 + x] - (double)J[p * 3 + x];
     for(int r = 0; r < 3; r++)
     {
       if(i == 0)
@@ -127,8 +130,8 @@ __global__ void stage_world_kernel(const int32_t * __restrict__ parent, const fl
     float * o = out + (f * NJ + i) * 16;
     for(int r = 0; r < 3; r++)
     {
-      for(int c = 0; c < 3; c++) o[r * 4 + c] = G[i][r * 4 + c];
-      o[r * 4 + 3] = G[i][r * 4 + 3] - (G[i][r * 4 + 0] * J[i * 3] + G[i][r * 4 + 1] * J[i * 3 + 1] + G[i][r * 4 + 2] * J[i * 3 + 2]);
+      for(int c = 0; c < 3; c++) o[r * 4 + c] = (float)G[i][r * 4 + c];
+      o[r * 4 + 3] = (float)(G[i][r * 4 + 3] - (G[i][r * 4 + 0] * J[i * 3] + G[i][r * 4 + 1] * J[i * 3 + 1] + G[i][r * 4 + 2] * J[i * 3 + 2]));
     }
     o[12] = o[13] = o[14] = 0.0f;
     o[15] = 1.0f;

@@ -432,11 +432,13 @@ class SMPL:
 
     def getAdjacentFaces(self, idx):
         """{face id: weight} like the reference's unordered_map (src/SMPL.cpp:537-540)."""
-        faces = (C.c_int64 * 64)()
-        w = (C.c_float * 64)()
-        cnt = C.c_int64()
-        check(_lib.load().smplpp_adjacent_faces(self.handle, int(idx), 64, faces, w, C.byref(cnt)))
-        return {int(faces[i]): float(w[i]) for i in range(min(cnt.value, 64))}
+        L, cap, cnt = _lib.load(), 64, C.c_int64()
+        while True:  # a vertex of more than 64 faces: ask again with the reported count (as include/smplpp/SMPL.h does)
+            faces, w = (C.c_int64 * cap)(), (C.c_float * cap)()
+            check(L.smplpp_adjacent_faces(self.handle, int(idx), cap, faces, w, C.byref(cnt)))
+            if cnt.value <= cap:
+                return {int(faces[i]): float(w[i]) for i in range(cnt.value)}
+            cap = cnt.value
 
     def _normals(self, ids, vertex, frame=None):
         verts = self._need("verts")
