@@ -1,4 +1,4 @@
-// The host decisions of a grouped L-BFGS handle (smplpp_lbfgs_create_grouped, lbfgs_wide.hip): P problems, problem p a run
+// The host decisions of a grouped L-BFGS handle (smplpp_lbfgs_create_grouped, lbfgs.hip): P problems, problem p a run
 // of consecutive rows row_start[p] .. row_start[p+1]-1 of the caller's x and g, carried by one workgroup of LBFGS_W_T threads under the
 // 1024-partial sum rule.  What the entry point refuses, where a problem's blocks lie in the handle's buffers, the launch, where the
 // working vector of the two-loop recursion lives, and the arithmetic by which a thread walks its elements j = t, t + 1024, ... of a
@@ -55,21 +55,14 @@ constexpr int64_t lbfgs_wide_slot_offset(int64_t N, int64_t m, int y, int slot)
   return ((int64_t)y * m + slot) * N;
 }
 
-// The step kernel's launch: one workgroup per problem, and the working vector in LDS when the longest problem allows
-struct LbfgsWideLaunch
-{
-  unsigned grid;
-  int threads;
-  bool lds_vector;
-  size_t lds_bytes;
-};
-inline LbfgsWideLaunch lbfgs_wide_launch(int64_t D, int64_t P, const int64_t * row_start)
+// The grouped step kernel's launch: one workgroup per problem, and the working vector in LDS when the longest problem allows
+inline LbfgsLaunch lbfgs_wide_launch(int64_t D, int64_t P, const int64_t * row_start)
 {
   int64_t longest = 0;
   for(int64_t p = 0; p < P; p++)
     if(row_start[p + 1] - row_start[p] > longest) longest = row_start[p + 1] - row_start[p];
   const bool lds = longest * D <= LBFGS_W_LDS_N;
-  return LbfgsWideLaunch{(unsigned)P, LBFGS_W_T, lds, lds ? sizeof(float) * (size_t)(longest * D) : 0};
+  return LbfgsLaunch{(unsigned)P, LBFGS_W_T, lds, lds ? sizeof(float) * (size_t)(longest * D) : 0};
 }
 
 // The walk of thread t through a problem's elements j = t, t + LBFGS_W_T, ...: element j is coordinate k = j mod D of the problem's row

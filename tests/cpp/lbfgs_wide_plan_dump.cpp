@@ -44,7 +44,7 @@ int main(int argc, char ** argv)
         std::fprintf(out, "%s\n", why);
         continue;
       }
-      const LbfgsWideLaunch L = lbfgs_wide_launch(D, P, start.data());
+      const LbfgsLaunch L = lbfgs_wide_launch(D, P, start.data());
       const LbfgsWideSizes z = lbfgs_wide_sizes(n, D, m, P);
       std::fprintf(out, "ok %u %d %d %zu %zu %zu %zu %zu %zu %zu", L.grid, L.threads, (int)L.lds_vector, L.lds_bytes, z.ints, z.floats, z.sy, z.vec, z.hist,
                    z.rows);

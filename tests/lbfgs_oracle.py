@@ -1,6 +1,6 @@
 """The per-frame rule of smplpp_lbfgs_step (include/smplpp_hip.h) restated in numpy with the dtype as a parameter: in float32,
 operation for operation with the 64-partial sums, it is the bit reference of the library; in float64 it is the numerical reference.
-Also the test functions the L-BFGS tests share, each returning (f, g) in the dtype of its argument.
+`rule` states it once with the sum rule as a parameter; lbfgs_groups_oracle.py calls it with the 1024-partial sum.  Also the test functions the L-BFGS tests share, each returning (f, g) in the dtype of its argument.
 
 A frame's sums run over vectors of 64 partials, one numpy operation per 64 coordinates, so that D = 20670 is cheap."""
 import numpy as np
@@ -30,6 +30,86 @@ def ring_push(head, count, m):
     if count < m:
         return (head + count) % m, head, count + 1
     return head, (head + 1) % m, count
+
+
+def rule(o, a, x, f, g, total):
+    """The rule, once: one evaluation of the problem with state `a` (a _Frame) at its flat vector x (overwritten in place) with energy
+    f and gradient g, under the options of `o` (dt, m, c1, tol_grad, tol_f, curv_eps, max_ls).  total(v) is the sum rule: sum64 for the
+    frames of smplpp_lbfgs_create, sum1024 of lbfgs_groups_oracle.py for the problems of a grouped handle; nothing else differs."""
+    dt = o.dt
+    fin = bool(np.isfinite(f)) and bool(np.isfinite(g).all())
+    gmax = np.abs(g).max()
+    if a.evaluations == 0:
+        a.evaluations = 1
+        a.x0, a.f0 = x.copy(), f
+        if not fin:
+            a.status = 4
+            return a.log.append("first_nonfinite")
+        if gmax <= o.tol_grad:
+            a.status = 1
+            return a.log.append("first_converged")
+        a.g0, a.d = g.copy(), -g
+        a.t = min(dt(1), dt(1) / total(np.abs(g)))
+        a.gtd = total(g * a.d)
+        x[:] = a.x0 + a.t * a.d
+        a.ls = 0
+        return a.log.append("first")
+    a.evaluations += 1
+    if not (fin and f <= a.f0 + (o.c1 * a.t) * a.gtd):
+        a.ls += 1
+        if a.ls > o.max_ls:
+            a.status = 3
+            x[:] = a.x0
+            return a.log.append("exhausted")
+        tn, how = dt(0.5) * a.t, "half"
+        if np.isfinite(f):
+            den = dt(2) * ((f - a.f0) - a.gtd * a.t)
+            if den > 0:
+                lo, hi = dt(0.1) * a.t, dt(0.5) * a.t
+                tn, how = -((a.gtd * a.t) * a.t) / den, "interpolated"
+                if not tn >= lo:
+                    tn, how = lo, "interpolated_low"
+                if tn > hi:
+                    tn, how = hi, "interpolated_high"
+        a.t = tn
+        x[:] = a.x0 + a.t * a.d
+        return a.log.append(how)
+    s, y = x - a.x0, g - a.g0
+    sy, yy = total(s * y), total(y * y)
+    if yy > 0 and sy > o.curv_eps * yy:
+        slot, a.head, a.count = ring_push(a.head, a.count, o.m)
+        a.S[slot], a.Y[slot], a.sy[slot], a.gamma = s, y, sy, sy / yy
+    fo = a.f0
+    a.x0, a.f0, a.g0 = x.copy(), f, g.copy()
+    a.iterations += 1
+    if gmax <= o.tol_grad:
+        a.status = 1
+        return a.log.append("converged")
+    if o.tol_f > 0 and fo - f <= o.tol_f * max(max(abs(fo), abs(f)), dt(1)):
+        a.status = 2
+        return a.log.append("flat")
+    q = g.copy()
+    alpha = [None] * a.count
+    for i in range(a.count):
+        sl = ring_slot(a.head, a.count, o.m, i)
+        alpha[i] = total(a.S[sl] * q) / a.sy[sl]
+        q = q - alpha[i] * a.Y[sl]
+    r = a.gamma * q if a.count else q
+    for i in range(a.count - 1, -1, -1):
+        sl = ring_slot(a.head, a.count, o.m, i)
+        c = alpha[i] - total(a.Y[sl] * r) / a.sy[sl]
+        r = r + c * a.S[sl]
+    a.d = -r
+    a.gtd = total(g * a.d)
+    how = "accepted"
+    if not a.gtd < 0:
+        a.head = a.count = 0
+        a.d = -g
+        a.gtd = -total(g * g)
+        how = "accepted_dropped"
+    a.t, a.ls = dt(1), 0
+    x[:] = a.x0 + a.d
+    a.log.append(how)
 
 
 class _Frame:
@@ -75,89 +155,12 @@ class LBFGS:
     def log(self):
         return [a.log for a in self.frames]
 
-    # ------------------------------------------------------------------ the rule
     def step(self, x, f, g):
         assert x.dtype == self.dt and x.shape == (self.n, self.D)
         with np.errstate(all="ignore"):
             for i, a in enumerate(self.frames):
                 if a.status == 0:
-                    self._frame(a, x[i], self.dt(f[i]), np.asarray(g[i], self.dt))
-
-    def _frame(self, a, x, f, g):
-        dt = self.dt
-        fin = bool(np.isfinite(f)) and bool(np.isfinite(g).all())
-        gmax = np.abs(g).max()
-        if a.evaluations == 0:
-            a.evaluations = 1
-            a.x0, a.f0 = x.copy(), f
-            if not fin:
-                a.status = 4
-                return a.log.append("first_nonfinite")
-            if gmax <= self.tol_grad:
-                a.status = 1
-                return a.log.append("first_converged")
-            a.g0, a.d = g.copy(), -g
-            a.t = min(dt(1), dt(1) / sum64(np.abs(g)))
-            a.gtd = sum64(g * a.d)
-            x[:] = a.x0 + a.t * a.d
-            a.ls = 0
-            return a.log.append("first")
-        a.evaluations += 1
-        if not (fin and f <= a.f0 + (self.c1 * a.t) * a.gtd):
-            a.ls += 1
-            if a.ls > self.max_ls:
-                a.status = 3
-                x[:] = a.x0
-                return a.log.append("exhausted")
-            tn, how = dt(0.5) * a.t, "half"
-            if np.isfinite(f):
-                den = dt(2) * ((f - a.f0) - a.gtd * a.t)
-                if den > 0:
-                    lo, hi = dt(0.1) * a.t, dt(0.5) * a.t
-                    tn, how = -((a.gtd * a.t) * a.t) / den, "interpolated"
-                    if not tn >= lo:
-                        tn, how = lo, "interpolated_low"
-                    if tn > hi:
-                        tn, how = hi, "interpolated_high"
-            a.t = tn
-            x[:] = a.x0 + a.t * a.d
-            return a.log.append(how)
-        s, y = x - a.x0, g - a.g0
-        sy, yy = sum64(s * y), sum64(y * y)
-        if yy > 0 and sy > self.curv_eps * yy:
-            slot, a.head, a.count = ring_push(a.head, a.count, self.m)
-            a.S[slot], a.Y[slot], a.sy[slot], a.gamma = s, y, sy, sy / yy
-        fo = a.f0
-        a.x0, a.f0, a.g0 = x.copy(), f, g.copy()
-        a.iterations += 1
-        if gmax <= self.tol_grad:
-            a.status = 1
-            return a.log.append("converged")
-        if self.tol_f > 0 and fo - f <= self.tol_f * max(max(abs(fo), abs(f)), dt(1)):
-            a.status = 2
-            return a.log.append("flat")
-        q = g.copy()
-        alpha = [None] * a.count
-        for i in range(a.count):
-            sl = ring_slot(a.head, a.count, self.m, i)
-            alpha[i] = sum64(a.S[sl] * q) / a.sy[sl]
-            q = q - alpha[i] * a.Y[sl]
-        r = a.gamma * q if a.count else q
-        for i in range(a.count - 1, -1, -1):
-            sl = ring_slot(a.head, a.count, self.m, i)
-            c = alpha[i] - sum64(a.Y[sl] * r) / a.sy[sl]
-            r = r + c * a.S[sl]
-        a.d = -r
-        a.gtd = sum64(g * a.d)
-        how = "accepted"
-        if not a.gtd < 0:
-            a.head = a.count = 0
-            a.d = -g
-            a.gtd = -sum64(g * g)
-            how = "accepted_dropped"
-        a.t, a.ls = dt(1), 0
-        x[:] = a.x0 + a.d
-        a.log.append(how)
+                    rule(self, a, x[i], self.dt(f[i]), np.asarray(g[i], self.dt), sum64)
 
 
 def run(opt, funcs, x, max_evals, after=None):
