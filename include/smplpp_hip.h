@@ -59,6 +59,8 @@ struct smplpp_pose_prior;                   /* a max-mixture Gaussian pose prior
                                                `struct smplpp_pose_prior` throughout, as above: the name alone is the evaluation call */
 struct smplpp_lbfgs;                        /* a batched L-BFGS over n independent frames (no reference counterpart); written
                                                `struct smplpp_lbfgs` throughout, as the two above */
+struct smplpp_sequence;                     /* the layout of sequences inside a grouped L-BFGS buffer (no reference counterpart); written
+                                               `struct smplpp_sequence` throughout, as the three above */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -696,6 +698,78 @@ int smplpp_lbfgs_create_grouped(int device, int64_t n, int64_t D, int64_t m, int
 /* The groups of a handle: *P (nullable) and row_start [P+1] (host, nullable).  A handle from smplpp_lbfgs_create reports P = n and
  * row_start = 0 .. n. */
 int smplpp_lbfgs_groups(const struct smplpp_lbfgs * opt, int64_t * P, int64_t * row_start /*[P+1] host, nullable*/);
+/* ------------------------------------------------------------------ sequence terms: temporal smoothness, shared rows and group sums
+ * What makes the rows of a grouped problem a sequence.  A layout handle is built from the optimiser's grouping (row_start, exactly what
+ * smplpp_lbfgs_groups returns): problem p owns the rows row_start[p] .. row_start[p+1]-1, and its last shared_rows rows (0 or 1) are not
+ * frames: the recipe above, a buffer [T+1, 75] whose last row carries beta.  Frames are numbered compactly in row order: F = rows - P
+ * shared_rows, problem p owns the frames frame_start[p] .. frame_start[p+1]-1 with frame_start[p+1] - frame_start[p] = rows_p -
+ * shared_rows, and every frame-side array below is compact [F, ...].  Creation validates on the host and uploads four small tables.
+ * All five calls below are fp32 with every operation rounded on its own (no FMA), without floating-point atomics, and every output
+ * element is one fixed-order sum.  sum1024(v) is the 1024-PARTIAL RULE of the grouped L-BFGS read over the frame's index j within its
+ * problem (or over the point k of a frame): j goes to partial j mod 1024 in ascending j from +0, and the partials meet as p_i = p_i +
+ * p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64.  The bits of a problem depend on nothing but that problem: not on P, on
+ * its slot, on the other problems' lengths, on the memory space, on ld, on the work split or on which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID (*out = NULL): P <= 0, what smplpp_lbfgs_create_grouped refuses for row_start, more rows than int32 indexes,
+ *    shared_rows not 0 or 1, a problem with no frame beside its shared row. */
+int smplpp_sequence_create(int device, int64_t P, const int64_t * row_start /*[P+1], host*/, int shared_rows /*0 or 1*/,
+                           struct smplpp_sequence ** out);
+int smplpp_sequence_destroy(struct smplpp_sequence * seq);
+int smplpp_sequence_info(const struct smplpp_sequence * seq, int64_t * P, int64_t * rows, int64_t * frames, int * shared_rows,
+                         int64_t * frame_start /*[P+1] host, nullable*/);
+/* The optimiser buffer (rows ld floats apart) -> the per-frame arrays, in one launch: frames[f] = rows[row of f][off_f .. off_f + C_f),
+ * shared[f] = rows[the shared row of f's problem][0 .. C_s).  With (off_f, C_f, C_s) = (0, 75, 10) these are theta [F,25,3] and beta
+ * [F,10], the inputs of smplpp_fk.  The copies are bit-exact, whatever the other floats of a row hold.  A host-space call stages the rows
+ * up to the last float read.
+ *  - SMPLPP_ERR_INVALID: a NULL seq or rows, both outputs NULL, ld <= 0, rows ld beyond int32 indexing; with frames: off_f < 0, C_f < 1,
+ *    off_f + C_f > ld; with shared: a layout with shared_rows = 0, C_s < 1, C_s > ld; outputs beyond int32 indexing; a bad space (the
+ *    outputs are untouched).  The arguments of an output that is NULL are not read. */
+int smplpp_sequence_split(struct smplpp_sequence * seq, const float * rows, int64_t ld, int64_t off_f, int64_t C_f,
+                          float * frames /*[F,C_f] nullable*/, int64_t C_s, float * shared /*[F,C_s] nullable, needs shared_rows = 1*/, int space,
+                          void * stream);
+/* Its vector-Jacobian product.  ALL D coordinates of every row of grad_rows (rows ld floats apart, D <= ld: what smplpp_lbfgs_step
+ * reads) are written: a frame row gets grad_frames[f] in [off_f, off_f + C_f) and +0 elsewhere (+0 everywhere when grad_frames is NULL);
+ * a shared row gets, per coordinate c < C_s, sum1024 over the problem's frames j of grad_shared[frame_start[p] + j][c], and +0 elsewhere
+ * (+0 everywhere when grad_shared is NULL).  accumulate = 0 stores the element, 1 adds it to what is there.
+ *  - SMPLPP_ERR_INVALID: a NULL seq or grad_rows, both inputs NULL, D < 1, D > ld, rows ld beyond int32 indexing; with grad_frames:
+ *    off_f < 0, C_f < 1, D < off_f + C_f; with grad_shared: a layout with shared_rows = 0, C_s < 1, D < C_s; inputs beyond int32
+ *    indexing; accumulate not 0 or 1; a bad space (the output is untouched). */
+int smplpp_sequence_merge(struct smplpp_sequence * seq, const float * grad_frames /*[F,C_f] nullable*/, int64_t off_f, int64_t C_f,
+                          const float * grad_shared /*[F,C_s] nullable*/, int64_t C_s, float * grad_rows, int64_t ld, int64_t D, int accumulate,
+                          int space, void * stream);
+/* problem_values[p] = scale * sum1024 over the problem's frames j of frame_values[frame_start[p] + j]; with accumulate = 1 that product
+ * is added to what is there, so a caller folds several terms into the f [P] of smplpp_lbfgs_step one call each.
+ *  - SMPLPP_ERR_INVALID: a NULL seq, frame_values or problem_values, accumulate not 0 or 1, a bad space (the output is untouched). */
+int smplpp_sequence_sum(struct smplpp_sequence * seq, const float * frame_values /*[F]*/, float scale, float * problem_values /*[P]*/,
+                        int accumulate, int space, void * stream);
+/* The temporal term.  Frame f of x is K points of C coordinates at x + f ld, ld >= K C, 1 <= C <= 16: joints [F,24,3] are (joints, 72,
+ * 24, 3), the rotations of a theta buffer (theta + 3, 75, 24, 3) with no copy, vertices (verts, 3V, V, 3), rotation matrices (rot, 216,
+ * 24, 9).  A stencil never crosses a problem boundary.  Per frame f and point k, with x[f] short for the point's C coordinates:
+ *  order 1:  a stencil exists at f when f+1 is in f's problem;  d_c = x[f+1]_c - x[f]_c.
+ *  order 2:  a stencil exists at f when f-1 and f+1 are both in f's problem;  d_c = (x[f+1]_c - x[f]_c) - (x[f]_c - x[f-1]_c).
+ *  q = sum_c d_c d_c in ascending c from +0;  w = weight[k] (NULL reads as 1).  Without a stencil or with w == 0: e = +0, and nothing of
+ *  x reaches the result, even NaN.  Else rho == 0: e = w q;  rho > 0: p2 = rho rho, e = w ((p2 q) / (p2 + q)), the Geman-McClure form of
+ *  smplpp_project_points.
+ * point_energy [F,K] = e;  frame_energy [F] = sum1024 of e over k.  Either may be NULL, not both.  A host-space call stages (F-1) ld +
+ * K C floats of x.
+ *  - SMPLPP_ERR_INVALID: a NULL seq or x, K <= 0, C outside [1, 16], ld < K C, order not 1 or 2, rho negative or not finite, a
+ *    host-space weight that is negative or not finite, every output NULL, F ld beyond int32 indexing, a bad space (the outputs are
+ *    untouched). */
+int smplpp_sequence_smoothness(struct smplpp_sequence * seq, const float * x, int64_t ld, int64_t K, int64_t C, int order /*1 or 2*/,
+                               const float * weight /*[K] nullable*/, float rho, float * frame_energy /*[F] nullable*/,
+                               float * point_energy /*[F,K] nullable*/, int space, void * stream);
+/* Its vector-Jacobian product to x; grad_x has the rows of x (the same ld), and only the K C coordinates of a row are written: with
+ * accumulate = 1 it lands directly in a grad_theta buffer.  A gather: each output element recomputes the at most three stencils that
+ * touch it.  For the stencil at frame h and point k:  g = grad_frame_energy[h] (NULL: +0), plus grad_point_energy[h,k] when given;
+ * v_c = +0 when g is exactly 0, when w == 0 or when there is no stencil at h, even on NaN data;  else s = (2 g) w for rho == 0, and for
+ * rho > 0 t = p2 / (p2 + q), s = ((2 g) w) (t t);  v_c = s d_c.  Then, an absent stencil (or a frame outside the problem) reading as +0:
+ *  order 1:  grad_x[f,k,c] = v[f-1]_c - v[f]_c.
+ *  order 2:  grad_x[f,k,c] = (v[f-1]_c + v[f+1]_c) - (2 v[f]_c).
+ * accumulate = 0 stores the element, 1 adds it to what is there.
+ *  - SMPLPP_ERR_INVALID: as the forward (cotangents for outputs), a NULL grad_x, accumulate not 0 or 1 (the output is untouched). */
+int smplpp_sequence_smoothness_vjp(struct smplpp_sequence * seq, const float * x, int64_t ld, int64_t K, int64_t C, int order,
+                                   const float * weight /*[K] nullable*/, float rho, const float * grad_frame_energy /*[F] nullable*/,
+                                   const float * grad_point_energy /*[F,K] nullable*/, float * grad_x /*rows of ld*/, int accumulate, int space,
+                                   void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -117,6 +117,14 @@ def load():
         "smplpp_lbfgs_create_grouped": [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
                                         C.POINTER(vp)],
         "smplpp_lbfgs_groups": [vp, i64p, i64p],
+        "smplpp_sequence_create": [C.c_int, C.c_int64, i64p, C.c_int, C.POINTER(vp)],
+        "smplpp_sequence_destroy": [vp],
+        "smplpp_sequence_info": [vp, i64p, i64p, i64p, C.POINTER(C.c_int), i64p],
+        "smplpp_sequence_split": [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int, vp],
+        "smplpp_sequence_merge": [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, vp],
+        "smplpp_sequence_sum": [vp, vp, C.c_float, vp, C.c_int, C.c_int, vp],
+        "smplpp_sequence_smoothness": [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, C.c_float, vp, vp, C.c_int, vp],
+        "smplpp_sequence_smoothness_vjp": [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, C.c_float, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],

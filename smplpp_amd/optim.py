@@ -42,7 +42,9 @@ class BatchedLBFGS:
     entries, and everything else works as without groups.  Sums follow the 1024-partial rule, so the numbers of a one-row problem are
     not those of the same row without groups: per-frame fits belong on a handle without groups.  The recipe for a vector shared by T
     frames: optimise a buffer [T + 1, 75] whose rows 0 .. T - 1 are theta and whose last row carries beta in its first 10 coordinates
-    (groups=[T + 1]); the closure reads beta from buf[T, :10], and the unused coordinates have zero gradient and never move."""
+    (groups=[T + 1]); the closure reads beta from buf[T, :10], and the unused coordinates have zero gradient and never move.
+    sequence.SequenceLayout.from_optimizer(opt, shared_rows=1) gives that closure its glue natively: the split of the buffer into per-frame
+    theta and beta, the smoothness term between consecutive frames and the per-problem sums, each with its backward."""
 
     def __init__(self, x, history=10, device=None, groups=None, **options):
         self._h = None
