@@ -61,6 +61,8 @@ struct smplpp_lbfgs;                        /* a batched L-BFGS over n independe
                                                `struct smplpp_lbfgs` throughout, as the two above */
 struct smplpp_sequence;                     /* the layout of sequences inside a grouped L-BFGS buffer (no reference counterpart); written
                                                `struct smplpp_sequence` throughout, as the three above */
+struct smplpp_volume;                       /* a signed-distance grid of a static scene, resident on the device (no reference
+                                               counterpart); written `struct smplpp_volume` throughout, as the four above */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -770,6 +772,71 @@ int smplpp_sequence_smoothness_vjp(struct smplpp_sequence * seq, const float * x
                                    const float * weight /*[K] nullable*/, float rho, const float * grad_frame_energy /*[F] nullable*/,
                                    const float * grad_point_energy /*[F,K] nullable*/, float * grad_x /*rows of ld*/, int accumulate, int space,
                                    void * stream);
+/* ------------------------------------------------------------------ the scene term: trilinear SDF volumes, penetration and contact
+ * Where the body is relative to what is not the body.  A volume handle holds a signed-distance grid of a static scene on the device:
+ * node (i, j, k), i < Gx, j < Gy, k < Gz, holds values[(k Gy + j) Gx + i] and sits at origin + (i hx, j hy, k hz) in VOLUME coordinates;
+ * world_to_volume [12] is a row-major [R|t] (R[0..8], t[0..2] below; NULL: the identity, and then no arithmetic is done on a point).
+ * `space` says where `values` lives (NULL: zeros); host-space values are not inspected, so a NaN node is legal.  The grid is stored in
+ * one of two layouts, `linear` (the array as given) or `cells` (one 32-byte record of its eight nodes per cell; 8 x the memory, and only
+ * while the records fit 1 GiB: above that the handle is linear); SMPLPP_VOLUME_LAYOUT=linear|cells, read at creation, forces one, and
+ * NO OUTPUT BIT DEPENDS ON THE LAYOUT.  smplpp_volume_info reports it as 0 (linear) or 1 (cells); every output of info is nullable.
+ *  - SMPLPP_ERR_INVALID (*out = NULL): a NULL out, a G outside [2, 1024], Gx Gy Gz > 2^27, a NULL origin or spacing, a spacing that is not
+ *    finite and positive, a non-finite origin or transform entry, a bad space, an unknown value of SMPLPP_VOLUME_LAYOUT. */
+int smplpp_volume_create(int device, int64_t Gx, int64_t Gy, int64_t Gz, const float origin[3], const float spacing[3],
+                         const float * world_to_volume /*[12] row-major [R|t], nullable = identity*/,
+                         const float * values /*[Gz,Gy,Gx], nullable: zeros*/, int space, struct smplpp_volume ** out);
+/* New node values into the handle's layout.  In device space it is one kernel on `stream`, with no allocation and no synchronisation:
+ * a grid can be refreshed inside an optimisation loop (from the signed distances of another body, say).
+ *  - SMPLPP_ERR_INVALID: a NULL vol or values, a bad space (the grid is untouched). */
+int smplpp_volume_set(struct smplpp_volume * vol, const float * values /*[Gz,Gy,Gx]*/, int space, void * stream);
+int smplpp_volume_info(const struct smplpp_volume * vol, int64_t G[3], float origin[3], float spacing[3], float world_to_volume[12],
+                       int * layout);
+int smplpp_volume_destroy(struct smplpp_volume * vol);
+/* THE SAMPLING RULE, for the world point p = (x, y, z).  All arithmetic is fp32, every operation rounded on its own (no FMA).
+ *  transform:   p'_a = ((R[3a] x + R[3a+1] y) + R[3a+2] z) + t[a];  without a transform p' = p.
+ *  coordinate:  g_a = (p'_a - origin_a) / h_a, a true division.
+ *  inside:      every g_a is finite and 0 <= g_a <= G_a - 1.
+ *  cell:        i_a = min((int)floor(g_a), G_a - 2),  f_a = g_a - (float)i_a: the far face belongs to the last cell with f = 1.
+ *  value:       with v_xyz the node (i_x + x, i_y + y, i_z + z):  d_yz = v_1yz - v_0yz,  c_yz = v_0yz + f_x d_yz;
+ *               e_z = c_1z - c_0z,  c_z = c_0z + f_y e_z;  s = c_0 + f_z (c_1 - c_0).
+ *  gradient in volume coordinates:  x_z = d_0z + f_y (d_1z - d_0z),  g_x = (x_0 + f_z (x_1 - x_0)) / h_x;
+ *               g_y = (e_0 + f_z (e_1 - e_0)) / h_y;  g_z = (c_1 - c_0) / h_z.  It is the derivative of the interpolant at a fixed cell.
+ *  gradient in world coordinates:  (R[a] g_x + R[3+a] g_y) + R[6+a] g_z (the pull of smplpp_project_points_vjp, right for any affine
+ *               transform); without a transform it is (g_x, g_y, g_z) as it stands.
+ *  valid:       1 when the point is inside and s is finite.  A point that is not valid gives value +0, gradient +0, energy +0 and
+ *               contributes to no gradient: the convention of refused points in smplpp_project_points.  A NaN node therefore takes out
+ *               the points of the (at most eight) cells that touch it and no others.
+ * points [n,K,3]; value [n,K], gradient [n,K,3] (d value / d world point) and valid [n,K] may each be NULL, not all.  A thread per point.
+ *  - SMPLPP_ERR_INVALID: a NULL vol or points, n or K <= 0, n K 3 beyond int32 indexing, every output NULL, a bad space (the outputs are
+ *    untouched). */
+int smplpp_volume_sample(struct smplpp_volume * vol, int64_t n, int64_t K, const float * points /*[n,K,3]*/, float * value /*[n,K] nullable*/,
+                         float * gradient /*[n,K,3] nullable*/, uint8_t * valid /*[n,K] nullable*/, int space, void * stream);
+/* THE TERM.  wp = w_pen[k] (NULL reads as 1), wc = w_con[k] (NULL reads as 0).  Per valid point, with s its sample and q = s s:
+ *  penetration:  e_pen = wp q when s < 0, else +0;
+ *  contact:      e_con = wc q for rho == 0, else p2 = rho rho, e_con = wc ((p2 q) / (p2 + q)), the Geman-McClure form of
+ *                smplpp_project_points;
+ *  point_energy = e_pen + e_con.  A point with wp == 0 and wc == 0 reads no grid value and its energy is +0, whatever the grid holds
+ *  there; its value and valid outputs, when asked for, are still computed.
+ * energy [n] = sum1024 of point_energy over k, the 1024-PARTIAL RULE of the grouped L-BFGS above: k goes to partial k mod 1024 in
+ * ascending k from +0, and the partials meet as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64.  The work
+ * split follows K (a wavefront per frame up to 64, a workgroup of 256 up to 1024, of 1024 above; a thread per point without energy) and
+ * changes no bit; nor do n, the frame's slot, the memory space, the layout or which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID: as smplpp_volume_sample, rho negative or not finite (the outputs are untouched). */
+int smplpp_scene_term(struct smplpp_volume * vol, int64_t n, int64_t K, const float * points /*[n,K,3]*/, const float * w_pen /*[K] nullable = 1*/,
+                      const float * w_con /*[K] nullable = 0*/, float rho, float * energy /*[n] nullable*/, float * point_energy /*[n,K] nullable*/,
+                      float * value /*[n,K] nullable*/, uint8_t * valid /*[n,K] nullable*/, int space, void * stream);
+/* Its vector-Jacobian product to the points, a thread per point with the sample recomputed by the forward's operations; no sums.  A NULL
+ * cotangent reads as +0.  Per valid point:
+ *  g = grad_energy[f] + grad_point_energy[f,k];
+ *  dE/ds = pen + con,  pen = (2 wp) s when s < 0, else +0;  con = (2 wc) s for rho == 0, else d = p2 / (p2 + q), con = ((2 wc) (d d)) s;
+ *  t = g dE/ds, or +0 when wp == 0 and wc == 0;  kk = grad_value[f,k] + t;  grad_points[f,k,a] = kk (the world gradient)_a.
+ * A point that is not valid, or one with wp == 0 and wc == 0 under a NULL grad_value (it reads no grid value), gets +0.  accumulate = 0
+ * stores the element, 1 adds it to what is there.
+ *  - SMPLPP_ERR_INVALID: as the forward (cotangents for outputs), a NULL grad_points, accumulate not 0 or 1 (the output is untouched). */
+int smplpp_scene_term_vjp(struct smplpp_volume * vol, int64_t n, int64_t K, const float * points, const float * w_pen, const float * w_con,
+                          float rho, const float * grad_energy /*[n] nullable*/, const float * grad_point_energy /*[n,K] nullable*/,
+                          const float * grad_value /*[n,K] nullable*/, float * grad_points /*[n,K,3]*/, int accumulate, int space,
+                          void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -125,6 +125,13 @@ def load():
         "smplpp_sequence_sum": [vp, vp, C.c_float, vp, C.c_int, C.c_int, vp],
         "smplpp_sequence_smoothness": [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, C.c_float, vp, vp, C.c_int, vp],
         "smplpp_sequence_smoothness_vjp": [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, C.c_float, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_volume_create": [C.c_int, C.c_int64, C.c_int64, C.c_int64, f32p, f32p, f32p, vp, C.c_int, C.POINTER(vp)],
+        "smplpp_volume_set": [vp, vp, C.c_int, vp],
+        "smplpp_volume_info": [vp, i64p, f32p, f32p, f32p, C.POINTER(C.c_int)],
+        "smplpp_volume_destroy": [vp],
+        "smplpp_volume_sample": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_scene_term": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_scene_term_vjp": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],
