@@ -511,6 +511,14 @@ int smplpp_silhouette_vjp(smplpp_model * m, int64_t n, const float * verts /*[n,
                           const int64_t * pix_source /*[n,H,W] nullable*/, const float * grad_vert_sq /*[n,V] nullable*/,
                           const float * grad_pix_sq /*[n,H,W] nullable*/, float * grad_verts /*[n,V,3]*/, int accumulate, int space,
                           void * stream);
+/* ------------------------------------------------------------------ FIXED-ORDER SUMS
+ * The energies and shared gradients of the sections below are each ONE fixed-order sum in fp32, every addition rounded on its own, by
+ * one of two rules over an index k < N that the call names:
+ *    sum64:    element k goes to partial k mod 64, the partials summed in ascending k starting from +0; then the 64 partials p_i meet
+ *              as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, and the sum is p_0.
+ *    sum1024:  the same with 1024 partials, the meeting continued by s = 512, 256, 128, 64.
+ * A partial that no element reaches is +0 and one that elements reach is never -0, so how a call splits the work over its threads
+ * changes no bit.  For N <= 64 the two rules coincide; from 65 on they do not. */
 /* ------------------------------------------------------------------ keypoints: landmark regression, projection, 2-D energy
  * A landmark regressor is a CSR matrix of L rows over V + 24 source columns: column c < V is vertex c, column V + j is joint j of
  * smplpp_fk's `joints`.  One regressor so expresses the 24 joints, vertex picks (nose, ears, toes) and sparse rows over the vertices
@@ -563,8 +571,8 @@ int smplpp_project_points(int device, int64_t n, int64_t K, const float * points
  *    grad_points, world component a = (R[a] jx + R[3+a] jy) + R[6+a] jz; a refused point gets +0.
  *  - grad_camera [n,16] in the layout of camera, R as NINE INDEPENDENT ENTRIES (the convention of smplpp_fk_rotmat_vjp): R[3a+b] sums
  *    j_a * x_b with x the world point, t[a] sums j_a, fx sums k.x * (xc.x / xc.z), fy sums k.y * (xc.y / xc.z), cx sums k.x, cy sums
- *    k.y, over the live points of the frame.  Each of the 16 is one fixed-order sum: point k goes to partial k mod 64, summed in
- *    ascending k starting from +0; the 64 partials p_i meet as p_i = p_i + p_(i xor m) for m = 32, 16, 8, 4, 2, 1.
+ *    k.y, over the live points of the frame.  Each of the 16 is sum64 (FIXED-ORDER SUMS above) over the frame's points k; a point
+ *    that is not live is left out of its partial.
  *  - accumulate = 0 stores, 1 adds the finished value to the output, for both outputs.  grad_uv or grad_energy (needs target) may be
  *    NULL, not both; grad_points or grad_camera may be NULL, not both.  No floating-point atomics; the bits do not depend on n, on the
  *    frame's position in the batch, on the memory space or on which outputs are asked for.
@@ -593,14 +601,13 @@ int smplpp_pose_prior_info(const struct smplpp_pose_prior * prior, int64_t * M, 
  * theta [n,25,3] buffer is (theta + 6, ld = 75, D = 69) with no copy.  A host-space call stages (n-1) ld + D floats.  In fp32 with every
  * operation rounded on its own (no FMA), per frame:
  *  mixture, per component m:  d_k = pose_k - mean[m][k];  y_j = sum_k mat[m][j][k] d_k, where partial p = k mod 8 runs s_p = s_p +
- *    mat[m][j][k] d_k in ascending k from +0 and y_j = ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7));  q_m = sum_j y_j y_j by the
- *    camera-sum rule of smplpp_project_points_vjp (j goes to partial j mod 64 in ascending j from +0; the 64 partials meet as p_i = p_i +
- *    p_(i xor s) for s = 32, 16, 8, 4, 2, 1);  e_m = q_m + offset[m].
+ *    mat[m][j][k] d_k in ascending k from +0 and y_j = ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7));  q_m = sum_j y_j y_j by
+ *    sum64 (FIXED-ORDER SUMS above) over j;  e_m = q_m + offset[m].
  *    The component starts at 0 and, for m = 1 .. M-1 in order, is replaced when e_m < e_best: a tie goes to the lowest m, a NaN e_m
  *    never replaces and a NaN e_0 is never replaced.  energy [n] = e of the chosen component, component [n] = its index, residual
  *    [n,D] = its y (energy = |residual|^2 + offset[component]).
  *  limits:  per coordinate a = pose_k - hi_k, b = lo_k - pose_k, v = a if a > 0, else b if b > 0, else +0 (so a NaN pose_k gives 0, and
- *    a coordinate exactly at a limit contributes nothing);  limit_energy [n] = sum_k limit_weight_k (v v) by the same 64-partial rule.
+ *    a coordinate exactly at a limit contributes nothing);  limit_energy [n] = sum_k limit_weight_k (v v) by sum64 over k.
  * Each output may be NULL, not all four.  The bits of a frame do not depend on n, on its position in the batch, on the memory space, on
  * the work split or on which outputs are asked for.
  *  - SMPLPP_ERR_INVALID: n <= 0, ld < D, a NULL pose, every output NULL, energy, component or residual on a prior with M = 0,
@@ -640,9 +647,8 @@ int smplpp_lbfgs_destroy(struct smplpp_lbfgs * opt);
 int smplpp_lbfgs_info(const struct smplpp_lbfgs * opt, int64_t * n, int64_t * D, int64_t * m);
 /* Every frame back to "not evaluated yet" (status 0, counters 0, an empty history), enqueued on `stream`. */
 int smplpp_lbfgs_reset(struct smplpp_lbfgs * opt, void * stream);
-/* One evaluation of every running frame.  In fp32 with every operation rounded on its own (no FMA).  sum(v) below is ONE fixed-order
- * sum by the camera-sum rule of smplpp_project_points_vjp: element k goes to partial k mod 64 in ascending k from +0, and the 64
- * partials meet as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1.  `finite` means: f and every g_k are neither NaN nor +-inf.
+/* One evaluation of every running frame.  In fp32 with every operation rounded on its own (no FMA).  sum(v) below is sum64 (FIXED-ORDER
+ * SUMS above) over the frame's coordinates k.  `finite` means: f and every g_k are neither NaN nor +-inf.
  * gmax = max_k |g_k|.  A frame keeps x0, f0, g0 (its last accepted point), d, t, gtd, ls, a ring of at most m pairs (s_i, y_i, sy_i)
  * and gamma.  Per frame whose status is 0:
  *  first evaluation:  evaluations = 1; x0 = x, f0 = f.  Not finite: status 4.  Else gmax <= tol_grad: status 1.  Else g0 = g, d_k = -g_k,
@@ -685,9 +691,8 @@ int smplpp_lbfgs_best(struct smplpp_lbfgs * opt, float * x, int64_t ld_x, float 
  * smplpp_lbfgs_step, _state, _best, _reset, _info and _destroy take such a handle unchanged: f and every array of _state (and f of _best)
  * have P entries, `running` counts problems, _info still reports n, D and m.
  * The rule of a grouped handle is the per-frame rule of smplpp_lbfgs_step word for word, applied to the problem's N elements (read
- * "problem" for "frame" and j < N for k), with one change: sum(v) is the 1024-PARTIAL RULE.  Element j goes to partial j mod 1024 in
- * ascending j, starting from +0, and the 1024 partials meet as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64.
- * `finite` and gmax run over all N elements.  fp32 throughout, every operation rounded on its own, no FMA contraction, no atomics.  A
+ * "problem" for "frame" and j < N for k), with one change: sum(v) is sum1024 (FIXED-ORDER SUMS above) over the
+ * problem's elements j.  `finite` and gmax run over all N elements.  fp32 throughout, every operation rounded on its own, no FMA contraction, no atomics.  A
  * grouped handle always uses this rule, also for a problem of one row, whose bits therefore differ from those of the same row on a handle
  * from smplpp_lbfgs_create: per-frame fits belong on the ungrouped handle (one wavefront a frame; a problem here costs a workgroup of 1024).
  * The bits of a problem depend on nothing but the problem: not on P, on its slot, on the lengths of the other problems, on the memory
@@ -707,9 +712,8 @@ int smplpp_lbfgs_groups(const struct smplpp_lbfgs * opt, int64_t * P, int64_t * 
  * shared_rows, problem p owns the frames frame_start[p] .. frame_start[p+1]-1 with frame_start[p+1] - frame_start[p] = rows_p -
  * shared_rows, and every frame-side array below is compact [F, ...].  Creation validates on the host and uploads four small tables.
  * All five calls below are fp32 with every operation rounded on its own (no FMA), without floating-point atomics, and every output
- * element is one fixed-order sum.  sum1024(v) is the 1024-PARTIAL RULE of the grouped L-BFGS read over the frame's index j within its
- * problem (or over the point k of a frame): j goes to partial j mod 1024 in ascending j from +0, and the partials meet as p_i = p_i +
- * p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64.  The bits of a problem depend on nothing but that problem: not on P, on
+ * element is one fixed-order sum.  sum1024(v) is that rule (FIXED-ORDER SUMS above) over the frame's index j within its problem, or over
+ * the point k of a frame.  The bits of a problem depend on nothing but that problem: not on P, on
  * its slot, on the other problems' lengths, on the memory space, on ld, on the work split or on which outputs are asked for.
  *  - SMPLPP_ERR_INVALID (*out = NULL): P <= 0, what smplpp_lbfgs_create_grouped refuses for row_start, more rows than int32 indexes,
  *    shared_rows not 0 or 1, a problem with no frame beside its shared row. */
@@ -817,8 +821,7 @@ int smplpp_volume_sample(struct smplpp_volume * vol, int64_t n, int64_t K, const
  *                smplpp_project_points;
  *  point_energy = e_pen + e_con.  A point with wp == 0 and wc == 0 reads no grid value and its energy is +0, whatever the grid holds
  *  there; its value and valid outputs, when asked for, are still computed.
- * energy [n] = sum1024 of point_energy over k, the 1024-PARTIAL RULE of the grouped L-BFGS above: k goes to partial k mod 1024 in
- * ascending k from +0, and the partials meet as p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64.  The work
+ * energy [n] = sum1024 (FIXED-ORDER SUMS above) of point_energy over the frame's points k.  The work
  * split follows K (a wavefront per frame up to 64, a workgroup of 256 up to 1024, of 1024 above; a thread per point without energy) and
  * changes no bit; nor do n, the frame's slot, the memory space, the layout or which outputs are asked for.
  *  - SMPLPP_ERR_INVALID: as smplpp_volume_sample, rho negative or not finite (the outputs are untouched). */

@@ -10,8 +10,9 @@
 //  pp_forward_kernel   per (frame, point): dr_project, then the energy.
 //  pp_vjp_points_kernel per (frame, point), when no gradient to the camera is asked for.
 //  pp_vjp_frame_kernel one wavefront per frame: lane p takes the points p, p + 64, ... in ascending order, stores their gradients and
-//                      keeps the 16 partial sums of the camera row, which meet in the xor tree 32, 16, 8, 4, 2, 1.
+//                      keeps the 16 partial sums of the camera row, which meet by sum64 (fixed_sum.h).
 #include "depth_raster_device.h"
+#include "fixed_sum.h"
 #include "landmark_tables.h"
 
 #pragma clang fp contract(off)
@@ -209,9 +210,7 @@ __global__ __launch_bounds__(PP_W) void pp_vjp_frame_kernel(const float * __rest
     s[14] = s[14] + o.kx;
     s[15] = s[15] + o.ky;
   }
-  for(int m = PP_W / 2; m >= 1; m >>= 1)
-#pragma unroll
-    for(int e = 0; e < 16; e++) s[e] = s[e] + __shfl_xor(s[e], m);
+  sum64_meet(s); // fixed_sum.h
   float mine = 0.0f; // lane e < 16 stores entry e
 #pragma unroll
   for(int e = 0; e < 16; e++)

@@ -6,14 +6,15 @@
 // write the rule out for their team of threads, and hist has its own layout for each: one body and one layout for both were built,
 // measured slower for frames and not kept ("One state, one file").
 //
-//  lbfgs_step_kernel       one wavefront per frame, LBFGS_FT frames a workgroup, no barrier: sums by the 64-partial rule.  The working
+//  lbfgs_step_kernel       one wavefront per frame, LBFGS_FT frames a workgroup, no barrier: sums by sum64 (fixed_sum.h).  The working
 //                          vector of the two-loop recursion lives in LDS when D <= LBFGS_LDS_D, else in the frame's direction row.
-//  lbfgs_wide_step_kernel  one workgroup of 1024 threads per problem: sums by the 1024-partial rule.  The working vector lives in LDS when
+//  lbfgs_wide_step_kernel  one workgroup of 1024 threads per problem: sums by sum1024 (fixed_sum.h).  The working vector lives in LDS when
 //                          the handle's longest problem has N <= LBFGS_W_LDS_N, else in the problem's direction block.
 //  lbfgs_best_kernel, lbfgs_wide_best_kernel  the accepted points into the caller's rows: a flat grid over n D, or a workgroup per problem.
 //  lbfgs_running_kernel    one workgroup counts the problems with status 0.
 #include <vector>
 
+#include "fixed_sum.h"
 #include "lbfgs_wide_plan.h"
 #include "staging.h"
 
@@ -50,18 +51,6 @@ struct LbfgsState
   int64_t n, P;
   int D, m;
 };
-
-// the 64 partials of a wavefront meet: p_i = p_i + p_(i xor s), s = 32, 16, 8, 4, 2, 1 (every lane ends with p_0's bits)
-__device__ inline float lb_tree(float p)
-{
-  for(int s = 32; s >= 1; s >>= 1) p = p + __shfl_xor(p, s);
-  return p;
-}
-__device__ inline float lb_tree_max(float p)
-{
-  for(int s = 32; s >= 1; s >>= 1) p = fmaxf(p, __shfl_xor(p, s));
-  return p;
-}
 
 // grid: ceil(n / LBFGS_FT); dynamic LDS: LBFGS_FT * D floats when LDS_VECTOR.  A frame whose status is not 0 returns before it reads
 // or writes anything of the caller's.  Lane l owns the coordinates k = l, l + 64, ... of every vector of its frame: partial l of each
@@ -102,7 +91,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
     pa = pa + a;
   }
   fin = __all(fin);
-  gmax = lb_tree_max(gmax);
+  gmax = max64_meet(gmax);
 
   if(evals == 0) // the first evaluation of the frame
   {
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
       if(lane == 0) I[LBFGS_STATUS * n] = fin ? 1 : 4;
       return;
     }
-    const float t = fminf(1.0f, 1.0f / lb_tree(pa));
+    const float t = fminf(1.0f, 1.0f / sum64_meet(pa));
     float p = 0.0f;
 #pragma unroll 4
     for(int k = lane; k < D; k += 64)
@@ -124,7 +113,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
       p = p + gk * dk;
       xr[k] = x0[k] + t * dk;
     }
-    const float gtd = lb_tree(p);
+    const float gtd = sum64_meet(p);
     if(lane == 0) F[LBFGS_STEP * n] = t, F[LBFGS_GTD * n] = gtd, I[LBFGS_LS * n] = 0;
     return;
   }
@@ -171,7 +160,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
     psy = psy + sk * yk;
     pyy = pyy + yk * yk;
   }
-  const float sy_new = lb_tree(psy), yy = lb_tree(pyy);
+  const float sy_new = sum64_meet(psy), yy = sum64_meet(pyy);
   const bool push = yy > 0.0f && sy_new > s.o.curv_eps * yy;
   float gamma = F[LBFGS_GAMMA * n];
   int slot = 0;
@@ -216,7 +205,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
         v[k] = qk;
         p = p + si[k] * qk;
       }
-      c = lb_tree(p) / sy[sl];
+      c = sum64_meet(p) / sy[sl];
       if(lane == i) akeep = c;
       u = Y + sl * D;
     }
@@ -241,7 +230,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
         if(u) rk = rk + c * u[k], v[k] = rk;
         p = p + yi[k] * rk;
       }
-      c = __shfl(akeep, i) - lb_tree(p) / sy[sl];
+      c = __shfl(akeep, i) - sum64_meet(p) / sy[sl];
       u = S + sl * D;
     }
     float p = 0.0f;
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
       dir[k] = dk;
       p = p + gr[k] * dk;
     }
-    gtd = lb_tree(p);
+    gtd = sum64_meet(p);
     if(!(gtd < 0.0f)) // not a descent direction: the history is dropped
     {
       lbfgs_ring_drop(head, count);
@@ -266,55 +255,13 @@ __global__ __launch_bounds__(LBFGS_T) void lbfgs_step_kernel(LbfgsState s, float
         dir[k] = -gk;
         p = p + gk * gk;
       }
-      gtd = -lb_tree(p);
+      gtd = -sum64_meet(p);
     }
 #pragma unroll 4
     for(int k = lane; k < D; k += 64) xr[k] = x0[k] + dir[k];
     if(lane == 0) F[LBFGS_STEP * n] = 1.0f, F[LBFGS_GTD * n] = gtd, I[LBFGS_LS * n] = 0;
   }
   if(lane == 0) I[LBFGS_HEAD * n] = head, I[LBFGS_COUNT * n] = count;
-}
-
-// K partials per thread meet at once: p_i = p_i op p_(i xor s) for s = 32, 16, 8, 4, 2, 1 inside the wavefront, then 512, 256, 128, 64
-// across the wavefronts (op: + , or max where MAXES has the value's bit).  cross[2][3][16]: two banks taken in turn, so that one barrier
-// per meeting is enough: a wavefront writes a bank again only after passing the barrier of the meeting in between, which every other
-// wavefront reaches after it has read that bank.  Every thread of the workgroup calls it, and ends with the same bits.
-template<int K, unsigned MAXES>
-__device__ inline void lbw_meet(float (&v)[K], float (*cross)[3][LBFGS_W_WAVES], int & turn)
-{
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for(int i = 0; i < K; i++)
-#pragma unroll
-    for(int s = 32; s >= 1; s >>= 1)
-    {
-      const float o = __shfl_xor(v[i], s);
-      v[i] = (MAXES >> i & 1u) ? fmaxf(v[i], o) : v[i] + o;
-    }
-  if(lane == 0)
-  {
-#pragma unroll
-    for(int i = 0; i < K; i++) cross[turn][i][w] = v[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for(int i = 0; i < K; i++)
-  {
-    v[i] = cross[turn][i][lane & (LBFGS_W_WAVES - 1)]; // lane u of every 16 holds wavefront u's value: xor 8, 4, 2, 1 there is xor 512 .. 64 of the partials
-#pragma unroll
-    for(int s = LBFGS_W_WAVES / 2; s >= 1; s >>= 1)
-    {
-      const float o = __shfl_xor(v[i], s);
-      v[i] = (MAXES >> i & 1u) ? fmaxf(v[i], o) : v[i] + o;
-    }
-  }
-  turn ^= 1;
-}
-__device__ inline float lbw_sum(float p, float (*cross)[3][LBFGS_W_WAVES], int & turn)
-{
-  float v[1] = {p};
-  lbw_meet<1, 0u>(v, cross, turn);
-  return v[0];
 }
 
 // grid: P; dynamic LDS: the longest problem's N floats when LDS_VECTOR.  Thread t owns the elements j = t, t + 1024, ... of every vector
@@ -328,7 +275,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
                                                                     const float * __restrict__ g, int64_t ld_g)
 {
   extern __shared__ __attribute__((aligned(16))) float lbw_smem[];
-  __shared__ float cross[2][3][LBFGS_W_WAVES];
+  __shared__ float cross[2][3][SUM1024_WAVES];
   const int t = threadIdx.x, lane = t & 63, P = s.P, p = blockIdx.x, D = s.D, m = s.m;
   int * I = s.ints + p;     // scalar j of the problem: I[j P]
   float * F = s.floats + p; // likewise
@@ -366,7 +313,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
       lbfgs_wide_advance(cg, sg, D);
     }
   }
-  lbw_meet<3, 3u>(a3, cross, turn);
+  sum1024_meet_many<3, 3u>(a3, cross, turn);
   const float gmax = a3[0];
   const bool fin = a3[1] == 0.0f;
 
@@ -401,7 +348,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
         lbfgs_wide_advance(cg, sg, D);
       }
     }
-    gtd = lbw_sum(pp, cross, turn);
+    gtd = sum1024_meet_one(pp, cross, turn);
     if(t == 0) I[LBFGS_EVAL * P] = 1, F[LBFGS_F0 * P] = fv, F[LBFGS_STEP * P] = tt, F[LBFGS_GTD * P] = gtd, I[LBFGS_LS * P] = 0;
     return;
   }
@@ -458,7 +405,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
       lbfgs_wide_advance(cg, sg, D);
     }
   }
-  lbw_meet<2, 0u>(a2, cross, turn);
+  sum1024_meet_many<2, 0u>(a2, cross, turn);
   const float sy_new = a2[0], yy = a2[1];
   const bool push = yy > 0.0f && sy_new > s.o.curv_eps * yy;
   int slot = -1;
@@ -512,7 +459,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
         v[j] = qk;
         pp = pp + si[j] * qk;
       }
-      c = lbw_sum(pp, cross, turn) / (sl == slot ? sy_new : sy[sl]);
+      c = sum1024_meet_one(pp, cross, turn) / (sl == slot ? sy_new : sy[sl]);
       if(lane == i) akeep = c;
       u = Y + lbfgs_wide_slot_offset(N, m, 0, sl);
     }
@@ -535,7 +482,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
         if(u) rk = rk + c * u[j], v[j] = rk;
         pp = pp + yi[j] * rk;
       }
-      c = __shfl(akeep, i) - lbw_sum(pp, cross, turn) / (sl == slot ? sy_new : sy[sl]);
+      c = __shfl(akeep, i) - sum1024_meet_one(pp, cross, turn) / (sl == slot ? sy_new : sy[sl]);
       u = S + lbfgs_wide_slot_offset(N, m, 0, sl);
     }
     float pp = 0.0f;
@@ -548,7 +495,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
       dir[j] = dk;
       pp = pp + g0[j] * dk;
     }
-    gtd = lbw_sum(pp, cross, turn);
+    gtd = sum1024_meet_one(pp, cross, turn);
     if(!(gtd < 0.0f)) // not a descent direction: the history is dropped
     {
       lbfgs_ring_drop(head, count);
@@ -560,7 +507,7 @@ __global__ __launch_bounds__(LBFGS_W_T) void lbfgs_wide_step_kernel(LbfgsState s
         dir[j] = -gk;
         pp = pp + gk * gk;
       }
-      gtd = -lbw_sum(pp, cross, turn);
+      gtd = -sum1024_meet_one(pp, cross, turn);
     }
     LbfgsWideCursor cx = cx0;
 #pragma unroll 4

@@ -12,7 +12,6 @@
 namespace smplpp_hip
 {
 constexpr int LBFGS_W_T = 1024;              // threads of a problem's workgroup: one partial of the sum rule each
-constexpr int LBFGS_W_WAVES = LBFGS_W_T / 64; // their wavefronts: 16 sums cross through LDS
 constexpr int64_t LBFGS_W_LDS_N = 32768;     // up to this N (the longest problem of the handle) the working vector stays in LDS (128 of the
                                              // compute unit's 160 KiB; above 64 KiB the launch opts in)
 

@@ -7,12 +7,13 @@
 //                        the PR_FT frames at once from the transposed image, so that one load of a matrix element serves the whole
 //                        tile.  The outputs 64 .. D-1 take a second round: a lane each when they are many, else eight lanes each, one
 //                        per partial (pr_matvec_split), which shortens the round from D dependent steps to D / 8.  y goes to LDS
-//                        (when the residual is asked for), y.y through the 64-partial xor tree, e_m to LDS; after a barrier one
+//                        (when the residual is asked for), y.y by sum64 (fixed_sum.h), e_m to LDS; after a barrier one
 //                        thread per frame selects, and the workgroup copies the chosen y out.  Then wave f sums the limit term of
 //                        frame f.
 //  prior_vjp_kernel      the same tile.  Without a given component the workgroup first selects as the forward does.  Then wave f takes
 //                        frame f: y of the chosen component by the same matrix-vector walk, v = (2 g) y + grad_residual in LDS, and
 //                        t = mat^T v by that walk on the untransposed image (lane k owns coordinate k).
+#include "fixed_sum.h"
 #include "pose_prior_tables.h"
 #include "staging.h"
 
@@ -150,13 +151,6 @@ __device__ inline void pr_wave_matvec(const float * __restrict__ img, const floa
     pr_matvec<FT>(img, vec, D, lane + 64, out[1]);
 }
 
-// the 64 partials of a wavefront meet: p_i = p_i + p_(i xor s), s = 32, 16, 8, 4, 2, 1 (every lane ends with p_0's bits)
-__device__ inline float pr_tree(float p)
-{
-  for(int s = 32; s >= 1; s >>= 1) p = p + __shfl_xor(p, s);
-  return p;
-}
-
 // By the whole workgroup (it holds barriers): e_m of the frames [frame0, frame0 + nf) into esh [PR_FT][M], and their y into
 // ysh [M][PR_FT][D] when ysh is given.  dsh: [PR_WAVES][PR_FT][D].  Rows of the tile past nf read zeros.
 __device__ inline void pr_mixture(const PriorTables & t, const float * __restrict__ pose, int64_t ld, int64_t frame0, int nf, float * dsh,
@@ -193,7 +187,7 @@ __device__ inline void pr_mixture(const PriorTables & t, const float * __restric
 #pragma unroll
       for(int f = 0; f < PR_FT; f++)
       {
-        const float q = pr_tree(qp[f]);
+        const float q = sum64_meet(qp[f]);
         if(lane == 0) esh[f * M + m] = q + t.offset[m];
       }
     }
@@ -255,7 +249,7 @@ __global__ __launch_bounds__(PR_T) void prior_forward_kernel(PriorTables t, cons
       const float v = a > 0.0f ? a : (b > 0.0f ? b : 0.0f);
       p = p + t.weight[k] * (v * v);
     }
-    p = pr_tree(p);
+    p = sum64_meet(p);
     if(lane == 0) limit_energy[frame] = p;
   }
 }

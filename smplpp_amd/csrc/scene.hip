@@ -2,24 +2,20 @@
 // penetration and contact energies on the sample, and their vector-Jacobian product to the points.  A volume handle keeps the grid on the
 // device in one of two storage layouts (volume_plan.h); smplpp_volume_set refreshes it with one kernel.  The rules are in
 // include/smplpp_hip.h; every fp32 operation below is rounded on its own (no contraction to FMA), the frame energy is one fixed-order
-// sum, and there are no floating-point atomics.  No output bit depends on the layout: both hand the same eight floats to vol_sample.
-//
-// The frame sum is the 1024-partial rule of the grouped L-BFGS (lbfgs.hip: lbw_meet; sequence.hip: seq_meet; restated here as
-// scene_meet, because those bodies live in their own translation units).  A partial that no point reaches is +0, and a partial that
-// points reach is never -0 (it starts from +0), so leaving out the additions of untouched partials changes no bit: that is what lets the
-// work split follow K.
+// sum (sum1024 of fixed_sum.h, whose two facts about +0 let the work split follow K), and there are no floating-point atomics.  No
+// output bit depends on the layout: both hand the same eight floats to vol_sample.
 //
 //  vol_set_kernel<L>          a thread per stored unit: a node (linear: a copy) or a cell record (cells: eight reads, two 16-byte writes).
 //  scene_sample_kernel<L>     a thread per point: value, gradient, valid.
 //  scene_points_kernel<L>     the term without the frame energy: a thread per point.
 //  scene_small_kernel<L>      K <= 64: a wavefront per frame, lane k owns point k (partial k; the partials past 63 are +0).
-//  scene_wide_kernel<L, NQ>   K > 64: a workgroup per frame: 256 threads up to K = 1024 (thread t owns the partials t + 256 q, q < 4), 1024
-//                             threads above (a partial each).
+//  scene_wide_kernel<L, NQ>   K > 64: a workgroup per frame, of 256 or 1024 threads by frame_sum_split: thread t owns the partials t + T q.
 //  scene_vjp_kernel<L>        a thread per point: it samples again by the forward's device function, so the bits match; no sums.
 // A point's three coordinates are three dword reads per lane (rows of 3 floats are not 16-byte aligned; a wavefront's three reads cover
 // the same 768 contiguous bytes).  The gather of the grid is the cost: 64 lanes in up to 64 different rows of it.
 #include <cstdlib>
 
+#include "fixed_sum.h"
 #include "staging.h"
 #include "volume_plan.h"
 
@@ -130,34 +126,6 @@ __device__ inline VolSample vol_sample(const VolView & v, float px, float py, fl
   return r;
 }
 
-// The 1024 partials meet: p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64 (lbfgs.hip: lbw_meet; sequence.hip:
-// seq_meet).  A workgroup of 1024 / NQ threads holds them, thread t the partials t + (1024 / NQ) q in v[q]: the first six meetings are
-// shuffles, the next log2(NQ) stay inside the thread, the rest cross the wavefronts through `cross` [1024 / NQ / 64] (one barrier; every
-// thread of the workgroup calls).  Only the positions that partial 0 descends from are kept; the result is p_0's bits, in every thread.
-template<int NQ>
-__device__ inline float scene_meet(float (&v)[NQ], float * cross)
-{
-  constexpr int WAVES = 1024 / NQ / 64;
-#pragma unroll
-  for(int q = 0; q < NQ; q++)
-#pragma unroll
-    for(int s = 32; s >= 1; s >>= 1) v[q] = v[q] + __shfl_xor(v[q], s);
-#pragma unroll
-  for(int h = NQ / 2; h >= 1; h >>= 1)
-#pragma unroll
-    for(int q = 0; q < h; q++) v[q] = v[q] + v[q + h];
-  if((threadIdx.x & 63) == 0) cross[threadIdx.x >> 6] = v[0];
-  __syncthreads();
-  float r[WAVES];
-#pragma unroll
-  for(int u = 0; u < WAVES; u++) r[u] = cross[u];
-#pragma unroll
-  for(int h = WAVES / 2; h >= 1; h >>= 1)
-#pragma unroll
-    for(int u = 0; u < h; u++) r[u] = r[u] + r[u + h];
-  return r[0];
-}
-
 // the term's arguments
 struct TermArgs
 {
@@ -256,8 +224,7 @@ __global__ __launch_bounds__(SCN_T) void scene_small_kernel(VolView v, TermArgs 
   if(f >= n) return;
   float e = 0.0f;
   if(k < a.K) e = scene_point<L>(v, a, f * a.K + k, k);
-  float s = 0.0f + e;
-  for(int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m);
+  const float s = sum64_meet(0.0f + e); // fixed_sum.h: partial k, the partials past 63 left out
   if(k == 0) energy[f] = s;
 }
 
@@ -278,7 +245,7 @@ __global__ __launch_bounds__(1024 / NQ) void scene_wide_kernel(VolView v, TermAr
       const int k = k0 + T * q + t;
       if(k < a.K) s[q] = s[q] + scene_point<L>(v, a, f * a.K + k, k);
     }
-  const float sum = scene_meet<NQ>(s, cross);
+  const float sum = sum1024_meet<NQ>(s, cross);
   if(t == 0) energy[f] = sum;
 }
 
@@ -483,13 +450,14 @@ extern "C" int smplpp_scene_term(struct smplpp_volume * q, int64_t n, int64_t K,
   a.value = fr.out(value, (size_t)total);
   a.valid = fr.out(valid, (size_t)total);
   return fr.run([&] {
+    const FrameSumSplit sp = frame_sum_split(K); // fixed_sum.h
     if(!e) SCN_LAUNCH(q, SCN_POINTS, dim3(scn_blocks(total, SCN_T)), dim3(SCN_T), fr.st, vol_view(q), a, (int)total);
-    else if(K <= 64)
+    else if(sp.nq == 0)
       SCN_LAUNCH(q, SCN_SMALL, dim3(scn_blocks(n, SCN_WAVES)), dim3(SCN_T), fr.st, vol_view(q), a, (int)n, e);
-    else if(K <= 1024)
-      SCN_LAUNCH(q, SCN_WIDE4, dim3((unsigned)n), dim3(256), fr.st, vol_view(q), a, e);
+    else if(sp.nq == 4)
+      SCN_LAUNCH(q, SCN_WIDE4, dim3((unsigned)n), dim3(sp.threads), fr.st, vol_view(q), a, e);
     else
-      SCN_LAUNCH(q, SCN_WIDE1, dim3((unsigned)n), dim3(1024), fr.st, vol_view(q), a, e);
+      SCN_LAUNCH(q, SCN_WIDE1, dim3((unsigned)n), dim3(sp.threads), fr.st, vol_view(q), a, e);
     return (int)SMPLPP_OK;
   });
 }

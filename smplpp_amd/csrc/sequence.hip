@@ -2,22 +2,19 @@
 // to compact frames; split / merge move between the optimiser buffer and the per-frame arrays (merge sums a shared row's gradient over the
 // problem's frames), sum folds frame values into problem values, and smoothness is the first- or second-difference term between
 // consecutive frames of a problem with its vector-Jacobian product.  The rules are in include/smplpp_hip.h; every fp32 operation below is
-// rounded on its own (no contraction to FMA), every output element is one fixed-order sum, and there are no floating-point atomics.
-//
-// Every sum is the 1024-partial rule of the grouped L-BFGS (lbfgs.hip: lbw_meet; restated here as seq_meet, because that body lives in
-// lbfgs.hip's translation unit).  A partial that no element reaches is +0, and a partial that elements reach is never -0 (it starts from
-// +0), so leaving out the additions of untouched partials changes no bit: that is what lets the work split follow the size.
+// rounded on its own (no contraction to FMA), every output element is one fixed-order sum (sum1024 of fixed_sum.h, whose two facts about
+// +0 let the work split follow the size), and there are no floating-point atomics.
 //
 //  seq_split_kernel         a thread per (frame, coordinate) of the two outputs together: one launch makes theta [F,C_f] and beta [F,C_s].
 //  seq_merge_kernel         a thread per (row, coordinate < D): a frame row's slice of grad_frames or +0, a shared row's +0 past C_s.
 //  seq_merge_shared_kernel  a wavefront per (problem, coordinate < C_s): lane l owns the partials l + 64 q, q < 16.
 //  seq_sum_kernel           a wavefront per problem, the same ownership.
 //  seq_smooth_small_kernel  K <= 64: a wavefront per frame, lane k owns point k (partial k; the partials past 63 are +0).
-//  seq_smooth_wide_kernel   K > 64: a workgroup per frame: 256 threads up to K = 1024 (thread t owns the partials t + 256 q, q < 4), 1024
-//                           threads above (a partial each, 16 wavefronts a compute unit where 256 frames would otherwise leave 4).
+//  seq_smooth_wide_kernel   K > 64: a workgroup per frame, of 256 or 1024 threads by frame_sum_split: thread t owns the partials t + T q.
 //  seq_smooth_vjp_kernel    a thread per (frame, point): it recomputes the at most three stencils that touch it (a gather).
 #include <algorithm>
 
+#include "fixed_sum.h"
 #include "sequence_tables.h"
 #include "staging.h"
 
@@ -45,55 +42,6 @@ struct SeqView
   const int *row_start, *frame_start, *problem_of, *row_of, *frame_of;
   int P, F, rows;
 };
-
-// The 1024 partials meet: p_i = p_i + p_(i xor s) for s = 32, 16, 8, 4, 2, 1, then 512, 256, 128, 64 (lbfgs.hip: lbw_meet).  A
-// workgroup of 1024 / NQ threads holds them, thread t the partials t + (1024 / NQ) q in v[q]: the first six meetings are shuffles, the
-// next log2(NQ) stay inside the thread, the rest cross the wavefronts through `cross` [1024 / NQ / 64] (one barrier; every thread of
-// the workgroup calls).  Only the positions that partial 0 descends from are kept; the result is p_0's bits, in every thread.
-template<int NQ>
-__device__ inline float seq_meet(float (&v)[NQ], float * cross)
-{
-  constexpr int WAVES = 1024 / NQ / 64;
-#pragma unroll
-  for(int q = 0; q < NQ; q++)
-#pragma unroll
-    for(int s = 32; s >= 1; s >>= 1) v[q] = v[q] + __shfl_xor(v[q], s);
-#pragma unroll
-  for(int h = NQ / 2; h >= 1; h >>= 1)
-#pragma unroll
-    for(int q = 0; q < h; q++) v[q] = v[q] + v[q + h];
-  if constexpr(WAVES == 1) return v[0];
-  else
-  {
-    if((threadIdx.x & 63) == 0) cross[threadIdx.x >> 6] = v[0];
-    __syncthreads();
-    float r[WAVES];
-#pragma unroll
-    for(int u = 0; u < WAVES; u++) r[u] = cross[u];
-#pragma unroll
-    for(int h = WAVES / 2; h >= 1; h >>= 1)
-#pragma unroll
-      for(int u = 0; u < h; u++) r[u] = r[u] + r[u + h];
-    return r[0];
-  }
-}
-
-// sum_j load(j), j < n, by the 1024-partial rule, in one wavefront: lane l owns the partials l + 64 q
-template<class Load>
-__device__ inline float seq_wave_sum(int n, int lane, Load load)
-{
-  float v[16];
-#pragma unroll
-  for(int q = 0; q < 16; q++) v[q] = 0.0f;
-  for(int j0 = 0; j0 < n; j0 += 1024)
-#pragma unroll
-    for(int q = 0; q < 16; q++)
-    {
-      const int j = j0 + 64 * q + lane;
-      if(j < n) v[q] = v[q] + load(j);
-    }
-  return seq_meet<16>(v, nullptr);
-}
 
 // grid: ceil(F W / SEQ_T), W = the widths of the outputs given
 __global__ __launch_bounds__(SEQ_T) void seq_split_kernel(SeqView s, const float * __restrict__ rows, int64_t ld, int off_f, int C_f,
@@ -134,7 +82,7 @@ __global__ __launch_bounds__(SEQ_T) void seq_merge_shared_kernel(SeqView s, cons
   if(w >= s.P * C_s) return;
   const int p = w / C_s, c = w % C_s, f0 = s.frame_start[p], T = s.frame_start[p + 1] - f0;
   const float * col = gs + (int64_t)f0 * C_s + c;
-  const float v = seq_wave_sum(T, lane, [&](int j) { return col[(int64_t)j * C_s]; });
+  const float v = sum1024_wave(T, lane, [&](int j) { return col[(int64_t)j * C_s]; });
   if(lane == 0)
   {
     float * o = gr + (s.row_start[p + 1] - 1) * ld + c;
@@ -149,7 +97,7 @@ __global__ __launch_bounds__(SEQ_T) void seq_sum_kernel(SeqView s, const float *
   if(p >= s.P) return;
   const int f0 = s.frame_start[p], T = s.frame_start[p + 1] - f0;
   const float * col = fv + f0;
-  const float v = scale * seq_wave_sum(T, lane, [&](int j) { return col[j]; });
+  const float v = scale * sum1024_wave(T, lane, [&](int j) { return col[j]; });
   if(lane == 0) pv[p] = accumulate ? pv[p] + v : v;
 }
 
@@ -210,8 +158,7 @@ __global__ __launch_bounds__(SEQ_T) void seq_smooth_small_kernel(SeqView s, Smoo
     if(point_energy) point_energy[(int64_t)f * a.K + k] = e;
   }
   if(!frame_energy) return;
-  float v = 0.0f + e;
-  for(int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
+  const float v = sum64_meet(0.0f + e); // fixed_sum.h: partial k, the partials past 63 left out
   if(k == 0) frame_energy[f] = v;
 }
 
@@ -240,7 +187,7 @@ __global__ __launch_bounds__(1024 / NQ) void seq_smooth_wide_kernel(SeqView s, S
       }
     }
   if(!frame_energy) return;
-  const float sum = seq_meet<NQ>(v, cross);
+  const float sum = sum1024_meet<NQ>(v, cross);
   if(t == 0) frame_energy[f] = sum;
 }
 
@@ -462,11 +409,12 @@ extern "C" int smplpp_sequence_smoothness(struct smplpp_sequence * q, const floa
   float * fe = fr.out(frame_energy, (size_t)F);
   float * pe = fr.out(point_energy, (size_t)(F * K));
   return fr.run([&] {
-    if(K <= 64) seq_smooth_small_kernel<<<dim3(seq_blocks(F, SEQ_WAVES)), dim3(SEQ_T), 0, fr.st>>>(seq_view(q), a, fe, pe);
-    else if(K <= 1024)
-      seq_smooth_wide_kernel<4><<<dim3((unsigned)F), dim3(256), 0, fr.st>>>(seq_view(q), a, fe, pe);
+    const FrameSumSplit sp = frame_sum_split(K); // fixed_sum.h
+    if(sp.nq == 0) seq_smooth_small_kernel<<<dim3(seq_blocks(F, SEQ_WAVES)), dim3(SEQ_T), 0, fr.st>>>(seq_view(q), a, fe, pe);
+    else if(sp.nq == 4)
+      seq_smooth_wide_kernel<4><<<dim3((unsigned)F), dim3(sp.threads), 0, fr.st>>>(seq_view(q), a, fe, pe);
     else
-      seq_smooth_wide_kernel<1><<<dim3((unsigned)F), dim3(1024), 0, fr.st>>>(seq_view(q), a, fe, pe);
+      seq_smooth_wide_kernel<1><<<dim3((unsigned)F), dim3(sp.threads), 0, fr.st>>>(seq_view(q), a, fe, pe);
     HIP_TRY(hipGetLastError());
     return (int)SMPLPP_OK;
   });

@@ -5,6 +5,8 @@ whose float32 autograd measures what a plain fp32 evaluation gets wrong.  Also t
 import numpy as np
 import torch
 
+from sum_rules import TREE64, meet
+
 f32 = np.float32
 SUB = f32(256.0)        # snapped units per pixel (the rasteriser's vertex rule)
 GUARD = f32(2.0 ** 23)  # its guard band in snapped units
@@ -134,7 +136,7 @@ def project(points, camera, near=0.05, target=None, rho=0.0):
 
 def project_vjp(points, camera, near=0.05, target=None, rho=0.0, grad_uv=None, grad_energy=None, base_points=None, base_camera=None):
     """(grad_points [n,K,3], grad_camera [n,16]): the cotangent k on (u, v), the pull through the projection, and per frame the 16
-    camera sums over 64 partials (point k to partial k mod 64, ascending k) met by the xor tree 32, 16, 8, 4, 2, 1."""
+    camera sums over 64 partials (point k to partial k mod 64, ascending k) met by the xor tree of sum_rules.sum64."""
     X, cam = np.asarray(points, f32), np.asarray(camera, f32)
     n, K = X.shape[:2]
     xc, u, v, ok = _project(X, cam, near)
@@ -167,10 +169,7 @@ def project_vjp(points, camera, near=0.05, target=None, rho=0.0, grad_uv=None, g
             m = min(64, K - k0)
             live = ok[:, k0:k0 + m, None]
             part[:, :m] = np.where(live, part[:, :m] + contrib[:, k0:k0 + m], part[:, :m])
-        lanes = np.arange(64)
-        for m in (32, 16, 8, 4, 2, 1):
-            part = part + part[:, lanes ^ m]
-        gc = part[:, 0]
+        gc = meet(part, TREE64, axis=1)
         if base_camera is not None:
             gc = np.asarray(base_camera, f32) + gc
     return np.ascontiguousarray(gp), np.ascontiguousarray(gc)

@@ -1,5 +1,5 @@
 """The rule of a grouped L-BFGS handle (smplpp_lbfgs_create_grouped, include/smplpp_hip.h) restated in numpy with the dtype as a parameter:
-the per-frame rule of smplpp_lbfgs_step on the N = rows * D elements of a problem, with every sum by the 1024-partial rule.  In float32,
+the per-frame rule of smplpp_lbfgs_step on the N = rows * D elements of a problem, with every sum by the 1024-partial rule (sum_rules.sum1024).  In float32,
 operation for operation, it is the bit reference of the library; in float64 the numerical one.  The rule itself (lbfgs_oracle.rule, called
 here with sum1024), the ring arithmetic, the options and the test functions are those of lbfgs_oracle.py; Chain couples the rows of a problem.
 
@@ -8,20 +8,7 @@ import numpy as np
 
 import lbfgs_oracle as LO
 from lbfgs_oracle import OPTIONS, ring_push, ring_slot
-
-_PARTS = np.arange(1024)
-_TREE = (32, 16, 8, 4, 2, 1, 512, 256, 128, 64)
-
-
-def sum1024(v):
-    """sum_j v[j]: j to partial j mod 1024 in ascending j from +0; the partials meet by the xor tree 32, 16, 8, 4, 2, 1, 512, 256, 128, 64."""
-    part = np.zeros(1024, v.dtype)
-    for j0 in range(0, len(v), 1024):
-        w = min(1024, len(v) - j0)
-        part[:w] = part[:w] + v[j0:j0 + w]
-    for s in _TREE:
-        part = part + part[_PARTS ^ s]
-    return part[0]
+from sum_rules import sum1024
 
 
 class GroupedLBFGS(LO.LBFGS):

@@ -1,23 +1,13 @@
 """The per-frame rule of smplpp_lbfgs_step (include/smplpp_hip.h) restated in numpy with the dtype as a parameter: in float32,
-operation for operation with the 64-partial sums, it is the bit reference of the library; in float64 it is the numerical reference.
-`rule` states it once with the sum rule as a parameter; lbfgs_groups_oracle.py calls it with the 1024-partial sum.  Also the test functions the L-BFGS tests share, each returning (f, g) in the dtype of its argument.
+operation for operation with the 64-partial sums (sum_rules.sum64), it is the bit reference of the library; in float64 it is the numerical reference.
+`rule` states it once with the sum rule as a parameter; lbfgs_groups_oracle.py calls it with sum_rules.sum1024.  Also the test functions the L-BFGS tests share, each returning (f, g) in the dtype of its argument.
 
 A frame's sums run over vectors of 64 partials, one numpy operation per 64 coordinates, so that D = 20670 is cheap."""
 import numpy as np
 
+from sum_rules import sum64
+
 OPTIONS = dict(c1=1e-4, tol_grad=1e-5, tol_f=0.0, max_ls=20, curv_eps=1e-10)
-_LANES = np.arange(64)
-
-
-def sum64(v):
-    """sum_k v[k]: k to partial k mod 64 in ascending k from +0; the partials meet by the xor tree 32, 16, 8, 4, 2, 1."""
-    part = np.zeros(64, v.dtype)
-    for k0 in range(0, len(v), 64):
-        w = min(64, len(v) - k0)
-        part[:w] = part[:w] + v[k0:k0 + w]
-    for s in (32, 16, 8, 4, 2, 1):
-        part = part + part[_LANES ^ s]
-    return part[0]
 
 
 def ring_slot(head, count, m, i):
@@ -35,7 +25,7 @@ def ring_push(head, count, m):
 def rule(o, a, x, f, g, total):
     """The rule, once: one evaluation of the problem with state `a` (a _Frame) at its flat vector x (overwritten in place) with energy
     f and gradient g, under the options of `o` (dt, m, c1, tol_grad, tol_f, curv_eps, max_ls).  total(v) is the sum rule: sum64 for the
-    frames of smplpp_lbfgs_create, sum1024 of lbfgs_groups_oracle.py for the problems of a grouped handle; nothing else differs."""
+    frames of smplpp_lbfgs_create, sum1024 for the problems of a grouped handle; nothing else differs."""
     dt = o.dt
     fin = bool(np.isfinite(f)) and bool(np.isfinite(g).all())
     gmax = np.abs(g).max()

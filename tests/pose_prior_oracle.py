@@ -7,6 +7,8 @@ A prior is a dict: mean [M,D], mat [M,D,D] (row j = output j), offset [M], and l
 import numpy as np
 import torch
 
+from sum_rules import sum64
+
 f32 = np.float32
 
 
@@ -68,23 +70,11 @@ def _matvec8(A, x):
     return ((s[0] + s[4]) + (s[2] + s[6])) + ((s[1] + s[5]) + (s[3] + s[7]))
 
 
-def _sum64(x):
-    """[f] = sum_j x[f, j]: j to partial j mod 64 in ascending j from +0; the partials meet by the xor tree 32, 16, 8, 4, 2, 1."""
-    part = np.zeros((x.shape[0], 64), f32)
-    for j0 in range(0, x.shape[1], 64):
-        m = min(64, x.shape[1] - j0)
-        part[:, :m] = part[:, :m] + x[:, j0:j0 + m]
-    lanes = np.arange(64)
-    for s in (32, 16, 8, 4, 2, 1):
-        part = part + part[:, lanes ^ s]
-    return part[:, 0]
-
-
 def _mixture(p, X):
     """(e [n,M], y [M,n,D]) of every component."""
     M = len(p["offset"])
     y = np.stack([_matvec8(p["mat"][m], X - p["mean"][m][None, :]) for m in range(M)])
-    e = np.stack([_sum64(y[m] * y[m]) + p["offset"][m] for m in range(M)], 1)
+    e = np.stack([sum64(y[m] * y[m]) + p["offset"][m] for m in range(M)], 1)
     return e, y
 
 
@@ -114,7 +104,7 @@ def forward(p, pose):
             out.update(energy=eb.astype(f32), component=best, residual=np.ascontiguousarray(y[best, np.arange(len(X))]))
         if p["lo"] is not None:
             v, _ = _limit(p, X)
-            out["limit_energy"] = _sum64(p["weight"][None, :] * (v * v))
+            out["limit_energy"] = sum64(p["weight"][None, :] * (v * v))
     return out
 
 

@@ -1,6 +1,6 @@
 """The rules of the scene term (smplpp_volume_sample, smplpp_scene_term, smplpp_scene_term_vjp; include/smplpp_hip.h) restated in numpy,
 operation by operation, with the dtype as a parameter: in float32 it is the bit reference of the library, in float64 the reference of the
-CPU tests.  The frame sum is lbfgs_groups_oracle.sum1024.  sample_t / energy_t are the DEFINITION in torch (any dtype), for autograd.
+CPU tests.  The frame sum is sum_rules.sum1024.  sample_t / energy_t are the DEFINITION in torch (any dtype), for autograd.
 plane / sphere / random_field fill grids with analytic fields."""
 import os
 import sys
@@ -8,7 +8,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from lbfgs_groups_oracle import sum1024  # noqa: E402
+from sum_rules import sum1024  # noqa: E402
 
 f32 = np.float32
 
@@ -111,7 +111,7 @@ def term(V, P, w_pen=None, w_con=None, rho=0.0):
             e_con = wc[None] * ((p2 * q) / (p2 + q))
         live = ((wp != 0) | (wc != 0))[None] & (valid != 0)
         pe = np.where(live, e_pen + e_con, dt(0)).astype(dt)
-        energy = np.array([sum1024(np.ascontiguousarray(r)) for r in pe], dt)
+        energy = sum1024(pe, axis=1)
     return energy, pe, value, valid
 
 

@@ -3,21 +3,9 @@ tables, split, merge, sum and the temporal smoothness term with its vector-Jacob
 library.  energy_t is the DEFINITION of the term in torch (any dtype), for autograd in float64."""
 import numpy as np
 
+from sum_rules import sum1024
+
 f32 = np.float32
-_PARTS = np.arange(1024)
-_TREE = (32, 16, 8, 4, 2, 1, 512, 256, 128, 64)
-
-
-def sum1024(v):
-    """sum_j v[j]: j to partial j mod 1024 in ascending j from +0; the partials meet by the xor tree 32, 16, 8, 4, 2, 1, 512, 256, 128, 64
-    (the rule of lbfgs_groups_oracle.sum1024, restated)."""
-    part = np.zeros(1024, v.dtype)
-    for j0 in range(0, len(v), 1024):
-        w = min(1024, len(v) - j0)
-        part[:w] = part[:w] + v[j0:j0 + w]
-    for s in _TREE:
-        part = part + part[_PARTS ^ s]
-    return part[0]
 
 
 def tables(P, row_start, shared_rows):
@@ -77,8 +65,7 @@ def merge(L, grad_frames, off_f, C_f, grad_shared, C_s, out, D, accumulate):
     if grad_shared is not None:
         for p in range(L["P"]):
             f0, f1 = L["frame_start"][p], L["frame_start"][p + 1]
-            for c in range(C_s):
-                val[L["row_start"][p + 1] - 1, c] = sum1024(np.ascontiguousarray(grad_shared[f0:f1, c], f32))
+            val[L["row_start"][p + 1] - 1, :C_s] = sum1024(np.asarray(grad_shared[f0:f1, :C_s], f32), axis=0)
     with np.errstate(all="ignore"):
         out[:, :D] = out[:, :D] + val if accumulate else val
     return out
@@ -87,7 +74,7 @@ def merge(L, grad_frames, off_f, C_f, grad_shared, C_s, out, D, accumulate):
 def seq_sum(L, frame_values, scale, out, accumulate):
     with np.errstate(all="ignore"):
         for p in range(L["P"]):
-            v = f32(scale) * sum1024(np.ascontiguousarray(frame_values[L["frame_start"][p]:L["frame_start"][p + 1]], f32))
+            v = f32(scale) * sum1024(np.asarray(frame_values[L["frame_start"][p]:L["frame_start"][p + 1]], f32))
             out[p] = out[p] + v if accumulate else v
     return out
 
@@ -125,7 +112,7 @@ def smoothness(L, x, K, C, order, weight, rho):
             p2 = dt(rho) * dt(rho)
             e = w[None] * ((p2 * q) / (p2 + q))
         e = np.where(st[:, None] & (w != 0)[None], e, dt(0)).astype(dt)
-        return np.array([sum1024(np.ascontiguousarray(r)) for r in e], dt), e
+        return sum1024(e, axis=1), e
 
 
 def smoothness_vjp(L, x, K, C, order, weight, rho, grad_frame_energy, grad_point_energy, out, accumulate):

@@ -191,21 +191,6 @@ def test_plans_walks_and_refusals_equal_python(dump_exe, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. the restatement
-def test_sum1024_is_the_stated_tree():
-    """The vectorised sum against the rule written out element by element, and against float64 within the rounding of 1024 + 10 adds."""
-    rng = np.random.default_rng(3)
-    for N in (1, 63, 1023, 1024, 1025, 2500):
-        v = rng.normal(size=N).astype(np.float32)
-        part = [np.float32(0)] * 1024
-        for j in range(N):
-            part[j % 1024] = part[j % 1024] + v[j]
-        for s in (32, 16, 8, 4, 2, 1, 512, 256, 128, 64):
-            part = [part[i] + part[i ^ s] for i in range(1024)]
-        assert all(_same_bits(np.array([p]), np.array([part[0]])) for p in part)  # every partial ends with the same bits
-        assert _same_bits(np.array([GO.sum1024(v)]), np.array([part[0]]))
-        assert abs(float(part[0]) - v.astype(np.float64).sum()) <= 16 * 2.0 ** -24 * np.abs(v).sum()
-
-
 def _solve(func, T, D, dtype, m=10, budget=500, **options):
     opt = GO.GroupedLBFGS([T], D, m, dtype, **options)
     x = np.zeros((T, D), dtype)

@@ -1,5 +1,5 @@
 """The sequence terms without a GPU: the numpy restatement of smplpp_sequence_smoothness and its backward (tests/sequence_oracle.py)
-against float64 autograd of the definition; its 1024-partial sum against the grouped L-BFGS's; the split / merge / sum restatements against
+against float64 autograd of the definition (its 1024-partial sum is sum_rules.sum1024, pinned in test_sum_rules_cpu.py); the split / merge / sum restatements against
 autograd; and the host table builder (smplpp_amd/csrc/sequence_tables.h) as a stand-alone program, tests/cpp/sequence_tables_dump.cpp, built
 with the address and undefined-behaviour sanitizers: its tables equal the Python builder's, and each refusal returns its reason without a
 sanitizer report."""
@@ -12,7 +12,6 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import lbfgs_groups_oracle as GO  # noqa: E402
 import sequence_oracle as SO  # noqa: E402
 from distance_cases import _rel, _same_bits  # noqa: E402
 
@@ -98,15 +97,7 @@ def test_nan_stays_in_its_stencils():
         assert (g0 == 0).all()
 
 
-# ---------------------------------------------------------------------------------------------------- 2. the 1024-partial rule
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 3000])
-def test_sum1024_is_the_grouped_lbfgs_rule(n):
-    v = np.random.default_rng(n).normal(size=n).astype(np.float32)
-    assert _same_bits(np.array([SO.sum1024(v)]), np.array([GO.sum1024(v)]))
-    assert _same_bits(np.array([SO.sum1024(v.astype(np.float64))]), np.array([GO.sum1024(v.astype(np.float64))]))
-
-
-# ---------------------------------------------------------------------------------------------------- 3. split, merge and sum
+# ---------------------------------------------------------------------------------------------------- 2. split, merge and sum
 def test_split_merge_sum_against_autograd():
     groups = [3, 2, 6]
     L = SO.layout(groups, 1)
@@ -131,7 +122,7 @@ def test_split_merge_sum_against_autograd():
     assert np.allclose(pv, want, rtol=8 * U, atol=8 * U)
 
 
-# ---------------------------------------------------------------------------------------------------- 4. the host table builder
+# ---------------------------------------------------------------------------------------------------- 3. the host table builder
 GOOD = {"one": ([0, 1], 0), "two": ([0, 2], 0), "three_shared": ([0, 3], 1), "ragged": ([0, 1, 3, 8, 11], 0), "ragged_shared": ([0, 2, 5, 11, 15], 1),
         "long_shared": ([0, 1031], 1)}
 # name -> (P, row_start or None, shared_rows, the reason)

@@ -1,7 +1,8 @@
 """Timing of the scene term (smplpp_volume_sample, smplpp_scene_term, smplpp_scene_term_vjp) on one MI355X, in both storage layouts.
 
 The points are the K = 6890 vertices of n posed synthetic bodies; the grid is a sphere field of 128^3 or 256^3 nodes whose spacing makes
-a body span about 80 voxels per axis.  Every call goes through the bare C entry point with device pointers, in `--reps` blocks of
+a body span about 80 voxels per axis.  Two more rows take the first K = 512 vertices on the 128^3 grid: the 256-thread form of the frame sum
+(64 < K <= 1024), which whole meshes do not reach.  Every call goes through the bare C entry point with device pointers, in `--reps` blocks of
 `--steps` back-to-back calls between HIP events after `--warmup` blocks.  Reported per (grid, n) and call, for each layout:
   - us: the median block, microseconds per call, with the least and the greatest block;
   - floor_us and over_floor: the bytes the call must move (a point's 12 bytes and its cell's 32, outputs written once) at 8 TB/s;
@@ -29,6 +30,7 @@ from smplpp_amd import _lib, model_io  # noqa: E402
 from smplpp_amd.smpl import SMPL, _stream  # noqa: E402
 
 GRIDS, BATCHES, SPAN, RHO = (128, 256), (1, 16, 256, 1024), 80, 0.05
+PART_K, PART_GRID, PART_BATCHES = 512, 128, (1, 256)
 
 
 def timed(fn, a):
@@ -54,11 +56,14 @@ def bodies(s, n):
     return verts, fk
 
 
-def row(s, G, n, volumes, geometry, a):
+def row(s, G, n, volumes, geometry, a, K=None):
+    """K: the first K vertices of every body only (fk_us stays the whole call's)."""
     import torch
     import torch.nn.functional as F
 
     verts, fk = bodies(s, n)
+    if K is not None:
+        verts = verts[:, :K].contiguous()
     K = verts.shape[1]
     origin, h, field = geometry
     w_con = torch.zeros(K, device="cuda")
@@ -149,6 +154,9 @@ def main():
         layouts[str(G)] = default
         for n in BATCHES:
             rows.append(row(s, G, n, volumes, (origin, h, field), a))
+        if G == PART_GRID:
+            for n in PART_BATCHES:
+                rows.append(row(s, G, n, volumes, (origin, h, field), a, PART_K))
     res = {"bytes_per_second": PEAK, "steps": a.steps, "reps": a.reps, "body_span_voxels": SPAN, "default_layout": layouts, "rows": rows}
     line = json.dumps(res)
     print(line)

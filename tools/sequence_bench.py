@@ -27,7 +27,8 @@ from lbfgs_bench import blocks  # noqa: E402
 from smplpp_amd import _lib  # noqa: E402
 from smplpp_amd.smpl import _stream  # noqa: E402
 
-SHAPES = ((1, 300, 24, 3), (16, 300, 24, 3), (256, 16, 24, 3), (4, 64, 6890, 3))
+# (16, 64, 512, 3): the 256-thread form of the frame sum (64 < K <= 1024), which the other shapes do not reach
+SHAPES = ((1, 300, 24, 3), (16, 300, 24, 3), (256, 16, 24, 3), (4, 64, 6890, 3), (16, 64, 512, 3))
 D, C_S = 75, 10
 
 
