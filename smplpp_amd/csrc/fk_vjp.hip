@@ -48,7 +48,7 @@ constexpr int VJ_KN = 224;             // columns of the operand image (k < 217 
 constexpr int VJ_NT = VJ_KN / 32;      // N tiles of the transposed GEMM
 constexpr int VJ_RS = NJ * 9 + 1;      // LDS stride of a frame's 24 rotations (odd: the 32 frames of a wave hit 32 banks)
 constexpr int VJ_RED = VJ_KN + 4;      // LDS row of the cross-wave reduction of the GEMM result
-// partial slab of one (chunk, frame): [g_c 224 | dG' 24 x 3x4 | g_root 3 | pad]
+// partial slab of one (chunk, frame): [g_c 224 | dG' 24 x 3x4 | g_root 3 high parts | g_root 3 low parts | pad]
 constexpr int VJ_DG = VJ_KN, VJ_ROOT = VJ_KN + NJ * 12, VJ_SLAB = VJ_ROOT + 8;
 
 struct VjpState
@@ -110,8 +110,7 @@ __global__ __launch_bounds__(256, 2) void vjp_skin_kernel(const float * __restri
                                                        float * __restrict__ slab, int64_t n, int64_t V, int VGn, int gpc, int nft)
 {
   __shared__ float sR[VJ_FT * VJ_RS];             // R' of the tile's frames
-  __shared__ float sT[4][16][6][VJ_FT];           // per wavefront, the half group's g~ (3) and rest (3) for the dG' phase
-  __shared__ float sRoot[4][2][VJ_FT][3];
+  __shared__ __align__(16) float sT[4][16][6][VJ_FT]; // per wavefront, the half group's g~ (3) and rest (3) for the dG' phase
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int ftile = blockIdx.x % nft, chunk = blockIdx.x / nft;
   const int64_t f0 = (int64_t)ftile * VJ_FT, f = f0 + r;
@@ -239,10 +238,14 @@ __global__ __launch_bounds__(256, 2) void vjp_skin_kernel(const float * __restri
   }
 
   // ---- the workgroup's partial slab
-  sRoot[w][h][r][0] = gr0;
-  sRoot[w][h][r][1] = gr1;
-  sRoot[w][h][r][2] = gr2;
   float * red = &sT[0][0][0][0]; // [32 frames][VJ_RED]
+  // g_root = sum_v g_v cancels (dense cotangents: |sum| ~ sum|g| / 66).  A lane's own sum stays fp32 (at most 64 terms); from here on
+  // the partial sums are large beside the result, so the eight lanes of a frame, and the chunks in vjp_chain_kernel, are added in double.
+  double * sRoot = reinterpret_cast<double *>(red + VJ_FT * VJ_RED); // [4 wavefronts][2 parities][32 frames][3], behind `red` in sT
+  static_assert((VJ_FT * VJ_RED) % 4 == 0 && sizeof(float) * VJ_FT * VJ_RED + sizeof(double) * 8 * VJ_FT * 3 <= sizeof(sT), "sT holds both");
+  sRoot[((w * 2 + h) * VJ_FT + r) * 3 + 0] = (double)gr0;
+  sRoot[((w * 2 + h) * VJ_FT + r) * 3 + 1] = (double)gr1;
+  sRoot[((w * 2 + h) * VJ_FT + r) * 3 + 2] = (double)gr2;
   for(int ww = 0; ww < 4; ww++)  // wavefront order: fixed
   {
     if(w == ww)
@@ -265,9 +268,14 @@ __global__ __launch_bounds__(256, 2) void vjp_skin_kernel(const float * __restri
   if(tid < VJ_FT * 3)
   {
     const int fl = tid / 3, x = tid % 3;
-    float s = 0.0f;
-    for(int ww = 0; ww < 4; ww++) s = (s + sRoot[ww][0][fl][x]) + sRoot[ww][1][fl][x];
-    if(f0 + fl < n) out[(int64_t)fl * VJ_SLAB + VJ_ROOT + x] = s;
+    double s = 0.0;
+    for(int ww = 0; ww < 4; ww++) s = (s + sRoot[((ww * 2 + 0) * VJ_FT + fl) * 3 + x]) + sRoot[((ww * 2 + 1) * VJ_FT + fl) * 3 + x];
+    if(f0 + fl < n) // the chunk's sum as an fp32 pair (48 bits)
+    {
+      const float hi = (float)s;
+      out[(int64_t)fl * VJ_SLAB + VJ_ROOT + x] = hi;
+      out[(int64_t)fl * VJ_SLAB + VJ_ROOT + 3 + x] = (float)(s - (double)hi);
+    }
   }
   if(fok)
   {
@@ -301,11 +309,22 @@ __global__ __launch_bounds__(256) void vjp_chain_kernel(const float * __restrict
   __shared__ float sG[NJ][12], sJ[NJ][3], sRot[NJ][9];
   __shared__ float dA[NJ][9], dgt[NJ][3], dJ[NJ][3], dR[NJ][9], cA[NJ][9], cJ[NJ][3];
   __shared__ int sPar[NJ], sDep[NJ], sMaxDep;
-  for(int t = tid; t < VJ_ROOT + 3; t += 256)
+  for(int t = tid; t < VJ_ROOT; t += 256)
   {
     float s = 0.0f;
     for(int c = 0; c < nch; c++) s += slab[((int64_t)c * n + f) * VJ_SLAB + t];
     sS[t] = s;
+  }
+  if(tid >= 256 - 3) // g_root: the chunks' pairs summed in double in chunk order, rounded once
+  {
+    const int t = VJ_ROOT + tid - (256 - 3);
+    double s = 0.0;
+    for(int c = 0; c < nch; c++)
+    {
+      const float * p = slab + ((int64_t)c * n + f) * VJ_SLAB + t;
+      s += (double)p[0] + (double)p[3];
+    }
+    sS[t] = (float)s;
   }
   for(int t = tid; t < NJ * 12; t += 256) sG[t / 12][t % 12] = Gp[f * NJ * 12 + t];
   for(int t = tid; t < NJ * 9; t += 256) sRot[t / 9][t % 9] = rot[f * NJ * 9 + t];

@@ -25,14 +25,18 @@ def rodrigues(th):
     return eye + s * K + (1 - c) * (K @ K)
 
 
-def fk(m, beta, theta):
-    """beta [n,10], theta [n,25,3] -> dict(verts [n,V,3], joints [n,24,3], rest [n,V,3], xforms [n,24,4,4])."""
+def fk(m, beta, theta, rest_value=None):
+    """beta [n,10], theta [n,25,3] -> dict(verts [n,V,3], joints [n,24,3], rest [n,V,3], xforms [n,24,4,4]).  rest_value [n,V,3]:
+    the skinning reads these numbers as its rest shape, while the derivative still runs through the graph's own rest (what
+    smplpp_fk_vjp does with the `rest` it is handed or recomputes)."""
     n = beta.shape[0]
     R = rodrigues(theta[:, 1:, :])  # [n,24,3,3]
     eye = torch.eye(3, dtype=beta.dtype)
     c = (R[:, 1:] - eye).reshape(n, -1)  # [n,207]
     shaped = m["T"] + torch.einsum("vxk,nk->nvx", m["S"], beta)
     rest = shaped + torch.einsum("vxk,nk->nvx", m["P"], c)
+    if rest_value is not None:
+        rest = rest + (rest_value - rest).detach()
     J = torch.einsum("jv,nvx->njx", m["Jreg"], shaped)
     A, g = [R[:, 0]], [J[:, 0]]
     for i in range(1, 24):
@@ -51,12 +55,12 @@ def fk(m, beta, theta):
     return dict(verts=verts, joints=J, rest=rest, xforms=X)
 
 
-def vjp(m, beta, theta, grad_verts=None, grad_joints=None, dtype=torch.float64):
-    """(dL/dbeta [n,10], dL/dtheta [n,25,3]) by autograd of `fk` in `dtype`."""
+def vjp(m, beta, theta, grad_verts=None, grad_joints=None, dtype=torch.float64, rest=None):
+    """(dL/dbeta [n,10], dL/dtheta [n,25,3]) by autograd of `fk` in `dtype`; `rest`: fk's rest_value."""
     mm = {k: (v.to(dtype) if torch.is_tensor(v) else v) for k, v in m.items()}
     b = torch.as_tensor(np.asarray(beta), dtype=dtype).clone().requires_grad_(True)
     th = torch.as_tensor(np.asarray(theta), dtype=dtype).clone().requires_grad_(True)
-    out = fk(mm, b, th)
+    out = fk(mm, b, th, None if rest is None else torch.as_tensor(np.asarray(rest), dtype=dtype))
     loss = 0
     if grad_verts is not None:
         loss = loss + (out["verts"] * torch.as_tensor(np.asarray(grad_verts), dtype=dtype)).sum()

@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fk_rotmat_oracle as RO  # noqa: E402
 import fk_vjp_oracle as O  # noqa: E402
+from vjp_blocks import eight_weights as _eight_weights  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,18 +54,6 @@ def smpl(models):
 @pytest.fixture(scope="module")
 def m64(synth_model):
     return RO.model_tensors(synth_model)
-
-
-def _eight_weights(synth_model):
-    md = {k: v.copy() for k, v in synth_model.items()}
-    rng = np.random.default_rng(5)
-    w = md["weights"].astype(np.float64)
-    for v in range(w.shape[0]):
-        extra = rng.choice(np.where(w[v] == 0)[0], size=int(rng.integers(1, 5)), replace=False)
-        w[v, extra] = rng.uniform(0.01, 0.1, len(extra))
-    w /= w.sum(axis=1, keepdims=True)
-    md["weights"] = w.astype(np.float32)
-    return md
 
 
 def _inputs(n, seed):

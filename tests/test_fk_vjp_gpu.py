@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fk_vjp_oracle as O  # noqa: E402
+from vjp_blocks import eight_weights as _eight_weights  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,18 +122,6 @@ def test_vjp_pinned_to_reference_autograd(synth_model, smpl):
         gt, gb = want[:75], want[D - 10:]
         assert _rel(out["theta"].reshape(-1).astype(np.float64), gt) < 1e-4, f
         assert _rel(out["beta"].reshape(-1).astype(np.float64), gb) < 1e-4, f
-
-
-def _eight_weights(synth_model):
-    md = {k: v.copy() for k, v in synth_model.items()}
-    rng = np.random.default_rng(5)
-    w = md["weights"].astype(np.float64)
-    for v in range(w.shape[0]):
-        extra = rng.choice(np.where(w[v] == 0)[0], size=int(rng.integers(1, 5)), replace=False)
-        w[v, extra] = rng.uniform(0.01, 0.1, len(extra))
-    w /= w.sum(axis=1, keepdims=True)
-    md["weights"] = w.astype(np.float32)
-    return md
 
 
 @pytest.mark.parametrize("form", ["e", "h", "b"])
