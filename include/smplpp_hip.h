@@ -840,6 +840,66 @@ int smplpp_scene_term_vjp(struct smplpp_volume * vol, int64_t n, int64_t K, cons
                           float rho, const float * grad_energy /*[n] nullable*/, const float * grad_point_energy /*[n,K] nullable*/,
                           const float * grad_value /*[n,K] nullable*/, float * grad_points /*[n,K,3]*/, int accumulate, int space,
                           void * stream);
+/* ------------------------------------------------------------------ the image term: bilinear sampling at projected points
+ * A dense image that a network produced (joint heatmaps, feature or colour maps, flow, a distance map) read at the unsnapped uv [n,K,2]
+ * of smplpp_project_points, with the gradient to uv and to the image.  image [B,H,W,C] is channels-last, as smplpp_raster_interpolate
+ * writes it; B, Tn and Wn are each 1 (shared by all frames) or n.  Without `channel` a point samples all C channels (Cs = C); with
+ * channel [K], point k samples channel channel[k] alone (Cs = 1: heatmap j for joint j).  The calls take no handle: `device` as the
+ * stage calls.  All arithmetic is fp32, every operation rounded on its own (no FMA), and there are no floating-point atomics.
+ * THE SAMPLING RULE, for the point (u, v):
+ *  coordinate:  pixel (row j, column i) has its centre at (i + 0.5, j + 0.5), the convention of smplpp_depth_raster and
+ *               smplpp_project_points: gx = u - 0.5, gy = v - 0.5.
+ *  inside:      both are finite, 0 <= gx <= W - 1 and 0 <= gy <= H - 1.
+ *  cell:        i = min((int)floor(gx), W - 2), fx = gx - (float)i;  j, fy alike from gy and H: the far edge belongs to the last cell
+ *               with f = 1.
+ *  value:       per sampled channel c, with v_xy the pixel (j + y, i + x):  d_y = v_1y - v_0y,  c_y = v_0y + fx d_y;  e = c_1 - c_0,
+ *               s = c_0 + fy e.
+ *  gradient:    ds/du = d_0 + fy (d_1 - d_0),  ds/dv = e, in pixels: the derivative of the interpolant at a fixed cell.
+ *  valid:       1 when the point is inside and every sampled s is finite.  A point that is not valid gives +0 in every output and
+ *               contributes to no gradient: the convention of smplpp_volume_sample.  A NaN pixel therefore takes out the points of the
+ *               (at most four) cells that touch it and no others.  A device-space channel[k] outside [0, C) makes the point not valid.
+ * value [n,K,Cs], gradient [n,K,Cs,2] = (ds/du, ds/dv) and valid [n,K] may each be NULL, not all.  A thread per point.
+ *  - SMPLPP_ERR_INVALID: n or K <= 0, H or W outside [2, 8192], C outside [1, 32], B not 1 or n, n K Cs 2 or B H W C beyond int32
+ *    indexing, a NULL uv or image, every output NULL, a bad space, a host-space channel entry outside [0, C) (the outputs are
+ *    untouched).  Device data is never refused. */
+int smplpp_image_sample(int device, int64_t n, int64_t K, const float * uv /*[n,K,2]*/, const float * image /*[B,H,W,C]*/, int64_t B, int64_t H,
+                        int64_t W, int64_t C, const int64_t * channel /*[K] nullable*/, float * value /*[n,K,Cs] nullable*/,
+                        float * gradient /*[n,K,Cs,2] nullable*/, uint8_t * valid /*[n,K] nullable*/, int space, void * stream);
+/* THE TERM.  w = weight[f or 0][k] (NULL reads as 1), t_c = target[f or 0][k][c] (NULL reads as 0).  Per valid point:
+ *  r_c = s_c - t_c;  q = the sum of r_c r_c over the sampled channels c, ascending from +0;
+ *  point_energy = w q for rho == 0, else p2 = rho rho, point_energy = w ((p2 q) / (p2 + q)), the Geman-McClure form of
+ *  smplpp_project_points.  A point with w == 0 reads no image value or target and its energy is +0, whatever they hold; its value and
+ *  valid outputs, when asked for, are still computed.
+ * energy [n] = sum1024 (FIXED-ORDER SUMS above) of point_energy over the frame's points k.  The work split follows K (a wavefront per
+ * frame up to 64, a workgroup of 256 up to 1024, of 1024 above; a thread per point without energy) and changes no bit; nor do n, the
+ * frame's slot, the memory space or which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID: as smplpp_image_sample, a given target or weight with Tn or Wn not 1 or n, rho negative or not finite (the
+ *    outputs are untouched). */
+int smplpp_image_term(int device, int64_t n, int64_t K, const float * uv, const float * image, int64_t B, int64_t H, int64_t W, int64_t C,
+                      const int64_t * channel /*[K] nullable*/, const float * target /*[Tn,K,Cs] nullable = 0*/, int64_t Tn,
+                      const float * weight /*[Wn,K] nullable = 1*/, int64_t Wn, float rho, float * energy /*[n] nullable*/,
+                      float * point_energy /*[n,K] nullable*/, float * value /*[n,K,Cs] nullable*/, uint8_t * valid /*[n,K] nullable*/,
+                      int space, void * stream);
+/* Its vector-Jacobian product to uv and to the image, with the sample recomputed by the forward's operations.  A NULL cotangent reads
+ * as +0.  Per valid point:
+ *  g = grad_energy[f] + grad_point_energy[f,k];  m = w for rho == 0, else d = p2 / (p2 + q), m = w (d d);
+ *  gamma_c = grad_value[f,k,c] + ((2 g) m) r_c; when w == 0 the second term is +0 and nothing of the term is read.
+ *  grad_uv[f,k] = (sum_c gamma_c ds_c/du, sum_c gamma_c ds_c/dv), each sum over c ascending from +0.  No sums across points.
+ *  grad_image:  with ax = 1 - fx, ay = 1 - fy, the point contributes (ax ay) gamma_c, (fx ay) gamma_c, (ax fy) gamma_c and
+ *  (fx fy) gamma_c to the pixels (j, i), (j, i + 1), (j + 1, i), (j + 1, i + 1) of its cell, in its sampled channels; a product that is 0
+ *  is included.  Element (b, j, i, c) is the sum of its contributions, from +0, IN ASCENDING FLAT POINT INDEX f K + k over the frames
+ *  that read image b (f = b when B = n, every f when B = 1): one fixed-order sum per element, a gather with no atomics.
+ * A point that is not valid, or one with w == 0 under a NULL grad_value (it reads no image value), contributes nothing: +0 in grad_uv.
+ * accumulate = 0 stores the finished value (untouched pixels get +0), 1 adds it to what is there, for both outputs.  grad_uv or
+ * grad_image may be NULL, not both.  The bits do not depend on n, on the frame's slot (B = n), on the memory space or on which output is
+ * asked for.  grad_image costs tiles x points (a workgroup per 16 x 16 pixels and 4 channels scans the points of its image).
+ *  - SMPLPP_ERR_INVALID: as the forward (cotangents for outputs), both outputs NULL, accumulate not 0 or 1 (the outputs are
+ *    untouched). */
+int smplpp_image_term_vjp(int device, int64_t n, int64_t K, const float * uv, const float * image, int64_t B, int64_t H, int64_t W, int64_t C,
+                          const int64_t * channel, const float * target, int64_t Tn, const float * weight, int64_t Wn, float rho,
+                          const float * grad_energy /*[n] nullable*/, const float * grad_point_energy /*[n,K] nullable*/,
+                          const float * grad_value /*[n,K,Cs] nullable*/, float * grad_uv /*[n,K,2] nullable*/,
+                          float * grad_image /*[B,H,W,C] nullable*/, int accumulate, int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

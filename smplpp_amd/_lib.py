@@ -132,6 +132,11 @@ def load():
         "smplpp_volume_sample": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_scene_term": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_scene_term_vjp": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_image_sample": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_image_term": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64,
+                              C.c_float, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_image_term_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64,
+                                  C.c_float, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],
