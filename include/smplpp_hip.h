@@ -900,6 +900,76 @@ int smplpp_image_term_vjp(int device, int64_t n, int64_t K, const float * uv, co
                           const float * grad_energy /*[n] nullable*/, const float * grad_point_energy /*[n,K] nullable*/,
                           const float * grad_value /*[n,K,Cs] nullable*/, float * grad_uv /*[n,K,2] nullable*/,
                           float * grad_image /*[B,H,W,C] nullable*/, int accumulate, int space, void * stream);
+/* ------------------------------------------------------------------ rigid and similarity alignment of point sets
+ * Per frame, the rotation R, translation t and scale s that minimise sum_k w_k |s (R x_k) + t - y_k|^2 over source x [n,K,3], target
+ * y [Tn,K,3] and weight w [Wn,K] (NULL reads as 1); Tn and Wn are each 1 (shared by all frames) or n.  It is closed form (Horn's
+ * quaternion method), and so is its vector-Jacobian product.  The calls take no handle: `device` as the stage calls.  All arithmetic is
+ * fp32, every operation rounded on its own (no FMA), '/' and sqrt are the correctly rounded ones, every sum over a frame's points is
+ * sum1024 (FIXED-ORDER SUMS above), and there are no floating-point atomics.  Products and sums associate from the left as written.
+ * THE FORWARD RULE, per frame:
+ *  1 live:      point k is live iff w_k is finite and > 0 and its six coordinates are finite.  A point that is not live adds +0 to every
+ *               sum below.  It is `moved` iff its three source coordinates are finite (a live point is).
+ *  2 centroids: W = sum w;  cx_a = (sum w x_a) / W,  cy_a = (sum w y_a) / W;  x~ = x - cx,  y~ = y - cy, in a second pass.
+ *  3 moments:   S_ab = sum (w x~_a) y~_b, nine sums;  vx = sum w ((x~_0 x~_0 + x~_1 x~_1) + x~_2 x~_2).
+ *  4 matrix:    the symmetric N [4,4]:  N00 = (Sxx + Syy) + Szz,  N11 = (Sxx - Syy) - Szz,  N22 = ((-Sxx) + Syy) - Szz,
+ *               N33 = ((-Sxx) - Syy) + Szz;  N01 = Syz - Szy,  N02 = Szx - Sxz,  N03 = Sxy - Syx,  N12 = Sxy + Syx,  N13 = Szx + Sxz,
+ *               N23 = Syz + Szy.
+ *  5 Jacobi:    V = I; SEVEN sweeps over the pairs (p, q) = (0,1), (0,2), (0,3), (1,2), (1,3), (2,3).  A pair with N_pq == 0 is skipped.
+ *               Else theta = (N_qq - N_pp) / (2 N_pq);  t = sg / (|theta| + sqrt(theta theta + 1)), sg = -1 for theta < 0, else 1 (a
+ *               theta theta that overflows gives t = 0, not a NaN);  c = 1 / sqrt(t t + 1);  s = t c;  h = t N_pq;  N_pp -= h;
+ *               N_qq += h;  N_pq = 0;  for r not in {p, q}: (N_rp, N_rq) = (c N_rp - s N_rq, s N_rp + c N_rq), on the old values and
+ *               kept symmetric;  for every r: (V_rp, V_rq) = (c V_rp - s V_rq, s V_rp + c V_rq).  lambda_i = N_ii, with column i of V.
+ *  6 rotation:  `top` is the index of the largest lambda, the lowest on ties; e = column top of V;  q = e / sqrt(((e0 e0 + e1 e1) +
+ *               e2 e2) + e3 e3) = (w, x, y, z);  R = [((ww + xx) - yy) - zz, 2 (xy - wz), 2 (xz + wy);  2 (xy + wz), ((ww - xx) + yy) - zz,
+ *               2 (yz - wx);  2 (xz - wy), 2 (yz + wx), ((ww - xx) - yy) + zz], ww = w w and so on.  Always a proper rotation: a
+ *               mirrored target gets the best rotation, as the SVD rule with the determinant correction does.
+ *  7 scale:     s = (sum_ab R_ab S_ba, a outer, b inner, from the first product) / vx with with_scale, else 1;
+ *               t_a = cy_a - s ((R_a0 cx_0 + R_a1 cx_1) + R_a2 cx_2).
+ *  8 outputs:   aligned_k,a = s ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a for EVERY k, live or not (align on a subset, move everything);
+ *               d = aligned_k - y_k;  point_error_k = (d_0 d_0 + d_1 d_1) + d_2 d_2, +0 where the point is not live;
+ *               energy = sum w point_error;  gap = (l1 - l2) / (l1 - l4) for the largest, second and smallest lambda, 0 unless
+ *               l1 - l4 > 0.  transform [n,13] = R row-major, t, s.
+ *  9 status:    bit 0: W is not finite and > 0: the transform is the identity, energy and gap are 0 and no other bit is set.  That is
+ *               a frame without a live point, and also one whose weights sum past the largest float: its live points then keep the
+ *               point_error of the identity, and in the backward the direct part (2 ge w) (aligned - y) of such a frame still flows,
+ *               as for every frame with a status bit.  Bit 1: vx == 0 (one live point, or coincident ones at weights whose centroid is exact): R = I, s = 1,
+ *               t = cy - cx.  Bit 2: gap <= min_gap: the rotation is not unique; the transform is still the rule's.
+ * Every output is nullable, not all.  The work split follows K (a wavefront per frame up to 64, a workgroup of 256 up to 1024, of 1024
+ * above) and changes no bit; nor do n, the frame's slot, the memory space or which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID: n or K <= 0, Tn or Wn not 1 or n, with_scale not 0 or 1, min_gap negative or not finite, a NULL source or
+ *    target, every output NULL, n K 3 beyond int32 indexing, a bad space (the outputs are untouched).  Device data is never refused. */
+int smplpp_align(int device, int64_t n, int64_t K, const float * source /*[n,K,3]*/, const float * target /*[Tn,K,3]*/, int64_t Tn,
+                 const float * weight /*[Wn,K] nullable = 1*/, int64_t Wn, int with_scale, float min_gap,
+                 float * transform /*[n,13] nullable*/, float * aligned /*[n,K,3] nullable*/, float * energy /*[n] nullable*/,
+                 float * point_error /*[n,K] nullable*/, float * gap /*[n] nullable*/, int32_t * status /*[n] nullable*/, int space,
+                 void * stream);
+/* Its vector-Jacobian product to source and target, with the forward recomputed by the forward's operations.  A NULL cotangent reads as
+ * +0; (gR [9], gt [3], gs) = grad_transform[f], R as nine independent entries (the convention of smplpp_fk_rotmat_vjp).  Per frame, with
+ * ge = grad_energy[f], c2_k = (2 ge) w_k and d_k = aligned_k - y_k:
+ *  ga_k = grad_aligned_k + c2_k d_k, the second term for live points only.
+ *  sums:  sg_a = sum ga_a and P_ab = sum ga_a x_b over the MOVED points (a point of weight 0 is moved with the rest, and its cotangent
+ *         reaches the transform), twelve sum1024.
+ *  G_t = gt + sg;  rc = R cx (as in step 7);  G_s = (gs + sum_ab R_ab P_ab) - ((G_t0 rc_0 + G_t1 rc_1) + G_t2 rc_2), 0 without with_scale;
+ *  G_R_ab = ((gR_ab + s P_ab) - (s G_t,a) cx_b) + (G_s S_ba) / vx;  g2 = 2 ((-(G_s s)) / vx).
+ *  g_q = 2 M q, M the matrix of step 4 built from G_R^T in S's place, each row ((M_r0 w + M_r1 x) + M_r2 y) + M_r3 z.
+ *  co_i = (((V_0i g_q0 + V_1i g_q1) + V_2i g_q2) + V_3i g_q3) / (lambda_top - lambda_i), +0 for i = top;
+ *  u_r = ((V_r0 co_0 + V_r1 co_1) + V_r2 co_2) + V_r3 co_3;  D_i = u_i q_i,  H_ij = u_i q_j + u_j q_i;
+ *  G_S: xx = ((D0 + D1) - D2) - D3, yy = ((D0 - D1) + D2) - D3, zz = ((D0 - D1) - D2) + D3, yz = H23 + H01, zy = H23 - H01,
+ *       zx = H13 + H02, xz = H13 - H02, xy = H12 + H03, yx = H12 - H03;   G_M_ab = (G_s R_ab) / vx + G_S_ba;  cs = -(s (R^T G_t)).
+ *  grad_source_k,a = s ((R_0a ga_0 + R_1a ga_1) + R_2a ga_2), and for a live point of a frame with status 0
+ *       (that + w ((G_M^T y~)_a + g2 x~_a)) + (w / W) cs_a;
+ *  grad_target_k,a = 0 - c2 d_a for a live point, else +0, and for a live point of a frame with status 0
+ *       (that + w (G_M x~)_a) + (w / W) G_t,a.
+ * The centring correction of the moment terms vanishes identically and is not computed.  A frame with any status bit set keeps its
+ * transform constant.  grad_target is always per frame [n,K,3]: with Tn = 1 the caller sums it.  There is no gradient to the weights.
+ * accumulate = 0 stores, 1 adds to what is there.  grad_source or grad_target may be NULL, not both.  The bits do not depend on n, the
+ * frame's slot, the memory space or which output is asked for.
+ *  - SMPLPP_ERR_INVALID: as the forward, every cotangent NULL, both outputs NULL, accumulate not 0 or 1 (the outputs are untouched). */
+int smplpp_align_vjp(int device, int64_t n, int64_t K, const float * source, const float * target, int64_t Tn, const float * weight, int64_t Wn,
+                     int with_scale, float min_gap, const float * grad_transform /*[n,13] nullable*/,
+                     const float * grad_aligned /*[n,K,3] nullable*/, const float * grad_energy /*[n] nullable*/,
+                     float * grad_source /*[n,K,3] nullable*/, float * grad_target /*[n,K,3] nullable*/, int accumulate, int space,
+                     void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).

@@ -137,6 +137,9 @@ def load():
                               C.c_float, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_image_term_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64,
                                   C.c_float, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_align": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_align_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, vp, vp, C.c_int,
+                             C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],
