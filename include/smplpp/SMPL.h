@@ -304,6 +304,73 @@ public:
     return {gb, gt, gr};
   }
 
+  // The skeleton alone (smplpp_skeleton; no reference counterpart): world [N,24,3,4] = [A_j | posed_j] row-major, the world orientation
+  // and position of every joint; posed [N,24,3] the posed joints; joints [N,24,3] the rest joints of getRestJoint.  One kernel, no
+  // vertex; nothing is kept for the getters or for a later backward: the backward calls below take beta and theta again.
+  struct Skeleton
+  {
+    Tensor world, posed, joints;
+  };
+  Skeleton skeleton(const Tensor & beta, const Tensor & theta) const
+  {
+    const bool hb = !beta.data.empty();
+    if(!m_ || theta.shape.size() != 3 || theta.size(1) != JOINT_NUM + 1 || theta.size(2) != 3 || theta.dtype != kFloat32
+       || (hb && (beta.numel() != theta.size(0) * SHAPE_BASIS_DIM || beta.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot pose the skeleton of a SMPL model!");
+    const int64_t n = theta.size(0);
+    Skeleton s{Tensor({n, JOINT_NUM, 3, 4}), Tensor({n, JOINT_NUM, 3}), Tensor({n, JOINT_NUM, 3})};
+    check(smplpp_skeleton(m_.get(), n, hb ? beta.ptr() : nullptr, theta.ptr(), s.world.ptr(), s.posed.ptr(), s.joints.ptr(), SMPLPP_HOST,
+                          nullptr),
+          "SMPL");
+    return s;
+  }
+
+  // skeleton from rotation matrices (smplpp_skeleton_rotmat): rot [N,24,3,3] used as given; an empty beta or trans = zero.
+  Skeleton skeletonRotmat(const Tensor & beta, const Tensor & trans, const Tensor & rot) const
+  {
+    checkSkeletonRotmat(beta, trans, rot);
+    const int64_t n = rot.size(0);
+    Skeleton s{Tensor({n, JOINT_NUM, 3, 4}), Tensor({n, JOINT_NUM, 3}), Tensor({n, JOINT_NUM, 3})};
+    check(smplpp_skeleton_rotmat(m_.get(), n, beta.data.empty() ? nullptr : beta.ptr(), trans.data.empty() ? nullptr : trans.ptr(), rot.ptr(),
+                                 s.world.ptr(), s.posed.ptr(), s.joints.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return s;
+  }
+
+  // {dL/dbeta [N,10], dL/dtheta [N,25,3]} of a loss on skeleton(beta, theta) with dL/dworld = gradWorld [N,24,3,4], dL/dposed =
+  // gradPosed [N,24,3] and dL/djoints = gradJoints [N,24,3] (an empty Tensor = zero; at least one).  smplpp_skeleton_vjp.
+  std::pair<Tensor, Tensor> skeletonBackward(const Tensor & beta, const Tensor & theta, const Tensor & gradWorld, const Tensor & gradPosed,
+                                             const Tensor & gradJoints) const
+  {
+    const bool hb = !beta.data.empty();
+    if(!m_ || theta.shape.size() != 3 || theta.size(1) != JOINT_NUM + 1 || theta.size(2) != 3 || theta.dtype != kFloat32
+       || (hb && (beta.numel() != theta.size(0) * SHAPE_BASIS_DIM || beta.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot back-propagate through the skeleton of a SMPL model!");
+    const int64_t n = theta.size(0);
+    checkSkeletonGrads(n, gradWorld, gradPosed, gradJoints);
+    Tensor gb({n, SHAPE_BASIS_DIM}), gt({n, JOINT_NUM + 1, 3});
+    check(smplpp_skeleton_vjp(m_.get(), n, hb ? beta.ptr() : nullptr, theta.ptr(), optional(gradWorld), optional(gradPosed),
+                              optional(gradJoints), gb.ptr(), gt.ptr(), 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return {gb, gt};
+  }
+
+  // {dL/dbeta [N,10], dL/dtrans [N,3], dL/drot [N,24,3,3]} of a loss on skeletonRotmat(beta, trans, rot); dL/drot is the gradient to
+  // nine independent entries per joint, as launchRotmatBackward's.  smplpp_skeleton_rotmat_vjp.
+  std::tuple<Tensor, Tensor, Tensor> skeletonRotmatBackward(const Tensor & beta, const Tensor & trans, const Tensor & rot,
+                                                            const Tensor & gradWorld, const Tensor & gradPosed, const Tensor & gradJoints) const
+  {
+    checkSkeletonRotmat(beta, trans, rot);
+    const int64_t n = rot.size(0);
+    checkSkeletonGrads(n, gradWorld, gradPosed, gradJoints);
+    Tensor gb({n, SHAPE_BASIS_DIM}), gt({n, 3}), gr({n, JOINT_NUM, 3, 3});
+    check(smplpp_skeleton_rotmat_vjp(m_.get(), n, beta.data.empty() ? nullptr : beta.ptr(), trans.data.empty() ? nullptr : trans.ptr(),
+                                     rot.ptr(), optional(gradWorld), optional(gradPosed), optional(gradJoints), gb.ptr(), gt.ptr(), gr.ptr(), 0,
+                                     SMPLPP_HOST, nullptr),
+          "SMPL");
+    return {gb, gt, gr};
+  }
+
   Tensor getVertex() const { return need(verts_); }       // [N,6890,3] copy (src/SMPL.cpp:492-506)
   Tensor getRestShape() const { return need(rest_); }
   Tensor getRestJoint() const { return need(joints_); }   // [N,24,3]
@@ -800,6 +867,22 @@ public:
   int64_t faceNum() const { return F_; }
 
 private:
+  // the argument checks of the skeleton calls
+  static const float * optional(const Tensor & t) { return t.data.empty() ? nullptr : t.ptr(); }
+  void checkSkeletonRotmat(const Tensor & beta, const Tensor & trans, const Tensor & rot) const
+  {
+    if(!m_ || rot.shape.size() != 4 || rot.size(1) != JOINT_NUM || rot.size(2) != 3 || rot.size(3) != 3 || rot.dtype != kFloat32
+       || (!beta.data.empty() && (beta.numel() != rot.size(0) * SHAPE_BASIS_DIM || beta.dtype != kFloat32))
+       || (!trans.data.empty() && (trans.numel() != rot.size(0) * 3 || trans.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot pose the skeleton of a SMPL model!");
+  }
+  static void checkSkeletonGrads(int64_t n, const Tensor & gw, const Tensor & gp, const Tensor & gj)
+  {
+    const bool hw = !gw.data.empty(), hp = !gp.data.empty(), hj = !gj.data.empty();
+    if((!hw && !hp && !hj) || (hw && (gw.numel() != n * JOINT_NUM * 12 || gw.dtype != kFloat32))
+       || (hp && (gp.numel() != n * JOINT_NUM * 3 || gp.dtype != kFloat32)) || (hj && (gj.numel() != n * JOINT_NUM * 3 || gj.dtype != kFloat32)))
+      throw Exception("SMPL", "Cannot back-propagate through the skeleton of a SMPL model!");
+  }
   // an integer mask tensor [N,H,W] as bytes (nonzero = set)
   static std::vector<uint8_t> maskBytes(const Tensor & mask, const char * what)
   {

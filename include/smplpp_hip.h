@@ -123,6 +123,44 @@ int smplpp_fk_rotmat(smplpp_model * m, int64_t n, const float * beta /*[n,10], N
 int smplpp_fk_rotmat_vjp(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot, const float * rest /*nullable*/,
                          const float * grad_verts, const float * grad_joints, float * grad_beta /*[n,10]*/, float * grad_trans /*[n,3]*/,
                          float * grad_rot /*[n,24,3,3]*/, int space, void * stream);
+/* The skeleton alone: the kinematic chain without a vertex, and its backward pass (no reference counterpart: the reference returns the
+ * rest joints, SMPL::getRestJoint, and keeps the world transforms inside WorldTransformation).  Outputs, any may be NULL but not all:
+ *   world  [n,24,3,4]  row-major [A_j | posed_j]: the world orientation and position of joint j
+ *   posed  [n,24,3]    the posed joints of the chain (what smplx returns as `joints`)
+ *   joints [n,24,3]    the rest joints J, the `joints` of smplpp_fk
+ * Forward rule, per frame: R_j = Rodrigues(theta[1+j]) as smplpp_fk computes it (rotmat entry: rot[j] used as given, as smplpp_fk_rotmat
+ * does); J = J0 + JS.beta; A_0 = R_0, g_0 = J_0; A_j = A_p R_j, g_j = A_p (J_j - J_p) + g_p, one tree level at a time, with the
+ * operations and operand order of smplpp_fk's pose step; posed_j = g_j + trans (one fp32 add), trans = theta[0] (rotmat entry: trans,
+ * NULL = +0).  So world[..., :3] has the BITS of the 3x3 block of the xforms of smplpp_fk / smplpp_fk_rotmat on the same inputs, and
+ * joints the bits of their joints.
+ * Backward rule, per frame (the forward is recomputed, no state is kept; every operation is rounded on its own):
+ *   seeds: dA_j = grad_world[j][:, :3], dg_j = grad_world[j][:, 3] + grad_posed[j], dJ_j = grad_joints[j]; a NULL cotangent reads as +0
+ *   grad_trans = sum of the 24 seed dg_j in ascending j from +0
+ *   from the deepest level to level 1, joint j with parent p: dR_j = A_p^T dA_j; cA_j = dA_j R_j^T + dg_j (J_j - J_p)^T;
+ *     cJ_j = A_p^T dg_j, dJ_j += cJ_j; the parent then gathers its children in ascending joint order: dA_p += cA_i, dg_p += dg_i,
+ *     dJ_p -= cJ_i
+ *   root: dR_0 = dA_0, dJ_0 += dg_0
+ *   grad_beta[k] = sum of JS[i][k] dJ[i] over i = 0..71 in ascending order from +0
+ *   grad_theta[1+j][m] = sum_q dR_j[q] dRodrigues(theta_j)/dtheta_m [q] in ascending q (row 0 = grad_trans); rotmat entry: grad_rot = dR,
+ *     NINE INDEPENDENT ENTRIES per joint (the convention of smplpp_fk_rotmat_vjp)
+ * accumulate = 0 stores the finished value, 1 adds it to the output (one fp32 add): after smplpp_fk_vjp into the same buffers that is
+ * the gradient of a loss on vertices AND skeleton.  At least one cotangent must be given and one gradient asked for.
+ * One kernel launch per call on the caller's stream; a device-space call touches nothing in the handle (no workspace, no status word,
+ * no profiling record).  A frame's bits depend on that frame's inputs only: not on n, its place in the batch, the memory space, or
+ * which outputs or cotangents are asked for; a frame of NaNs leaves its neighbours alone.  Any tree smplpp_model_create accepts works.
+ * SMPLPP_ERR_INVALID (outputs untouched): n <= 0, NULL theta or rot, nothing asked for, no cotangent, accumulate not 0 or 1. */
+int smplpp_skeleton(smplpp_model * m, int64_t n, const float * beta /*[n,10], NULL = 0*/, const float * theta /*[n,25,3]*/,
+                    float * world /*[n,24,3,4] nullable*/, float * posed /*[n,24,3] nullable*/, float * joints /*[n,24,3] nullable*/,
+                    int space, void * stream);
+int smplpp_skeleton_rotmat(smplpp_model * m, int64_t n, const float * beta /*nullable*/, const float * trans /*[n,3] nullable*/,
+                           const float * rot /*[n,24,3,3]*/, float * world, float * posed, float * joints, int space, void * stream);
+int smplpp_skeleton_vjp(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * grad_world /*[n,24,3,4] nullable*/,
+                        const float * grad_posed /*[n,24,3] nullable*/, const float * grad_joints /*[n,24,3] nullable*/,
+                        float * grad_beta /*[n,10] nullable*/, float * grad_theta /*[n,25,3] nullable*/, int accumulate, int space,
+                        void * stream);
+int smplpp_skeleton_rotmat_vjp(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot,
+                               const float * grad_world, const float * grad_posed, const float * grad_joints, float * grad_beta,
+                               float * grad_trans /*[n,3]*/, float * grad_rot /*[n,24,3,3]*/, int accumulate, int space, void * stream);
 /* Input range of the fp16x2 form (SMPLPP_SKIN=h): |beta| < 1023 and relative transforms whose
  * translations stay within 16 x the template's extent (65504 / sG).  Outside it the operand pieces overflow fp16 and the
  * vertices of the frame are not finite, where the reference and the default form (and SMPLPP_SKIN=b|v) stay finite.  A launch that
@@ -537,6 +575,9 @@ int smplpp_landmarks_info(const struct smplpp_landmarks * lm, int64_t * L, int64
  * e of the row has rank r = e - row_ptr[l]; partial p = r mod 8 runs s_p = s_p + val[e] * x[col[e]] over its entries in ascending r,
  * starting from +0; the result is ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7)).  An empty row gives +0.  The bits of a frame do
  * not depend on n, on its position in the batch, on the memory space or on the work split.
+ * Column V + j reads row j of WHATEVER [n,24,3] array is passed as `joints`: smplpp_fk's rest joints, or the `posed` of
+ * smplpp_skeleton, which makes those columns the posed skeleton; the grad_joints smplpp_landmarks_vjp returns is then the
+ * grad_posed of smplpp_skeleton_vjp.
  *  - SMPLPP_ERR_INVALID: n <= 0, a NULL array, n (V + 24) or n L 3 beyond int32 indexing (the output is untouched). */
 int smplpp_landmarks(struct smplpp_landmarks * lm, int64_t n, const float * verts /*[n,V,3]*/, const float * joints /*[n,24,3]*/,
                      float * points /*[n,L,3]*/, int space, void * stream);

@@ -63,6 +63,10 @@ def load():
         "smplpp_fk_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_fk_rotmat": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_fk_rotmat_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_skeleton": [vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_skeleton_rotmat": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_skeleton_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_skeleton_rotmat_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_stage_blend_shape": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_joint_regression": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_world_transformation": [C.c_int, C.c_int64, vp, vp, vp, vp, C.c_int, vp],

@@ -15,7 +15,9 @@ from .smpl import _Call, _ptr, torch
 
 class Landmarks:
     """An L-row regressor over the V + 24 sources of `smpl` (an initialised SMPL): column c < V is vertex c, column V + j is joint j
-    of launch's joints.  row_ptr [L+1], col [nnz], val [nnz] as in scipy's csr_matrix; a column may repeat within a row."""
+    of launch's joints.  row_ptr [L+1], col [nnz], val [nnz] as in scipy's csr_matrix; a column may repeat within a row.
+    Column V + j reads row j of whatever [N,24,3] array is passed as `joints`: launch's rest joints, or the `posed` of
+    SMPL.skeleton, which makes those columns the posed skeleton; the returned grad_joints is then SMPL.skeletonBackward's grad_posed."""
 
     def __init__(self, smpl, row_ptr, col, val):
         self._h = None

@@ -392,6 +392,96 @@ class SMPL:
             raise SmplppError(1, "forward_rotmat_differentiable needs torch")
         return _FKRotmatFunction.apply(beta, trans, rot, self)
 
+    # ---- the skeleton alone (smplpp_skeleton / smplpp_skeleton_rotmat and their vector-Jacobian products)
+    _SKELETON_OUT = (("world", (24, 3, 4)), ("posed", (24, 3)), ("joints", (24, 3)))
+
+    def _skeleton(self, c, beta, trans, pose, rot_in, want, out=None):
+        """smplpp_skeleton (pose = theta) or smplpp_skeleton_rotmat (pose = rot) in the space of `c`: (beta, trans, pose as passed to
+        it, {"world", "posed", "joints"})."""
+        n = int(pose.shape[0]) if c.dev else len(pose)
+        beta, trans = c.input(beta, (n, 10)), c.input(trans, (n, 3))
+        pose = c.input(pose, (n, 24, 3, 3) if rot_in else (n, 25, 3))
+        pre = out or {}
+        out = {k: c.inout(pre[k], (n,) + s) if k in pre else (c.empty((n,) + s) if k in want else None) for k, s in self._SKELETON_OUT}
+        if all(v is None for v in out.values()):
+            c.refuse("world, posed or joints must be asked for")
+        ptrs = [_ptr(out[k]) for k, _ in self._SKELETON_OUT]
+        L = _lib.load()
+        if rot_in:
+            check(L.smplpp_skeleton_rotmat(self.handle, n, _ptr(beta), _ptr(trans), _ptr(pose), *ptrs, c.space, c.stream))
+        else:
+            check(L.smplpp_skeleton(self.handle, n, _ptr(beta), _ptr(pose), *ptrs, c.space, c.stream))
+        return beta, trans, pose, {k: v for k, v in out.items() if v is not None}
+
+    def _skeleton_backward(self, name, beta, trans, pose, rot_in, grad_world, grad_posed, grad_joints, want, out):
+        acc = out is not None
+        c = _Call(name, pose, beta, trans, grad_world, grad_posed, grad_joints, *(out.values() if acc else ()))
+        n = int(pose.shape[0]) if c.dev else len(pose)
+        beta, trans = c.input(beta, (n, 10)), c.input(trans, (n, 3))
+        pose = c.input(pose, (n, 24, 3, 3) if rot_in else (n, 25, 3))
+        gw, gp, gj = c.input(grad_world, (n, 24, 3, 4)), c.input(grad_posed, (n, 24, 3)), c.input(grad_joints, (n, 24, 3))
+        if gw is None and gp is None and gj is None:
+            c.refuse("grad_world, grad_posed or grad_joints must be given")
+        shapes = {"beta": (n, 10), "trans": (n, 3), "rot": (n, 24, 3, 3)} if rot_in else {"beta": (n, 10), "theta": (n, 25, 3)}
+        keys = [k for k in shapes if k in (out if acc else want)]
+        if not keys:
+            c.refuse("%s must be asked for" % " or ".join(shapes))
+        res = {k: c.inout(out[k], shapes[k]) if acc else c.empty(shapes[k]) for k in keys}
+        L = _lib.load()
+        if rot_in:
+            check(L.smplpp_skeleton_rotmat_vjp(self.handle, n, _ptr(beta), _ptr(trans), _ptr(pose), _ptr(gw), _ptr(gp), _ptr(gj),
+                                               _ptr(res.get("beta")), _ptr(res.get("trans")), _ptr(res.get("rot")), int(acc), c.space,
+                                               c.stream))
+        else:
+            check(L.smplpp_skeleton_vjp(self.handle, n, _ptr(beta), _ptr(pose), _ptr(gw), _ptr(gp), _ptr(gj), _ptr(res.get("beta")),
+                                        _ptr(res.get("theta")), int(acc), c.space, c.stream))
+        return res
+
+    def skeleton(self, beta, theta, want=("world", "posed", "joints"), out=None):
+        """The kinematic chain alone, without a vertex (smplpp_skeleton): beta [N,10] (None = zero), theta [N,25,3] as in launch.
+        Returns a dict of world [N,24,3,4] (row-major [A_j | posed_j]: the world orientation and position of every joint), posed
+        [N,24,3] (the posed joints, what smplx calls joints) and joints [N,24,3] (the REST joints launch returns).  world[..., :3]
+        and joints have the bits of launch's xforms[:, :, :3, :3] and joints.  One kernel launch; nothing in the model's workspace is
+        touched and nothing is kept for the getters.  `want` drops outputs; `out` (a dict keyed the same way) supplies preallocated
+        arrays.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("skeleton", theta, beta)
+        return self._skeleton(c, beta, None, theta, False, want, out)[3]
+
+    def skeletonBackward(self, beta, theta, grad_world=None, grad_posed=None, grad_joints=None, want=("beta", "theta"), out=None):
+        """Vector-Jacobian product of `skeleton` (smplpp_skeleton_vjp): {"beta": dL/dbeta [N,10], "theta": dL/dtheta [N,25,3]} for the
+        cotangents grad_world [N,24,3,4], grad_posed [N,24,3] and grad_joints [N,24,3] (None = zero; at least one).  `want` drops
+        one; with `out` (a dict keyed the same way) the gradients are ADDED into its arrays, so the arrays launchBackward filled then
+        hold the gradient of a loss on vertices and skeleton."""
+        return self._skeleton_backward("skeletonBackward", beta, None, theta, False, grad_world, grad_posed, grad_joints, want, out)
+
+    def skeletonRotmat(self, beta, trans, rot, want=("world", "posed", "joints"), out=None):
+        """`skeleton` from rotation matrices (smplpp_skeleton_rotmat): beta [N,10] (None = zero), trans [N,3] (None = zero), rot
+        [N,24,3,3] used as given, as launchRotmat uses them."""
+        c = _Call("skeletonRotmat", rot, beta, trans)
+        return self._skeleton(c, beta, trans, rot, True, want, out)[3]
+
+    def skeletonRotmatBackward(self, beta, trans, rot, grad_world=None, grad_posed=None, grad_joints=None, want=("beta", "trans", "rot"),
+                               out=None):
+        """Vector-Jacobian product of `skeletonRotmat` (smplpp_skeleton_rotmat_vjp): {"beta": [N,10], "trans": [N,3], "rot": [N,24,3,3]},
+        "rot" as nine independent entries per joint (the convention of launchRotmatBackward).  Cotangents, `want` and `out` as in
+        skeletonBackward."""
+        return self._skeleton_backward("skeletonRotmatBackward", beta, trans, rot, True, grad_world, grad_posed, grad_joints, want, out)
+
+    def skeleton_differentiable(self, beta, theta):
+        """(world [N,24,3,4], posed [N,24,3], joints [N,24,3]) for device tensors beta [N,10], theta [N,25,3], differentiable with
+        torch.autograd in both: one smplpp_skeleton forward, one smplpp_skeleton_vjp backward, on torch's current stream.  First
+        derivatives only.  The outputs feed project_points_differentiable, align, Landmarks (as its `joints`) and the sequence terms."""
+        if torch is None:
+            raise SmplppError(1, "skeleton_differentiable needs torch")
+        return _SkeletonFunction.apply(beta, theta, self)
+
+    def skeleton_rotmat_differentiable(self, beta, trans, rot):
+        """skeleton_differentiable from rotation matrices: differentiable in beta [N,10], trans [N,3] and rot [N,24,3,3] (nine
+        independent entries per joint): smplpp_skeleton_rotmat forward, smplpp_skeleton_rotmat_vjp backward."""
+        if torch is None:
+            raise SmplppError(1, "skeleton_rotmat_differentiable needs torch")
+        return _SkeletonRotmatFunction.apply(beta, trans, rot, self)
+
     def launchStatus(self):
         """Status word of the launches since the last read (synchronises the current stream): bit 0 = an operand left the
         input range of the default fused kernel (include/smplpp_hip.h, smplpp_fk_status).  Host-space launches raise instead."""
@@ -1149,6 +1239,46 @@ if torch is not None:
                 return None, None, None, None
             g = ctx.smpl.launchRotmatBackward(beta, trans, rot, grad_verts=grad_verts, grad_joints=grad_joints, rest=rest)
             return tuple(g[k] if need else None for k, need in zip(("beta", "trans", "rot"), ctx.needs_input_grad)) + (None,)
+
+    class _SkeletonFunction(torch.autograd.Function):
+        """smplpp_skeleton forward / smplpp_skeleton_vjp backward (SMPL.skeleton_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, beta, theta, smpl):
+            c = _Call("skeleton_differentiable", theta, beta, device_only=True)
+            beta, _, theta, out = smpl._skeleton(c, beta, None, theta, False, ("world", "posed", "joints"))
+            ctx.smpl = smpl
+            ctx.save_for_backward(beta, theta)
+            return out["world"], out["posed"], out["joints"]
+
+        @staticmethod
+        def backward(ctx, grad_world, grad_posed, grad_joints):
+            beta, theta = ctx.saved_tensors
+            want = tuple(k for k, need in zip(("beta", "theta"), ctx.needs_input_grad) if need)
+            if not want or (grad_world is None and grad_posed is None and grad_joints is None):
+                return None, None, None
+            g = ctx.smpl.skeletonBackward(beta, theta, grad_world, grad_posed, grad_joints, want=want)
+            return g.get("beta"), g.get("theta"), None
+
+    class _SkeletonRotmatFunction(torch.autograd.Function):
+        """smplpp_skeleton_rotmat forward / smplpp_skeleton_rotmat_vjp backward (SMPL.skeleton_rotmat_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, beta, trans, rot, smpl):
+            c = _Call("skeleton_rotmat_differentiable", rot, beta, trans, device_only=True)
+            beta, trans, rot, out = smpl._skeleton(c, beta, trans, rot, True, ("world", "posed", "joints"))
+            ctx.smpl = smpl
+            ctx.save_for_backward(beta, trans, rot)
+            return out["world"], out["posed"], out["joints"]
+
+        @staticmethod
+        def backward(ctx, grad_world, grad_posed, grad_joints):
+            beta, trans, rot = ctx.saved_tensors
+            want = tuple(k for k, need in zip(("beta", "trans", "rot"), ctx.needs_input_grad) if need)
+            if not want or (grad_world is None and grad_posed is None and grad_joints is None):
+                return None, None, None, None
+            g = ctx.smpl.skeletonRotmatBackward(beta, trans, rot, grad_world, grad_posed, grad_joints, want=want)
+            return g.get("beta"), g.get("trans"), g.get("rot"), None
 
     class _FKDisplacedFunction(torch.autograd.Function):
         """smplpp_fk + smplpp_vertex_offsets forward / smplpp_vertex_offsets_vjp + smplpp_fk_vjp(rest = rest_displaced) backward
