@@ -261,6 +261,23 @@ public:
     return rot;
   }
 
+  // Its vector-Jacobian product (smplpp_axis_angle_to_rotmat_vjp): dL/daa [..., 3] for dL/drot = gradRot [..., 3, 3], nine independent
+  // entries per matrix, by the derivative launchBackward and skeletonBackward contract with (finite at aa = 0 and at |aa| = pi).
+  // `accumulate` non-null: the gradient is added into it (and it is returned).
+  Tensor axisAngleToRotmatBackward(const Tensor & aa, const Tensor & gradRot, Tensor * accumulate = nullptr) const
+  {
+    if(aa.shape.empty() || aa.shape.back() != 3 || aa.numel() == 0 || aa.dtype != kFloat32 || gradRot.dtype != kFloat32 ||
+       gradRot.numel() != aa.numel() * 3 || (accumulate && (accumulate->dtype != kFloat32 || accumulate->numel() != aa.numel())))
+      throw Exception("SMPL", "axisAngleToRotmatBackward: expected float32 aa [..., 3] and gradRot [..., 3, 3]");
+    Tensor local;
+    if(!accumulate) local = Tensor(std::vector<int64_t>(aa.shape.begin(), aa.shape.end()));
+    Tensor & out = accumulate ? *accumulate : local;
+    check(smplpp_axis_angle_to_rotmat_vjp(device_.index, aa.numel() / 3, aa.ptr(), gradRot.ptr(), out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST,
+                                          nullptr),
+          "SMPL");
+    return out;
+  }
+
   // launch from rotation matrices (smplpp_fk_rotmat): beta [N,10], trans [N,3] (root translation), rot [N,24,3,3] row-major, joint 0
   // the root orientation, used as given.  An empty beta or trans = zero.  The getters return its outputs as they do launch's.
   void launchRotmat(const Tensor & beta, const Tensor & trans, const Tensor & rot)

@@ -1011,6 +1011,59 @@ int smplpp_align_vjp(int device, int64_t n, int64_t K, const float * source, con
                      const float * grad_aligned /*[n,K,3] nullable*/, const float * grad_energy /*[n] nullable*/,
                      float * grad_source /*[n,K,3] nullable*/, float * grad_target /*[n,K,3] nullable*/, int accumulate, int space,
                      void * stream);
+/* ------------------------------------------------------------------ the orientation term on world joint frames
+ * What consumes the orientations smplpp_skeleton returns: per frame f and sensor s, the 3 x 3 block A of joint joint[s] in
+ * frames [n,J,3,row_stride] against a target, through a constant bone-to-sensor offset.  frames is read in place: row_stride = 4 takes
+ * smplpp_skeleton's `world` as it is (column 3 is never read, and never written in grad_frames), row_stride = 3 a stack of matrices
+ * [n,J,3,3].  C = 3 compares whole orientations (an IMU), C = 1 or 2 the images of one or two bone-frame axes (a foot's up axis against
+ * the ground normal, a gaze direction, gravity).  O = offset[s] [3,C] (NULL reads as the first C columns of the identity, with the bits
+ * of passing them), T = target[f or 0][s] [3,C], w = weight[f or 0][s] (NULL reads as 1); Tn and Wn are each 1 (shared by all frames) or
+ * n.  The calls take no handle and no workspace: `device` as the stage calls.  All arithmetic is fp32, every operation rounded on its
+ * own (no FMA), '/' is the correctly rounded one, and there are no atomics.
+ * THE FORWARD RULE, per live sensor:
+ *  M_rc = (A_r0 O_0c + A_r1 O_1c) + A_r2 O_2c;   E = M - T, and residual = E;
+ *  q = the sum of E_rc E_rc, row-major (r outer, c inner), ascending from +0;
+ *  sensor_energy = w q for rho == 0, else p2 = rho rho, sensor_energy = w ((p2 q) / (p2 + q)), the Geman-McClure form of
+ *  smplpp_image_term.  For rotations and C = 3, q = 4 (1 - cos phi), phi the geodesic angle between A O and T.
+ * energy [n] = sum1024 (FIXED-ORDER SUMS above) of sensor_energy over the frame's sensors s.  The work split follows S (a wavefront per
+ * frame up to 64, a workgroup of 256 up to 1024, of 1024 above; a thread per sensor without energy) and changes no bit.
+ * DEAD SENSORS.  A sensor is dead when w is 0 or not finite, when joint[s] is outside [0, J) (nothing is read through it), or when any
+ * of the 9 entries of A, the 3 C of O or the 3 C of T is not finite.  It gives +0 in every output and every gradient, and touches
+ * neither its neighbours nor its frame's other sums.  (A negative finite weight is live.)
+ * energy [n], sensor_energy [n,S] and residual [n,S,3,C] may each be NULL, not all.  The bits do not depend on n, on the frame's slot, on
+ * the memory space or on which outputs are asked for.
+ *  - SMPLPP_ERR_INVALID: n, J or S <= 0, C outside 1..3, row_stride not 3 or 4, Tn or Wn not 1 or n, rho negative or not finite, a NULL
+ *    frames, joint or target, every output NULL, n J 12 or n S 9 beyond int32 indexing, a bad space (the outputs are untouched).  Device
+ *    data is never refused. */
+int smplpp_orientation_term(int device, int64_t n, int64_t J, int64_t row_stride /*3 or 4*/, const float * frames /*[n,J,3,row_stride]*/,
+                            int64_t S, int64_t C /*1, 2 or 3*/, const int64_t * joint /*[S]*/, const float * offset /*[S,3,C] nullable*/,
+                            const float * target /*[Tn,S,3,C]*/, int64_t Tn, const float * weight /*[Wn,S] nullable = 1*/, int64_t Wn,
+                            float rho, float * energy /*[n] nullable*/, float * sensor_energy /*[n,S] nullable*/,
+                            float * residual /*[n,S,3,C] nullable*/, int space, void * stream);
+/* Its vector-Jacobian product to the frames, the offsets and the target, with the forward recomputed by the forward's operations.  A NULL
+ * cotangent reads as +0.  Per live sensor:
+ *  g = grad_energy[f] + grad_sensor_energy[f,s];  m = w for rho == 0, else d = p2 / (p2 + q), m = w (d d);
+ *  G_rc = ((2 g) m) E_rc + grad_residual[f,s]_rc.
+ *  grad_frames[f,j]_rk, the 3 x 3 entries only: the sum over the live sensors with joint[s] = j, IN ASCENDING s FROM +0, of (G O^T)_rk =
+ *       the sum over c of G_rc O_kc, ascending c from the first product (G_r0 O_k0, then + G_r1 O_k1, then + G_r2 O_k2, up to C).  A
+ *       gather with no atomics: several sensors may share a joint.  A joint with no live sensor gets +0, and is left alone under
+ *       accumulate.  Column 3 of a row_stride = 4 buffer is never written, so with accumulate = 1 the result lands in the grad_world
+ *       buffer that goes to smplpp_skeleton_vjp.
+ *  grad_target[f,s] = -G for Tn = n; for Tn = 1, grad_target[0,s]_rc = sum1024 over the frames f, ascending, of -G_rc.
+ *  grad_offset[s]_kc = sum1024 over the frames f, ascending, of (A^T G)_kc = (A_0k G_0c + A_1k G_1c) + A_2k G_2c.  It may be asked for
+ *       under a NULL offset (the gradient at the identity columns).
+ * A dead sensor adds +0 to every sum.  There is no gradient to the weights.  accumulate = 0 stores, 1 is one fp32 add onto what is there.
+ * Each output may be NULL, not all.  The bits do not depend on n (per-frame outputs), on the memory space or on which outputs and
+ * cotangents are given.  At most two launches: grad_frames and a per-frame grad_target together (a thread per (frame, sensor), then a
+ * thread per (frame, joint) that adds its sensors from LDS), and the sums across the frames (a workgroup of 1024 per sensor).
+ *  - SMPLPP_ERR_INVALID: as the forward (cotangents for outputs), every cotangent NULL, accumulate not 0 or 1 (the outputs are
+ *    untouched). */
+int smplpp_orientation_term_vjp(int device, int64_t n, int64_t J, int64_t row_stride, const float * frames, int64_t S, int64_t C,
+                                const int64_t * joint, const float * offset, const float * target, int64_t Tn, const float * weight, int64_t Wn,
+                                float rho, const float * grad_energy /*[n] nullable*/, const float * grad_sensor_energy /*[n,S] nullable*/,
+                                const float * grad_residual /*[n,S,3,C] nullable*/, float * grad_frames /*[n,J,3,row_stride] nullable*/,
+                                float * grad_offset /*[S,3,C] nullable*/, float * grad_target /*[Tn,S,3,C] nullable*/, int accumulate,
+                                int space, void * stream);
 /* The sweep grid of node/node.cpp:1023-1073 for ONE frame of posed vertices [V,3]: cells of GRID_SCALE = 0.025 m
  * (toolbox/GridUtils.hpp:28) from getGridIdxFloor(min) to getGridIdxCeil(max) per axis (:46-60) -> grid_min [3] (cell
  * index of the first cell), grid_num [3]; cells are ordered x outermost, z innermost like the reference's loops (:1037-1048).
@@ -1174,6 +1227,15 @@ int smplpp_rotmat_to_axis_angle(int device, int64_t n, const float * rot, float 
  * angle = ||aa + 1e-8||, so aa = 0 gives the identity without a branch), with the operation order of smplpp_fk's pose step: the bits
  * smplpp_fk computes internally for the same axis-angle. */
 int smplpp_axis_angle_to_rotmat(int device, int64_t n, const float * aa /*[n,3]*/, float * rot /*[n,3,3]*/, int space, void * stream);
+/* Its vector-Jacobian product: grad_aa[i][m] = sum_q grad_rot[i][q] dR_q/daa_m, q ascending from +0, each product and each sum rounded
+ * on its own, grad_rot as nine independent entries per row.  dR/daa_m is the derivative of the same formula, ||aa + 1e-8|| included, by
+ * the function smplpp_skeleton_vjp and smplpp_fk_vjp contract with: it is finite at aa = 0 and at |aa| = pi.  So fed with the grad_rot
+ * of smplpp_skeleton_rotmat_vjp it gives grad_theta[:, 1:] of smplpp_skeleton_vjp (to rounding: the shared function is compiled into
+ * each kernel).  With smplpp_sequence_smoothness_vjp at C = 9 it carries a rotation-space smoothness back to theta.  accumulate = 0
+ * stores, 1 is one fp32 add onto what is there.  A thread per (row, m); no handle, no workspace.
+ *  - SMPLPP_ERR_INVALID: n <= 0, a NULL pointer, accumulate not 0 or 1, a bad space (grad_aa is untouched). */
+int smplpp_axis_angle_to_rotmat_vjp(int device, int64_t n, const float * aa /*[n,3]*/, const float * grad_rot /*[n,3,3]*/,
+                                    float * grad_aa /*[n,3]*/, int accumulate, int space, void * stream);
 
 #ifdef __cplusplus
 }

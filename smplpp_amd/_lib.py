@@ -144,6 +144,10 @@ def load():
         "smplpp_align": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_align_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, vp, vp, C.c_int,
                              C.c_int, vp],
+        "smplpp_orientation_term": [C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64,
+                                    C.c_float, vp, vp, vp, C.c_int, vp],
+        "smplpp_orientation_term_vjp": [C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64,
+                                        C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_sweep_grid": [vp, vp, vp, vp, C.c_int64, vp, vp, i64p, C.c_int, vp],
         "smplpp_adjacent_faces": [vp, C.c_int64, C.c_int64, i64p, f32p, i64p],
         "smplpp_ik_create": [vp, C.c_int64, C.c_int64, vp, C.POINTER(vp)],
@@ -173,6 +177,7 @@ def load():
         "smplpp_vposer_jacobian": [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_rotmat_to_axis_angle": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
         "smplpp_axis_angle_to_rotmat": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
+        "smplpp_axis_angle_to_rotmat_vjp": [C.c_int, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name, None)

@@ -143,7 +143,7 @@ struct DevBuf
 };
 
 // The staging slots of a handle's host-space calls (staging.h): slot k holds the k-th staged argument of whichever call is running
-constexpr int ARENA_SLOTS = 10; // the widest call stages 10 arguments: smplpp_image_term_vjp (smplpp_image_term 9; smplpp_silhouette and others 8)
+constexpr int ARENA_SLOTS = 11; // the widest call stages 11 arguments: smplpp_orientation_term_vjp (smplpp_image_term_vjp 10, smplpp_image_term 9)
 struct Arena
 {
   DevBuf slot[ARENA_SLOTS];

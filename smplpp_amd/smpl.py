@@ -346,6 +346,15 @@ class SMPL:
         check(_lib.load().smplpp_axis_angle_to_rotmat(self._device, rows, _ptr(aa), _ptr(rot), c.space, c.stream))
         return rot.reshape(tuple(shape[:-1]) + (3, 3))
 
+    def axisAngleToRotmatBackward(self, aa, grad_rot, out=None):
+        """Vector-Jacobian product of axisAngleToRotmat (smplpp_axis_angle_to_rotmat_vjp): dL/daa [..., 3] for dL/drot = grad_rot
+        [..., 3, 3], nine independent entries per matrix, by the derivative skeletonBackward and launchBackward contract with (finite
+        at aa = 0 and at |aa| = pi).  With `out` the gradient is added into it.  orientation.axis_angle_to_rotmat_differentiable is
+        the autograd form."""
+        from . import orientation
+
+        return orientation.axis_angle_to_rotmat_backward(aa, grad_rot, out=out, device=self._device)
+
     def _fk_rotmat(self, c, beta, trans, rot, want, out=None):
         """smplpp_fk_rotmat in the space of `c`: (beta, trans, rot as passed to it, {"verts", "joints", "xforms", "rest"})."""
         n, V = int(rot.shape[0]) if c.dev else len(rot), self.vertex_num
