@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <fstream>
+#include <limits>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -521,6 +522,58 @@ public:
   {
     return distanceBackward(smplpp_mesh_point_distance_vjp, true, points, index, gradSqdist, gradPoints, accumulate,
                             "Cannot back-propagate through the mesh-to-point distance!");
+  }
+  // Normal-compatible, distance-capped correspondences on the last launch's vertices (smplpp_point_mesh_distance_compatible /
+  // smplpp_mesh_point_distance_compatible, which state the rule).  pointNormals [N,K,3] need not be unit; an undefined tensor (Tensor()): no
+  // normal test.  maxSqdist is the squared cap (+inf: none).  An unmatched row has face / index -1 and zeros elsewhere.  The faces go to
+  // pointMeshDistanceCompatibleBackward, the indices straight to meshPointDistanceBackward (which ignores -1).
+  PointMeshDistance pointMeshDistanceCompatible(const Tensor & points, const Tensor & pointNormals, float cosMin = 0.5f,
+                                                float maxSqdist = std::numeric_limits<float>::infinity()) const
+  {
+    const char * what = "Cannot compute the compatible point-to-mesh distance!";
+    const int64_t n = pointsFor(points, what), K = points.size(1);
+    const bool normals = pointNormals.defined();
+    if(normals && (pointNormals.dtype != kFloat32 || pointNormals.shape != points.shape)) throw Exception("SMPL", what);
+    PointMeshDistance r{Tensor({n, K}, kInt64), Tensor({n, K, 3}), Tensor({n, K, 3}), Tensor({n, K})};
+    check(smplpp_point_mesh_distance_compatible(m_.get(), n, verts_.ptr(), K, points.ptr(), normals ? pointNormals.ptr() : nullptr, cosMin,
+                                                maxSqdist, r.face.idata.data(), r.weights.ptr(), r.closest.ptr(), r.sqdist.ptr(), SMPLPP_HOST,
+                                                nullptr),
+          "SMPL");
+    return r;
+  }
+  // pointMeshDistanceBackward at the faces pointMeshDistanceCompatible chose: an unmatched query (face -1) contributes nothing (it
+  // goes to smplpp_point_mesh_distance_vjp, which refuses -1 in host space, as face 0 with a zero cotangent).
+  Tensor pointMeshDistanceCompatibleBackward(const Tensor & points, const Tensor & face, const Tensor & gradSqdist,
+                                             Tensor * gradPoints = nullptr, Tensor * accumulate = nullptr) const
+  {
+    Tensor f = face, g = gradSqdist;
+    if(f.idata.size() == g.data.size())
+      for(size_t i = 0; i < f.idata.size(); i++)
+        if(f.idata[i] < 0)
+        {
+          f.idata[i] = 0;
+          g.data[i] = 0.0f;
+        }
+    return pointMeshDistanceBackward(points, f, g, gradPoints, accumulate);
+  }
+  // vertNormals [N,V,3] null: the whole-mesh vertex normals of the last launch (calcMeshVertexNormals)
+  MeshPointDistance meshPointDistanceCompatible(const Tensor & points, const Tensor & pointNormals, float cosMin = 0.5f,
+                                                float maxSqdist = std::numeric_limits<float>::infinity(),
+                                                const Tensor * vertNormals = nullptr) const
+  {
+    const char * what = "Cannot compute the compatible mesh-to-point distance!";
+    const int64_t n = pointsFor(points, what), K = points.size(1);
+    const bool normals = pointNormals.defined();
+    if(normals && (pointNormals.dtype != kFloat32 || pointNormals.shape != points.shape)) throw Exception("SMPL", what);
+    if(vertNormals && (vertNormals->dtype != kFloat32 || vertNormals->shape != verts_.shape)) throw Exception("SMPL", what);
+    Tensor own;
+    if(normals && !vertNormals) own = calcMeshVertexNormals();
+    const float * vn = !normals ? nullptr : vertNormals ? vertNormals->ptr() : own.ptr();
+    MeshPointDistance r{Tensor({n, V_}, kInt64), Tensor({n, V_})};
+    check(smplpp_mesh_point_distance_compatible(m_.get(), n, verts_.ptr(), vn, K, points.ptr(), normals ? pointNormals.ptr() : nullptr,
+                                                cosMin, maxSqdist, r.index.idata.data(), r.sqdist.ptr(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
   }
   // Generalized winding numbers of each frame's mesh at points [N,K,3] on the last launch's vertices (smplpp_point_mesh_winding):
   // winding [N,K] (the bits calcSweepGrid's cells have at the same position), inside [N,K] kInt64 0 / 1 (winding > 0.5).

@@ -286,6 +286,51 @@ int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const float * ve
                                    const int64_t * index /*[n,V]*/, const float * grad_sqdist /*[n,V]*/,
                                    float * grad_verts /*[n,V,3] nullable*/, float * grad_points /*[n,K,3] nullable*/,
                                    int accumulate, int space, void * stream);
+/* Normal-compatible, distance-capped scan correspondences: smplpp_point_mesh_distance and smplpp_mesh_point_distance with the two
+ * filters of every registration pipeline INSIDE the search (a filter after the search loses the point: the right face was never
+ * found).  The rule, stated once; a float32 numpy restatement reproduces every bit:
+ *  - compatibility of two normals m, q (neither is normalised by the library): s = (m.x q.x + m.y q.y) + m.z q.z, and mm, qq
+ *    formed the same way from (m, m) and (q, q); compatible iff  s >= 0  &&  mm*qq > 0  &&  s*s >= (cos_min*cos_min)*(mm*qq).
+ *    Every operation is rounded to fp32 on its own (no FMA).  A NaN anywhere makes the pair incompatible, and so does a zero
+ *    normal (mm*qq = 0).  cos_min lies in [0, 1]: the angle between the normals is at most acos(cos_min).
+ *  - face normal: m = (b - a) x (c - a) of the face's stored corners a, b, c, with e1 = b - a, e2 = c - a:
+ *    m.x = (e1.y*e2.z) - (e1.z*e2.y), m.y = (e1.z*e2.x) - (e1.x*e2.z), m.z = (e1.x*e2.y) - (e1.y*e2.x), unfused.  A degenerate
+ *    face has mm = 0 and is never compatible.
+ *  - vertex normals: vert_normals is the caller's (smplpp_mesh_vertex_normals gives one); the library adds no rule.
+ *  - point -> mesh: a face is a candidate iff it is compatible with the query's normal and its squared distance d, from the
+ *    point-triangle evaluation of smplpp_point_mesh_distance, has d <= max_sqdist.  With mn the minimum of d over the candidates, the
+ *    answer is the lowest face id among the candidates with d <= mn (1 + 1e-6) + 1e-12; weights, closest and sqdist are those
+ *    smplpp_point_mesh_distance gives for that face.
+ *  - mesh -> point: smplpp_mesh_point_distance's rule (the smallest d, on equal d the lowest point index, a non-finite d never
+ *    chosen) over the points that are compatible with the vertex's normal and have d <= max_sqdist.
+ *  - max_sqdist may be +inf (no cap); a threshold equal to an attained d keeps it (<=).
+ *  - no candidate: face / index = -1 and every other output of that row is +0.
+ *  - a query or vertex with a non-finite coordinate or (when given) normal is unmatched, whatever the filter; a point with a
+ *    non-finite normal is never chosen.
+ *  - a NULL normals pointer: no normal test.  smplpp_mesh_point_distance_compatible tests normals only when BOTH arrays are given.
+ *    Without a normal test and with max_sqdist = +inf, finite inputs (whose distances do not overflow) give exactly the bits of
+ *    smplpp_point_mesh_distance / smplpp_mesh_point_distance.
+ *  - the bits do not depend on n, on the frame's position in the batch, on the memory space, on the dispatch form
+ *    (SMPLPP_POINT_DISTANCE_FORM, as for smplpp_point_mesh_distance: both forms evaluate the minimum and every face of the band;
+ *    the tiled form's cull radius starts at max_sqdist, not at the nearest vertex, which may have ineligible faces only) or on how
+ *    the mesh -> point call splits K.  One exception, inherited: `weights` has the bits smplpp_point_mesh_distance gives in the same
+ *    form, and that call's two forms round the weights of a point inside a face differently (measured: the last bits, never face,
+ *    closest or sqdist).
+ *  - backward: there is no new product.  smplpp_point_mesh_distance_vjp and smplpp_mesh_point_distance_vjp take the face / index
+ *    returned here.  In device space both ignore -1.  In HOST space smplpp_mesh_point_distance_vjp accepts -1 but
+ *    smplpp_point_mesh_distance_vjp refuses it: replace the face of an unmatched query by 0 and give it a zero cotangent (a zero
+ *    cotangent contributes nothing); the Python wrappers do so.
+ *  - weights and closest are nullable; face / index and sqdist are not.
+ *  - SMPLPP_ERR_INVALID (outputs untouched): bad arguments, cos_min outside [0, 1] or NaN, max_sqdist negative or NaN, the limits
+ *    of the unfiltered calls (point -> mesh: a model without faces, n * K beyond int32; mesh -> point: n * K or n * V beyond int32). */
+int smplpp_point_mesh_distance_compatible(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t K,
+                                          const float * points /*[n,K,3]*/, const float * point_normals /*[n,K,3] nullable*/, float cos_min,
+                                          float max_sqdist, int64_t * face /*[n,K]*/, float * weights /*[n,K,3] nullable*/,
+                                          float * closest /*[n,K,3] nullable*/, float * sqdist /*[n,K]*/, int space, void * stream);
+int smplpp_mesh_point_distance_compatible(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/,
+                                          const float * vert_normals /*[n,V,3] nullable*/, int64_t K, const float * points /*[n,K,3]*/,
+                                          const float * point_normals /*[n,K,3] nullable*/, float cos_min, float max_sqdist,
+                                          int64_t * index /*[n,V]*/, float * sqdist /*[n,V]*/, int space, void * stream);
 /* Generalized winding numbers at K query points per frame (which points lie inside the body: penetration and one-sided scan
  * terms): for each of n frames, igl::winding_number of that frame's posed mesh verts [n,V,3] at each of K points [n,K,3].
  *  - winding [n,K] has exactly the bits smplpp_sweep_grid gives at a cell of the same fp32 position: the same per-face term

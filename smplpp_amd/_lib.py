@@ -82,6 +82,8 @@ def load():
         "smplpp_point_mesh_distance_vjp": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_mesh_point_distance": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_mesh_point_distance_vjp": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_point_mesh_distance_compatible": [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_mesh_point_distance_compatible": [vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_float, C.c_float, vp, vp, C.c_int, vp],
         "smplpp_point_mesh_winding": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_point_mesh_signed_distance": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_point_mesh_signed_distance_vjp": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],

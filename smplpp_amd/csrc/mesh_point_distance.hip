@@ -15,6 +15,7 @@
 //                         cotangent or an index out of [0, K) gives no record (key -1) and a zero grad_verts.
 //  record_gather_kernel<MpdRecord>  (distance_vjp.h) grad_points: one fixed-order sum per point, ascending vertex.
 #include "distance_vjp.h"
+#include "scan_compat.h"
 
 #include <cmath>
 
@@ -154,6 +155,105 @@ __global__ __launch_bounds__(MPD_THREADS) void mpd_scan_kernel(const float * __r
   }
 }
 
+// smplpp_mesh_point_distance_compatible: mpd_scan_kernel's scan restricted to the points with d <= max_sq whose normal passes
+// compat_normals (scan_compat.h) against the vertex's (NORMALS).  The vertex normal (m, mm) sits in registers beside the vertex, the
+// point normals (q, qq) pass through LDS in a second float4 tile; a non-finite normal is staged as NaN, which fails the test.  The
+// same K chunks, partials and mpd_reduce_kernel: a chunk without an eligible point writes (+inf, -1).
+template<bool NORMALS>
+__global__ __launch_bounds__(MPD_THREADS) void mpdc_scan_kernel(const float * __restrict__ verts, const float * __restrict__ vnormals,
+                                                                const float * __restrict__ points, const float * __restrict__ pnormals,
+                                                                float c2, float max_sq, int64_t * __restrict__ index_out,
+                                                                float * __restrict__ sq_out, float * __restrict__ part_d,
+                                                                int32_t * __restrict__ part_k, int64_t V, int64_t K, int64_t vblocks,
+                                                                int64_t chunks, int64_t chunk)
+{
+  __shared__ float4 s_p[MPD_TILE];
+  __shared__ float4 s_q[NORMALS ? MPD_TILE : 1];
+  const uint32_t b = blockIdx.x; // (the grid is below 2^31: 32-bit index arithmetic)
+  const int64_t vb = b % (uint32_t)vblocks;
+  const int64_t fc = b / (uint32_t)vblocks; // frame * chunks + c
+  const int64_t c = (uint32_t)fc % (uint32_t)chunks, frame = (uint32_t)fc / (uint32_t)chunks;
+  const int64_t k0 = c * chunk, k1 = k0 + chunk < K ? k0 + chunk : K;
+  const int t = threadIdx.x;
+  const float * vf = verts + frame * V * 3;
+  const float * pf = points + frame * K * 3;
+  float vx[MPD_VPL], vy[MPD_VPL], vz[MPD_VPL], bd[MPD_VPL];
+  float4 vm[MPD_VPL];
+  int bk[MPD_VPL];
+#pragma unroll
+  for(int i = 0; i < MPD_VPL; i++)
+  {
+    int64_t v = vb * MPD_VBLOCK + i * MPD_THREADS + t;
+    if(v >= V) v = V - 1; // lanes past V repeat the last vertex and write nothing
+    vx[i] = vf[v * 3];
+    vy[i] = vf[v * 3 + 1];
+    vz[i] = vf[v * 3 + 2];
+    vm[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr(NORMALS)
+    {
+      const float * nf = vnormals + (frame * V + v) * 3;
+      const float nx = nf[0], ny = nf[1], nz = nf[2];
+      vm[i] = compat_finite3(nx, ny, nz) ? make_float4(nx, ny, nz, compat_dot(nx, ny, nz, nx, ny, nz)) : make_float4(NAN, NAN, NAN, NAN);
+    }
+    bd[i] = INFINITY;
+    bk[i] = -1;
+  }
+  for(int64_t base = k0; base < k1; base += MPD_TILE)
+  {
+    const int cnt = (int)(k1 - base < MPD_TILE ? k1 - base : MPD_TILE);
+    __syncthreads();
+    for(int j = t; j < cnt; j += MPD_THREADS)
+    {
+      const float * p = pf + (base + j) * 3;
+      s_p[j] = make_float4(p[0], p[1], p[2], 0.0f);
+      if constexpr(NORMALS)
+      {
+        const float * qf = pnormals + (frame * K + base + j) * 3;
+        const float qx = qf[0], qy = qf[1], qz = qf[2];
+        s_q[j] = compat_finite3(qx, qy, qz) ? make_float4(qx, qy, qz, compat_dot(qx, qy, qz, qx, qy, qz)) : make_float4(NAN, NAN, NAN, NAN);
+      }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for(int j = 0; j < cnt; j++)
+    {
+      const float4 p = s_p[j];
+      const int k = (int)base + j;
+#pragma unroll
+      for(int i = 0; i < MPD_VPL; i++)
+      {
+        const float d = mpd_sqdist(vx[i], vy[i], vz[i], p.x, p.y, p.z);
+        if(d < bd[i] && d <= max_sq)
+        {
+          bool take = true;
+          if constexpr(NORMALS) take = compat_normals(vm[i], s_q[j], c2);
+          if(take)
+          {
+            bd[i] = d;
+            bk[i] = k;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for(int i = 0; i < MPD_VPL; i++)
+  {
+    const int64_t v = vb * MPD_VBLOCK + i * MPD_THREADS + t;
+    if(v >= V) continue;
+    if(chunks == 1)
+    {
+      index_out[frame * V + v] = bk[i];
+      sq_out[frame * V + v] = bk[i] < 0 ? 0.0f : bd[i];
+    }
+    else
+    {
+      part_d[fc * V + v] = bd[i];
+      part_k[fc * V + v] = bk[i];
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void mpd_reduce_kernel(const float * __restrict__ part_d, const int32_t * __restrict__ part_k,
                                                          int64_t * __restrict__ index_out, float * __restrict__ sq_out, int64_t V,
                                                          int64_t chunks, int64_t nv)
@@ -244,6 +344,37 @@ static int mpd_forward_device(smplpp_model * m, MeshPointDistState * s, int64_t 
   return SMPLPP_OK;
 }
 
+// smplpp_mesh_point_distance_compatible, all pointers on the device: NORMALS when both normal arrays are given
+template<bool NORMALS>
+static int mpdc_forward_device(smplpp_model * m, MeshPointDistState * s, int64_t n, const float * verts, const float * vnormals, int64_t K,
+                               const float * points, const float * pnormals, float c2, float max_sq, int64_t * index, float * sqdist,
+                               hipStream_t st)
+{
+  const int64_t V = m->V;
+  const int64_t vblocks = (V + MPD_VBLOCK - 1) / MPD_VBLOCK;
+  const int64_t chunk = mpd_chunk_len(n, K, vblocks);
+  const int64_t chunks = (K + chunk - 1) / chunk;
+  float * pd = nullptr;
+  int32_t * pk = nullptr;
+  if(chunks > 1)
+  {
+    HIP_TRY(s->part_d.reserve(sizeof(float) * (size_t)(n * chunks * V)));
+    HIP_TRY(s->part_k.reserve(sizeof(int32_t) * (size_t)(n * chunks * V)));
+    pd = s->part_d.as<float>();
+    pk = s->part_k.as<int32_t>();
+  }
+  mpdc_scan_kernel<NORMALS><<<dim3((unsigned)(n * chunks * vblocks)), dim3(MPD_THREADS), 0, st>>>(verts, vnormals, points, pnormals, c2, max_sq,
+                                                                                                  index, sqdist, pd, pk, V, K, vblocks, chunks,
+                                                                                                  chunk);
+  HIP_TRY(hipGetLastError());
+  if(chunks > 1)
+  {
+    mpd_reduce_kernel<<<dim3((unsigned)((n * V + 255) / 256)), dim3(256), 0, st>>>(pd, pk, index, sqdist, V, chunks, n * V);
+    HIP_TRY(hipGetLastError());
+  }
+  return SMPLPP_OK;
+}
+
 static int mpd_vjp_device(smplpp_model * m, MeshPointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
                           const int64_t * index, const float * gsq, float * gv, float * gp, int accumulate, hipStream_t st)
 {
@@ -284,6 +415,31 @@ extern "C" int smplpp_mesh_point_distance(smplpp_model * m, int64_t n, const flo
   int64_t * io = fr.out(index, (size_t)n * m->V);
   float * so = fr.out(sqdist, (size_t)n * m->V);
   return fr.run([&] { return mpd_forward_device(m, s, n, v, K, p, io, so, fr.st); });
+}
+
+extern "C" int smplpp_mesh_point_distance_compatible(smplpp_model * m, int64_t n, const float * verts, const float * vert_normals, int64_t K,
+                                                     const float * points, const float * point_normals, float cos_min, float max_sqdist,
+                                                     int64_t * index, float * sqdist, int space, void * stream)
+{
+  const char * fn = "smplpp_mesh_point_distance_compatible";
+  if(!m || n <= 0 || K <= 0 || !verts || !points || !index || !sqdist) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
+  int rc = compat_args(fn, cos_min, max_sqdist);
+  if(rc) return rc;
+  if((rc = mpd_check(fn, m, n, K, space))) return rc;
+  const bool normals = vert_normals && point_normals; // the test needs both sides
+  Frame fr(m->device, &m->arena, space, stream, "mesh-point distance (compatible)");
+  MeshPointDistState * s = mpd_state(m);
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * vn = normals ? fr.in(vert_normals, (size_t)n * m->V * 3) : nullptr;
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  const float * pn = normals ? fr.in(point_normals, (size_t)n * K * 3) : nullptr;
+  int64_t * io = fr.out(index, (size_t)n * m->V);
+  float * so = fr.out(sqdist, (size_t)n * m->V);
+  const float c2 = cos_min * cos_min;
+  return fr.run([&] {
+    return normals ? mpdc_forward_device<true>(m, s, n, v, vn, K, p, pn, c2, max_sqdist, io, so, fr.st)
+                   : mpdc_forward_device<false>(m, s, n, v, nullptr, K, p, nullptr, c2, max_sqdist, io, so, fr.st);
+  });
 }
 
 extern "C" int smplpp_mesh_point_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,

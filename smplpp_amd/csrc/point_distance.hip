@@ -18,6 +18,9 @@
 //                        Both culls are tri_culled_v's conservative sphere test, so the minimum and every face of the band are
 //                        evaluated; a minimum over fp32 values and the lowest id of a band do not depend on the scan order, and
 //                        every distance comes from the one noinline tri_sqdist_vals, so the bits are smplpp_closest_points'.
+// Compatible, distance-capped forward (smplpp_point_mesh_distance_compatible): pdc_query_kernel / pdc_tri_image_kernel /
+//  pdc_tiled_kernel<NORMALS> beside the kernels above, which stay as they are: the same two passes over the faces that pass the
+//  normal test of scan_compat.h and lie within max_sq, no seed, unmatched queries written as (-1, +0).
 // Backward (no search: the forward's face is an input):
 //  pd_vjp_record_kernel  per query: c and w recomputed with the forward's evaluation, r = p - c; grad_points = 2 g r and the record
 //                        (the face's three vertex ids, -2 g w_j r for j = 0..2).  A zero cotangent or an out-of-range face gives no
@@ -25,6 +28,7 @@
 //  record_gather_kernel<PdRecord>  (distance_vjp.h) grad_verts: one fixed-order sum per vertex, ascending record index, then corner.
 #include "mesh_device.h"
 #include "point_distance.h"
+#include "scan_compat.h"
 
 #include <cmath>
 
@@ -367,6 +371,343 @@ __global__ __launch_bounds__(PD_THREADS) void pd_tiled_kernel(const float * __re
   }
 }
 
+// ---- compatible, distance-capped search (smplpp_point_mesh_distance_compatible): new kernels beside the ones above, over the same
+// device headers.  A face is a candidate iff its unfused normal m passes compat_normals (scan_compat.h) against the query's normal
+// (NORMALS) and its distance d, from tri_sqdist_vals, has d <= max_sq.  Over the candidates: the minimum mn, then the lowest id
+// with d <= mn (1 + 1e-6) + 1e-12.  There is no nearest-vertex seed (a near vertex may belong to ineligible faces only): the cull
+// radius starts at max_sq.  A query without a candidate, or with a non-finite coordinate or normal, gets face -1 and +0 elsewhere.
+__device__ inline void pdc_write_unmatched(int64_t i, int64_t * face_out, float * w_out, float * closest_out, float * sq_out)
+{
+  face_out[i] = -1;
+  sq_out[i] = 0.0f;
+  for(int x = 0; x < 3; x++)
+  {
+    if(closest_out) closest_out[i * 3 + x] = 0.0f;
+    if(w_out) w_out[i * 3 + x] = 0.0f;
+  }
+}
+
+// per-query form: one 256-thread workgroup per query, closest_point_block's two passes restricted to the candidates
+template<bool NORMALS>
+__global__ __launch_bounds__(256) void pdc_query_kernel(const float * __restrict__ verts, const int32_t * __restrict__ faces,
+                                                        const float * __restrict__ points, const float * __restrict__ pnormals, float c2,
+                                                        float max_sq, int64_t * __restrict__ face_out, float * __restrict__ w_out,
+                                                        float * __restrict__ closest_out, float * __restrict__ sq_out, int64_t V, int64_t F,
+                                                        int64_t K)
+{
+  __shared__ float s_d[4], s_min;
+  __shared__ int s_f[4], s_argmin;
+  __shared__ int64_t s_face;
+  __shared__ float s_c[3], s_sq;
+  const int64_t i = blockIdx.x;
+  const float * vf = verts + (i / K) * V * 3;
+  const float p[3] = {points[i * 3], points[i * 3 + 1], points[i * 3 + 2]};
+  float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  bool ok = compat_finite3(p[0], p[1], p[2]); // (the same on every thread)
+  if constexpr(NORMALS)
+  {
+    q.x = pnormals[i * 3];
+    q.y = pnormals[i * 3 + 1];
+    q.z = pnormals[i * 3 + 2];
+    q.w = compat_dot(q.x, q.y, q.z, q.x, q.y, q.z);
+    ok = ok && compat_finite3(q.x, q.y, q.z);
+  }
+  if(!ok)
+  {
+    if(threadIdx.x == 0) pdc_write_unmatched(i, face_out, w_out, closest_out, sq_out);
+    return;
+  }
+  const int wave = threadIdx.x >> 6;
+  // pass 1: the minimum over the candidates
+  float best = INFINITY, lim = max_sq;
+  int bf = 0x7fffffff;
+  float sq = sqrtf(lim);
+  for(int64_t base = threadIdx.x; base < F; base += 256 * CP_BATCH)
+  {
+    TriBatch t;
+    load_tri_batch(vf, faces, F, base, 256, t);
+#pragma unroll
+    for(int b = 0; b < CP_BATCH; b++)
+    {
+      if(!t.valid[b]) continue;
+      const float * a = t.v[b];
+      if constexpr(NORMALS)
+        if(!compat_normals(compat_face_normal(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]), q, c2)) continue;
+      if(lim < INFINITY && tri_culled_v(a, a + 3, a + 6, p, sq)) continue;
+      const float d = tri_sqdist_vals(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], p[0], p[1], p[2]).x;
+      if(!(d <= max_sq)) continue;
+      const int f = (int)(base + (int64_t)b * 256);
+      if(d < best || (d == best && f < bf))
+      {
+        best = d;
+        bf = f;
+        if(d < lim)
+        {
+          lim = d;
+          sq = sqrtf(lim);
+        }
+      }
+    }
+  }
+  for(int off = 32; off > 0; off >>= 1)
+  {
+    const float od = __shfl_down(best, off, 64);
+    const int of = __shfl_down(bf, off, 64);
+    if(od < best || (od == best && of < bf))
+    {
+      best = od;
+      bf = of;
+    }
+  }
+  if((threadIdx.x & 63) == 0)
+  {
+    s_d[wave] = best;
+    s_f[wave] = bf;
+  }
+  __syncthreads();
+  if(threadIdx.x == 0)
+  {
+    int w = 0;
+    for(int j = 1; j < 4; j++)
+      if(s_d[j] < s_d[w] || (s_d[j] == s_d[w] && s_f[j] < s_f[w])) w = j;
+    s_min = s_d[w];
+    s_argmin = s_f[w];
+  }
+  __syncthreads();
+  const int amin = s_argmin;
+  if(amin == 0x7fffffff) // no candidate
+  {
+    if(threadIdx.x == 0) pdc_write_unmatched(i, face_out, w_out, closest_out, sq_out);
+    return;
+  }
+  // pass 2: the lowest candidate id within the tie band
+  const float thr = s_min * (1.0f + 1e-6f) + 1e-12f;
+  const float sq_thr = sqrtf(thr);
+  int cf = 0x7fffffff;
+  for(int64_t base = threadIdx.x; base < F && (int)base < cf; base += 256 * CP_BATCH)
+  {
+    TriBatch t;
+    load_tri_batch(vf, faces, F, base, 256, t);
+#pragma unroll
+    for(int b = 0; b < CP_BATCH; b++)
+    {
+      const int f = (int)(base + (int64_t)b * 256);
+      if(!t.valid[b] || f >= cf) continue; // ids ascend within a thread
+      const float * a = t.v[b];
+      if constexpr(NORMALS)
+        if(!compat_normals(compat_face_normal(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]), q, c2)) continue;
+      if(thr < INFINITY && tri_culled_v(a, a + 3, a + 6, p, sq_thr)) continue;
+      const float d = tri_sqdist_vals(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], p[0], p[1], p[2]).x;
+      if(d <= thr && d <= max_sq) cf = f;
+    }
+  }
+  for(int off = 32; off > 0; off >>= 1)
+  {
+    const int of = __shfl_down(cf, off, 64);
+    cf = of < cf ? of : cf;
+  }
+  __syncthreads(); // s_f is reused
+  if((threadIdx.x & 63) == 0) s_f[wave] = cf;
+  __syncthreads();
+  // (from here on written as closest_point_block ends and pd_query_kernel writes: the weights' evaluation is inlined, and how
+  // the compiler fuses its products follows the code around it)
+  if(threadIdx.x == 0)
+  {
+    int b = s_f[0];
+    for(int j = 1; j < 4; j++) b = s_f[j] < b ? s_f[j] : b;
+    if(b < 0 || (int64_t)b >= F) b = amin; // empty band: never index out of range
+    float c[3];
+    const float d = tri_sqdist_dev(vf, faces, b, p, c);
+    s_face = b;
+    s_c[0] = c[0]; s_c[1] = c[1]; s_c[2] = c[2];
+    s_sq = d;
+  }
+  __syncthreads();
+  if(threadIdx.x != 0) return;
+  const int64_t b = s_face;
+  face_out[i] = b;
+  sq_out[i] = s_sq;
+  if(closest_out)
+  {
+    closest_out[i * 3] = s_c[0];
+    closest_out[i * 3 + 1] = s_c[1];
+    closest_out[i * 3 + 2] = s_c[2];
+  }
+  if(w_out)
+  {
+    const float * a = vf + 3 * faces[b * 3];
+    const float * bb = vf + 3 * faces[b * 3 + 1];
+    const float * c = vf + 3 * faces[b * 3 + 2];
+    const float * p = points + i * 3;
+    float w[3];
+    tri_weights_vals(a[0], a[1], a[2], bb[0], bb[1], bb[2], c[0], c[1], c[2], p[0], p[1], p[2], w);
+    w_out[i * 3] = w[0];
+    w_out[i * 3 + 1] = w[1];
+    w_out[i * 3 + 2] = w[2];
+  }
+}
+
+// tiled form: pd_tri_image_kernel's image with, under NORMALS, a fourth float4 per face: (m.x, m.y, m.z, mm)
+template<bool NORMALS>
+__global__ __launch_bounds__(256) void pdc_tri_image_kernel(const float * __restrict__ verts, const int32_t * __restrict__ faces,
+                                                            float4 * __restrict__ img, int64_t V, int64_t F, int64_t n)
+{
+  constexpr int S = NORMALS ? 4 : 3;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n * F) return;
+  const int64_t f = i % F;
+  const float * vf = verts + (i / F) * V * 3;
+  const float * a = vf + 3 * faces[f * 3];
+  const float * b = vf + 3 * faces[f * 3 + 1];
+  const float * c = vf + 3 * faces[f * 3 + 2];
+  const float e1 = (b[0] - a[0]) * (b[0] - a[0]) + (b[1] - a[1]) * (b[1] - a[1]) + (b[2] - a[2]) * (b[2] - a[2]);
+  const float e2 = (c[0] - a[0]) * (c[0] - a[0]) + (c[1] - a[1]) * (c[1] - a[1]) + (c[2] - a[2]) * (c[2] - a[2]);
+  img[i * S] = make_float4(a[0], a[1], a[2], sqrtf(fmaxf(e1, e2)));
+  img[i * S + 1] = make_float4(b[0], b[1], b[2], 0.0f);
+  img[i * S + 2] = make_float4(c[0], c[1], c[2], 0.0f);
+  if constexpr(NORMALS) img[i * S + 3] = compat_face_normal(a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]);
+}
+
+// pd_tiled_kernel without the seed: 64 queries per workgroup, its 16 wavefronts split every tile of faces (1024 faces of three
+// float4, or 768 of four under NORMALS: the same 48 KiB).  The compatibility test reads the face's fourth float4 alone and comes
+// first; pass 1 culls against min(max_sq, running minimum over candidates), pass 2 against the band.
+template<bool NORMALS>
+__global__ __launch_bounds__(PD_THREADS) void pdc_tiled_kernel(const float4 * __restrict__ img, const float * __restrict__ points,
+                                                               const float * __restrict__ pnormals, float c2, float max_sq,
+                                                               const int32_t * __restrict__ perm, int64_t * __restrict__ face_out,
+                                                               float * __restrict__ w_out, float * __restrict__ closest_out,
+                                                               float * __restrict__ sq_out, int64_t F, int64_t K, int64_t blocks_per_frame)
+{
+  constexpr int S = NORMALS ? 4 : 3;
+  constexpr int TILE = PD_TILE * 3 / S, CH = TILE / PD_WAVES; // faces per tile, and per wavefront of a tile
+  __shared__ float4 s_tri[TILE * S];
+  __shared__ float s_d[PD_WAVES][64];
+  __shared__ int s_f[PD_WAVES][64];
+  const int64_t frame = blockIdx.x / blocks_per_frame;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t qn = (blockIdx.x % blocks_per_frame) * 64 + lane;
+  const bool live = qn < K;
+  const int64_t k = perm[frame * K + (live ? qn : K - 1)]; // lanes past K repeat the last query: they cull like it
+  const int64_t qi = frame * K + k;
+  const float p0 = points[qi * 3], p1 = points[qi * 3 + 1], p2 = points[qi * 3 + 2];
+  float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  bool ok = compat_finite3(p0, p1, p2);
+  if constexpr(NORMALS)
+  {
+    q.x = pnormals[qi * 3];
+    q.y = pnormals[qi * 3 + 1];
+    q.z = pnormals[qi * 3 + 2];
+    q.w = compat_dot(q.x, q.y, q.z, q.x, q.y, q.z);
+    ok = ok && compat_finite3(q.x, q.y, q.z);
+  }
+  const float4 * tf = img + frame * F * S;
+
+  // pass 1: the minimum over the candidates
+  float best = INFINITY, lim = max_sq;
+  int bf = 0x7fffffff;
+  float sq = sqrtf(lim);
+  for(int64_t fb = 0; fb < F; fb += TILE)
+  {
+    __syncthreads();
+    for(int j = threadIdx.x; j < TILE * S; j += PD_THREADS)
+      if(fb * S + j < F * S) s_tri[j] = tf[fb * S + j];
+    __syncthreads();
+    const int cnt = (int)(F - fb < TILE ? F - fb : TILE);
+    const int j1 = ok ? min(cnt, (wave + 1) * CH) : 0; // (a query that cannot match scans nothing)
+    for(int j = wave * CH; j < j1; j++)
+    {
+      if constexpr(NORMALS)
+        if(!compat_normals(s_tri[j * S + 3], q, c2)) continue;
+      const float4 A = s_tri[j * S];
+      if(lim < INFINITY && pd_culled(A, p0, p1, p2, sq)) continue;
+      const float4 B = s_tri[j * S + 1], C = s_tri[j * S + 2];
+      const float d = tri_sqdist_vals(A.x, A.y, A.z, B.x, B.y, B.z, C.x, C.y, C.z, p0, p1, p2).x;
+      if(!(d <= max_sq)) continue;
+      const int f = (int)fb + j;
+      if(d < best || (d == best && f < bf))
+      {
+        best = d;
+        bf = f;
+        if(d < lim)
+        {
+          lim = d;
+          sq = sqrtf(lim);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  s_d[wave][lane] = best;
+  s_f[wave][lane] = bf;
+  __syncthreads();
+  float mn = s_d[0][lane];
+  int amin = s_f[0][lane];
+  for(int w = 1; w < PD_WAVES; w++)
+    if(s_d[w][lane] < mn || (s_d[w][lane] == mn && s_f[w][lane] < amin))
+    {
+      mn = s_d[w][lane];
+      amin = s_f[w][lane];
+    }
+  const bool none = amin == 0x7fffffff; // no candidate (the same in every wavefront's copy of the lane)
+
+  // pass 2: the lowest candidate id within the tie band (ids ascend within a lane)
+  const float thr = mn * (1.0f + 1e-6f) + 1e-12f;
+  const float sq_thr = sqrtf(thr);
+  int cf = 0x7fffffff;
+  for(int64_t fb = 0; fb < F; fb += TILE)
+  {
+    if(__syncthreads_and(none || cf < (int)fb + wave * CH)) break; // every lane is done, or holds a lower id than it would see next
+    for(int j = threadIdx.x; j < TILE * S; j += PD_THREADS)
+      if(fb * S + j < F * S) s_tri[j] = tf[fb * S + j];
+    __syncthreads();
+    const int cnt = (int)(F - fb < TILE ? F - fb : TILE);
+    const int j1 = none ? 0 : min(cnt, (wave + 1) * CH);
+    for(int j = wave * CH; j < j1; j++)
+    {
+      const int f = (int)fb + j;
+      if(f >= cf) break;
+      if constexpr(NORMALS)
+        if(!compat_normals(s_tri[j * S + 3], q, c2)) continue;
+      const float4 A = s_tri[j * S];
+      if(thr < INFINITY && pd_culled(A, p0, p1, p2, sq_thr)) continue;
+      const float4 B = s_tri[j * S + 1], C = s_tri[j * S + 2];
+      const float d = tri_sqdist_vals(A.x, A.y, A.z, B.x, B.y, B.z, C.x, C.y, C.z, p0, p1, p2).x;
+      if(d <= thr && d <= max_sq) cf = f;
+    }
+  }
+  __syncthreads();
+  s_f[wave][lane] = cf;
+  __syncthreads();
+  if(wave != 0 || !live) return;
+  if(none)
+  {
+    pdc_write_unmatched(qi, face_out, w_out, closest_out, sq_out);
+    return;
+  }
+  int b = s_f[0][lane];
+  for(int w = 1; w < PD_WAVES; w++) b = min(b, s_f[w][lane]);
+  if(b < 0 || (int64_t)b >= F) b = amin; // empty band: never index out of range
+  // (written as pd_tiled_kernel writes: the weights' evaluation is inlined, and its rounding follows the code around it)
+  const float4 A = tf[(int64_t)b * S], B = tf[(int64_t)b * S + 1], C = tf[(int64_t)b * S + 2];
+  const float4 r = tri_sqdist_vals(A.x, A.y, A.z, B.x, B.y, B.z, C.x, C.y, C.z, p0, p1, p2);
+  face_out[qi] = b;
+  sq_out[qi] = r.x;
+  if(closest_out)
+  {
+    closest_out[qi * 3] = r.y;
+    closest_out[qi * 3 + 1] = r.z;
+    closest_out[qi * 3 + 2] = r.w;
+  }
+  if(w_out)
+  {
+    float w[3];
+    tri_weights_vals(A.x, A.y, A.z, B.x, B.y, B.z, C.x, C.y, C.z, p0, p1, p2, w);
+    w_out[qi * 3] = w[0];
+    w_out[qi * 3 + 1] = w[1];
+    w_out[qi * 3 + 2] = w[2];
+  }
+}
+
 // ---- backward
 __global__ __launch_bounds__(256) void pd_vjp_record_kernel(const float * __restrict__ verts, const int32_t * __restrict__ faces,
                                                             const float * __restrict__ points, const int64_t * __restrict__ face,
@@ -457,6 +798,36 @@ int pd_forward_device(smplpp_model * m, PointDistState * s, int64_t n, const flo
   return SMPLPP_OK;
 }
 
+// smplpp_point_mesh_distance_compatible, all pointers on the device (pnormals may be null); the forms are chosen as above
+template<bool NORMALS>
+static int pdc_forward_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
+                              const float * pnormals, float c2, float max_sq, int64_t * face, float * weights, float * closest,
+                              float * sqdist, hipStream_t st)
+{
+  constexpr int S = NORMALS ? 4 : 3;
+  const bool tiled = m->pd_form == 't' || (m->pd_form != 'q' && n * K >= PD_TILED_MIN_NK);
+  const int64_t V = m->V, F = m->F;
+  if(!tiled)
+  {
+    pdc_query_kernel<NORMALS><<<dim3((unsigned)(n * K)), dim3(256), 0, st>>>(verts, m->faces.get(), points, pnormals, c2, max_sq, face, weights,
+                                                                             closest, sqdist, V, F, K);
+    HIP_TRY(hipGetLastError());
+    return SMPLPP_OK;
+  }
+  HIP_TRY(s->tri.reserve(sizeof(float4) * (size_t)n * F * S));
+  HIP_TRY(s->perm.reserve(sizeof(int32_t) * (size_t)n * K));
+  pdc_tri_image_kernel<NORMALS><<<dim3((unsigned)((n * F + 255) / 256)), dim3(256), 0, st>>>(verts, m->faces.get(), s->tri.as<float4>(), V, F, n);
+  HIP_TRY(hipGetLastError());
+  pd_sort_kernel<<<dim3((unsigned)n), dim3(1024), 0, st>>>(points, s->perm.as<int32_t>(), K);
+  HIP_TRY(hipGetLastError());
+  const int64_t bpf = (K + 63) / 64;
+  pdc_tiled_kernel<NORMALS><<<dim3((unsigned)(n * bpf)), dim3(PD_THREADS), 0, st>>>(s->tri.as<float4>(), points, pnormals, c2, max_sq,
+                                                                                    s->perm.as<int32_t>(), face, weights, closest, sqdist, F,
+                                                                                    K, bpf);
+  HIP_TRY(hipGetLastError());
+  return SMPLPP_OK;
+}
+
 int pd_vjp_device(smplpp_model * m, PointDistState * s, int64_t n, const float * verts, int64_t K, const float * points,
                   const int64_t * face, const float * gsq, float * gv, float * gp, int accumulate, hipStream_t st)
 {
@@ -502,6 +873,31 @@ extern "C" int smplpp_point_mesh_distance(smplpp_model * m, int64_t n, const flo
   float * co = fr.out(closest, (size_t)n * K * 3);
   float * so = fr.out(sqdist, (size_t)n * K);
   return fr.run([&] { return pd_forward_device(m, s, n, v, K, p, fo, wo, co, so, fr.st); });
+}
+
+extern "C" int smplpp_point_mesh_distance_compatible(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,
+                                                     const float * point_normals, float cos_min, float max_sqdist, int64_t * face,
+                                                     float * weights, float * closest, float * sqdist, int space, void * stream)
+{
+  const char * fn = "smplpp_point_mesh_distance_compatible";
+  if(!m || n <= 0 || K <= 0 || !verts || !points || !face || !sqdist) return fail(SMPLPP_ERR_INVALID, std::string(fn) + ": bad argument");
+  int rc = compat_args(fn, cos_min, max_sqdist);
+  if(rc) return rc;
+  if((rc = pd_check(fn, m, n, K, space))) return rc;
+  Frame fr(m->device, &m->arena, space, stream, "point-mesh distance (compatible)");
+  PointDistState * s = pd_state(m);
+  const float * v = fr.in(verts, (size_t)n * m->V * 3);
+  const float * p = fr.in(points, (size_t)n * K * 3);
+  const float * pn = fr.in(point_normals, (size_t)n * K * 3);
+  int64_t * fo = fr.out(face, (size_t)n * K);
+  float * wo = fr.out(weights, (size_t)n * K * 3);
+  float * co = fr.out(closest, (size_t)n * K * 3);
+  float * so = fr.out(sqdist, (size_t)n * K);
+  const float c2 = cos_min * cos_min;
+  return fr.run([&] {
+    return point_normals ? pdc_forward_device<true>(m, s, n, v, K, p, pn, c2, max_sqdist, fo, wo, co, so, fr.st)
+                         : pdc_forward_device<false>(m, s, n, v, K, p, nullptr, c2, max_sqdist, fo, wo, co, so, fr.st);
+  });
 }
 
 extern "C" int smplpp_point_mesh_distance_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t K, const float * points,

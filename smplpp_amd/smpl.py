@@ -779,6 +779,88 @@ class SMPL:
             raise SmplppError(1, "mesh_point_distance_differentiable needs torch")
         return _MeshPointDistanceFunction.apply(verts, points, self)
 
+    # ---- normal-compatible, distance-capped correspondences (smplpp_point_mesh_distance_compatible / smplpp_mesh_point_distance_compatible)
+    @staticmethod
+    def _compat_cap(max_dist, max_sqdist):
+        """The squared cap as the fp32 value the call receives: max_sqdist as given, else fp32(max_dist)^2, else +inf."""
+        if max_sqdist is not None:
+            return float(np.float32(max_sqdist))
+        if max_dist is None:
+            return float("inf")
+        return float(np.float32(max_dist) * np.float32(max_dist))
+
+    def _pmdc(self, c, verts, points, normals, K, cos_min, cap, want_closest=True):
+        n = len(verts)
+        normals = c.input(normals, (n, K, 3))
+        face, w, sq = c.empty((n, K), "int64"), c.empty((n, K, 3)), c.empty((n, K))
+        closest = c.empty((n, K, 3)) if want_closest else None
+        check(_lib.load().smplpp_point_mesh_distance_compatible(self.handle, n, _ptr(verts), K, _ptr(points), _ptr(normals), float(cos_min), cap,
+                                                                _ptr(face), _ptr(w), _ptr(closest), _ptr(sq), c.space, c.stream))
+        return face, w, closest, sq
+
+    def _mpdc(self, c, verts, points, point_normals, vert_normals, K, cos_min, cap):
+        n, V = len(verts), self.vertex_num
+        pn = c.input(point_normals, (n, K, 3))
+        vn = c.input(vert_normals, (n, V, 3))
+        if pn is not None and vn is None:
+            vn = self._normals_at(c, verts, 2, None)[0]
+        index, sq = c.empty((n, V), "int64"), c.empty((n, V))
+        check(_lib.load().smplpp_mesh_point_distance_compatible(self.handle, n, _ptr(verts), _ptr(vn), K, _ptr(points), _ptr(pn), float(cos_min),
+                                                                cap, _ptr(index), _ptr(sq), c.space, c.stream))
+        return index, sq
+
+    def pointMeshDistanceCompatible(self, verts, points, point_normals, cos_min=0.5, max_dist=None, max_sqdist=None):
+        """pointMeshDistance restricted, inside the search, to the faces whose normal is compatible with the query's and that lie
+        within max_dist (smplpp_point_mesh_distance_compatible, which states the exact rule): returns (face [N,K] int64, weights
+        [N,K,3], closest [N,K,3], sqdist [N,K], matched [N,K] bool).  point_normals [N,K,3] need not be unit (None: no normal test);
+        a face passes when the angle between its normal and the query's is at most acos(cos_min).  max_dist in metres (None: no
+        cap); max_sqdist gives the squared cap directly.  An unmatched query (no candidate, or a non-finite row) has face -1, zeros
+        elsewhere and matched False.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("pointMeshDistanceCompatible", verts, points, point_normals)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        face, w, closest, sq = self._pmdc(c, verts, points, point_normals, K, cos_min, self._compat_cap(max_dist, max_sqdist))
+        return face, w, closest, sq, face >= 0
+
+    def pointMeshDistanceCompatibleBackward(self, verts, points, face, grad_sqdist, out=None, grad_points=None):
+        """pointMeshDistanceBackward at the faces pointMeshDistanceCompatible chose: unmatched queries (face -1) contribute
+        nothing.  (In host space smplpp_point_mesh_distance_vjp refuses -1, so they are passed as face 0 with a zero cotangent.)"""
+        c = _Call("pointMeshDistanceCompatibleBackward", verts, points, grad_sqdist, out, grad_points)
+        if not c.dev:
+            face = np.asarray(face, np.int64)
+            grad_sqdist = np.where(face < 0, np.float32(0), _np32(grad_sqdist).reshape(face.shape))
+            face = np.where(face < 0, 0, face)
+        return self.pointMeshDistanceBackward(verts, points, face, grad_sqdist, out, grad_points)
+
+    def point_mesh_distance_compatible_differentiable(self, verts, points, point_normals, cos_min=0.5, max_dist=None, max_sqdist=None):
+        """(face [N,K], weights [N,K,3], matched [N,K] bool, sqdist [N,K]) of device points [N,K,3] with normals point_normals
+        against device vertices verts [N,V,3] (the bits of pointMeshDistanceCompatible), with sqdist differentiable in verts and
+        points through torch.autograd: smplpp_point_mesh_distance_compatible forward, smplpp_point_mesh_distance_vjp backward.  The
+        normals steer the selection only: nothing flows to them, and an unmatched query has sqdist 0 and no gradient."""
+        if torch is None:
+            raise SmplppError(1, "point_mesh_distance_compatible_differentiable needs torch")
+        return _PointDistanceCompatibleFunction.apply(verts, points, self, point_normals, cos_min, self._compat_cap(max_dist, max_sqdist))
+
+    def meshPointDistanceCompatible(self, verts, points, point_normals, vert_normals=None, cos_min=0.5, max_dist=None, max_sqdist=None):
+        """meshPointDistance restricted, inside the search, to the points whose normal is compatible with the vertex's and that lie
+        within max_dist (smplpp_mesh_point_distance_compatible): returns (index [N,V] int64, sqdist [N,V], matched [N,V] bool).
+        vert_normals [N,V,3] None: the whole-mesh vertex normals of verts (smplpp_mesh_vertex_normals).  point_normals None: no
+        normal test.  A vertex without an eligible point has (-1, 0, False)."""
+        c = _Call("meshPointDistanceCompatible", verts, points, point_normals, vert_normals)
+        verts, points, K = self._pmd_inputs(c, verts, points)
+        index, sq = self._mpdc(c, verts, points, point_normals, vert_normals, K, cos_min, self._compat_cap(max_dist, max_sqdist))
+        return index, sq, index >= 0
+
+    def mesh_point_distance_compatible_differentiable(self, verts, points, point_normals, vert_normals=None, cos_min=0.5, max_dist=None,
+                                                      max_sqdist=None):
+        """(index [N,V], matched [N,V] bool, sqdist [N,V]) of device vertices against device points with normals (the bits of
+        meshPointDistanceCompatible), with sqdist differentiable in verts and points through torch.autograd:
+        smplpp_mesh_point_distance_compatible forward, smplpp_mesh_point_distance_vjp backward.  The normals (vert_normals None: the
+        whole-mesh normals of verts) steer the selection only: nothing flows to them or through them."""
+        if torch is None:
+            raise SmplppError(1, "mesh_point_distance_compatible_differentiable needs torch")
+        return _MeshPointDistanceCompatibleFunction.apply(verts, points, self, point_normals, vert_normals, cos_min,
+                                                          self._compat_cap(max_dist, max_sqdist))
+
     # ---- winding numbers and the signed point-to-mesh distance (smplpp_point_mesh_winding / smplpp_point_mesh_signed_distance[_vjp])
     def pointMeshWinding(self, verts, points):
         """Generalized winding numbers of each frame's mesh verts [N,V,3] at K points [N,K,3] (smplpp_point_mesh_winding): returns
@@ -1391,6 +1473,46 @@ if torch is not None:
             ctx.smpl, ctx.K = smpl, K
             ctx.save_for_backward(verts, points, index)
             return index, sq
+
+    class _PointDistanceCompatibleFunction(_DistanceFunction):
+        """smplpp_point_mesh_distance_compatible forward / smplpp_point_mesh_distance_vjp backward, which ignores face -1 in device
+        space (SMPL.point_mesh_distance_compatible_differentiable).  The normals and the filter's arguments get no gradient."""
+
+        @staticmethod
+        def forward(ctx, verts, points, smpl, normals, cos_min, cap):
+            ctx.call_name, ctx.mesh_to_point = "point_mesh_distance_compatible_differentiable", False
+            c = _Call(ctx.call_name, verts, points, normals, device_only=True)
+            verts, points, K = smpl._pmd_inputs(c, verts, points)
+            face, w, _, sq = smpl._pmdc(c, verts, points, normals, K, cos_min, cap, want_closest=False)
+            matched = face >= 0
+            ctx.mark_non_differentiable(face, w, matched)
+            ctx.smpl, ctx.K = smpl, K
+            ctx.save_for_backward(verts, points, face)
+            return face, w, matched, sq
+
+        @staticmethod
+        def backward(ctx, *grads):
+            return _DistanceFunction.backward(ctx, *grads) + (None, None, None)
+
+    class _MeshPointDistanceCompatibleFunction(_DistanceFunction):
+        """smplpp_mesh_point_distance_compatible forward / smplpp_mesh_point_distance_vjp backward
+        (SMPL.mesh_point_distance_compatible_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, points, smpl, point_normals, vert_normals, cos_min, cap):
+            ctx.call_name, ctx.mesh_to_point = "mesh_point_distance_compatible_differentiable", True
+            c = _Call(ctx.call_name, verts, points, point_normals, vert_normals, device_only=True)
+            verts, points, K = smpl._pmd_inputs(c, verts, points)
+            index, sq = smpl._mpdc(c, verts, points, point_normals, vert_normals, K, cos_min, cap)
+            matched = index >= 0
+            ctx.mark_non_differentiable(index, matched)
+            ctx.smpl, ctx.K = smpl, K
+            ctx.save_for_backward(verts, points, index)
+            return index, matched, sq
+
+        @staticmethod
+        def backward(ctx, *grads):
+            return _DistanceFunction.backward(ctx, *grads) + (None, None, None, None)
 
 
     class _SignedDistanceFunction(_DistanceFunction):
