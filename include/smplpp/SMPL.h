@@ -829,6 +829,44 @@ public:
     check(smplpp_mesh_laplacian(m_.get(), x.size(0), x.ptr(), x.size(2), out.ptr(), accumulate ? 1 : 0, SMPLPP_HOST, nullptr), "SMPL");
     return out;
   }
+  // Bound points (smplpp_skin_points, smplpp_unskin_points and their backward passes): K points that are not the model's vertices,
+  // carried by the blend of the joint transforms of `skeleton` (world [N,24,3,4], joints [N,24,3]).  points is [K,3] or [1,K,3] (one
+  // cloud for every frame) or [N,K,3].  A binding is face [K] | [B,K] (kInt64) with bary [B,K,3], what pointMeshDistance returns as
+  // face and weights, or dense weights [B,K,24] used as given, B = 1 or N; the other members stay empty.
+  struct PointBinding
+  {
+    Tensor face, bary, weights;
+  };
+  // out [N,K,3]; blend [N,K,3,4], each point's own transform; valid [N,K] kInt64, 1 for a live point (a dead one gives zeros)
+  struct BoundPoints
+  {
+    Tensor out, blend, valid;
+  };
+  BoundPoints skinPoints(const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & binding) const
+  {
+    return boundPoints(false, world, joints, points, binding);
+  }
+  // the inverse: points are posed points, out the rest-pose points that skinPoints carries onto them under the same binding
+  BoundPoints unskinPoints(const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & binding) const
+  {
+    return boundPoints(true, world, joints, points, binding);
+  }
+  // points: shaped [P,K,3] like the cloud (P = 1: the frames' sum); world [N,24,3,4] and joints [N,24,3]: the cotangents
+  // skeletonBackward takes; weights [B,K,24]: for a weight binding only (empty otherwise)
+  struct BoundPointsGrad
+  {
+    Tensor points, world, joints, weights;
+  };
+  BoundPointsGrad skinPointsBackward(const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & binding,
+                                     const Tensor & gradOut) const
+  {
+    return boundPointsBackward(false, world, joints, points, binding, gradOut);
+  }
+  BoundPointsGrad unskinPointsBackward(const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & binding,
+                                       const Tensor & gradOut) const
+  {
+    return boundPointsBackward(true, world, joints, points, binding, gradOut);
+  }
   // Exact Euclidean feature transform of binary images mask [N,H,W] (integer tensor, nonzero = set; smplpp_mask_distance_transform):
   // nearest [N,H,W] kInt64 (the linear index of the nearest set pixel of the frame, the lowest among equal distances; -1 without a
   // set pixel) and sqdist [N,H,W] kInt64 (px^2).
@@ -952,6 +990,55 @@ private:
     if((!hw && !hp && !hj) || (hw && (gw.numel() != n * JOINT_NUM * 12 || gw.dtype != kFloat32))
        || (hp && (gp.numel() != n * JOINT_NUM * 3 || gp.dtype != kFloat32)) || (hj && (gj.numel() != n * JOINT_NUM * 3 || gj.dtype != kFloat32)))
       throw Exception("SMPL", "Cannot back-propagate through the skeleton of a SMPL model!");
+  }
+  // the shapes of a bound-points call: frames n, points K, the frames of the cloud and of the binding
+  struct BoundShape
+  {
+    int64_t n, K, pointFrames, bindFrames;
+    bool byWeights;
+  };
+  BoundShape checkBound(const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & b, const char * what) const
+  {
+    const bool hw = !b.weights.data.empty(), hf = !b.face.idata.empty(), hb = !b.bary.data.empty();
+    if(!m_ || world.dim() != 4 || world.size(1) != JOINT_NUM || world.size(2) != 3 || world.size(3) != 4 || world.dtype != kFloat32
+       || world.size(0) < 1 || joints.dtype != kFloat32 || joints.numel() != world.size(0) * JOINT_NUM * 3 || points.dtype != kFloat32
+       || points.dim() < 2 || points.dim() > 3 || points.size(points.dim() - 1) != 3 || points.numel() < 3 || hw == (hf || hb) || hf != hb)
+      throw Exception("SMPL", what);
+    BoundShape s{world.size(0), points.size(points.dim() - 2), points.dim() == 3 ? points.size(0) : 1, 0, hw};
+    const int64_t rows = hw ? b.weights.numel() / JOINT_NUM : b.bary.numel() / 3;
+    s.bindFrames = rows / s.K;
+    if((s.pointFrames != 1 && s.pointFrames != s.n) || rows % s.K != 0 || (s.bindFrames != 1 && s.bindFrames != s.n)
+       || (hw ? b.weights.dtype != kFloat32 || b.weights.numel() != rows * JOINT_NUM
+              : b.bary.dtype != kFloat32 || b.bary.numel() != rows * 3 || b.face.dtype != kInt64 || b.face.numel() != rows))
+      throw Exception("SMPL", what);
+    return s;
+  }
+  BoundPoints boundPoints(bool unskin, const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & b) const
+  {
+    const BoundShape s = checkBound(world, joints, points, b, unskin ? "Cannot unskin the points!" : "Cannot skin the points!");
+    BoundPoints r{Tensor({s.n, s.K, 3}), Tensor({s.n, s.K, 3, 4}), Tensor({s.n, s.K}, kInt64)};
+    std::vector<uint8_t> valid((size_t)(s.n * s.K));
+    check((unskin ? smplpp_unskin_points : smplpp_skin_points)(m_.get(), s.n, world.ptr(), joints.ptr(), s.K, points.ptr(), s.pointFrames,
+                                                              s.byWeights ? nullptr : b.face.idata.data(), optional(b.bary), optional(b.weights),
+                                                              s.bindFrames, r.out.ptr(), r.blend.ptr(), valid.data(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    for(size_t i = 0; i < valid.size(); i++) r.valid.idata[i] = valid[i];
+    return r;
+  }
+  BoundPointsGrad boundPointsBackward(bool unskin, const Tensor & world, const Tensor & joints, const Tensor & points, const PointBinding & b,
+                                      const Tensor & gradOut) const
+  {
+    const char * what = "Cannot back-propagate through the bound points!";
+    const BoundShape s = checkBound(world, joints, points, b, what);
+    if(gradOut.dtype != kFloat32 || gradOut.numel() != s.n * s.K * 3) throw Exception("SMPL", what);
+    BoundPointsGrad g{Tensor({s.pointFrames, s.K, 3}), Tensor({s.n, JOINT_NUM, 3, 4}), Tensor({s.n, JOINT_NUM, 3}),
+                      s.byWeights ? Tensor({s.bindFrames, s.K, JOINT_NUM}) : Tensor()};
+    check((unskin ? smplpp_unskin_points_vjp : smplpp_skin_points_vjp)(
+              m_.get(), s.n, world.ptr(), joints.ptr(), s.K, points.ptr(), s.pointFrames, s.byWeights ? nullptr : b.face.idata.data(),
+              optional(b.bary), optional(b.weights), s.bindFrames, gradOut.ptr(), g.points.ptr(), g.world.ptr(), g.joints.ptr(),
+              s.byWeights ? g.weights.ptr() : nullptr, 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return g;
   }
   // an integer mask tensor [N,H,W] as bytes (nonzero = set)
   static std::vector<uint8_t> maskBytes(const Tensor & mask, const char * what)

@@ -535,6 +535,93 @@ int smplpp_vertex_offsets_vjp(smplpp_model * m, int64_t n, const float * xforms 
  *    n * V * C beyond int32 indexing (the output is untouched, nothing is launched). */
 int smplpp_mesh_laplacian(smplpp_model * m, int64_t n, const float * x /*[n,V,C], 1 <= C <= 32*/, int64_t C, float * out /*[n,V,C]*/,
                           int accumulate, int space, void * stream);
+#define SMPLPP_UNSKIN_MIN_DET 1e-4f /* smplpp_unskin_points: a blend with |det M| <= this * s^3 has collapsed (a blend of rotations has det / s^3 in (0, 1]) */
+/* Skinning of bound points: K points that are not the model's vertices (a garment, hair, the samples of an avatar, markers off the
+ * skin), each carried by the blend of the world joint transforms.  world [n,24,3,4] = [A_j | p_j] and joints [n,24,3] = J_j are what
+ * smplpp_skeleton returned; the root translation is inside p_j, there is no separate trans.  The translation of joint j's relative
+ * transform is c_j[a] = p_j[a] - ((A_j[a][0] J_j[0] + A_j[a][1] J_j[1]) + A_j[a][2] J_j[2]).  points is [point_frames,K,3] and the
+ * binding is over bind_frames, each 1 (shared by the frames) or n.  Exactly one binding is given, the other's pointers are NULL:
+ *  - a face binding, face [bind_frames,K] and bary [bind_frames,K,3], the `face` and `weights` outputs of smplpp_point_mesh_distance:
+ *    with (v0, v1, v2) the corners of the face and W the model's kept skinning weights (0 where none is kept),
+ *    w_j = (bary0 W[v0][j] + bary1 W[v1][j]) + bary2 W[v2][j];
+ *  - a weight binding, weights [bind_frames,K,24], used as given: w_j = weights[k][j].  They need not sum to 1.
+ * In fp32 with every operation rounded on its own (no FMA), per (frame, point), over the joints with w_j != 0 in ascending j, each
+ * sum starting from +0:
+ *    s = sum w_j,    M[a][b] = sum w_j A_j[a][b],    t[a] = sum w_j c_j[a];
+ *    h[a] = ((M[a][0] x[0] + M[a][1] x[1]) + M[a][2] x[2]) + t[a],    out[a] = h[a] / s,         x = the rest-pose point.
+ * blend [n,K,3,4] (nullable) is the point's own transform, blend[a][b] = M[a][b] / s and blend[a][3] = t[a] / s, with which a caller
+ * rotates normals or covariances; valid [n,K] (nullable) is 1 for a live point.  A point is DEAD when its face id is outside [0, F)
+ * (device space; a host-space id out of range is refused), when a coordinate of it, a bary or one of its 24 weights is not finite,
+ * or when !(s > 0).  A dead point gives +0 in every output and valid = 0 and never touches its neighbours.  The bits do not depend on
+ * n, on the frame's position in the batch, on the memory space, on which outputs are asked for, or on the frames a workgroup takes
+ * (by n and K; SMPLPP_SKIN_POINTS_FRAMES = 1..32 in the environment of smplpp_model_create fixes it, for tests).  A device-space call
+ * touches nothing in the handle and keeps no workspace.
+ *  - SMPLPP_ERR_INVALID: n <= 0 or K <= 0, a NULL world, joints, points or out, both bindings or neither, a face binding on a model
+ *    without faces, point_frames or bind_frames neither 1 nor n, a host-space face id out of range, n * K * 24 (or n * 288) beyond
+ *    int32 indexing (the outputs are untouched, nothing is launched). */
+int smplpp_skin_points(smplpp_model * m, int64_t n, const float * world /*[n,24,3,4]*/, const float * joints /*[n,24,3]*/, int64_t K,
+                       const float * points /*[point_frames,K,3]*/, int64_t point_frames /*1 or n*/,
+                       const int64_t * face /*[bind_frames,K] or NULL*/, const float * bary /*[bind_frames,K,3] or NULL*/,
+                       const float * weights /*[bind_frames,K,24] or NULL*/, int64_t bind_frames /*1 or n*/, float * out /*[n,K,3]*/,
+                       float * blend /*[n,K,3,4] nullable*/, uint8_t * valid /*[n,K] nullable*/, int space, void * stream);
+/* The inverse (unposing, canonicalisation): points are POSED points y and out the rest-pose points x with skin(x) = y under the same
+ * binding.  With s, M, t as above, indices taken mod 3:
+ *    q[a] = s y[a] - t[a];      C[a][b] = M[a+1][b+1] M[a+2][b+2] - M[a+1][b+2] M[a+2][b+1]      (the cofactors, in cyclic form);
+ *    det = (M[0][0] C[0][0] + M[0][1] C[0][1]) + M[0][2] C[0][2];      out[b] = ((C[0][b] q[0] + C[1][b] q[1]) + C[2][b] q[2]) / det.
+ * blend and valid are as in smplpp_skin_points (the transform of the FORWARD map: out goes to y by it).  A point is dead as there,
+ * and also when !(|det| > ((SMPLPP_UNSKIN_MIN_DET s) s) s): the blend has collapsed, as half and half of two rotations pi apart does.
+ * Refusals as smplpp_skin_points. */
+int smplpp_unskin_points(smplpp_model * m, int64_t n, const float * world /*[n,24,3,4]*/, const float * joints /*[n,24,3]*/, int64_t K,
+                         const float * points /*[point_frames,K,3]*/, int64_t point_frames /*1 or n*/,
+                         const int64_t * face /*[bind_frames,K] or NULL*/, const float * bary /*[bind_frames,K,3] or NULL*/,
+                         const float * weights /*[bind_frames,K,24] or NULL*/, int64_t bind_frames /*1 or n*/, float * out /*[n,K,3]*/,
+                         float * blend /*[n,K,3,4] nullable*/, uint8_t * valid /*[n,K] nullable*/, int space, void * stream);
+/* Vector-Jacobian product of smplpp_skin_points for g = grad_out [n,K,3].  The forward is recomputed; no state is kept.  Per live
+ * (frame, point), with s, M as above:
+ *    gt[a] = g[a] / s;      grad_points[b] = (M[0][b] gt[0] + M[1][b] gt[1]) + M[2][b] gt[2].
+ * Per (frame, joint j), by sum1024 over the points k (FIXED-ORDER SUMS below: element k goes to partial k mod 1024), leaving out the
+ * points with w_kj == 0 and the dead ones, which is bit-neutral under that rule:
+ *    dc[a] = sum1024_k (w_kj gt_k[a]);      dR[a][b] = sum1024_k ((w_kj gt_k[a]) x_k[b]);
+ * and, written once per (frame, joint) in the cotangent layout smplpp_skeleton_vjp takes,
+ *    grad_world[j][a][b] = dR[a][b] - dc[a] J_j[b];      grad_world[j][a][3] = dc[a];
+ *    grad_joints[j][b] = -((A_j[0][b] dc[0] + A_j[1][b] dc[1]) + A_j[2][b] dc[2]).
+ * The weights are divided by their sum, so sum_j dc_j = sum_k g_k: the grad_trans that smplpp_skeleton_vjp forms from column 3 of
+ * grad_world is the right one, and no separate translation gradient exists.  For a weight binding only, for all 24 joints including
+ * those with w_j = 0 (the gradient a learned skinning field needs):
+ *    d[a] = (((A_j[a][0] x[0] + A_j[a][1] x[1]) + A_j[a][2] x[2]) + c_j[a]) - out[a];      grad_weights[k][j] = (gt[0] d[0] + gt[1] d[1]) + gt[2] d[2].
+ * There is no gradient to face or bary: they are fixed correspondences.  A dead point contributes no term and receives +0.
+ *  - point_frames = 1: grad_points [1,K,3] is the sum over the frames; bind_frames = 1: grad_weights [1,K,24] likewise.  Both use the
+ *    two-level order of smplpp_vertex_offsets_vjp: tiles of SMPLPP_VERTEX_OFFSETS_TILE frames, ascending within a tile from its first
+ *    term and then across the tiles (a dead (frame, point) is the term +0).
+ *  - any output may be NULL, not all.  accumulate = 0 stores the finished value, 1 adds it to what the output holds (one addition at
+ *    the end), so grad_world can share a buffer with smplpp_orientation_term_vjp's grad_frames.
+ *  - the bits do not depend on n, on the slot, on the memory space, on which outputs are asked for, on the frames a workgroup takes or
+ *    on who holds which partial of sum1024 (by K, as frame_sum_split; SMPLPP_SKIN_POINTS_SPLIT = 4 or 1 in the environment of
+ *    smplpp_model_create fixes a workgroup of 256 or 1024 threads, for tests).
+ *  - SMPLPP_ERR_INVALID: as the forward, a NULL grad_out, every gradient NULL, grad_weights with a face binding, accumulate not 0 or
+ *    1 (the outputs are untouched, nothing is launched). */
+int smplpp_skin_points_vjp(smplpp_model * m, int64_t n, const float * world /*[n,24,3,4]*/, const float * joints /*[n,24,3]*/, int64_t K,
+                           const float * points /*[point_frames,K,3]*/, int64_t point_frames /*1 or n*/,
+                           const int64_t * face /*[bind_frames,K] or NULL*/, const float * bary /*[bind_frames,K,3] or NULL*/,
+                           const float * weights /*[bind_frames,K,24] or NULL*/, int64_t bind_frames /*1 or n*/,
+                           const float * grad_out /*[n,K,3]*/, float * grad_points /*[point_frames,K,3] nullable*/,
+                           float * grad_world /*[n,24,3,4] nullable*/, float * grad_joints /*[n,24,3] nullable*/,
+                           float * grad_weights /*[bind_frames,K,24] nullable*/, int accumulate, int space, void * stream);
+/* Vector-Jacobian product of smplpp_unskin_points for g = grad_out = dL/dx [n,K,3].  Per live (frame, point), with C, det, s and the
+ * recomputed forward output x as above:
+ *    u[a] = ((C[a][0] g[0] + C[a][1] g[1]) + C[a][2] g[2]) / det;      grad_points[a] = s u[a]      (to the posed points).
+ * The per-joint sums, grad_world and grad_joints are exactly those of smplpp_skin_points_vjp with gt := -u and x := the recomputed
+ * forward output.  For a weight binding, with y the posed point given:
+ *    r_j[a] = ((A_j[a][0] x[0] + A_j[a][1] x[1]) + A_j[a][2] x[2]) + c_j[a];      d[a] = y[a] - r_j[a];
+ *    grad_weights[k][j] = (u[0] d[0] + u[1] d[1]) + u[2] d[2].
+ * Shared inputs, accumulate, the independence of the bits and the refusals are those of smplpp_skin_points_vjp. */
+int smplpp_unskin_points_vjp(smplpp_model * m, int64_t n, const float * world /*[n,24,3,4]*/, const float * joints /*[n,24,3]*/, int64_t K,
+                             const float * points /*[point_frames,K,3]*/, int64_t point_frames /*1 or n*/,
+                             const int64_t * face /*[bind_frames,K] or NULL*/, const float * bary /*[bind_frames,K,3] or NULL*/,
+                             const float * weights /*[bind_frames,K,24] or NULL*/, int64_t bind_frames /*1 or n*/,
+                             const float * grad_out /*[n,K,3]*/, float * grad_points /*[point_frames,K,3] nullable*/,
+                             float * grad_world /*[n,24,3,4] nullable*/, float * grad_joints /*[n,24,3] nullable*/,
+                             float * grad_weights /*[bind_frames,K,24] nullable*/, int accumulate, int space, void * stream);
 /* Exact Euclidean feature transform of n binary images mask [n,H,W] (a nonzero byte = set), all in integers.  For pixel p = (row j,
  * column i) and the set pixels q = (j', i') of the same frame, d2(p, q) = (i-i')^2 + (j-j')^2: sqdist[p] is the minimum and
  * nearest[p] the linear index j' W + i' of the set pixel that attains it; among equal distances the lowest linear index wins (the

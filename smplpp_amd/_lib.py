@@ -98,6 +98,12 @@ def load():
         "smplpp_vertex_offsets": [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_vertex_offsets_vjp": [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp],
         "smplpp_mesh_laplacian": [vp, C.c_int64, vp, C.c_int64, vp, C.c_int, C.c_int, vp],
+        "smplpp_skin_points": [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int, vp],
+        "smplpp_unskin_points": [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int, vp],
+        "smplpp_skin_points_vjp": [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int,
+                                   vp],
+        "smplpp_unskin_points_vjp": [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int,
+                                     vp],
         "smplpp_mask_distance_transform": [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int, vp],
         "smplpp_silhouette": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_silhouette_vjp": [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],

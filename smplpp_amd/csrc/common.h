@@ -247,5 +247,7 @@ struct smplpp_model
   smplpp_hip::StatePtr<smplpp_hip::SilhouetteState> sil; // silhouette workspace (silhouette.hip): null until its first call
   int vo_frames = 0;            // SMPL+D: frames per tile of the forward and the per-frame backward (SMPLPP_VERTEX_OFFSETS_FRAMES, read at model creation): 0 = by n
   smplpp_hip::StatePtr<smplpp_hip::VertexOffsetsState> vo; // SMPL+D shared-backward workspace (vertex_offsets.hip): null until its first call
+  int sp_frames = 0;            // bound points: frames a workgroup of sp_point_kernel holds in LDS (SMPLPP_SKIN_POINTS_FRAMES, read at model creation): 0 = by n and K
+  int sp_split = 0;             // bound points: threads per partial of the per-joint sums (SMPLPP_SKIN_POINTS_SPLIT = 4 | 1, read at model creation): 0 = by K
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

@@ -292,7 +292,7 @@ extern "C" int smplpp_model_destroy(smplpp_model * m)
   return SMPLPP_OK;
 }
 
-// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM, SMPLPP_DEPTH_RASTER_INLINE and SMPLPP_VERTEX_OFFSETS_FRAMES are read here, once per model (m.maxw and m.VGPn are set)
+// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM, SMPLPP_DEPTH_RASTER_INLINE, SMPLPP_VERTEX_OFFSETS_FRAMES and SMPLPP_SKIN_POINTS_* are read here, once per model (m.maxw and m.VGPn are set)
 static void read_env(smplpp_model & m)
 {
   std::tie(m.form, m.form_ik) = choose_forms(getenv("SMPLPP_SKIN"), m.maxw, m.VGPn);
@@ -303,6 +303,12 @@ static void read_env(smplpp_model & m)
   const char * vo_env = getenv("SMPLPP_VERTEX_OFFSETS_FRAMES"); // 1..32: frames per tile of smplpp_vertex_offsets and its per-frame backward (no bit depends on it)
   const int vo_ft = vo_env ? atoi(vo_env) : 0;
   m.vo_frames = vo_ft >= 1 && vo_ft <= SMPLPP_VERTEX_OFFSETS_TILE ? vo_ft : 0;
+  const char * spf_env = getenv("SMPLPP_SKIN_POINTS_FRAMES"); // 1..32: frames a workgroup of the bound points' per-point kernel holds (no bit depends on it)
+  const int sp_ft = spf_env ? atoi(spf_env) : 0;
+  m.sp_frames = sp_ft >= 1 && sp_ft <= SMPLPP_VERTEX_OFFSETS_TILE ? sp_ft : 0;
+  const char * sps_env = getenv("SMPLPP_SKIN_POINTS_SPLIT"); // 4 | 1: partials per thread of the bound points' per-joint sums (no bit depends on it)
+  const int sp_nq = sps_env ? atoi(sps_env) : 0;
+  m.sp_split = sp_nq == 4 || sp_nq == 1 ? sp_nq : 0;
 }
 
 // Validate, build the host tables (model_tables.h), then upload them and lay the bases out on the device.

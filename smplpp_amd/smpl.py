@@ -1191,6 +1191,117 @@ class SMPL:
             raise SmplppError(1, "forward_displaced_differentiable needs torch")
         return _FKDisplacedFunction.apply(beta, theta, offsets, self)
 
+    # ---- bound points: skinning and its inverse (smplpp_skin_points / smplpp_unskin_points and their VJPs)
+    def _bound_inputs(self, c, world, joints, points, face, bary, weights):
+        """(n, K, world, joints, points, point_frames, face, bary, weights, bind_frames) of a bound-points call in the space of `c`.
+        points [K,3], [1,K,3] or [n,K,3]; the binding is (face [K] | [1,K] | [n,K] with bary of the same frames) or weights
+        [K,24] | [1,K,24] | [n,K,24]."""
+        if len(world.shape) != 4 or tuple(world.shape[1:]) != (24, 3, 4) or world.shape[0] < 1:
+            c.refuse("expected world of shape (N, 24, 3, 4)")
+        n = int(world.shape[0])
+        world, joints = c.input(world, (n, 24, 3, 4)), c.input(joints, (n, 24, 3))
+        if joints is None or points is None:
+            c.refuse("joints and points must be given")
+        if len(points.shape) == 2:
+            points = points.reshape((1,) + tuple(points.shape))
+        if len(points.shape) != 3 or points.shape[2] != 3 or points.shape[0] not in (1, n) or points.shape[1] < 1:
+            c.refuse("expected points of shape (K, 3), (1, K, 3) or (N, K, 3)")
+        pf, K = int(points.shape[0]), int(points.shape[1])
+        points = c.input(points, (pf, K, 3))
+        if (weights is None) == (face is None and bary is None) or (weights is None and (face is None or bary is None)):
+            c.refuse("give face and bary, or weights")
+        if weights is not None:
+            if len(weights.shape) == 2:
+                weights = weights.reshape((1,) + tuple(weights.shape))
+            if len(weights.shape) != 3 or tuple(weights.shape[1:]) != (K, 24) or weights.shape[0] not in (1, n):
+                c.refuse("expected weights of shape (K, 24), (1, K, 24) or (N, K, 24)")
+            bf = int(weights.shape[0])
+            return n, K, world, joints, points, pf, None, None, c.input(weights, (bf, K, 24)), bf
+        if len(bary.shape) == 2:
+            bary = bary.reshape((1,) + tuple(bary.shape))
+        if len(bary.shape) != 3 or tuple(bary.shape[1:]) != (K, 3) or bary.shape[0] not in (1, n):
+            c.refuse("expected bary of shape (K, 3), (1, K, 3) or (N, K, 3)")
+        bf = int(bary.shape[0])
+        face = c.ids(face)
+        if face.shape[0] != bf * K:
+            c.refuse("expected face ids of shape %s" % ((bf, K),))
+        return n, K, world, joints, points, pf, face, c.input(bary, (bf, K, 3)), None, bf
+
+    def _bound_forward(self, name, unskin, world, joints, points, face, bary, weights, want, device_only=False):
+        c = _Call(name, world, joints, points, bary, weights, device_only=device_only)
+        n, K, world, joints, points, pf, face, bary, weights, bf = self._bound_inputs(c, world, joints, points, face, bary, weights)
+        out = c.empty((n, K, 3))
+        blend = c.empty((n, K, 3, 4)) if "blend" in want else None
+        valid = c.empty((n, K), "uint8") if "valid" in want else None
+        L = _lib.load()
+        fn = L.smplpp_unskin_points if unskin else L.smplpp_skin_points
+        check(fn(self.handle, n, _ptr(world), _ptr(joints), K, _ptr(points), pf, _ptr(face), _ptr(bary), _ptr(weights), bf, _ptr(out),
+                 _ptr(blend), _ptr(valid), c.space, c.stream))
+        return out, blend, valid
+
+    def skinPoints(self, world, joints, points, face=None, bary=None, weights=None, want=("blend", "valid")):
+        """Skinning of bound points (smplpp_skin_points): K rest-pose points `points` ([K,3] or [1,K,3]: one cloud for every frame;
+        [N,K,3]: one per frame) carried by the blend of the joint transforms `world` [N,24,3,4] and `joints` [N,24,3] as `skeleton`
+        returns them.  The binding is either `face` and `bary` (the face and weights of pointMeshDistance: the model's skinning
+        weights interpolated over the face) or dense `weights` [K,24] | [1,K,24] | [N,K,24] used as given.  Returns (out [N,K,3],
+        blend [N,K,3,4], valid [N,K] uint8): the posed points, each point's own transform (for normals or covariances) and 1 for a
+        live point; a dead point (C header) gives zeros.  An output missing from `want` is returned as None.  numpy (the call
+        synchronises) or float32 device tensors (torch's current stream)."""
+        return self._bound_forward("skinPoints", False, world, joints, points, face, bary, weights, want)
+
+    def unskinPoints(self, world, joints, points, face=None, bary=None, weights=None, want=("blend", "valid")):
+        """The inverse of skinPoints (smplpp_unskin_points): `points` are posed points and the result the rest-pose points that
+        skinPoints carries onto them under the same binding: the canonicalisation of a posed scan.  A point whose blend has
+        collapsed (|det| <= 1e-4 s^3) is dead.  Arguments and returns as skinPoints; blend is the transform of the forward map."""
+        return self._bound_forward("unskinPoints", True, world, joints, points, face, bary, weights, want)
+
+    def _bound_backward(self, name, unskin, world, joints, points, grad_out, face, bary, weights, want, out):
+        acc = out is not None
+        c = _Call(name, world, joints, points, bary, weights, grad_out, *(out.values() if acc else ()))
+        n, K, world, joints, points, pf, face, bary, weights, bf = self._bound_inputs(c, world, joints, points, face, bary, weights)
+        if grad_out is None:
+            c.refuse("grad_out must be given")
+        g = c.input(grad_out, (n, K, 3))
+        shapes = {"points": (pf, K, 3), "world": (n, 24, 3, 4), "joints": (n, 24, 3), "weights": (bf, K, 24)}
+        keys = [k for k in shapes if k in (out if acc else want) and (k != "weights" or weights is not None or acc)]
+        if not keys:
+            c.refuse("points, world, joints or weights must be asked for")
+        res = {k: c.inout(out[k], shapes[k]) if acc else c.empty(shapes[k]) for k in keys}
+        L = _lib.load()
+        fn = L.smplpp_unskin_points_vjp if unskin else L.smplpp_skin_points_vjp
+        check(fn(self.handle, n, _ptr(world), _ptr(joints), K, _ptr(points), pf, _ptr(face), _ptr(bary), _ptr(weights), bf, _ptr(g),
+                 _ptr(res.get("points")), _ptr(res.get("world")), _ptr(res.get("joints")), _ptr(res.get("weights")), int(acc), c.space,
+                 c.stream))
+        return res
+
+    def skinPointsBackward(self, world, joints, points, grad_out, face=None, bary=None, weights=None,
+                           want=("points", "world", "joints", "weights"), out=None):
+        """Vector-Jacobian product of skinPoints (smplpp_skin_points_vjp) for grad_out = dL/dout [N,K,3]: a dict of "points" (the
+        shape of the points as passed, [1,K,3] for a shared cloud: the frames' sum), "world" [N,24,3,4] and "joints" [N,24,3] (the
+        cotangents skeletonBackward takes) and, for a weight binding, "weights" ([1,K,24] for shared weights: the frames' sum).
+        `want` drops outputs; with `out` (a dict keyed the same way) the gradients are ADDED into its arrays."""
+        return self._bound_backward("skinPointsBackward", False, world, joints, points, grad_out, face, bary, weights, want, out)
+
+    def unskinPointsBackward(self, world, joints, points, grad_out, face=None, bary=None, weights=None,
+                             want=("points", "world", "joints", "weights"), out=None):
+        """Vector-Jacobian product of unskinPoints (smplpp_unskin_points_vjp) for grad_out = dL/d(rest points) [N,K,3]; "points" is
+        the gradient to the posed points.  Otherwise as skinPointsBackward."""
+        return self._bound_backward("unskinPointsBackward", True, world, joints, points, grad_out, face, bary, weights, want, out)
+
+    def skin_points_differentiable(self, world, joints, points, face=None, bary=None, weights=None):
+        """skinPoints' posed points [N,K,3] for device tensors, differentiable with torch.autograd in world, joints, points and
+        weights (not in face or bary: fixed correspondences); composes with skeleton_differentiable.  smplpp_skin_points forward,
+        smplpp_skin_points_vjp backward, on torch's current stream.  First derivatives only."""
+        if torch is None:
+            raise SmplppError(1, "skin_points_differentiable needs torch")
+        return _SkinPointsFunction.apply(world, joints, points, weights, face, bary, self, False)
+
+    def unskin_points_differentiable(self, world, joints, points, face=None, bary=None, weights=None):
+        """unskinPoints' rest-pose points [N,K,3], differentiable as skin_points_differentiable (points: the posed points)."""
+        if torch is None:
+            raise SmplppError(1, "unskin_points_differentiable needs torch")
+        return _SkinPointsFunction.apply(world, joints, points, weights, face, bary, self, True)
+
     # ---- silhouette term (smplpp_mask_distance_transform / smplpp_silhouette / smplpp_silhouette_vjp)
     def maskDistanceTransform(self, mask, want=("nearest", "sqdist")):
         """Exact Euclidean feature transform of binary images mask [N,H,W] (nonzero = set; smplpp_mask_distance_transform): returns
@@ -1396,6 +1507,32 @@ if torch is not None:
                 shared = ctx.offsets_shape != (n, V, 3)
                 gd = ctx.smpl.vertexOffsetsBackward(xforms, grad_verts.contiguous(), shared=shared).reshape(ctx.offsets_shape)
             return gb, gt, gd, None
+
+    class _SkinPointsFunction(torch.autograd.Function):
+        """smplpp_skin_points / smplpp_unskin_points forward, their VJPs backward (SMPL.skin_points_differentiable and
+        unskin_points_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, world, joints, points, weights, face, bary, smpl, unskin):
+            name = "unskin_points_differentiable" if unskin else "skin_points_differentiable"
+            out, _, _ = smpl._bound_forward(name, unskin, world, joints, points, face, bary, weights, (), device_only=True)
+            ctx.smpl, ctx.unskin, ctx.face = smpl, unskin, face
+            ctx.shapes = (tuple(points.shape), None if weights is None else tuple(weights.shape))
+            ctx.save_for_backward(world, joints, points, weights, bary)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            world, joints, points, weights, bary = ctx.saved_tensors
+            keys = ("world", "joints", "points", "weights")
+            want = tuple(k for k, need in zip(keys, ctx.needs_input_grad) if need and (k != "weights" or weights is not None))
+            if not want:
+                return (None,) * 8
+            fn = ctx.smpl.unskinPointsBackward if ctx.unskin else ctx.smpl.skinPointsBackward
+            g = fn(world, joints, points, grad_out.contiguous(), face=ctx.face, bary=bary, weights=weights, want=want)
+            gp, gw = g.get("points"), g.get("weights")
+            return (g.get("world"), g.get("joints"), None if gp is None else gp.reshape(ctx.shapes[0]),
+                    None if gw is None else gw.reshape(ctx.shapes[1]), None, None, None, None)
 
     class _LaplacianFunction(torch.autograd.Function):
         """smplpp_mesh_laplacian forward and, the operator being symmetric, backward (SMPL.mesh_laplacian_differentiable)."""
