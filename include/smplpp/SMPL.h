@@ -618,6 +618,44 @@ public:
     for(size_t i = 0; i < in.size(); i++) in[i] = inside.idata[i] != 0 ? 1 : 0;
     return distanceBackward(smplpp_point_mesh_distance_vjp, false, points, face, gradSignedSqdist, gradPoints, accumulate, what, in.data());
   }
+  // Ray casting against the last launch's meshes (smplpp_ray_cast): origin and dir [1,K,3] (one set of rays for every frame) or
+  // [N,K,3]; dir is used as given, t is in units of |dir|.  face [N,K] kInt64 (-1: no hit), t [N,K] (0 without a hit), bary [N,K,3],
+  // hits [N,K,2] kInt64 (front, back faces met in (tMin, tMax]).  facing: 1 front, 2 back, 3 both.
+  struct RayCast
+  {
+    Tensor face, t, bary, hits;
+  };
+  RayCast rayCast(const Tensor & origin, const Tensor & dir, float tMin = 0.0f, float tMax = std::numeric_limits<float>::infinity(),
+                  int facing = 3) const
+  {
+    int64_t rf = 0;
+    const int64_t n = raysFor(origin, dir, rf, "Cannot cast the rays!"), K = origin.size(1);
+    std::vector<int32_t> h((size_t)(n * K * 2));
+    RayCast r{Tensor({n, K}, kInt64), Tensor({n, K}), Tensor({n, K, 3}), Tensor({n, K, 2}, kInt64)};
+    check(smplpp_ray_cast(m_.get(), n, verts_.ptr(), rf, K, origin.ptr(), dir.ptr(), tMin, tMax, facing, r.face.idata.data(), r.t.ptr(),
+                          r.bary.ptr(), h.data(), SMPLPP_HOST, nullptr),
+          "SMPL");
+    for(size_t i = 0; i < h.size(); i++) r.hits.idata[i] = h[i];
+    return r;
+  }
+  // Its backward pass (smplpp_ray_cast_vjp) at the faces `face` [N,K] it gave, for gradT = dL/dt [N,K]: verts [N,V,3], origin and
+  // dir in the rays' shape ([1,K,3]: the frames' sum).
+  struct RayCastGrad
+  {
+    Tensor verts, origin, dir;
+  };
+  RayCastGrad rayCastBackward(const Tensor & origin, const Tensor & dir, const Tensor & face, const Tensor & gradT) const
+  {
+    const char * what = "Cannot back-propagate through the ray cast!";
+    int64_t rf = 0;
+    const int64_t n = raysFor(origin, dir, rf, what), K = origin.size(1);
+    if(face.dtype != kInt64 || face.numel() != n * K || gradT.dtype != kFloat32 || gradT.numel() != n * K) throw Exception("SMPL", what);
+    RayCastGrad r{Tensor({n, V_, 3}), Tensor({rf, K, 3}), Tensor({rf, K, 3})};
+    check(smplpp_ray_cast_vjp(m_.get(), n, verts_.ptr(), rf, K, origin.ptr(), dir.ptr(), face.idata.data(), gradT.ptr(), r.verts.ptr(),
+                              r.origin.ptr(), r.dir.ptr(), 0, SMPLPP_HOST, nullptr),
+          "SMPL");
+    return r;
+  }
   // Self-intersections of the last launch's meshes (smplpp_self_intersections): pairs [N,maxPairs,2] kInt64 in ascending (f, g),
   // -1 past count, and count [N] kInt64, the true totals (a frame with more than maxPairs pairs keeps the lowest maxPairs).
   struct SelfIntersections
@@ -1086,6 +1124,17 @@ private:
     const int64_t n = verts_.size(0);
     if(points.dtype != kFloat32 || points.dim() != 3 || points.size(0) != n || points.size(1) < 1 || points.size(2) != 3)
       throw Exception("SMPL", what);
+    return n;
+  }
+  // frames of the last launch, checked against rays origin and dir [1 or N,K,3]; rf = the rays' frames
+  int64_t raysFor(const Tensor & origin, const Tensor & dir, int64_t & rf, const char * what) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0);
+    if(origin.dtype != kFloat32 || dir.dtype != kFloat32 || origin.dim() != 3 || origin.shape != dir.shape || (origin.size(0) != 1 && origin.size(0) != n)
+       || origin.size(1) < 1 || origin.size(2) != 3)
+      throw Exception("SMPL", what);
+    rf = origin.size(0);
     return n;
   }
   // the *DistanceBackward: ids and gradSqdist hold one entry per vertex (perVertex) or per point; inside non-null: the signed distance's

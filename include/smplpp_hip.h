@@ -364,6 +364,63 @@ int smplpp_point_mesh_signed_distance_vjp(smplpp_model * m, int64_t n, const flo
                                           const int64_t * face /*[n,K]*/, const uint8_t * inside /*[n,K]*/,
                                           const float * grad_signed_sqdist /*[n,K]*/, float * grad_verts /*[n,V,3] nullable*/,
                                           float * grad_points /*[n,K,3] nullable*/, int accumulate, int space, void * stream);
+/* Ray casting: where each of K rays per frame first meets that frame's posed mesh verts [n,V,3] (range sensors that are no pinhole
+ * grid, normal shooting, occlusion of arbitrary segments, thickness).  A ray is origin + t dir; dir is used as given, not
+ * normalised, and t is in units of |dir|.  With ray_frames = 1 the one set of rays [1,K,3] is cast against every frame.
+ * The rule is fp32, every operation rounded on its own (no FMA), divisions correctly rounded:
+ *  - per ray: kz = the axis of the largest |dir| (the lowest on a tie), kx = (kz + 1) mod 3, ky = (kz + 2) mod 3, Sx = dir[kx] / dir[kz],
+ *    Sy = dir[ky] / dir[kz].  A ray is DEAD when a coordinate of origin or dir is not finite or dir[kz] == 0: face -1, t 0, bary 0,
+ *    hits 0.
+ *  - per (ray, vertex): P = x - origin, X = P[kx] - Sx P[kz], Y = P[ky] - Sy P[kz]: the vertex in the ray's own sheared plane.  These
+ *    two fp32 numbers depend on the ray and the vertex only, never on the face, so two faces see a shared edge identically.
+ *  - per edge p -> q of a face, in stored corner order (c0,c1), (c1,c2), (c2,c0): e = the sign of the EXACT real number
+ *    X_p Y_q - Y_p X_q (the two rounded fp32 products compared where they differ, which is exact because rounding is monotone; in
+ *    fp64, where both products are exact, where they are equal).  Where that number is zero, e = the sign of Y_p - Y_q, and where
+ *    that is zero too, of X_q - X_p: the sign the edge function takes when the ray is moved by (eps, eps^2) in its plane for every
+ *    small enough eps > 0.  (A tie rule on vertex ids, p < q, gives a ray on a shared edge to one of its two faces but a ray through a
+ *    vertex to as many faces of its fan as the ids happen to descend through it, none or several; the shift is one geometric
+ *    direction for all faces, so the ray is inside exactly the faces a generic ray beside it is inside.)
+ *  - a face is COVERED with sign s in {+1, -1} when its three edges have e = s, and is FRONT when s sign(dir[kz]) < 0 (in exact
+ *    arithmetic s |dir[kz]| has the sign of n . dir, n = (b - a) x (c - a): front = the ray runs against the stored winding's normal),
+ *    else BACK.  facing = 1 keeps front faces, 2 back faces, 3 both.  A face with a corner that is not finite covers nothing (device
+ *    data is never refused).  On a closed consistently oriented mesh every live ray is covered by as many front as back faces.
+ *  - range of a covered face (a, b, c): A = a - origin, e1 = b - a, e2 = c - a, n = e1 x e2 (each component u v - w z),
+ *    na = (n.x A.x + n.y A.y) + n.z A.z, nd the same form with dir, t = na / nd.  The candidate is dropped unless t is finite and
+ *    t_min < t <= t_max.
+ *  - the winner is the smallest t, on equal bits the lowest face id: the minimum of bits(t) << 32 | face (monotone: t > t_min >= 0).
+ *    face = -1 and t = 0 when nothing is left.
+ *  - bary [n,K,3] (nullable), as smplpp_depth_raster forms it from the hit point: w = t dir - A,
+ *    beta_b = (w x e2) . n / nn, beta_c = (e1 x w) . n / nn, beta_a = (1 - beta_b) - beta_c, nn = (n.x n.x + n.y n.y) + n.z n.z,
+ *    every cross component u v - w z and every dot (x + y) + z.  0 without a hit.
+ *  - hits [n,K,2] (nullable) = (front, back) counts of the ray's accepted candidates under `facing` (integers).
+ *  - the bits do not depend on n, on the frame's slot, on ray_frames, on the memory space, on the outputs asked for or on how the call
+ *    deals the 256-face chunks over workgroups (from n and K alone; SMPLPP_RAY_SLICES = 1..4096 in the environment of
+ *    smplpp_model_create fixes the count, for tests).  Workgroups meet through a 64-bit integer minimum and integer adds; there are
+ *    no floating-point atomics.
+ *  - SMPLPP_ERR_INVALID: bad arguments, a model without faces, ray_frames not 1 or n, K < 1, t_min not finite or < 0, t_max NaN or
+ *    <= t_min (+inf is allowed), facing outside 1..3, n K, n V or n F beyond int32 indexing. */
+int smplpp_ray_cast(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t ray_frames /*1 or n*/, int64_t K,
+                    const float * origin /*[ray_frames,K,3]*/, const float * dir /*[ray_frames,K,3]*/, float t_min, float t_max,
+                    int facing /*1 front, 2 back, 3 both*/, int64_t * face /*[n,K]*/, float * t /*[n,K]*/,
+                    float * bary /*[n,K,3] nullable*/, int32_t * hits /*[n,K,2] nullable*/, int space, void * stream);
+/* Vector-Jacobian product of t above for g = grad_t [n,K], at the faces `face` the forward gave, held fixed.  The range is recomputed
+ * on the named face (na, nd, t, then the barycentrics of t dir as above) and no state is kept.  For a ray with 0 <= face < F, not
+ * dead, and g != 0:
+ *    vec = (g / nd) n;   corner i (a, b, c) receives beta_i vec;   grad_origin = -vec;   grad_dir = -(t vec).
+ * Every other ray (face = -1, a dead ray, g == 0, a device-space id out of range) contributes nothing, even on NaN data.
+ *  - grad_verts [n,V,3] is one fixed-order sum per vertex from +0: ascending ray, then corner (the record gather of the scan
+ *    distances); no floating-point atomics.
+ *  - ray_frames = 1: grad_origin and grad_dir [1,K,3] are the frames' sums in the two-level order of smplpp_vertex_offsets_vjp (tiles
+ *    of SMPLPP_VERTEX_OFFSETS_TILE frames, ascending within a tile from its first term, then across the tiles; a ray that contributes
+ *    nothing is the term +0).
+ *  - any output may be NULL, not all.  accumulate = 0 stores the finished value, 1 adds it to what the output holds (one addition at
+ *    the end).  There is no cotangent for bary: a hit point's cotangent is composed by the caller through origin + t dir.
+ *  - SMPLPP_ERR_INVALID: as the forward's (without t_min, t_max, facing), accumulate not 0 or 1, a host-space face id outside [-1, F)
+ *    (the outputs are untouched). */
+int smplpp_ray_cast_vjp(smplpp_model * m, int64_t n, const float * verts, int64_t ray_frames, int64_t K, const float * origin,
+                        const float * dir, const int64_t * face /*[n,K], held fixed*/, const float * grad_t /*[n,K]*/,
+                        float * grad_verts /*[n,V,3] nullable*/, float * grad_origin /*[ray_frames,K,3] nullable*/,
+                        float * grad_dir /*[ray_frames,K,3] nullable*/, int accumulate, int space, void * stream);
 /* Self-intersections of each frame's posed mesh verts [n,V,3]: every pair of the model's faces (f, g), f < g, that share no vertex
  * and intersect under this exact fp32 rule (every operation rounded on its own, no FMA):
  *  - orient(a,b,c,d): u = b-a, v = c-a, w = d-a; cx = u.y v.z - u.z v.y, cy = u.z v.x - u.x v.z, cz = u.x v.y - u.y v.x;

@@ -87,6 +87,8 @@ def load():
         "smplpp_point_mesh_winding": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int, vp],
         "smplpp_point_mesh_signed_distance": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_point_mesh_signed_distance_vjp": [vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_ray_cast": [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_ray_cast_vjp": [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_self_intersections": [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int, vp],
         "smplpp_self_penetration": [vp, C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, C.c_int, vp],
         "smplpp_self_penetration_vjp": [vp, C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],

@@ -169,6 +169,7 @@ struct SelfPenState;    // self-intersections, the self-penetration energy and i
 struct DepthRasterState; // the depth rasteriser, its backward pass and that of the raster interpolation (raster_walk.h)
 struct SilhouetteState;  // the mask distance transform, the silhouette residuals and their backward pass (silhouette.hip)
 struct VertexOffsetsState; // the tile sums of the shared SMPL+D backward (vertex_offsets.hip)
+struct RayCastState;     // ray casting: the rays' keys, the backward pass's records and per-frame terms (ray_cast.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -182,6 +183,7 @@ struct StateDelete
   void operator()(DepthRasterState * s) const;
   void operator()(SilhouetteState * s) const;
   void operator()(VertexOffsetsState * s) const;
+  void operator()(RayCastState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -249,5 +251,7 @@ struct smplpp_model
   smplpp_hip::StatePtr<smplpp_hip::VertexOffsetsState> vo; // SMPL+D shared-backward workspace (vertex_offsets.hip): null until its first call
   int sp_frames = 0;            // bound points: frames a workgroup of sp_point_kernel holds in LDS (SMPLPP_SKIN_POINTS_FRAMES, read at model creation): 0 = by n and K
   int sp_split = 0;             // bound points: threads per partial of the per-joint sums (SMPLPP_SKIN_POINTS_SPLIT = 4 | 1, read at model creation): 0 = by K
+  int ray_slices = 0;           // ray casting: workgroups that share a (frame, ray block)'s face chunks (SMPLPP_RAY_SLICES, read at model creation): 0 = by n and K
+  smplpp_hip::StatePtr<smplpp_hip::RayCastState> rc; // ray casting workspace (ray_cast.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

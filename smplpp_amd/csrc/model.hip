@@ -292,7 +292,7 @@ extern "C" int smplpp_model_destroy(smplpp_model * m)
   return SMPLPP_OK;
 }
 
-// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM, SMPLPP_DEPTH_RASTER_INLINE, SMPLPP_VERTEX_OFFSETS_FRAMES and SMPLPP_SKIN_POINTS_* are read here, once per model (m.maxw and m.VGPn are set)
+// SMPLPP_SKIN, SMPLPP_POINT_DISTANCE_FORM, SMPLPP_DEPTH_RASTER_INLINE, SMPLPP_VERTEX_OFFSETS_FRAMES, SMPLPP_SKIN_POINTS_* and SMPLPP_RAY_SLICES are read here, once per model (m.maxw and m.VGPn are set)
 static void read_env(smplpp_model & m)
 {
   std::tie(m.form, m.form_ik) = choose_forms(getenv("SMPLPP_SKIN"), m.maxw, m.VGPn);
@@ -309,6 +309,9 @@ static void read_env(smplpp_model & m)
   const char * sps_env = getenv("SMPLPP_SKIN_POINTS_SPLIT"); // 4 | 1: partials per thread of the bound points' per-joint sums (no bit depends on it)
   const int sp_nq = sps_env ? atoi(sps_env) : 0;
   m.sp_split = sp_nq == 4 || sp_nq == 1 ? sp_nq : 0;
+  const char * rs_env = getenv("SMPLPP_RAY_SLICES"); // 1..4096: workgroups that share a (frame, ray block)'s face chunks in smplpp_ray_cast (no bit depends on it)
+  const int rs = rs_env ? atoi(rs_env) : 0;
+  m.ray_slices = rs >= 1 && rs <= 4096 ? rs : 0;
 }
 
 // Validate, build the host tables (model_tables.h), then upload them and lay the bases out on the device.

@@ -70,6 +70,21 @@ def pinhole_camera_rows(camera, n):
     return np.ascontiguousarray(camera)
 
 
+def camera_rays(camera, H, W):
+    """The depth rasteriser's pixel-centre rays in world space, for SMPL.rayCast: (origin [n,H*W,3], dir [n,H*W,3]) float32 of camera
+    rows [n,16] (or [16]) as pinhole_camera lays them out.  Pixel (row j, column i) is ray j * W + i with origin -R^T t and
+    dir = R^T ((i + 0.5 - cx) / fx, (j + 0.5 - cy) / fy, 1), so the range t along it is the rasteriser's depth.  Formed in float64,
+    then rounded once."""
+    cam = np.asarray(camera, np.float64).reshape(-1, 16)
+    R, t = cam[:, :9].reshape(-1, 3, 3), cam[:, 9:12]
+    j, i = np.meshgrid(np.arange(int(H), dtype=np.float64), np.arange(int(W), dtype=np.float64), indexing="ij")
+    dx = ((i.reshape(1, -1) + 0.5) - cam[:, 14:15]) / cam[:, 12:13]
+    dy = ((j.reshape(1, -1) + 0.5) - cam[:, 15:16]) / cam[:, 13:14]
+    dc = np.stack([dx, dy, np.ones_like(dx)], 2)
+    origin = np.broadcast_to(-np.einsum("nji,nj->ni", R, t)[:, None], dc.shape)
+    return np.ascontiguousarray(origin, np.float32), np.ascontiguousarray(np.einsum("nji,nkj->nki", R, dc), np.float32)
+
+
 class _Call:
     """The memory space of one ABI call, decided by its first array argument: numpy arrays are host space (converted to float32; the
     call stages and synchronises), torch tensors device space (CUDA float32 only; enqueued on torch's current stream).  `fail` is
@@ -911,6 +926,79 @@ class SMPL:
             raise SmplppError(1, "point_mesh_signed_distance_differentiable needs torch")
         return _SignedDistanceFunction.apply(verts, points, self)
 
+    # ---- ray casting (smplpp_ray_cast / smplpp_ray_cast_vjp)
+    def _ray_inputs(self, c, verts, origin, dir):
+        """verts [N,V,3] and the rays ([K,3] or [1,K,3]: one set for every frame; [N,K,3]: one per frame) checked in the space of `c`;
+        returns (n, frames of the rays, K, verts, origin, dir)."""
+        n = len(verts)
+        if not c.dev:
+            origin, dir = _np32(origin), _np32(dir)
+        if len(origin.shape) == 2:
+            origin = origin.reshape((1,) + tuple(origin.shape))
+        if len(dir.shape) == 2:
+            dir = dir.reshape((1,) + tuple(dir.shape))
+        shape = tuple(origin.shape)
+        if len(shape) != 3 or shape[0] not in (1, n) or shape[1] < 1 or shape[2] != 3 or tuple(dir.shape) != shape:
+            c.refuse("expected origin and dir of one shape (K, 3), (1, K, 3) or (%d, K, 3), got %s and %s" % (n, shape, tuple(dir.shape)))
+        rf, K = int(shape[0]), int(shape[1])
+        return n, rf, K, c.input(verts, (n, self.vertex_num, 3)), c.input(origin, (rf, K, 3)), c.input(dir, (rf, K, 3))
+
+    def _ray_cast(self, c, n, rf, K, verts, origin, dir, t_min, t_max, facing, want):
+        face, t = c.empty((n, K), "int64"), c.empty((n, K))
+        bary = c.empty((n, K, 3)) if "bary" in want else None
+        hits = c.empty((n, K, 2), "int32") if "hits" in want else None
+        check(_lib.load().smplpp_ray_cast(self.handle, n, _ptr(verts), rf, K, _ptr(origin), _ptr(dir), float(t_min), float(t_max), int(facing),
+                                          _ptr(face), _ptr(t), _ptr(bary), _ptr(hits), c.space, c.stream))
+        return face, t, bary, hits
+
+    def rayCast(self, verts, origin, dir, t_min=0.0, t_max=float("inf"), facing=3, want=("bary", "hits")):
+        """Where each ray origin + t dir first meets each frame's mesh verts [N,V,3] (smplpp_ray_cast).  origin and dir are [K,3] or
+        [1,K,3] (one set of rays cast against every frame) or [N,K,3]; dir is used as given, so t is in units of |dir|.  Returns a dict
+        of face [N,K] int64 (-1: no hit), t [N,K] (0 without a hit), bary [N,K,3] (of the face's corners at the hit), hits [N,K,2]
+        int32 (front and back faces met in (t_min, t_max]) and hit [N,K] bool = face >= 0.  facing = 1 keeps the faces the ray meets
+        against their normal (front), 2 the others (back), 3 both; only t_min < t <= t_max counts.  The hit point is
+        origin + t[..., None] * dir.  A ray with a coordinate that is not finite, or a zero dir, hits nothing.  `want` drops bary or hits.
+        numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("rayCast", verts, origin, dir)
+        n, rf, K, verts, origin, dir = self._ray_inputs(c, verts, origin, dir)
+        face, t, bary, hits = self._ray_cast(c, n, rf, K, verts, origin, dir, t_min, t_max, facing, want)
+        out = dict(face=face, t=t, hit=face >= 0)
+        if bary is not None:
+            out["bary"] = bary
+        if hits is not None:
+            out["hits"] = hits
+        return out
+
+    def rayCastBackward(self, verts, origin, dir, face, grad_t, want=("verts", "origin", "dir"), out=None):
+        """Vector-Jacobian product of rayCast's t at the faces `face` [N,K] it gave, held fixed (smplpp_ray_cast_vjp): a dict of "verts"
+        [N,V,3], "origin" and "dir" (the rays' shape as cast: [1,K,3] for shared rays, the frames' sum) for dL/dt = grad_t [N,K].  A ray
+        without a hit contributes nothing.  `want` drops outputs; with `out` (a dict keyed the same way) the gradients are ADDED into
+        its arrays."""
+        acc = out is not None
+        c = _Call("rayCastBackward", verts, origin, dir, grad_t, *(out.values() if acc else ()))
+        n, rf, K, verts, origin, dir = self._ray_inputs(c, verts, origin, dir)
+        ids = c.ids(face)
+        if ids.shape[0] != n * K:
+            c.refuse("expected face ids of shape %s" % ((n, K),))
+        g = c.input(grad_t, (n, K))
+        shapes = {"verts": (n, self.vertex_num, 3), "origin": (rf, K, 3), "dir": (rf, K, 3)}
+        keys = [k for k in shapes if k in (out if acc else want)]
+        if not keys:
+            c.refuse("verts, origin or dir must be asked for")
+        res = {k: c.inout(out[k], shapes[k]) if acc else c.empty(shapes[k]) for k in keys}
+        check(_lib.load().smplpp_ray_cast_vjp(self.handle, n, _ptr(verts), rf, K, _ptr(origin), _ptr(dir), _ptr(ids), _ptr(g), _ptr(res.get("verts")),
+                                              _ptr(res.get("origin")), _ptr(res.get("dir")), int(acc), c.space, c.stream))
+        return res
+
+    def ray_cast_differentiable(self, verts, origin, dir, t_min=0.0, t_max=float("inf"), facing=3):
+        """rayCast's dict for device tensors (the same bits), with t differentiable in verts, origin and dir through torch.autograd:
+        smplpp_ray_cast forward, smplpp_ray_cast_vjp backward at the faces hit, on torch's current stream.  face, bary, hits and hit
+        are constants; a hit point with a gradient is origin + t[..., None] * dir.  A range term is e.g. ((t - measured)[hit] ** 2).sum()."""
+        if torch is None:
+            raise SmplppError(1, "ray_cast_differentiable needs torch")
+        face, t, bary, hits, hit = _RayCastFunction.apply(verts, origin, dir, self, float(t_min), float(t_max), int(facing))
+        return dict(face=face, t=t, bary=bary, hits=hits, hit=hit)
+
     # ---- self-intersections and the self-penetration energy (smplpp_self_intersections / smplpp_self_penetration[_vjp])
     def _sp_forward(self, name, verts, max_pairs, sigma, check_count, energy, device_only=False):
         c = _Call(name, verts, device_only=device_only)
@@ -1668,6 +1756,31 @@ if torch is not None:
             ctx.save_for_backward(verts, points, face)
             return face, w, inside, sq
 
+
+    class _RayCastFunction(torch.autograd.Function):
+        """smplpp_ray_cast forward / smplpp_ray_cast_vjp backward (SMPL.ray_cast_differentiable)."""
+
+        @staticmethod
+        def forward(ctx, verts, origin, dir, smpl, t_min, t_max, facing):
+            c = _Call("ray_cast_differentiable", verts, origin, dir, device_only=True)
+            n, rf, K, v, o, d = smpl._ray_inputs(c, verts, origin, dir)
+            face, t, bary, hits = smpl._ray_cast(c, n, rf, K, v, o, d, t_min, t_max, facing, ("bary", "hits"))
+            hit = face >= 0
+            ctx.mark_non_differentiable(face, bary, hits, hit)
+            ctx.smpl, ctx.shapes = smpl, (tuple(origin.shape), tuple(dir.shape))
+            ctx.save_for_backward(v, o, d, face)
+            return face, t, bary, hits, hit
+
+        @staticmethod
+        def backward(ctx, _gf, grad_t, _gb, _gh, _ghit):
+            v, o, d, face = ctx.saved_tensors
+            want = tuple(k for k, need in zip(("verts", "origin", "dir"), ctx.needs_input_grad) if need)
+            if not want:
+                return (None,) * 7
+            g = ctx.smpl.rayCastBackward(v, o, d, face, grad_t.contiguous(), want=want)
+            go, gd = g.get("origin"), g.get("dir")
+            return (g.get("verts"), None if go is None else go.reshape(ctx.shapes[0]), None if gd is None else gd.reshape(ctx.shapes[1]), None,
+                    None, None, None)
 
     class _SelfPenetrationFunction(torch.autograd.Function):
         """smplpp_self_penetration forward / smplpp_self_penetration_vjp backward (SMPL.self_penetration_differentiable)."""
