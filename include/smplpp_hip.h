@@ -63,6 +63,8 @@ struct smplpp_sequence;                     /* the layout of sequences inside a 
                                                `struct smplpp_sequence` throughout, as the three above */
 struct smplpp_volume;                       /* a signed-distance grid of a static scene, resident on the device (no reference
                                                counterpart); written `struct smplpp_volume` throughout, as the four above */
+struct smplpp_measure;                      /* regions of a model's faces and plane sections through them, for body measurements (no
+                                               reference counterpart); written `struct smplpp_measure` throughout, as the five above */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -1377,6 +1379,71 @@ int smplpp_gather_selfcheck(void * comm, int rank, const float * send, float * r
  * arithmetic shared by the two collectives; callable without a GPU. */
 int smplpp_gather_offsets(const int64_t * rows_per_rank, int world, int64_t row_floats, int64_t * offsets);
 
+/* ------------------------------------------------------------------ body measurements: part areas, volumes and plane girths
+ * How large the posed body is: the surface area and the enclosed volume of regions of the mesh, and the length of the curve a plane
+ * cuts from a region (chest, waist, hip, thigh).  No reference counterpart.  A REGION is a list of faces of the model (0-based ids): a
+ * body part, or all faces.  1 <= R <= 256; regions may overlap ("whole body" and "torso" on one handle); a region may be empty; a face
+ * appears at most once in a region; the order of a region's list is the order of its sums.  A SECTION is a plane paired with the
+ * region whose faces it cuts, 0 <= S <= 256: the chest plane paired with the torso keeps the arms out of the chest girth.  region_ptr
+ * [R+1], region_face [nnz = region_ptr[R]] and section_region [S] are host pointers.  The handle copies what it needs of the model (V,
+ * the faces, the per-vertex adjacency, the device): it may outlive it.  Creation builds, on the host, the region lists as int32, for
+ * every face the (region, slot) pairs that hold it in ascending region, and for every region its sections in ascending s.
+ *  - SMPLPP_ERR_INVALID: R outside [1, 256], S outside [0, 256], region_ptr[0] != 0 or not non-decreasing, a face id outside [0, F), a
+ *    face twice in one region, a section_region outside [0, R), a NULL array that is needed (*out = NULL). */
+int smplpp_measure_create(smplpp_model * m, int64_t R, const int64_t * region_ptr /*[R+1] host*/,
+                          const int64_t * region_face /*[nnz] host, 0-based face ids*/, int64_t S,
+                          const int64_t * section_region /*[S] host*/, struct smplpp_measure ** out);
+int smplpp_measure_destroy(struct smplpp_measure * ms);
+int smplpp_measure_info(const struct smplpp_measure * ms, int64_t * R, int64_t * nnz, int64_t * S);
+/* area [n,R], volume [n,R], section [n,S], crossings [n,S] of verts [n,V,3].  fp32, every operation rounded on its own (no FMA),
+ * division and square root correctly rounded.
+ * Per face f with corners 0, 1, 2 in stored order, p_i = v_i - c with c = center[frame] (NULL: zeros, the same bits as a zero array):
+ *    a = p1 - p0, b = p2 - p0, cr = a x b,   area_f = 0.5f * sqrtf((cr.x cr.x + cr.y cr.y) + cr.z cr.z)
+ *    w = p1 x p2,                             vol_f  = ((p0.x w.x + p0.y w.y) + p0.z w.z) / 6.0f
+ * (u x v = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x)).  On a closed, outward-oriented region `volume` is the enclosed
+ * volume and in exact arithmetic does not depend on center; an open region's volume is that of the cone from center over it.  center
+ * exists because a body 2.5 m from the origin loses digits to cancellation; it is a constant of the definition and has no cotangent.
+ * Section s of region r, plane (nx, ny, nz, d) = planes[frame or 0][s], the plane n.x = d, used as given (not normalised):
+ *    per corner, on the raw vertex:  s_i = ((nx x_i + ny y_i) + nz z_i) - d,  above_i = (s_i >= 0)    (no face enters: both faces of
+ *    an edge see the same value); the face is crossed iff one or two corners are above.  L is the corner alone on its side, M and N
+ *    the other two in cyclic corner order after L.  For the edges (L, M) and (L, N) in turn, a is the end below and b the end above:
+ *    t = s_a / (s_a - s_b),  q = a + t (b - a) per coordinate (s_a < 0 <= s_b: the divisor is never zero);  with e = q_(L,N) - q_(L,M)
+ *    the face's term is sqrtf((e.x e.x + e.y e.y) + e.z e.z).  crossings counts the crossed faces.
+ * This is the contour of {s >= 0} on the surface, the plane moved by +eps: an edge lying in the plane is counted once, by the face
+ * below it; a face lying in the plane contributes nothing itself and its border is counted by its below-side neighbours; a plane
+ * through a vertex needs no special case.
+ * area[i,r], volume[i,r] and section[i,s] are each ONE sum1024 (FIXED-ORDER SUMS) over the region's list index k; a face that is not
+ * crossed adds +0.  Dead data: a face with a corner that is not finite adds +0 to every sum and is not counted; a plane with an entry
+ * that is not finite or with a zero normal gives section 0 and crossings 0.  Each output may be NULL, not all.  The bits of a frame do
+ * not depend on n, on its position in the batch, on the memory space, on the outputs asked for or on what else shares the handle.
+ *  - SMPLPP_ERR_INVALID: n <= 0, verts NULL, plane_frames not 1 or n, planes NULL with S > 0, no output, n V 3, n R or n S 4 beyond
+ *    int32 indexing (the outputs are untouched). */
+int smplpp_measure(struct smplpp_measure * ms, int64_t n, const float * verts /*[n,V,3]*/, const float * center /*[n,3] nullable = 0*/,
+                   const float * planes /*[plane_frames,S,4] (nx,ny,nz,d): n.x = d; NULL iff S = 0*/, int64_t plane_frames /*1 or n*/,
+                   float * area /*[n,R] nullable*/, float * volume /*[n,R] nullable*/, float * section /*[n,S] nullable*/,
+                   int32_t * crossings /*[n,S] nullable*/, int space, void * stream);
+/* Its vector-Jacobian product in closed form, at the crossing pattern of the forward.  A TERM is the gradient of one face's share
+ * of one output; it exists only where its cotangent is given and not 0, the face is live and, for a section, the plane is live, the
+ * face is crossed and its term is not 0; for an area, |cr| != 0.  With g the cotangent:
+ *    area:    k = (g 0.5f) / |cr|, gc = k cr;  to corner 1: ga = b x gc, to corner 2: gb = gc x a, to corner 0: -(ga + gb)
+ *    volume:  k = g / 6.0f;  to corner 0: k (p1 x p2), to corner 1: k (p2 x p0), to corner 2: k (p0 x p1)
+ *    section: gu = g (e / len) per coordinate; the edge (L, M) takes gq = -gu, the edge (L, N) gq = gu.  Per edge, with ba = b - a:
+ *             gt = (gq.x ba.x + gq.y ba.y) + gq.z ba.z,  r = gt / (s_a - s_b),  gsa = -(r (s_b / (s_a - s_b))),  gsb = r t;
+ *             to a: (1.0f - t) gq + gsa n, to b: t gq + gsb n (each coordinate: product + product);
+ *             to the plane: (gsa a + gsb b per coordinate, (-gsa) - gsb).
+ *             L receives its share of (L, M) plus its share of (L, N); the plane the share of (L, M) plus that of (L, N).
+ * grad_verts[i,v] is one sequential sum from +0 of the terms that exist, in this order: the vertex's incident faces in the order of
+ * the model's adjacency table (ascending face id); for a face, its corners that are v in ascending corner (one, unless the face is
+ * degenerate); then the regions that list the face in ascending r; for each region the area term, the volume term, then the region's
+ * sections in ascending s.  grad_planes[i,s,:] is four sum1024 over the region's list index k (a face without a term adds +0); with
+ * plane_frames = 1 and n > 1 the frames' sums are then summed in the two-level tile order of smplpp_vertex_offsets_vjp.  accumulate =
+ * 0 stores, 1 adds the finished sum once.  A NULL cotangent is zero and costs nothing.  No floating-point atomics; the handle's own
+ * workspace ([n,S,4] floats for shared planes); deterministic, with the independence of the forward.  One caller thread per handle.
+ *  - SMPLPP_ERR_INVALID: as the forward, accumulate not 0 or 1 (the outputs are untouched). */
+int smplpp_measure_vjp(struct smplpp_measure * ms, int64_t n, const float * verts, const float * center, const float * planes,
+                       int64_t plane_frames, const float * grad_area /*[n,R] nullable = 0*/, const float * grad_volume /*nullable*/,
+                       const float * grad_section /*[n,S] nullable*/, float * grad_verts /*[n,V,3] nullable*/,
+                       float * grad_planes /*[plane_frames,S,4] nullable*/, int accumulate, int space, void * stream);
 /* ------------------------------------------------------------------ VPoser decoder (src/VPoser.cpp) */
 /* VPoserDecoderImpl (VPoser.h:53-90): Linear(32,512) LeakyReLU Dropout(eval) Linear(512,512) LeakyReLU
  * Linear(512,126) -> 6D -> rotation (Gram-Schmidt, :129-141) -> axis-angle (:25-120).  Weights are

@@ -116,6 +116,11 @@ def load():
         "smplpp_landmarks_vjp": [vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_project_points": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, C.c_float, vp, vp, vp, C.c_int, vp],
         "smplpp_project_points_vjp": [C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_float, vp, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_measure_create": [vp, C.c_int64, vp, vp, C.c_int64, vp, C.POINTER(vp)],
+        "smplpp_measure_destroy": [vp],
+        "smplpp_measure_info": [vp, i64p, i64p, i64p],
+        "smplpp_measure": [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_measure_vjp": [vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_pose_prior_create": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
         "smplpp_pose_prior_destroy": [vp],
         "smplpp_pose_prior_info": [vp, i64p, i64p, C.POINTER(C.c_int)],
