@@ -1492,6 +1492,67 @@ int smplpp_axis_angle_to_rotmat(int device, int64_t n, const float * aa /*[n,3]*
  *  - SMPLPP_ERR_INVALID: n <= 0, a NULL pointer, accumulate not 0 or 1, a bad space (grad_aa is untouched). */
 int smplpp_axis_angle_to_rotmat_vjp(int device, int64_t n, const float * aa /*[n,3]*/, const float * grad_rot /*[n,3,3]*/,
                                     float * grad_aa /*[n,3]*/, int accumulate, int space, void * stream);
+/* ------------------------------------------------------------------ scan preparation: neighbours, normals, farthest points
+ * What a raw cloud needs before the scan terms take it: the k nearest cloud points of every query, a normal and a surface variation
+ * per point from those lists, and a thinning to M well-spread points.  The scan is data, so none has a vector-Jacobian product.  The
+ * calls take no handle and no workspace: `device` as the stage calls.  All arithmetic is fp32, every operation rounded on its own (no
+ * FMA), '/' and sqrt are the correctly rounded ones, every sum is sequential in the stated order, every choice is the minimum or maximum
+ * of a total order, and there are no floating-point atomics: no bit depends on the work split, on n, on the frame's slot, on the memory
+ * space or on which outputs are asked for.  THE DISTANCE of all three:  d(a, b) = ((dx dx + dy dy) + dz dz),  dx = a_x - b_x and so on
+ * (the distance of smplpp_mesh_point_distance).
+ *
+ * smplpp_cloud_knn: for every query q of frame f, the k nearest of the frame's K points.  queries NULL: the cloud queries itself
+ * (Q is not read and taken as K), and candidate j = q, the query's own index, is left out; another point with the same coordinates is
+ * listed at d = 0.  THE RULE: candidate j is listed iff d = d(query, p_j) is finite and d <= max_sqdist (+inf: no cap).  The listed
+ * candidates are ordered by the pair (d, j) lexicographically, ascending; count = min(k, how many are listed); rank r < count holds
+ * (index, sqdist) = the r-th pair, every rank from count on holds (-1, +0).  A query with a coordinate that is not finite has no finite
+ * d, so its count is 0.  index [n,Q,k] int32, sqdist [n,Q,k], count [n,Q] int32; each nullable, not all.  n, K or Q = 0 is no work
+ * (K = 0 with queries: every count 0).
+ *  - SMPLPP_ERR_INVALID: k outside 1..32, a negative n, K or Q, a NaN max_sqdist, every output NULL, a NULL points with K > 0, n Q k or
+ *    n K 3 or n Q 3 beyond int32 indexing, a bad space (the outputs are untouched). */
+int smplpp_cloud_knn(int device, int64_t n, int64_t K, const float * points /*[n,K,3]*/, int64_t Q, const float * queries /*[n,Q,3] nullable*/,
+                     int k, float max_sqdist, int32_t * index /*[n,Q,k] nullable*/, float * sqdist /*[n,Q,k] nullable*/,
+                     int32_t * count /*[n,Q] nullable*/, int space, void * stream);
+/* smplpp_cloud_normals: per point i of frame f, from its neighbour list index[f][i][0..k) (smplpp_cloud_knn in self-query mode; any
+ * k >= 1).  THE RULE, p = p_i:
+ *  1 neighbours: in rank order, each listed j with 0 <= j < K and e = p_j - p finite in all three components counts; any other entry is
+ *                skipped (a j >= K is skipped on the device and refused from host space).  m = that count + 1: the point itself, e = 0.
+ *  2 covariance: s_a = sum e_a and T_ab = sum e_a e_b (a <= b), both from +0 in rank order;  mean_a = s_a / m;
+ *                C_ab = T_ab - m (mean_a mean_b), m as a float.
+ *  3 Jacobi:     V = I; FOUR sweeps over the pairs (p, q) = (0,1), (0,2), (1,2).  A pair with C_pq == 0 is skipped.  Else
+ *                tau = (C_qq - C_pp) / (2 C_pq);  t = sg / (|tau| + sqrt(tau tau + 1)), sg = -1 for tau < 0, else 1 (t = 1 at tau = 0;
+ *                a tau tau that overflows gives t = 0);  c = 1 / sqrt(t t + 1);  s = t c;  h = t C_pq;  C_pp -= h;  C_qq += h;
+ *                C_pq = 0;  for the third index r: (C_rp, C_rq) = (c C_rp - s C_rq, s C_rp + c C_rq), on the old values and kept
+ *                symmetric;  for every r: (V_rp, V_rq) = (c V_rp - s V_rq, s V_rp + c V_rq).  lambda_i = C_ii, with column i of V.
+ *  4 order:      (lambda_0, lambda_1, lambda_2) with their columns sorted ascending by (value, column): the exchanges (0,1), (1,2),
+ *                (0,1), each made iff the later value < the earlier one.
+ *  5 normal:     v = the column of lambda_0;  normal = v / sqrt((v0 v0 + v1 v1) + v2 v2).  With a viewpoint c (Vn = 1: one for all
+ *                frames; Vn = n: one per frame) it is negated iff (n0 (c0 - p0) + n1 (c1 - p1)) + n2 (c2 - p2) < 0; with Vn = 0 iff the
+ *                component of largest magnitude (the lowest axis on ties) is < 0.
+ *  6 curvature:  lambda_0 / ((lambda_0 + lambda_1) + lambda_2), the surface variation, +0 unless that sum is > 0.
+ *  7 status:     1 (bit 0): m < 3 or p is not finite: normal and curvature are +0 and no other bit is set.  2 (bit 1): lambda_2 <= 0 or
+ *                (lambda_1 - lambda_0) < min_gap lambda_2: the normal is not unique (a line, a point); it is still written.
+ * A zero normal is what the compatible scan searches treat as unmatched, so `normal` goes straight into them.  normal [n,K,3],
+ * curvature [n,K], status [n,K] int32; each nullable, not all.  n or K = 0 is no work.
+ *  - SMPLPP_ERR_INVALID: k < 1, a negative n or K, Vn not 0, 1 or n, a NULL viewpoint with Vn > 0, min_gap negative or not finite,
+ *    every output NULL, a NULL points or index, n K k or n K 3 beyond int32 indexing, a host-space index >= K, a bad space (the outputs
+ *    are untouched). */
+int smplpp_cloud_normals(int device, int64_t n, int64_t K, const float * points /*[n,K,3]*/, int k, const int32_t * index /*[n,K,k]*/,
+                         const float * viewpoint /*[Vn,3]*/, int64_t Vn, float min_gap, float * normal /*[n,K,3] nullable*/,
+                         float * curvature /*[n,K] nullable*/, int32_t * status /*[n,K] nullable*/, int space, void * stream);
+/* smplpp_cloud_farthest_points: per frame, M of the K points by farthest-point sampling.  THE RULE: dmin_j = +inf for every finite
+ * point; a point that is not finite is never chosen.  Pick 0 is start[f] (NULL: 0) if that is a finite point of the frame, else the
+ * lowest finite index.  After pick s:  dmin_j = d < dmin_j ? d : dmin_j  with d = d(p_j, p_s) for every finite j, and s is marked
+ * chosen.  The next pick is the unchosen finite point with the largest dmin, the lowest index on ties (a total order, so the reduction
+ * tree is free).  radius_sq[i] is the pick's dmin when it was chosen (+inf for pick 0): the sequence never increases, and radius_sq[M-1]
+ * bounds the spacing of the sample from below.  When no unchosen finite point is left, the remaining picks hold (-1, +0).  min_sqdist
+ * [n,K] is every point's final dmin, +0 for the chosen points and for the ones that are not finite: the coverage of the sample.  It is
+ * required: above 16384 points it is the kernel's working array.  index [n,M] int32 and radius_sq [n,M] are nullable.  n = 0 is no work.
+ *  - SMPLPP_ERR_INVALID: a negative n, K or M, M outside 1..K, a NULL points or min_sqdist, n K 3 beyond int32 indexing, a host-space
+ *    start outside [0, K) (on the device it reads as "not a finite point"), a bad space (the outputs are untouched). */
+int smplpp_cloud_farthest_points(int device, int64_t n, int64_t K, const float * points /*[n,K,3]*/, int64_t M,
+                                 const int32_t * start /*[n] nullable = 0*/, int32_t * index /*[n,M] nullable*/,
+                                 float * radius_sq /*[n,M] nullable*/, float * min_sqdist /*[n,K]*/, int space, void * stream);
 
 #ifdef __cplusplus
 }

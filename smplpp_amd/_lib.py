@@ -193,6 +193,9 @@ def load():
         "smplpp_rotmat_to_axis_angle": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
         "smplpp_axis_angle_to_rotmat": [C.c_int, C.c_int64, vp, vp, C.c_int, vp],
         "smplpp_axis_angle_to_rotmat_vjp": [C.c_int, C.c_int64, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_cloud_knn": [C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int, C.c_float, vp, vp, vp, C.c_int, vp],
+        "smplpp_cloud_normals": [C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp, vp, C.c_int64, C.c_float, vp, vp, vp, C.c_int, vp],
+        "smplpp_cloud_farthest_points": [C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name, None)
