@@ -575,6 +575,26 @@ public:
           "SMPL");
     return r;
   }
+  // Distance along the mesh's edges on the last launch's vertices (smplpp_mesh_geodesic, which states the rule): dist [N,S,V] from S
+  // source sets, lists of vertex indices that the frames share (a set may be empty: its field is +inf).  +inf where no path leads and
+  // where dist > maxDist (+inf: no cap).  A graph distance: an upper bound of the surface's.  smplpp::SelfContact (Contact.h) builds
+  // the self-contact search on it.
+  Tensor meshGeodesic(const std::vector<std::vector<int64_t>> & sources, float maxDist = std::numeric_limits<float>::infinity()) const
+  {
+    need(verts_);
+    const int64_t n = verts_.size(0), S = (int64_t)sources.size();
+    if(S < 1) throw Exception("SMPL", "Cannot compute the geodesic distance!");
+    std::vector<int64_t> ptr(1, 0), ids;
+    for(const auto & s : sources)
+    {
+      ids.insert(ids.end(), s.begin(), s.end());
+      ptr.push_back((int64_t)ids.size());
+    }
+    ids.push_back(0); // (never an empty array)
+    Tensor dist({n, S, V_});
+    check(smplpp_mesh_geodesic(m_.get(), n, verts_.ptr(), S, ptr.data(), ids.data(), maxDist, dist.ptr(), SMPLPP_HOST, nullptr), "SMPL");
+    return dist;
+  }
   // Generalized winding numbers of each frame's mesh at points [N,K,3] on the last launch's vertices (smplpp_point_mesh_winding):
   // winding [N,K] (the bits calcSweepGrid's cells have at the same position), inside [N,K] kInt64 0 / 1 (winding > 0.5).
   struct PointMeshWinding

@@ -65,6 +65,8 @@ struct smplpp_volume;                       /* a signed-distance grid of a stati
                                                counterpart); written `struct smplpp_volume` throughout, as the four above */
 struct smplpp_measure;                      /* regions of a model's faces and plane sections through them, for body measurements (no
                                                reference counterpart); written `struct smplpp_measure` throughout, as the five above */
+struct smplpp_self_contact;                 /* the far relation of a model's rest mesh, for the self-contact search (no reference
+                                               counterpart); written `struct smplpp_self_contact` throughout, as the six above */
 
 const char * smplpp_last_error(void);
 /* Number of HIP devices visible; SMPLPP_ERR_HIP (and *count = 0) when there is none. */
@@ -1553,6 +1555,70 @@ int smplpp_cloud_normals(int device, int64_t n, int64_t K, const float * points 
 int smplpp_cloud_farthest_points(int device, int64_t n, int64_t K, const float * points /*[n,K,3]*/, int64_t M,
                                  const int32_t * start /*[n] nullable = 0*/, int32_t * index /*[n,M] nullable*/,
                                  float * radius_sq /*[n,M] nullable*/, float * min_sqdist /*[n,K]*/, int space, void * stream);
+/* ------------------------------------------------------------------ surface geodesics and the self-contact search
+ * Distance along the surface, and with it the rule "a vertex's contact partner is the nearest other vertex in space among those that
+ * are far along the surface" (the self-contact terms of TUCH and SMPLify-XMC).  All arithmetic is fp32, every operation rounded on its
+ * own (no FMA), sqrt is the correctly rounded one, every choice is the minimum of a total order, and there are no floating-point atomics:
+ * no bit depends on n, on the frame's slot, on the memory space, on the other fields of a call or on how the work is split.
+ *
+ * smplpp_mesh_geodesic: field s of frame i is the distance along the edges of the mesh from the source set
+ * source_vertex[source_ptr[s] .. source_ptr[s+1]), which the frames share.  The edges are the undirected edges of the model's faces,
+ * each once.  THE RULE:
+ *  length    w(u, v) = sqrt((dx dx + dy dy) + dz dz),  d = x_hi - x_lo,  lo = min(u, v),  hi = max(u, v): the same bits in both
+ *            directions.  An edge whose length is not finite does not exist (a NaN or inf vertex is routed around); 0 is a length.
+ *  distance  dist[v] = the minimum over all edge paths from any source of the set to v of the left-to-right fp32 sum of the path's
+ *            lengths, the sum starting from +0 at the source.  fl(a + w) is monotone in a, so this is the fixed point of
+ *            dist[v] <- min(dist[v], fl(dist[u] + w(u, v)))  from dist = +inf, dist[source] = 0, reached in any order of relaxation
+ *            (smplpp_amd/csrc/edge_tables.h carries the argument).
+ *  outputs   an unreachable vertex: +inf.  An empty set: all +inf.  A repeated source is harmless.  dist[v] > max_dist is reported as
+ *            +inf: the bits of thresholding the uncapped field (max_dist = +inf: no cap).
+ * The distance is a graph distance, an upper bound of the exact surface geodesic.  It has no vector-Jacobian product.
+ *  - SMPLPP_ERR_INVALID (dist untouched): n <= 0 or S <= 0; a NULL verts, source_ptr or dist, or a NULL source_vertex with a source
+ *    listed; source_ptr not starting at 0 or not non-decreasing (a device-space source_ptr is read back for this check: the call then
+ *    waits for the stream once); a HOST-space source outside [0, V) (a device-space one is ignored); max_dist negative or NaN; a model
+ *    without faces; n S V or n V 3 beyond int32 indexing; V > 32768 (the field of a workgroup lives in LDS); a bad space. */
+int smplpp_mesh_geodesic(smplpp_model * m, int64_t n, const float * verts /*[n,V,3]*/, int64_t S, const int64_t * source_ptr /*[S+1]*/,
+                         const int64_t * source_vertex /*[source_ptr[S]]*/, float max_dist, float * dist /*[n,S,V]*/, int space,
+                         void * stream);
+/* The self-contact handle: the far relation of a rest mesh.  Creation runs smplpp_mesh_geodesic's rule on `rest` (the template, or a frame
+ * of smplpp_fk's `rest` for the subject's beta; a HOST array) from every vertex as a single source.  THE RELATION, for v != u:
+ *   far(v, u) = far(u, v) = (the field of source min(v, u), read at max(v, u)) > geo_min;      far(v, v) = 0.
+ * The lower index is named as the source because the fp32 sum along a path is not the sum along its reverse.  An unreachable pair is
+ * far.  THE MASK is a bit matrix [V, W = ceil(V / 32)] of uint32: bit (u & 31) of word (u >> 5) of row v holds far(v, u); bits past V
+ * are 0.  far_pairs counts the unordered far pairs.  The handle copies what it needs of the model and may outlive it.
+ *  - SMPLPP_ERR_INVALID (*out = NULL): geo_min negative or not finite, a rest value not finite, a NULL rest, a model without faces,
+ *    V > 32768. */
+int smplpp_self_contact_create(smplpp_model * m, const float * rest /*[V,3] host*/, float geo_min, struct smplpp_self_contact ** out);
+int smplpp_self_contact_destroy(struct smplpp_self_contact * sc);
+/* Each output nullable. */
+int smplpp_self_contact_info(const struct smplpp_self_contact * sc, int64_t * V, int64_t * words_per_row, float * geo_min,
+                             int64_t * far_pairs);
+/* The mask [V,W] copied out in `space`. */
+int smplpp_self_contact_mask(const struct smplpp_self_contact * sc, uint32_t * mask /*[V,W]*/, int space, void * stream);
+/* smplpp_self_contact: for vertex v of frame i, vertex u of the same frame is a CANDIDATE when all of these hold:
+ *  - far(v, u);
+ *  - d = ((dx dx + dy dy) + dz dz), dx = x_v - x_u and so on, is finite and d <= max_sqdist (+inf: no cap);
+ *  - with vert_normals, the two normals oppose (touching surfaces face each other): with m = n_v, q = n_u,
+ *    s = (m.x q.x + m.y q.y) + m.z q.z, mm and qq the same sums of m with m and q with q:
+ *      s <= 0  &&  mm qq > 0  &&  s s >= (cos_min cos_min) (mm qq),      cos_min in [0, 1]
+ *    which are the bits of the normal test of smplpp_mesh_point_distance_compatible on (m, -q).  A normal that is not finite, or zero,
+ *    matches nothing.
+ * The answer is the candidate of smallest d, on equal d the lowest u: index [n,V], sqdist [n,V].  Without a candidate (also: a vertex
+ * that is not finite) index = -1 and sqdist = +0.
+ *  - SMPLPP_ERR_INVALID (outputs untouched): no handle, n <= 0, a NULL verts, index or sqdist, cos_min outside [0, 1], max_sqdist
+ *    negative or NaN, n V 3 beyond int32 indexing, a bad space.
+ * smplpp_self_contact_vjp: sqdist's vector-Jacobian product at the partners `index` the search chose.  There is no new product:
+ * grad_verts has exactly the bits of two device calls in this order,
+ *   smplpp_mesh_point_distance_vjp(verts, K = V, points = verts, index, grad_sqdist, grad_verts, NULL, accumulate), then
+ *   smplpp_mesh_point_distance_vjp(the same, NULL, grad_points = grad_verts, accumulate = 1):
+ * each vertex gets its own 2 g r, r = x_v - x_index, then one add brings in the ascending-v sum of -2 g r over the vertices that chose
+ * it.  A zero cotangent or an index of -1 contributes nothing; a HOST-space index outside [-1, V) is refused.
+ *  - SMPLPP_ERR_INVALID: as above, and a NULL index, grad_sqdist or grad_verts, accumulate not 0 or 1. */
+int smplpp_self_contact(struct smplpp_self_contact * sc, int64_t n, const float * verts /*[n,V,3]*/,
+                        const float * vert_normals /*[n,V,3] nullable*/, float cos_min, float max_sqdist, int64_t * index /*[n,V]*/,
+                        float * sqdist /*[n,V]*/, int space, void * stream);
+int smplpp_self_contact_vjp(struct smplpp_self_contact * sc, int64_t n, const float * verts /*[n,V,3]*/, const int64_t * index /*[n,V]*/,
+                            const float * grad_sqdist /*[n,V]*/, float * grad_verts /*[n,V,3]*/, int accumulate, int space, void * stream);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,13 @@ def load():
         "smplpp_cloud_knn": [C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int, C.c_float, vp, vp, vp, C.c_int, vp],
         "smplpp_cloud_normals": [C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp, vp, C.c_int64, C.c_float, vp, vp, vp, C.c_int, vp],
         "smplpp_cloud_farthest_points": [C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, C.c_int, vp],
+        "smplpp_mesh_geodesic": [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_float, vp, C.c_int, vp],
+        "smplpp_self_contact_create": [vp, vp, C.c_float, C.POINTER(vp)],
+        "smplpp_self_contact_destroy": [vp],
+        "smplpp_self_contact_info": [vp, i64p, i64p, f32p, i64p],
+        "smplpp_self_contact_mask": [vp, vp, C.c_int, vp],
+        "smplpp_self_contact": [vp, C.c_int64, vp, vp, C.c_float, C.c_float, vp, vp, C.c_int, vp],
+        "smplpp_self_contact_vjp": [vp, C.c_int64, vp, vp, vp, vp, C.c_int, C.c_int, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name, None)

@@ -170,6 +170,7 @@ struct DepthRasterState; // the depth rasteriser, its backward pass and that of 
 struct SilhouetteState;  // the mask distance transform, the silhouette residuals and their backward pass (silhouette.hip)
 struct VertexOffsetsState; // the tile sums of the shared SMPL+D backward (vertex_offsets.hip)
 struct RayCastState;     // ray casting: the rays' keys, the backward pass's records and per-frame terms (ray_cast.hip)
+struct GeodesicState;    // surface geodesics: the model's edge table and the frames' edge lengths (geodesic.hip)
 struct VPoserJxWork;    // a workspace of the exact-fp32 decoder Jacobian (vposer_jac_exact.hip): the decoder's own, or an IK solver's
 // each overload is `delete s`, defined where its state is
 struct StateDelete
@@ -184,6 +185,7 @@ struct StateDelete
   void operator()(SilhouetteState * s) const;
   void operator()(VertexOffsetsState * s) const;
   void operator()(RayCastState * s) const;
+  void operator()(GeodesicState * s) const;
   void operator()(VPoserJxWork * s) const;
 };
 template<class T>
@@ -253,5 +255,6 @@ struct smplpp_model
   int sp_split = 0;             // bound points: threads per partial of the per-joint sums (SMPLPP_SKIN_POINTS_SPLIT = 4 | 1, read at model creation): 0 = by K
   int ray_slices = 0;           // ray casting: workgroups that share a (frame, ray block)'s face chunks (SMPLPP_RAY_SLICES, read at model creation): 0 = by n and K
   smplpp_hip::StatePtr<smplpp_hip::RayCastState> rc; // ray casting workspace (ray_cast.hip): null until its first call
+  smplpp_hip::StatePtr<smplpp_hip::GeodesicState> geo; // edge table and edge-length workspace of smplpp_mesh_geodesic (geodesic.hip): null until its first call
   ~smplpp_model(); // (model.hip) destroys prof_events, then the members free themselves
 };

@@ -876,6 +876,38 @@ class SMPL:
         return _MeshPointDistanceCompatibleFunction.apply(verts, points, self, point_normals, vert_normals, cos_min,
                                                           self._compat_cap(max_dist, max_sqdist))
 
+    # ---- surface geodesics (smplpp_mesh_geodesic); the self-contact search built on them is smplpp_amd.contact
+    def meshGeodesic(self, verts, sources, max_dist=None):
+        """Distance along the mesh's edges from S source sets to every vertex of each frame of verts [N,V,3] (smplpp_mesh_geodesic):
+        dist [N,S,V].  `sources` is a list of S lists of vertex indices (a set may be empty: its field is +inf), or a 1-D array of S
+        single sources; the frames share them.  dist is the exact fp32 minimum over edge paths of the left-to-right sum of the edge
+        lengths: +inf where no path leads, and where dist > max_dist (None: no cap).  A graph distance, an upper bound of the
+        surface's.  numpy (the call synchronises) or float32 device tensors (torch's current stream)."""
+        c = _Call("meshGeodesic", verts)
+        if len(verts.shape) != 3 or verts.shape[0] < 1:
+            c.refuse("expected verts of shape (N, V, 3)")
+        n, V = int(verts.shape[0]), self.vertex_num
+        verts = c.input(verts, (n, V, 3))
+        if _is_torch(sources):
+            sources = sources.detach().cpu().numpy()
+        if isinstance(sources, np.ndarray) and sources.ndim == 1:
+            sets = [[int(s)] for s in sources]
+        else:
+            sets = [np.asarray(s, np.int64).reshape(-1).tolist() for s in sources]
+        if not sets:
+            c.refuse("at least one source set is needed")
+        ptr = np.concatenate([[0], np.cumsum([len(s) for s in sets])]).astype(np.int64)
+        ids = np.asarray([v for s in sets for v in s] + [0], np.int64)  # (one spare entry: never an empty array)
+        if ids[:-1].size and (ids[:-1].min() < 0 or ids[:-1].max() >= V):
+            c.refuse("a source vertex is outside [0, V)")
+        S = len(sets)
+        if c.dev:
+            ptr, ids = torch.from_numpy(ptr).to(c.device), torch.from_numpy(ids).to(c.device)
+        dist = c.empty((n, S, V))
+        cap = float("inf") if max_dist is None else float(np.float32(max_dist))
+        check(_lib.load().smplpp_mesh_geodesic(self.handle, n, _ptr(verts), S, _ptr(ptr), _ptr(ids), cap, _ptr(dist), c.space, c.stream))
+        return dist
+
     # ---- winding numbers and the signed point-to-mesh distance (smplpp_point_mesh_winding / smplpp_point_mesh_signed_distance[_vjp])
     def pointMeshWinding(self, verts, points):
         """Generalized winding numbers of each frame's mesh verts [N,V,3] at K points [N,K,3] (smplpp_point_mesh_winding): returns
