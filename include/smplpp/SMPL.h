@@ -322,6 +322,46 @@ public:
     return {gb, gt, gr};
   }
 
+  // Forward mode of the last launch (smplpp_fk_jvp, reusing its rest shape; no reference counterpart): for T tangents dBeta [N,T,10]
+  // and dTheta [N,T,25,3] (an empty Tensor = zero, not both; row 0 of dTheta is the tangent of the root translation) the tangents
+  // verts [N,T,V,3] of getVertex, joints [N,T,24,3] of getRestJoint and world [N,T,24,3,4] of skeleton().world.  shared: the tangents
+  // are [T,10] / [T,25,3], one set applied to every frame (the one-hot basis of a Jacobian).  With dTheta = the pose rate these are
+  // velocities.
+  struct Tangent
+  {
+    Tensor verts, joints, world;
+  };
+  Tangent launchTangent(const Tensor & dBeta, const Tensor & dTheta, bool shared = false) const
+  {
+    const Tensor & rest = need(rest_);
+    if(beta_.data.empty()) throw Exception("SMPL", "Cannot push a tangent through a SMPL model!");
+    const int64_t n = beta_.size(0), tf = shared ? 1 : n;
+    const int64_t T = tangentCount(tf, {&dBeta, &dTheta}, {SHAPE_BASIS_DIM, (JOINT_NUM + 1) * 3});
+    Tangent t{Tensor({n, T, V_, 3}), Tensor({n, T, JOINT_NUM, 3}), Tensor({n, T, JOINT_NUM, 3, 4})};
+    check(smplpp_fk_jvp(m_.get(), n, T, beta_.ptr(), theta_.ptr(), rest.ptr(), dBeta.data.empty() ? nullptr : dBeta.ptr(),
+                        dTheta.data.empty() ? nullptr : dTheta.ptr(), shared ? 1 : 0, t.verts.ptr(), t.joints.ptr(), t.world.ptr(),
+                        SMPLPP_HOST, nullptr),
+          "SMPL");
+    return t;
+  }
+
+  // The same for the last launchRotmat (smplpp_fk_rotmat_jvp): tangents dBeta [N,T,10], dTrans [N,T,3] and dRot [N,T,24,3,3] (nine
+  // independent entries per joint, used as given; an empty Tensor = zero, not all three); shared drops their leading N.
+  Tangent launchRotmatTangent(const Tensor & dBeta, const Tensor & dTrans, const Tensor & dRot, bool shared = false) const
+  {
+    const Tensor & rest = need(rest_);
+    if(rot_.data.empty()) throw Exception("SMPL", "Cannot push a tangent through a SMPL model!");
+    const int64_t n = rot_.size(0), tf = shared ? 1 : n;
+    const int64_t T = tangentCount(tf, {&dBeta, &dTrans, &dRot}, {SHAPE_BASIS_DIM, 3, JOINT_NUM * 9});
+    Tangent t{Tensor({n, T, V_, 3}), Tensor({n, T, JOINT_NUM, 3}), Tensor({n, T, JOINT_NUM, 3, 4})};
+    check(smplpp_fk_rotmat_jvp(m_.get(), n, T, betaR_.data.empty() ? nullptr : betaR_.ptr(), transR_.data.empty() ? nullptr : transR_.ptr(),
+                               rot_.ptr(), rest.ptr(), dBeta.data.empty() ? nullptr : dBeta.ptr(), dTrans.data.empty() ? nullptr : dTrans.ptr(),
+                               dRot.data.empty() ? nullptr : dRot.ptr(), shared ? 1 : 0, t.verts.ptr(), t.joints.ptr(), t.world.ptr(),
+                               SMPLPP_HOST, nullptr),
+          "SMPL");
+    return t;
+  }
+
   // The skeleton alone (smplpp_skeleton; no reference counterpart): world [N,24,3,4] = [A_j | posed_j] row-major, the world orientation
   // and position of every joint; posed [N,24,3] the posed joints; joints [N,24,3] the rest joints of getRestJoint.  One kernel, no
   // vertex; nothing is kept for the getters or for a later backward: the backward calls below take beta and theta again.
@@ -1110,6 +1150,22 @@ private:
   {
     if(t.data.empty()) throw Exception("LinearBlendSknning", "Failed to get vertices of new pose!"); // LinearBlendSkinning.cpp:413
     return t;
+  }
+  // T of a forward-mode call: every non-empty tangent holds tf x T rows of its width
+  static int64_t tangentCount(int64_t tf, std::initializer_list<const Tensor *> tangents, std::initializer_list<int64_t> widths)
+  {
+    int64_t T = 0;
+    auto w = widths.begin();
+    for(const Tensor * t : tangents)
+    {
+      const int64_t row = tf * *w++;
+      if(t->data.empty()) continue;
+      if(t->dtype != kFloat32 || t->numel() == 0 || t->numel() % row != 0 || (T && t->numel() / row != T))
+        throw Exception("SMPL", "Cannot push a tangent through a SMPL model!");
+      T = t->numel() / row;
+    }
+    if(T == 0) throw Exception("SMPL", "Cannot push a tangent through a SMPL model!");
+    return T;
   }
   Tensor normalsBackward(int kind, const std::vector<int64_t> & ids, const Tensor & gradNormal, Tensor * accumulate) const
   {

@@ -165,6 +165,45 @@ int smplpp_skeleton_vjp(smplpp_model * m, int64_t n, const float * beta, const f
 int smplpp_skeleton_rotmat_vjp(smplpp_model * m, int64_t n, const float * beta, const float * trans, const float * rot,
                                const float * grad_world, const float * grad_posed, const float * grad_joints, float * grad_beta,
                                float * grad_trans /*[n,3]*/, float * grad_rot /*[n,24,3,3]*/, int accumulate, int space, void * stream);
+/* Jacobian-vector product (forward mode) of smplpp_fk and smplpp_skeleton (no reference counterpart: the reference differentiates in
+ * reverse mode only): for T tangents per frame it returns how the vertices, the rest joints and the world joint frames change,
+ *   dverts  [n,T,V,3]     tangent of smplpp_fk's verts
+ *   djoints [n,T,24,3]    tangent of the rest joints (smplpp_fk's joints)
+ *   dworld  [n,T,24,3,4]  tangent of smplpp_skeleton's world = [dA_j | dg_j + dtrans]
+ * (any may be NULL, not all).  dbeta [tf,T,10] and dtheta [tf,T,25,3] (row 0 = the tangent of the root translation) are the tangents,
+ * NULL = zero, not both; shared = 0: tf = n, one set of T tangents per frame; shared = 1: tf = 1, ONE set of T tangents applied to
+ * every frame (the one-hot basis of a Jacobian, held once).  With dtheta = the pose rate the outputs are velocities.
+ * Rule, per frame and tangent, with R, J, A, g, G'_j = [A_j | t_j = g_j - A_j J_j], rest and wSum_v = sum_j w_vj as smplpp_fk has them:
+ *   dR_j = sum_m dtheta[1+j][m] dRodrigues(theta_j)/dtheta_m, the derivative smplpp_fk_vjp contracts with (finite at theta = 0 and at
+ *     |theta| = pi);  dJ = JS dbeta;  drest_v = S_v dbeta + P_v vec(dR_j, j >= 1)
+ *   dA_0 = dR_0, dg_0 = dJ_0; level by level, joint j with parent p: dA_j = dA_p R_j + A_p dR_j,
+ *     dg_j = dA_p (J_j - J_p) + A_p (dJ_j - dJ_p) + dg_p;  dt_j = dg_j - dA_j J_j - A_j dJ_j
+ *   dverts_v = ((sum_j w_vj dA_j) rest_v + sum_j w_vj dt_j + (sum_j w_vj A_j) drest_v) / wSum_v + dtrans
+ * rest: as smplpp_fk_vjp (the rest shape the forward returned, rest + D for an SMPL+D body, NULL = recomputed with the model's form in
+ * the backward's own workspace; smplpp_fk's workspace, status words and profiling record stay as they were); read for dverts only.
+ * All tangent arithmetic is fp32 whatever SMPLPP_SKIN is: the drest contraction on v_mfma_f32_32x32x2_f32 (operands carried exactly),
+ * everything else in fp32 FMAs.  No atomics; the outputs are overwritten; same inputs -> same bits.  The bits of a (frame, tangent)
+ * depend on that frame's inputs and that tangent only: not on n, T, the place in the batch, `shared`, the memory space or which
+ * outputs are asked for; a frame or tangent of NaNs leaves its neighbours alone.  Without dverts the call is one kernel launch that
+ * touches nothing in the handle in device space, on any tree smplpp_model_create accepts; with dverts the first call on a model builds
+ * the operand image smplpp_fk_vjp builds (shared with it).  n T <= 2^31 - 1; element offsets are 64-bit.
+ * SMPLPP_ERR_INVALID (outputs untouched): n <= 0 or T <= 0, NULL beta or theta, every tangent NULL, no output asked for, shared not
+ * 0 or 1. */
+int smplpp_fk_jvp(smplpp_model * m, int64_t n, int64_t T, const float * beta /*[n,10]*/, const float * theta /*[n,25,3]*/,
+                  const float * rest /*[n,V,3] nullable*/, const float * dbeta /*[tf,T,10] nullable = 0*/,
+                  const float * dtheta /*[tf,T,25,3] nullable = 0*/, int shared /*0: tf = n, 1: tf = 1*/,
+                  float * dverts /*[n,T,V,3] nullable*/, float * djoints /*[n,T,24,3] nullable*/,
+                  float * dworld /*[n,T,24,3,4] nullable*/, int space, void * stream);
+/* smplpp_fk_jvp for the rotation-matrix entry (smplpp_fk_rotmat / smplpp_skeleton_rotmat): the tangents are dbeta [tf,T,10], dtrans
+ * [tf,T,3] and drot [tf,T,24,3,3], NINE INDEPENDENT ENTRIES per joint used as given (dR_j = drot[j]: the map is polynomial in them, no
+ * projection onto the rotations), any NULL = zero, not all.  beta NULL = zero; trans is accepted for symmetry and not read (no tangent
+ * depends on it).  With drot = sum_m dtheta_m dRodrigues/dtheta_m and dtrans = dtheta[0] it is smplpp_fk_jvp to rounding; with drot
+ * NULL or zero and the same dbeta the two entries agree bit for bit on a body with rot = smplpp_axis_angle_to_rotmat(theta[:,1:]).
+ * Everything else as smplpp_fk_jvp; SMPLPP_ERR_INVALID also for NULL rot. */
+int smplpp_fk_rotmat_jvp(smplpp_model * m, int64_t n, int64_t T, const float * beta /*nullable*/, const float * trans /*nullable*/,
+                         const float * rot /*[n,24,3,3]*/, const float * rest /*nullable*/, const float * dbeta /*nullable*/,
+                         const float * dtrans /*[tf,T,3] nullable*/, const float * drot /*[tf,T,24,3,3] nullable*/, int shared,
+                         float * dverts, float * djoints, float * dworld, int space, void * stream);
 /* Input range of the fp16x2 form (SMPLPP_SKIN=h): |beta| < 1023 and relative transforms whose
  * translations stay within 16 x the template's extent (65504 / sG).  Outside it the operand pieces overflow fp16 and the
  * vertices of the frame are not finite, where the reference and the default form (and SMPLPP_SKIN=b|v) stay finite.  A launch that

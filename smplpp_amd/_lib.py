@@ -67,6 +67,8 @@ def load():
         "smplpp_skeleton_rotmat": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_skeleton_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
         "smplpp_skeleton_rotmat_vjp": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp],
+        "smplpp_fk_jvp": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp],
+        "smplpp_fk_rotmat_jvp": [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_blend_shape": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_joint_regression": [C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp],
         "smplpp_stage_world_transformation": [C.c_int, C.c_int64, vp, vp, vp, vp, C.c_int, vp],

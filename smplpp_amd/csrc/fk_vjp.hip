@@ -27,6 +27,7 @@
 // the vertex coordinates along K.  Built from the vertex-major bases the model keeps (Pvm / Svm; the K-major Bm is freed by the
 // default forms) on the first call on a model, owned by the model's backward state.
 #include "common.h"
+#include "fk_vjp_state.h"
 #include "pose_body.h"
 #include "rodrigues_grad.h"
 #include "staging.h"
@@ -44,21 +45,11 @@ int fk_rotmat_device(smplpp_model * m, int64_t n, const float * beta, const floa
                      float * xforms44, float * rest, hipStream_t st, int range_slot, int * range_word);
 
 constexpr int VJ_FT = 32;              // frames per workgroup of the hot kernel (the MFMA rows)
-constexpr int VJ_KN = 224;             // columns of the operand image (k < 217 live)
 constexpr int VJ_NT = VJ_KN / 32;      // N tiles of the transposed GEMM
 constexpr int VJ_RS = NJ * 9 + 1;      // LDS stride of a frame's 24 rotations (odd: the 32 frames of a wave hit 32 banks)
 constexpr int VJ_RED = VJ_KN + 4;      // LDS row of the cross-wave reduction of the GEMM result
 // partial slab of one (chunk, frame): [g_c 224 | dG' 24 x 3x4 | g_root 3 high parts | g_root 3 low parts | pad]
 constexpr int VJ_DG = VJ_KN, VJ_ROOT = VJ_KN + NJ * 12, VJ_SLAB = VJ_ROOT + 8;
-
-struct VjpState
-{
-  DevPtr<float> BT;     // operand image (above)
-  Workspace fws;        // the forward's workspace while smplpp_fk_vjp recomputes `rest` (smplpp_fk's own stays untouched)
-  DevPtr<int> range_word; // where that recomputation reports an fp16x2 range miss (not smplpp_fk's words)
-  DevBuf Gp, joints, rot, slab;
-  DevBuf rest;          // the rest shape recomputed when the caller passes none
-};
 
 void StateDelete::operator()(VjpState * s) const
 {
@@ -463,9 +454,7 @@ static void vjp_chunks(const smplpp_model * m, int64_t n, int & nft, int & nch, 
 
 // rot_in (smplpp_fk_rotmat_vjp): `theta` is rot [n][24][9], `trans` [n][3] (nullable) the root translation, gtheta = grad_rot
 // [n][24][9] and gtrans = grad_trans [n][3]
-static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * gv,
-                      const float * gj, float * gbeta, float * gtheta, hipStream_t st, bool rot_in = false, const float * trans = nullptr,
-                      float * gtrans = nullptr)
+int fk_vjp_image(smplpp_model * m, hipStream_t st, const float ** BT)
 {
   VjpState * s = m->vjp.get();
   if(!s->BT)
@@ -475,21 +464,38 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
     vjp_image_kernel<<<dim3((unsigned)((rows * VJ_KN + 255) / 256)), dim3(256), 0, st>>>(m->Pvm.get(), m->Svm.get(), s->BT.get(), m->V, rows);
     HIP_TRY(hipGetLastError());
   }
+  *BT = s->BT.get();
+  return SMPLPP_OK;
+}
+
+int fk_vjp_rest(smplpp_model * m, int64_t n, const float * beta, const float * pose, const float * trans, bool rot_in, hipStream_t st,
+                const float ** rest)
+{
+  // the model's forward form into the backward's own workspace: smplpp_fk's workspace, range words and profiling record stay as they were
+  VjpState * s = m->vjp.get();
+  HIP_TRY(s->rest.reserve(sizeof(float) * (size_t)n * m->V * 3));
+  std::swap(m->ws, s->fws);
+  const bool prof = m->profiling;
+  m->profiling = false;
+  int rc = rot_in ? fk_rotmat_device(m, n, beta, trans, pose, nullptr, nullptr, nullptr, s->rest.as<float>(), st, RANGE_DEVICE,
+                                     s->range_word.get())
+                  : fk_device(m, n, beta, pose, nullptr, nullptr, nullptr, s->rest.as<float>(), nullptr, st, RANGE_DEVICE, s->range_word.get());
+  m->profiling = prof;
+  std::swap(m->ws, s->fws);
+  if(rc) return rc;
+  *rest = s->rest.as<float>();
+  return SMPLPP_OK;
+}
+
+static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * gv,
+                      const float * gj, float * gbeta, float * gtheta, hipStream_t st, bool rot_in = false, const float * trans = nullptr,
+                      float * gtrans = nullptr)
+{
+  VjpState * s = m->vjp.get();
+  const float * BT = nullptr; // (launch_vjp_skin reads it from the state)
+  if(int rc = fk_vjp_image(m, st, &BT)) return rc;
   if(gv && !rest)
-  {
-    // the model's forward form into the backward's own workspace: smplpp_fk's workspace, range words and profiling record stay as they were
-    HIP_TRY(s->rest.reserve(sizeof(float) * (size_t)n * m->V * 3));
-    std::swap(m->ws, s->fws);
-    const bool prof = m->profiling;
-    m->profiling = false;
-    int rc = rot_in ? fk_rotmat_device(m, n, beta, trans, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), st, RANGE_DEVICE,
-                                       s->range_word.get())
-                    : fk_device(m, n, beta, theta, nullptr, nullptr, nullptr, s->rest.as<float>(), nullptr, st, RANGE_DEVICE, s->range_word.get());
-    m->profiling = prof;
-    std::swap(m->ws, s->fws);
-    if(rc) return rc;
-    rest = s->rest.as<float>();
-  }
+    if(int rc = fk_vjp_rest(m, n, beta, theta, trans, rot_in, st, &rest)) return rc;
   HIP_TRY(s->Gp.reserve(sizeof(float) * (size_t)n * NJ * 12));
   HIP_TRY(s->joints.reserve(sizeof(float) * (size_t)n * NJ * 3));
   if(!rot_in) HIP_TRY(s->rot.reserve(sizeof(float) * (size_t)n * NJ * 9));
@@ -529,12 +535,8 @@ static int vjp_device(smplpp_model * m, int64_t n, const float * beta, const flo
   HIP_TRY(hipGetLastError());
   return SMPLPP_OK;
 }
-} // namespace smplpp_hip
-
-using namespace smplpp_hip;
-
 // the backward state of a model, created by the first backward call on it
-static int vjp_state(smplpp_model * m)
+int fk_vjp_state(smplpp_model * m)
 {
   if(!m->vjp)
   {
@@ -545,6 +547,9 @@ static int vjp_state(smplpp_model * m)
   }
   return SMPLPP_OK;
 }
+} // namespace smplpp_hip
+
+using namespace smplpp_hip;
 
 extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, const float * theta, const float * rest, const float * grad_verts,
                              const float * grad_joints, float * grad_beta, float * grad_theta, int space, void * stream)
@@ -555,7 +560,7 @@ extern "C" int smplpp_fk_vjp(smplpp_model * m, int64_t n, const float * beta, co
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_vjp: too many frames");
   Frame fr(m->device, &m->arena, space, stream, "backward SMPL");
   if(!fr.ok()) return fr.finish();
-  if(int rc = vjp_state(m)) return rc;
+  if(int rc = fk_vjp_state(m)) return rc;
   if(!grad_beta && !grad_theta) return SMPLPP_OK;
   if(space == SMPLPP_DEVICE)
     return fr.run([&] { return vjp_device(m, n, beta, theta, rest, grad_verts, grad_joints, grad_beta, grad_theta, fr.st); });
@@ -581,7 +586,7 @@ extern "C" int smplpp_fk_rotmat_vjp(smplpp_model * m, int64_t n, const float * b
   if(n > 0x7fffffffLL) return fail(SMPLPP_ERR_INVALID, "smplpp_fk_rotmat_vjp: too many frames");
   Frame fr(m->device, &m->arena, space, stream, "backward SMPL");
   if(!fr.ok()) return fr.finish();
-  if(int rc = vjp_state(m)) return rc;
+  if(int rc = fk_vjp_state(m)) return rc;
   if(!grad_beta && !grad_trans && !grad_rot) return SMPLPP_OK;
   // `trans` is not read: neither the rest shape nor any of the three gradients depends on it (and the call stages eight arguments)
   (void)trans;

@@ -416,6 +416,74 @@ class SMPL:
             raise SmplppError(1, "forward_rotmat_differentiable needs torch")
         return _FKRotmatFunction.apply(beta, trans, rot, self)
 
+    # ---- forward mode (smplpp_fk_jvp / smplpp_fk_rotmat_jvp): tangents of the vertices, the rest joints and the world joint frames
+    _TANGENT_OUT = (("verts", None), ("joints", (24, 3)), ("world", (24, 3, 4)))
+
+    def _tangent(self, name, rot_in, beta, trans, pose, tangents, rest, shared, want, out):
+        """One forward-mode call: `tangents` = (dbeta, dtheta) or (dbeta, dtrans, drot), each [n,T,...] or, shared, [T,...]."""
+        c = _Call(name, pose, beta, trans, rest, *tangents, *((out or {}).values()))
+        n, V = int(pose.shape[0]) if c.dev else len(pose), self.vertex_num
+        first = next((t for t in tangents if t is not None), None)
+        if first is None:
+            c.refuse("at least one tangent must be given")
+        shape = tuple(first.shape) if c.dev else np.shape(first)
+        lead = 1 if shared else 2
+        if len(shape) < lead + 1 or (not shared and shape[0] != n):
+            c.refuse("tangents carry a T axis: [n,T,...], or [T,...] when shared")
+        T = int(shape[lead - 1])
+        pre = (T,) if shared else (n, T)
+        tails = ((10,), (3,), (24, 3, 3)) if rot_in else ((10,), (25, 3))
+        tangents = [c.input(t, pre + s) for t, s in zip(tangents, tails)]
+        beta, trans = c.input(beta, (n, 10)), c.input(trans, (n, 3))
+        pose, rest = c.input(pose, (n, 24, 3, 3) if rot_in else (n, 25, 3)), c.input(rest, (n, V, 3))
+        given = out or {}
+        res = {k: c.inout(given[k], (n, T) + (s or (V, 3))) if k in given else (c.empty((n, T) + (s or (V, 3))) if k in want else None)
+               for k, s in self._TANGENT_OUT}
+        if all(v is None for v in res.values()):
+            c.refuse("verts, joints or world must be asked for")
+        ptrs = [_ptr(res[k]) for k, _ in self._TANGENT_OUT]
+        L = _lib.load()
+        if rot_in:
+            check(L.smplpp_fk_rotmat_jvp(self.handle, n, T, _ptr(beta), _ptr(trans), _ptr(pose), _ptr(rest), _ptr(tangents[0]),
+                                         _ptr(tangents[1]), _ptr(tangents[2]), int(bool(shared)), *ptrs, c.space, c.stream))
+        else:
+            check(L.smplpp_fk_jvp(self.handle, n, T, _ptr(beta), _ptr(pose), _ptr(rest), _ptr(tangents[0]), _ptr(tangents[1]),
+                                  int(bool(shared)), *ptrs, c.space, c.stream))
+        return {k: v for k, v in res.items() if v is not None}
+
+    def launchTangent(self, beta, theta, dbeta=None, dtheta=None, rest=None, shared=False, want=("verts", "joints", "world"), out=None):
+        """Jacobian-vector product of `launch` and `skeleton` (smplpp_fk_jvp): for T tangents (dbeta [N,T,10], dtheta [N,T,25,3]; None =
+        zero, not both; row 0 of dtheta is the tangent of the root translation) a dict of verts [N,T,V,3], joints [N,T,24,3] (the REST
+        joints) and world [N,T,24,3,4] (`skeleton`'s world): how each output changes along each tangent.  With dtheta = the pose rate
+        these are velocities.  shared=True: the tangents are [T,10] / [T,25,3], one set applied to every frame.  `rest` as in
+        launchBackward (None recomputes it; rest + D for an SMPL+D body).  `want` drops outputs (without "verts" the call is one
+        small kernel); `out` (a dict keyed the same way) supplies preallocated arrays.  numpy (the call synchronises) or float32
+        device tensors (torch's current stream).  Deterministic; a (frame, tangent)'s bits do not depend on N, T or its place."""
+        return self._tangent("launchTangent", False, beta, None, theta, (dbeta, dtheta), rest, shared, want, out)
+
+    def launchRotmatTangent(self, beta, trans, rot, dbeta=None, dtrans=None, drot=None, rest=None, shared=False,
+                            want=("verts", "joints", "world"), out=None):
+        """launchTangent for the rotation-matrix entry (smplpp_fk_rotmat_jvp): tangents dbeta [N,T,10], dtrans [N,T,3] and drot
+        [N,T,24,3,3] (nine independent entries per joint, used as given; None = zero, not all three); shared=True drops their
+        leading N.  beta and trans may be None (zero).  Outputs, `rest`, `want` and `out` as in launchTangent."""
+        return self._tangent("launchRotmatTangent", True, beta, trans, rot, (dbeta, dtrans, drot), rest, shared, want, out)
+
+    def jacobian(self, beta, theta, wrt=("beta", "theta"), rest=None, want=("verts",)):
+        """The dense Jacobian of `launch` / `skeleton` by one launchTangent on the shared one-hot basis: a dict keyed like `want` of
+        verts [N,T,V,3], joints [N,T,24,3], world [N,T,24,3,4], whose axis 1 is the TANGENT AXIS: T = 10 (if "beta" in wrt) + 75 (if
+        "theta" in wrt), beta's ten columns first, then theta's 25 x 3 in row-major order (row 0 = the root translation).  So
+        out["verts"][f].reshape(T, -1).T is the [3V, T] Jacobian of frame f."""
+        c = _Call("jacobian", beta, theta, rest)
+        nb, nt = (10 if "beta" in wrt else 0), (75 if "theta" in wrt else 0)
+        if nb + nt == 0:
+            c.refuse("wrt must name beta or theta")
+        eye = np.eye(nb + nt, dtype=np.float32)
+        db = np.ascontiguousarray(eye[:, :nb]) if nb else None
+        dt = np.ascontiguousarray(eye[:, nb:]).reshape(nb + nt, 25, 3) if nt else None
+        if c.dev:
+            db, dt = (None if a is None else torch.from_numpy(a).to(c.device) for a in (db, dt))
+        return self.launchTangent(beta, theta, dbeta=db, dtheta=dt, rest=rest, shared=True, want=want)
+
     # ---- the skeleton alone (smplpp_skeleton / smplpp_skeleton_rotmat and their vector-Jacobian products)
     _SKELETON_OUT = (("world", (24, 3, 4)), ("posed", (24, 3)), ("joints", (24, 3)))
 
@@ -1532,6 +1600,7 @@ if torch is not None:
             beta, theta, out = smpl._fk(c, beta, theta, ("verts", "joints", "rest"))
             ctx.smpl = smpl
             ctx.save_for_backward(beta, theta, out["rest"])
+            ctx.save_for_forward(beta, theta, out["rest"])
             return out["verts"], out["joints"]
 
         @staticmethod
@@ -1542,6 +1611,16 @@ if torch is not None:
             g = ctx.smpl.launchBackward(beta, theta, grad_verts=grad_verts, grad_joints=grad_joints, rest=rest)
             return (g["beta"] if ctx.needs_input_grad[0] else None, g["theta"] if ctx.needs_input_grad[1] else None, None)
 
+        @staticmethod
+        def jvp(ctx, dbeta, dtheta, _):
+            """Forward mode (torch.autograd.forward_ad): one smplpp_fk_jvp with T = 1; a tangent of None counts as zero."""
+            beta, theta, rest = ctx.saved_tensors
+            if dbeta is None and dtheta is None:
+                return None, None
+            d = ctx.smpl.launchTangent(beta, theta, dbeta=None if dbeta is None else dbeta.unsqueeze(1),
+                                       dtheta=None if dtheta is None else dtheta.unsqueeze(1), rest=rest, want=("verts", "joints"))
+            return d["verts"].squeeze(1), d["joints"].squeeze(1)
+
     class _FKRotmatFunction(torch.autograd.Function):
         """smplpp_fk_rotmat forward / smplpp_fk_rotmat_vjp backward (SMPL.forward_rotmat_differentiable)."""
 
@@ -1551,8 +1630,19 @@ if torch is not None:
             beta, trans, rot, out = smpl._fk_rotmat(c, beta, trans, rot, ("verts", "joints", "xforms", "rest"))
             ctx.smpl = smpl
             ctx.save_for_backward(beta, trans, rot, out["rest"])
+            ctx.save_for_forward(beta, trans, rot, out["rest"])
             ctx.mark_non_differentiable(out["xforms"])
             return out["verts"], out["joints"], out["xforms"]
+
+        @staticmethod
+        def jvp(ctx, dbeta, dtrans, drot, _):
+            """Forward mode: one smplpp_fk_rotmat_jvp with T = 1; a tangent of None counts as zero, xforms has no tangent."""
+            beta, trans, rot, rest = ctx.saved_tensors
+            if dbeta is None and dtrans is None and drot is None:
+                return None, None, None
+            t = [None if a is None else a.unsqueeze(1) for a in (dbeta, dtrans, drot)]
+            d = ctx.smpl.launchRotmatTangent(beta, trans, rot, dbeta=t[0], dtrans=t[1], drot=t[2], rest=rest, want=("verts", "joints"))
+            return d["verts"].squeeze(1), d["joints"].squeeze(1), None
 
         @staticmethod
         def backward(ctx, grad_verts, grad_joints, _grad_xforms):
